@@ -6,14 +6,20 @@ HBM -> vt_encode_tag (HIP encoder + decoder) -> [B,N] logits -> (N>1) one RCCL a
 Workload at N=1: BASELINE.json configs[2] -- batch 16, 1024x1024, 8-head attention decoder, 10k tags,
 bf16 MFMA operands / fp32 accumulate.  Weak scaling: the per-GPU batch is fixed as N grows.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the implicit-GEMM MFMA conv):
-achieved = its algorithmic FLOPs / its summed launch durations, from HIP events recorded on the launch
-stream over the timed region (vt_profile_begin/end in the C ABI; ~140 event records per step -- the same K steps are run
-once more without them and reported as `ms_per_step_without_events`).  `cpu_baseline` times the CPU oracle (oracle/, kind "port") on this box's host cores,
-rank 0, N=1 only, on a bounded sample; `max_abs_dlogit` / `max_abs_dlatent` compare image 0 of the measured batch with it.
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W untimed steps, times K steps and reports them: `value` (images/sec) and
+`ms_per_step` come from those K steps.  `roofline` is for the dominant kernel (the implicit-GEMM MFMA conv) of the same K steps:
+achieved = its algorithmic FLOPs / its summed launch durations, from HIP events recorded on the launch stream over the timed region
+(vt_profile_begin/end in the C ABI; ~140 event records per step).  `--dump-outputs DIR` writes what the last timed step returned
+(the logits, or the latents with --encode-only) as DIR/<name>.npy in float32.
+
+`--full` adds everything else, after the timed steps: the same K steps once more without the event records
+(`ms_per_step_without_events`) with the socket power polled (`power`, `joules_per_image`); `cpu_baseline`, which times the CPU
+oracle (oracle/, kind "port") on the host's cores, rank 0, N=1 only, on a bounded sample, and `max_abs_dlogit` /
+`max_abs_dlatent` / `parity`, which compare image 0 of the measured batch with it; and, on the default workload, the other
+single-GPU configs of BASELINE.json and the precision mode as `also`.
 """
 import argparse
 import ctypes
@@ -33,6 +39,7 @@ MFMA_FP8_DENSE_PEAK_TFLOPS = 5000.0      # MI355X_MICROARCH.md: ~5 PF dense fp8 
 MFMA_BF16_MEASURED_BARE_TFLOPS = 2040.0
 MFMA_FP8_MEASURED_BARE_TFLOPS = 4100.0
 HBM_PEAK_GBS = 8000.0                    # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_BUDGET_BYTES = 64 << 20             # --dump-outputs writes at most this much in all
 
 
 def parse():
@@ -54,8 +61,13 @@ def parse():
     p.add_argument("--f16", action="store_true",
                    help="fp16 instead of bf16 MFMA operands for the convolutions (vt_set_flag 18): the precision mode -- latents ~6x closer to the "
                         "fp32 reference for a few per cent of the images/s; not BASELINE.json's dtype, never the default line")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-also", action="store_true", help="skip the configs[4] / configs[3] legs attached to the default run's line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned as DIR/<name>.npy (float32; at most 64 MB in all, a fixed sample beyond)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also: the same steps without event records + socket power, the CPU oracle baseline and "
+                        "parity, and (default workload) the other BASELINE configs and the precision mode as `also`")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline and parity")
+    p.add_argument("--no-also", action="store_true", help="with --full: skip the configs[4] / configs[3] legs attached to the default run's line")
     p.add_argument("--generic-conv", action="store_true", help="A/B: disable the halo-tile 3x3 kernel")
     p.add_argument("--no-occ2", action="store_true", help="A/B: 128-cout convs on the one-workgroup-per-CU tile")
     p.add_argument("--lib", default=None, help="A/B: path of an alternative build of libvae_tagger_hip.so")
@@ -132,6 +144,25 @@ def cpu_baseline(x0, tags, flops_target, budget_s=85.0):
                  "rows": rows, "total_seconds": round(time.perf_counter() - t_start, 1)}
 
 
+def dump_outputs(dirpath, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write {name: tensor} as dirpath/<name>.npy, float32 (float64 stays float64).  Each array gets an equal share of `budget`;
+    one larger than its share is written as a fixed sample of its flattened elements (every k-th from a seeded offset), so two
+    builds given the same arguments write the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            stride = -(-t.numel() // keep)
+            start = int(torch.randint(stride, (1,), generator=torch.Generator().manual_seed(0)))
+            t = t.reshape(-1)[start::stride]
+        np.save(os.path.join(dirpath, name + ".npy"), t.numpy())
+
+
 def pmc_traffic(kernel, batch, height, width, fp8=False):
     """HBM bytes per launch of `kernel` from the committed rocprofv3 --pmc summary (tools/profile_round.sh: separate
     FETCH_SIZE and WRITE_SIZE passes; both in KB; FETCH_SIZE doubled per the gfx950 note in MI355X_MICROARCH.md -- round 4's
@@ -203,7 +234,7 @@ class SocketPower:
 
 def main():
     a = parse()
-    power = SocketPower()
+    power = SocketPower() if a.full else None
     if a.lib:
         from vae_tagger_amd import _lib
         _lib.LIB_PATH = os.path.abspath(a.lib)
@@ -413,13 +444,17 @@ def main():
         f()
     elapsed, out, prof = timed(steps)
     assert torch.isfinite(out).all()
-    # the same K steps without the per-launch event records (the production path): reported beside the contract number
-    with power:
-        elapsed_plain, out, _ = timed(steps, profile=False)
-    power_main = power.summary() if rank == 0 else None
+    last_step_out = out
+    if a.full:
+        # the same K steps without the per-launch event records (the production path): reported beside the contract number
+        with power:
+            elapsed_plain, out, _ = timed(steps, profile=False)
+        power_main = power.summary() if rank == 0 else None
     status = prof_ctx.status()
     assert status == 0, (f"vt_status = {status}: " + ("non-finite activations inside the encoder" if status & 1 else
                                                        "activations clamped to the e4m3 range (fp8 mode unsuitable for these weights)"))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"latent" if a.encode_only else "logits": last_step_out})
 
     res = None
     if rank == 0:
@@ -444,17 +479,21 @@ def main():
                            "1024^2", "1024^2" if (a.height, a.width) == (1024, 1024) else f"{a.width}x{a.height}").replace(
                            "bf16", "fp16 conv operands (attention bf16)" if a.f16 else "bf16"),
             "value": round(ips, 3), "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(elapsed / a.steps * 1e3, 3), "ms_per_step_without_events": round(elapsed_plain / a.steps * 1e3, 3),
+            "ms_per_step": round(elapsed / a.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "fp8" if a.fp8 else ("f16" if a.f16 else "bf16"), "data": "synthetic",
-            "config": cfg, "roofline": roof, "hbm_pass": hbm, "power": power_main,
-            # the figure of merit under the 1400-W cap: socket power of the untraced steps / their images per second
-            "joules_per_image": None if not power_main else round(power_main["socket_w_median"] / (images_per_step / world * a.steps / elapsed_plain), 3),
+            "config": cfg, "roofline": roof, "hbm_pass": hbm,
         }
+        if a.full:
+            res.update({
+                "ms_per_step_without_events": round(elapsed_plain / a.steps * 1e3, 3), "power": power_main,
+                # the figure of merit under the 1400-W cap: socket power of the untraced steps / their images per second
+                "joules_per_image": None if not power_main else round(power_main["socket_w_median"] / (images_per_step / world * a.steps / elapsed_plain), 3),
+            })
 
-    # ---- the other single-GPU configs of BASELINE.json on the same pipeline, attached to the ONE line as "also" (default run only):
+    # ---- the other single-GPU configs of BASELINE.json on the same pipeline, attached to the ONE line as "also" (--full, default workload only):
     # configs[4] per GPU (fp8 mode, same batch) and configs[3] (bucketed batches); ~2 s of GPU time, headline keys untouched
-    default_run = (world == 1 and not (a.fp8 or a.f16 or a.bucketed or a.encode_only or a.generic_conv or a.no_occ2 or a.flag)
+    default_run = (a.full and world == 1 and not (a.fp8 or a.f16 or a.bucketed or a.encode_only or a.generic_conv or a.no_occ2 or a.flag)
                    and not a.no_also)
     also_f8_logits = also_f8_idx = also_f16 = None
     if default_run:
@@ -549,7 +588,7 @@ def main():
         res["also"] = also
 
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline and not a.bucketed:
+        if a.full and world == 1 and not a.no_cpu_baseline and not a.bucketed:
             # parity half of the metric: image 0 of the measured batch through the HIP path (outside the timed region) against
             # the CPU oracle's warm-up run on the same image
             xs = x[:1]

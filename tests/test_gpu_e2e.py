@@ -736,6 +736,43 @@ def test_bench_two_ranks_on_one_gpu_rehearsal(tmp_path, extra):
     assert res["value"] > 0 and res["scaling"] == "weak" and "cpu_baseline" not in res
 
 
+@pytest.mark.parametrize("extra", [[], ["--encode-only"]], ids=["encode_tag", "encode_only"])
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_step(tmp_path, vae, extra):
+    """A plain `bench.py` run (no --full): K timed steps behind `value` / `ms_per_step`, none of the --full measurements on the line,
+    and --dump-outputs writes what the timed path returns -- compared here with the same seeded weights and images run in this process."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    from vae_tagger_amd.modules import create_attention_decoder
+    from vae_tagger_amd.pipeline import EncodeTagPipeline
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, H, W, n, K = 2, 256, 256, 1000, 3
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "1", "--batch", str(B),
+           "--height", str(H), "--width", str(W), "--tags", str(n), "--dump-outputs", str(tmp_path / "out")] + extra
+    r = subprocess.run(cmd, env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"), cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == K and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["higher_is_better"] is True
+    assert abs(res["value"] * res["ms_per_step"] / 1e3 - B) <= 0.01 * B           # images per step = value x seconds per step
+    assert not {"also", "cpu_baseline", "parity", "power", "ms_per_step_without_events"} & set(res)
+    x = synth.synth_images(B, H, W, seed=1000).cuda()
+    if extra:
+        name, want = "latent", vae.encode(x)
+    else:
+        dec = create_attention_decoder(16, H // 8, W // 8, n, {"use_spatial_attention": True, "use_self_attention": True,
+                                                               "use_cross_attention": False, "attention_heads": 8})
+        dec.load_state_dict(synth.synth_state_dict(synth.attention_decoder_manifest(n), seed=1), strict=False)
+        name, want = "logits", EncodeTagPipeline(vae, dec.to("cuda").eval()).logits(x)
+    assert sorted(os.listdir(tmp_path / "out")) == [name + ".npy"]
+    got = np.load(tmp_path / "out" / (name + ".npy"))
+    assert got.dtype == np.float32 and got.shape == tuple(want.shape)
+    assert torch.allclose(torch.from_numpy(got), want.cpu(), rtol=0, atol=1e-4)
+
+
 def test_rccl_one_rank_communicator_runs_the_logits_all_gather(tmp_path):
     """RCCL executes on this ROCm build: a child process creates a ONE-rank "nccl" (= RCCL) process group on cuda:0 before any
     other GPU call, runs the exact collective `bench.py --gpus N` uses -- sharding.all_gather_logits' all_gather_into_tensor

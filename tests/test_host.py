@@ -275,6 +275,28 @@ def test_bench_socket_power_picks_the_loaded_card_and_tolerates_missing_files(tm
     assert q.summary() is None
 
 
+# ---- bench.py --dump-outputs: float32 files, whole when they fit, a fixed sample of the same elements every run when they do not ---------------
+def test_bench_dump_outputs_writes_float_files_within_the_budget(tmp_path):
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    small = torch.randn(10, 10, generator=g).to(torch.bfloat16)                  # 100 float32 elements = 400 bytes: fits its share
+    big = torch.randn(1000, generator=g, dtype=torch.float64)                      # 8000 bytes: sampled down to <= 50 elements
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big}, budget=800)
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (10, 10) and np.array_equal(s, small.float().numpy())
+    b = np.load(tmp_path / "a" / "big.npy")
+    assert b.dtype == np.float64 and 0 < b.size <= 50 and b.nbytes <= 400
+    start = int(np.flatnonzero(big.numpy() == b[0])[0])
+    assert np.array_equal(b, big.numpy()[start::20])
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 800 + 2 * 256     # payload + two .npy headers
+
+
 _GATHER_WORKER = '''
 import os, sys
 sys.path.insert(0, sys.argv[1])

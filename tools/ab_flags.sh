@@ -4,7 +4,7 @@ out=$1; reps=$2; shift 2
 : > $out
 for r in $(seq 1 $reps); do
   for v in "$@"; do
-    line=$(python3 bench.py --no-cpu-baseline --no-also --steps 15 --warmup 4 $v 2>/dev/null | tail -1)
+    line=$(python3 bench.py --full --no-cpu-baseline --no-also --steps 15 --warmup 4 $v 2>/dev/null | tail -1)
     python3 - "$r" "$v" "$line" >> $out <<'PY'
 import json, sys
 r, v, line = sys.argv[1:4]

@@ -16,7 +16,7 @@ def smi(args):
         return f"({args[0]}: {e})"
 print(smi(["rocm-smi", "--showpower", "--showclocks", "--showmaxpower", "--showtemp"]), flush=True)
 extra = sys.argv[1:]
-child = subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-also", "--steps", "150", "--warmup", "5"] + extra,
+child = subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-also", "--steps", "150", "--warmup", "5"] + extra,
                          stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
 rows = []
 t0 = time.time()

@@ -5,7 +5,7 @@ set -e
 out=gpurun_out/trace_gaps
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $out/t -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-also "$@" > $out/log.txt 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $out/t -- python3 bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-also "$@" > $out/log.txt 2>&1
 python3 - "$@" <<'PY'
 import csv, glob, sys
 f = glob.glob("gpurun_out/trace_gaps/t/*/*kernel_trace.csv")[0]
