@@ -27,7 +27,7 @@ typedef struct vt_context vt_context;
 
 enum { VT_OK = 0, VT_ERR_INVALID = 1, VT_ERR_HIP = 2, VT_ERR_STATE = 3, VT_ERR_MISSING_WEIGHT = 4,
        VT_ERR_WORKSPACE = 5 };
-enum { VT_F32 = 0, VT_BF16 = 1, VT_F16 = 2 };
+enum { VT_F32 = 0, VT_BF16 = 1, VT_F16 = 2, VT_U8 = 3 /* evaluator labels only */ };
 
 const char* vt_version(void);
 int vt_create(int device, vt_context** out);
@@ -112,6 +112,41 @@ size_t vt_resize_workspace_bytes(int crop_h, int crop_w, int dst_h, int dst_w, i
 int vt_resize_table(int in_size, int out_size, int filter, int* table_out, int table_ints);
 int vt_resize_u8(vt_context* ctx, const uint8_t* src_hwc, int src_h, int src_w, int crop_left, int crop_top, int crop_w, int crop_h,
                  uint8_t* dst_hwc, int dst_h, int dst_w, int filter, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- streaming multi-label evaluator <- MultiLabelEvaluator.compute_metrics / find_optimal_threshold, evaluation.py:13-275, without the
+ * n x c host matrix: the state lives in ONE caller-owned device block and is fed batch by batch in stream order; no call below
+ * synchronises the host.  The state remembers nothing about its own shape: every call takes (N classes, T thresholds, capacity)
+ * as the reset call did, and checks every buffer's byte size before anything is launched -- an undersized buffer is
+ * VT_ERR_WORKSPACE, a null / misaligned pointer or an out-of-range argument VT_ERR_INVALID, and nothing is written.
+ * Block layout (every section 256-B aligned): thresholds fp64 [32] | row_stats uint64 [3] | per-row scratch uint32 [4096] |
+ * support uint32 [N] | counts uint32 [N][T][2] = (tp, fp) | keys uint64 [N][capacity].
+ *   - a prediction is (double)p > thresholds[t], strict and in fp64 (numpy's float32_array > float64_scalar; for the fp32 comparison
+ *     of a Python float pass the threshold rounded to fp32); a label is positive when > 0 (VT_F32 or VT_U8 labels);
+ *   - row_stats = { rows whose prediction at t_main equals the label row, mismatching elements at t_main, non-finite probabilities };
+ *   - capacity = samples the key store can hold; 0 = counts only (no average precision).  Key of (class j, sample i): high word = the
+ *     monotone unsigned map of the probability's fp32 bits that the confidence sort uses, low word = (~i << 1) | label; stored class-major;
+ *   - limits: T <= 32, B <= 4096 per update, n_seen + B < 2^31; micro AP on the device while n_seen * N < 2^31 (beyond that the
+ *     workspace query returns 0: pass micro_ap_out = NULL and average on the host).
+ * The grow call copies a state into a larger block (new_capacity >= old_capacity) in stream order.  The average-precision call sorts
+ * the first n_seen keys of every class row IN PLACE (the state stays valid for further updates) and writes AP per class as fp64
+ * (NaN for a class without a positive; scikit-learn's step-wise definition, ties grouped); with micro_ap_out != NULL it also ranks the
+ * flattened store in `workspace`.  The read call copies counts [N][T][2], support [N] and row_stats [3] in stream order into device or
+ * pinned host memory: they are valid once `stream` has passed the call. */
+size_t vt_eval_state_bytes(int N, int T, long long capacity);
+int vt_eval_reset(vt_context* ctx, void* state, size_t state_bytes, int N, int T, const double* thresholds /* host [T] */, int t_main,
+                  long long capacity, void* stream);
+int vt_eval_update(vt_context* ctx, void* state, size_t state_bytes, int N, int T, int t_main, long long capacity,
+                   const float* probs /* [B][N] */, const void* labels /* [B][N] */, int labels_dtype /* VT_F32 | VT_U8 */, int B,
+                   long long n_seen /* samples of the earlier updates */, void* stream);
+int vt_eval_grow(vt_context* ctx, const void* old_state, size_t old_state_bytes, long long old_capacity, void* new_state,
+                 size_t new_state_bytes, long long new_capacity, int N, int T, long long n_seen, void* stream);
+size_t vt_eval_ap_workspace_bytes(int N, long long n_seen);
+int vt_eval_average_precision(vt_context* ctx, void* state, size_t state_bytes, int N, int T, long long capacity, long long n_seen,
+                              double* ap_out /* [N] */, size_t ap_bytes, double* micro_ap_out /* [1], may be NULL */, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int vt_eval_read_counts(vt_context* ctx, const void* state, size_t state_bytes, int N, int T, long long capacity, uint32_t* counts_out,
+                        size_t counts_bytes, uint32_t* support_out, size_t support_bytes, uint64_t* row_stats_out, size_t row_stats_bytes,
+                        void* stream);
 
 /* algorithmic FLOPs of one encoder forward at HxW -- for roofline reporting */
 double vt_encoder_flops(const vt_context* ctx, int H, int W);

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (VAE_TAGGER_HIP_LIB: an alternative build of the same library, for A/B runs of the test suite)
 LIB_PATH = os.environ.get("VAE_TAGGER_HIP_LIB") or os.path.join(_HERE, "csrc", "libvae_tagger_hip.so")
 
-VT_F32, VT_BF16, VT_F16 = 0, 1, 2
+VT_F32, VT_BF16, VT_F16, VT_U8 = 0, 1, 2, 3
 VT_STATUS_NONFINITE, VT_STATUS_FP8_SATURATED = 1, 2      # bits of vt_status (include/vae_tagger_hip.h)
 ENCODE_MOMENTS, ENCODE_MODE, ENCODE_MODE_SCALED = 0, 1, 2
 
@@ -42,6 +42,13 @@ PROTOTYPES = {
     "vt_resize_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "vt_resize_table": (_i, [_i, _i, _i, _c.POINTER(_i), _i]),
     "vt_resize_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "vt_eval_state_bytes": (_sz, [_i, _i, _ll]),
+    "vt_eval_reset": (_i, [_vp, _vp, _sz, _i, _i, _c.POINTER(_c.c_double), _i, _ll, _vp]),
+    "vt_eval_update": (_i, [_vp, _vp, _sz, _i, _i, _i, _ll, _vp, _vp, _i, _i, _ll, _vp]),
+    "vt_eval_grow": (_i, [_vp, _vp, _sz, _ll, _vp, _sz, _ll, _i, _i, _ll, _vp]),
+    "vt_eval_ap_workspace_bytes": (_sz, [_i, _ll]),
+    "vt_eval_average_precision": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "vt_eval_read_counts": (_i, [_vp, _vp, _sz, _i, _i, _ll, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "vt_encoder_flops": (_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),

@@ -12,6 +12,7 @@
 
 #include "../../include/vae_tagger_hip.h"
 #include "vt_decoder.h"
+#include "vt_eval.h"
 #include "vt_kernels.h"
 
 namespace {
@@ -1669,6 +1670,116 @@ int vt_status_async(vt_context* c, int clear, int* status_out, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     HIPCK(c, hipMemcpyAsync(status_out, c->status, sizeof(int), hipMemcpyDefault, s), "vt_status_async copy");
     if (clear) HIPCK(c, hipMemsetAsync(c->status, 0, sizeof(int), s), "vt_status_async clear");
+    return VT_OK;
+}
+
+// ---- streaming evaluator (eval_metrics.hip).  Every argument is checked on the host before anything is launched or written. ----
+namespace {
+bool eval_dims_ok(int N, int T, long long capacity) {
+    return N > 0 && T > 0 && T <= VT_EVAL_MAX_T && capacity >= 0 && capacity <= VT_EVAL_MAX_N_SEEN &&
+           (capacity == 0 || (unsigned long long)N * (unsigned long long)capacity < (1ull << 40));
+}
+bool misaligned(const void* p) { return ((uintptr_t)p & (ALIGN - 1)) != 0; }
+int eval_check_state(vt_context* c, const char* who, const void* state, size_t state_bytes, int N, int T, long long capacity) {
+    if (!eval_dims_ok(N, T, capacity)) return c->fail(VT_ERR_INVALID, "%s: bad dimensions (N = %d, T = %d of at most %d, capacity = %lld)", who, N, T, VT_EVAL_MAX_T, capacity);
+    if (!state || misaligned(state)) return c->fail(VT_ERR_INVALID, "%s: state is null or not 256-B aligned", who);
+    const size_t need = vt_eval_layout(N, T, capacity).total;
+    if (state_bytes < need) return c->fail(VT_ERR_WORKSPACE, "%s: state holds %zu bytes, %zu needed", who, state_bytes, need);
+    return VT_OK;
+}
+}  // namespace
+
+size_t vt_eval_state_bytes(int N, int T, long long capacity) {
+    return eval_dims_ok(N, T, capacity) ? vt_eval_layout(N, T, capacity).total : 0;
+}
+
+int vt_eval_reset(vt_context* c, void* state, size_t state_bytes, int N, int T, const double* thresholds, int t_main, long long capacity,
+                  void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = eval_check_state(c, "vt_eval_reset", state, state_bytes, N, T, capacity)) return r;
+    if (!thresholds || t_main < 0 || t_main >= T) return c->fail(VT_ERR_INVALID, "vt_eval_reset: null thresholds or t_main = %d outside [0, %d)", t_main, T);
+    EvalThresholds th;
+    for (int i = 0; i < VT_EVAL_MAX_T; ++i) th.v[i] = i < T ? thresholds[i] : INFINITY;
+    HIPCK(c, vt_eval_launch_reset(state, vt_eval_layout(N, T, capacity), th, (hipStream_t)stream), "eval_reset");
+    return VT_OK;
+}
+
+int vt_eval_update(vt_context* c, void* state, size_t state_bytes, int N, int T, int t_main, long long capacity, const float* probs,
+                   const void* labels, int labels_dtype, int B, long long n_seen, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = eval_check_state(c, "vt_eval_update", state, state_bytes, N, T, capacity)) return r;
+    if (t_main < 0 || t_main >= T) return c->fail(VT_ERR_INVALID, "vt_eval_update: t_main = %d outside [0, %d)", t_main, T);
+    if (!probs || !labels || (labels_dtype != VT_F32 && labels_dtype != VT_U8)) return c->fail(VT_ERR_INVALID, "vt_eval_update: null input or labels neither VT_F32 nor VT_U8");
+    if (B <= 0 || B > VT_EVAL_MAX_B || n_seen < 0 || n_seen + B > VT_EVAL_MAX_N_SEEN)
+        return c->fail(VT_ERR_INVALID, "vt_eval_update: B = %d outside [1, %d] or n_seen = %lld out of range", B, VT_EVAL_MAX_B, n_seen);
+    if (capacity > 0 && n_seen + B > capacity) return c->fail(VT_ERR_INVALID, "vt_eval_update: n_seen + B = %lld exceeds the capacity %lld", n_seen + B, capacity);
+    HIPCK(c, vt_eval_launch_update(state, vt_eval_layout(N, T, capacity), probs, labels, labels_dtype == VT_U8, B, N, T, t_main, capacity, n_seen,
+                                   (hipStream_t)stream), "eval_update");
+    return VT_OK;
+}
+
+int vt_eval_grow(vt_context* c, const void* old_state, size_t old_bytes, long long old_capacity, void* new_state, size_t new_bytes,
+                 long long new_capacity, int N, int T, long long n_seen, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = eval_check_state(c, "vt_eval_grow (old)", old_state, old_bytes, N, T, old_capacity)) return r;
+    if (int r = eval_check_state(c, "vt_eval_grow (new)", new_state, new_bytes, N, T, new_capacity)) return r;
+    if (old_capacity <= 0 || new_capacity < old_capacity || n_seen < 0 || n_seen > old_capacity || old_state == new_state)
+        return c->fail(VT_ERR_INVALID, "vt_eval_grow: capacities %lld -> %lld with n_seen = %lld", old_capacity, new_capacity, n_seen);
+    const EvalLayout lo = vt_eval_layout(N, T, old_capacity), ln = vt_eval_layout(N, T, new_capacity);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCK(c, hipMemcpyAsync(new_state, old_state, lo.head_bytes, hipMemcpyDeviceToDevice, s), "eval_grow head");
+    if (n_seen > 0)
+        HIPCK(c, hipMemcpy2DAsync((char*)new_state + ln.keys, (size_t)new_capacity * 8, (const char*)old_state + lo.keys, (size_t)old_capacity * 8,
+                                  (size_t)n_seen * 8, (size_t)N, hipMemcpyDeviceToDevice, s), "eval_grow keys");
+    return VT_OK;
+}
+
+size_t vt_eval_ap_workspace_bytes(int N, long long n_seen) {
+    if (N <= 0 || n_seen <= 0 || (unsigned long long)N * (unsigned long long)n_seen > (unsigned long long)VT_EVAL_MICRO_LIMIT) return 0;
+    return vt_eval_align((size_t)N * (size_t)n_seen * 8);
+}
+
+int vt_eval_average_precision(vt_context* c, void* state, size_t state_bytes, int N, int T, long long capacity, long long n_seen,
+                              double* ap_out, size_t ap_bytes, double* micro_ap_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = eval_check_state(c, "vt_eval_average_precision", state, state_bytes, N, T, capacity)) return r;
+    if (capacity <= 0) return c->fail(VT_ERR_STATE, "vt_eval_average_precision: the state keeps no keys (capacity 0)");
+    if (n_seen <= 0 || n_seen > capacity) return c->fail(VT_ERR_INVALID, "vt_eval_average_precision: n_seen = %lld outside [1, capacity = %lld]", n_seen, capacity);
+    if (!ap_out || ((uintptr_t)ap_out & 7)) return c->fail(VT_ERR_INVALID, "vt_eval_average_precision: ap_out is null or misaligned");
+    if (ap_bytes < (size_t)N * 8) return c->fail(VT_ERR_WORKSPACE, "vt_eval_average_precision: ap_out holds %zu bytes, %zu needed", ap_bytes, (size_t)N * 8);
+    if (micro_ap_out) {
+        const size_t need = vt_eval_ap_workspace_bytes(N, n_seen);
+        if (need == 0) return c->fail(VT_ERR_INVALID, "vt_eval_average_precision: micro AP runs on the device while n_seen * N < 2^31");
+        if ((uintptr_t)micro_ap_out & 7) return c->fail(VT_ERR_INVALID, "vt_eval_average_precision: micro_ap_out is misaligned");
+        if (!workspace || misaligned(workspace)) return c->fail(VT_ERR_INVALID, "vt_eval_average_precision: workspace is null or not 256-B aligned");
+        if (workspace_bytes < need) return c->fail(VT_ERR_WORKSPACE, "vt_eval_average_precision: workspace holds %zu bytes, %zu needed", workspace_bytes, need);
+    }
+    HIPCK(c, vt_eval_launch_ap(state, vt_eval_layout(N, T, capacity), N, capacity, n_seen, ap_out, micro_ap_out, (unsigned long long*)workspace,
+                               (hipStream_t)stream), "eval_average_precision");
+    return VT_OK;
+}
+
+int vt_eval_read_counts(vt_context* c, const void* state, size_t state_bytes, int N, int T, long long capacity, uint32_t* counts_out,
+                        size_t counts_bytes, uint32_t* support_out, size_t support_bytes, uint64_t* row_stats_out, size_t row_stats_bytes,
+                        void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = eval_check_state(c, "vt_eval_read_counts", state, state_bytes, N, T, capacity)) return r;
+    if (!counts_out || !support_out || !row_stats_out) return c->fail(VT_ERR_INVALID, "vt_eval_read_counts: null output");
+    const size_t nc = (size_t)N * T * 2 * 4, ns = (size_t)N * 4, nr = 3 * 8;
+    if (counts_bytes < nc || support_bytes < ns || row_stats_bytes < nr)
+        return c->fail(VT_ERR_WORKSPACE, "vt_eval_read_counts: outputs hold %zu / %zu / %zu bytes, %zu / %zu / %zu needed", counts_bytes, support_bytes,
+                       row_stats_bytes, nc, ns, nr);
+    const EvalLayout l = vt_eval_layout(N, T, capacity);
+    hipStream_t s = (hipStream_t)stream;
+    const char* st = (const char*)state;
+    HIPCK(c, hipMemcpyAsync(counts_out, st + l.counts, nc, hipMemcpyDefault, s), "eval_read counts");
+    HIPCK(c, hipMemcpyAsync(support_out, st + l.support, ns, hipMemcpyDefault, s), "eval_read support");
+    HIPCK(c, hipMemcpyAsync(row_stats_out, st + l.row_stats, nr, hipMemcpyDefault, s), "eval_read row_stats");
     return VT_OK;
 }
 

@@ -8,6 +8,7 @@
 //   get_confidence                    modules.py:470-475 -> sort (descending logit, ascending index on ties)
 #include "vt_common.h"
 #include "vt_decoder.h"
+#include "vt_sort_network.h"
 
 namespace {
 
@@ -340,24 +341,14 @@ __global__ void dec_add_kernel(float* __restrict__ a, const float* __restrict__ 
 // ---- get_confidence: descending sort of (logit, tag index) per image ------------------------------------------------
 // One 64-bit key per tag whose unsigned order IS the output order: high word = the logit mapped to a monotone unsigned
 // (NaN -> 1: after every real value, -inf included), low word = ~index (equal logits: ascending index).  Keys are unique, so
-// the order is strict and total.  The network is the single-direction ("flip") bitonic sort: stage k compares i with
-// i ^ (2k' - 1) first and then i ^ j for j = k'/2 .. 1, every exchange in the same direction, so tags beyond N are virtual
-// minimum keys that never move and N needs no power-of-two padding.  Up to SORT_CH tags the whole sort runs in LDS in one
-// launch; beyond that each 16384-block is sorted in LDS, the j > SORT_CH/2 steps of the later stages run as global-memory
-// passes over the key array (kept in the int64 index output) and each stage's tail runs in LDS again.
-constexpr int SORT_CH = 16384;
+// the order is strict and total.  The network itself (LDS passes up to SORT_CH keys, global-memory passes beyond; the key array
+// is kept in the int64 index output) is vt_sort_network.h, shared with the evaluator's per-class ranking (eval_metrics.hip).
+constexpr int SORT_CH = VT_SORT_CH;
 
 __device__ __forceinline__ unsigned long long sort_key(float f, int i) {
-    unsigned u = __float_as_uint(f);
-    if (u == 0x80000000u) u = 0u;                             // -0.0 ties with +0.0, as in a comparison sort
-    u = (f != f) ? 1u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-    return ((unsigned long long)u << 32) | (unsigned)(~i);
+    return ((unsigned long long)vt_sort_key_hi(f) << 32) | (unsigned)(~i);
 }
-__device__ __forceinline__ float sort_key_logit(unsigned long long k) {
-    const unsigned u = (unsigned)(k >> 32);
-    if (u == 1u) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
+__device__ __forceinline__ float sort_key_logit(unsigned long long k) { return vt_sort_key_score((unsigned)(k >> 32)); }
 
 // MODE 0: build the keys of block c from the logits and sort the block (stages k = 2 .. SORT_CH).
 // MODE 1: load the keys of block c and run the steps j = SORT_CH/2 .. 1 of a later stage.
@@ -378,24 +369,8 @@ __global__ __launch_bounds__(1024) void dec_sort_local_kernel(const float* __res
         key[i] = k;
     }
     __syncthreads();
-    auto step = [&](int j, bool flip, int kk) {
-        for (int i = threadIdx.x; i < np; i += 1024) {
-            const int l = flip ? (i ^ (kk - 1)) : (i ^ j);
-            if (l > i && l < n) {
-                const unsigned long long a = key[i], c = key[l];
-                if (a < c) { key[i] = c; key[l] = a; }       // descending
-            }
-        }
-        __syncthreads();
-    };
-    if (MODE == 0) {
-        for (int k = 2; k <= np; k <<= 1) {
-            step(0, true, k);
-            for (int j = k >> 2; j > 0; j >>= 1) step(j, false, 0);
-        }
-    } else {
-        for (int j = SORT_CH >> 1; j > 0; j >>= 1) step(j, false, 0);
-    }
+    if (MODE == 0) vt_sort_lds_full(key, n, np);
+    else vt_sort_lds_tail(key, n, np);
     for (int i = threadIdx.x; i < n; i += 1024) {
         const long long o = (long long)b * N + base + i;
         if (final) {
@@ -411,13 +386,7 @@ __global__ __launch_bounds__(1024) void dec_sort_local_kernel(const float* __res
 __global__ __launch_bounds__(256) void dec_sort_global_kernel(unsigned long long* __restrict__ keys, int N, int k, int j, int flip) {
     const int b = blockIdx.y;
     const int t = blockIdx.x * 256 + threadIdx.x;            // pair number
-    const int half = flip ? (k >> 1) : j;
-    const int i = ((t / half) * 2) * half + (t % half);      // lower element of pair t
-    const int l = flip ? (i ^ (k - 1)) : (i ^ j);
-    if (l >= N || i >= N) return;
-    unsigned long long* kb = keys + (long long)b * N;
-    const unsigned long long a = kb[i], c = kb[l];
-    if (a < c) { kb[i] = c; kb[l] = a; }
+    vt_sort_global_step<int>(keys + (long long)b * N, N, k, j, flip, t);
 }
 
 // ---- per-image summary of the sorted confidences (infer_full.py:106-125) on the device: the number of tags at or above the

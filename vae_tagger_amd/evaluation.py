@@ -155,8 +155,17 @@ def _probabilities(model, decoder, loader, device):
     return np.vstack(probs), np.vstack(labels)
 
 
-def evaluate_model(model, decoder, test_loader, class_names, device="cuda", threshold=0.5, output_dir=None):
+def evaluate_model(model, decoder, test_loader, class_names, device="cuda", threshold=0.5, output_dir=None, device_metrics=False):
+    """device_metrics=True: the probabilities never leave the GPU (DeviceMultiLabelEvaluator); same dict, prints and files."""
     model.eval(); decoder.eval()
+    if device_metrics:
+        ev = _device_pass(model, decoder, test_loader, class_names, device, threshold)
+        metrics = ev.compute_metrics()
+        ev.print_metrics(metrics)
+        if output_dir:
+            os.makedirs(output_dir, exist_ok=True)
+            ev.save_metrics(metrics, os.path.join(output_dir, "evaluation_results.csv"))
+        return metrics
     y_prob, y_true = _probabilities(model, decoder, test_loader, device)
     ev = MultiLabelEvaluator(class_names, device)
     ev.update((y_prob > threshold).astype(np.float32), y_true, y_prob)
@@ -168,9 +177,18 @@ def evaluate_model(model, decoder, test_loader, class_names, device="cuda", thre
     return metrics
 
 
-def find_optimal_threshold(model, decoder, val_loader, class_names, device="cuda", output_dir=None):
-    """Per-class and global (macro-F1) threshold search over 0.10, 0.15 ... 0.85, all classes at once per threshold."""
+def find_optimal_threshold(model, decoder, val_loader, class_names, device="cuda", output_dir=None, device_metrics=False):
+    """Per-class and global (macro-F1) threshold search over 0.10, 0.15 ... 0.85, all classes at once per threshold.
+    device_metrics=True: from the device evaluator's integer counts (counts only: no key store is kept)."""
     model.eval(); decoder.eval()
+    if device_metrics:
+        results = _device_pass(model, decoder, val_loader, class_names, device, 0.5, capacity=0).optimal_thresholds()
+        print(f"global threshold {results['global_threshold']:.3f} (macro F1 {results['global_f1']:.4f})")
+        if output_dir:
+            os.makedirs(output_dir, exist_ok=True)
+            with open(os.path.join(output_dir, "optimal_thresholds.json"), "w", encoding="utf-8") as fh:
+                json.dump(results, fh, indent=2, ensure_ascii=False)
+        return results
     y_prob, y_true = _probabilities(model, decoder, val_loader, device)
     y_true = y_true > 0
     thresholds = np.arange(0.1, 0.9, 0.05)
@@ -196,3 +214,279 @@ def find_optimal_threshold(model, decoder, val_loader, class_names, device="cuda
         with open(os.path.join(output_dir, "optimal_thresholds.json"), "w", encoding="utf-8") as fh:
             json.dump(results, fh, indent=2, ensure_ascii=False)
     return results
+
+
+# ---- device-side evaluator ---------------------------------------------------------------------------------------------------------
+# The state (integer confusion counts for every threshold, support, row statistics, one sort key per class and sample) lives in HBM and
+# is fed in stream order (vt_eval_update); nothing is read back per batch.  The host finishes in fp64 from the integers with the formulas
+# of MultiLabelEvaluator.compute_metrics / find_optimal_threshold above -- same integers in, same floats out.
+
+THRESHOLD_GRID = np.arange(0.1, 0.9, 0.05)       # find_optimal_threshold's grid
+
+
+def finish_from_counts(counts, support, row_stats, n, ap=None, micro_ap=None, t_main=0, class_names=None, search=None):
+    """Pure numpy: metrics from the evaluator's integers.  counts [c][T][2] = (tp, fp) per class and threshold, support [c],
+    row_stats = (exactly matching rows, mismatching elements, non-finite probabilities) at threshold index t_main, n samples,
+    ap [c] with nan for a class without a positive (None: the AP keys are left out), micro_ap a float.
+    Returns (metrics, optimal): `metrics` is MultiLabelEvaluator.compute_metrics' dict at threshold t_main; `optimal` is
+    find_optimal_threshold's dict over the (threshold value, index into T) pairs of `search`, or None without `search`."""
+    counts = np.asarray(counts)
+    c = counts.shape[0]
+    n = int(n)
+    if int(row_stats[2]) != 0:
+        raise FloatingPointError(f"{int(row_stats[2])} non-finite probabilities reached the evaluator")
+    support = np.asarray(support).astype(np.float64)
+    tp = counts[:, t_main, 0].astype(np.float64)
+    fp = counts[:, t_main, 1].astype(np.float64)
+    fn = support - tp
+    p, r, f = _prf(tp, fp, fn)
+    m = {"accuracy": float(int(row_stats[0]) / n), "hamming_loss": float(int(row_stats[1]) / (n * c))}
+    mp, mr, mf = _prf(tp.sum(), fp.sum(), fn.sum())
+    w = support / support.sum() if support.sum() > 0 else np.zeros(c)
+    for name, per, micro in (("precision", p, mp), ("recall", r, mr), ("f1", f, mf)):
+        m[f"{name}_micro"] = float(micro)
+        m[f"{name}_macro"] = float(per.mean())
+        m[f"{name}_weighted"] = float((per * w).sum())
+    if ap is not None:
+        ap = np.nan_to_num(np.asarray(ap, dtype=np.float64), nan=0.0)
+        m["mAP"] = float(ap.mean())
+        m["mAP_micro"] = float(np.nan_to_num(np.float64(micro_ap), nan=0.0))
+        m["mAP_weighted"] = float((ap * w).sum())
+    per_class = {}
+    for i in range(c):
+        name = class_names[i] if class_names else f"Class_{i}"
+        if support[i] == 0:
+            d = {"precision": 0.0, "recall": 0.0, "f1": 0.0, "ap": 0.0, "support": 0}
+        elif support[i] == n:                            # every sample positive: AP is 1 by convention
+            q = float((tp[i] + fp[i]) / n)
+            d = {"precision": q, "recall": 1.0, "f1": 2 * q / (1 + q) if q > 0 else 0.0, "ap": 1.0, "support": int(support[i])}
+        else:
+            d = {"precision": float(p[i]), "recall": float(r[i]), "f1": float(f[i]),
+                 "ap": float(ap[i]) if ap is not None else None, "support": int(support[i])}
+        if ap is None:
+            del d["ap"]
+        per_class[name] = d
+    m["per_class"] = per_class
+    optimal = None
+    if search is not None:
+        best_f, best_t = np.zeros(c), np.full(c, 0.5)
+        g_f, g_t = 0.0, 0.5
+        for t, k in search:
+            tp_t = counts[:, k, 0].astype(np.float64)
+            fp_t = counts[:, k, 1].astype(np.float64)
+            f_t = _prf(tp_t, fp_t, support - tp_t)[2]
+            better = (f_t > best_f) & (support > 0)
+            best_f[better], best_t[better] = f_t[better], t
+            if f_t.mean() > g_f:
+                g_f, g_t = float(f_t.mean()), float(t)
+        names = class_names if class_names else [f"Class_{i}" for i in range(c)]
+        optimal = {"global_threshold": g_t, "global_f1": g_f,
+                   "per_class_thresholds": {nm: {"threshold": float(best_t[i]), "f1_score": float(best_f[i])}
+                                            for i, nm in enumerate(names)}}
+    return m, optimal
+
+
+class DeviceMultiLabelEvaluator(MultiLabelEvaluator):
+    """MultiLabelEvaluator whose accumulation runs on the GPU (vt_eval_* of the C ABI).  `thresholds` is the search grid (default: the grid
+    of find_optimal_threshold, compared in fp64 as numpy compares a float32 array with a float64 scalar); `threshold` is the operating
+    point of compute_metrics (compared in fp32, as `y_prob > 0.5` is).  capacity: samples the key store holds -- None grows it
+    geometrically, 0 keeps counts only (no average precision)."""
+
+    def __init__(self, class_names, device="cuda", thresholds=None, threshold=0.5, capacity=None, context=None):
+        from . import _lib
+        self.class_names = list(class_names)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.VTError("DeviceMultiLabelEvaluator runs on a HIP device; MultiLabelEvaluator is the host evaluator")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        grid = THRESHOLD_GRID if thresholds is None else np.asarray(thresholds, dtype=np.float64)
+        self.grid = grid
+        self.threshold = threshold
+        self.thr = np.concatenate([grid, [np.float64(np.float32(threshold))]])
+        self.t_main = len(grid)
+        if len(self.thr) > 32:
+            raise ValueError("at most 31 search thresholds")
+        self.ctx = context if context is not None else _lib.Context(self.device.index)
+        self.N, self.T = len(self.class_names), len(self.thr)
+        self.auto_grow = capacity is None
+        self.capacity = 1024 if capacity is None else int(capacity)
+        self.reset_metrics()
+
+    def _stream(self):
+        import ctypes
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _alloc(self, capacity):
+        nbytes = self.ctx.lib.vt_eval_state_bytes(self.N, self.T, capacity)
+        if nbytes == 0:
+            raise ValueError(f"evaluator state of {self.N} classes x {self.T} thresholds x capacity {capacity} is not supported")
+        buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        return buf, (buf.data_ptr() + 255) // 256 * 256, nbytes
+
+    def reset_metrics(self):
+        import ctypes
+        self.n_seen = 0
+        self._buf, self._ptr, self._bytes = self._alloc(self.capacity)
+        thr = (ctypes.c_double * self.T)(*self.thr.tolist())
+        self.ctx.call("vt_eval_reset", ctypes.c_void_p(self._ptr), self._bytes, self.N, self.T, thr, self.t_main, self.capacity, self._stream())
+
+    def _grow(self, need):
+        import ctypes
+        cap = self.capacity
+        while cap < need:
+            cap *= 2
+        buf, ptr, nbytes = self._alloc(cap)
+        self.ctx.call("vt_eval_grow", ctypes.c_void_p(self._ptr), self._bytes, self.capacity, ctypes.c_void_p(ptr), nbytes, cap, self.N, self.T,
+                      self.n_seen, self._stream())
+        self._buf.record_stream(torch.cuda.current_stream(self.device))      # the old block is read by the copy just queued
+        self._buf, self._ptr, self._bytes, self.capacity = buf, ptr, nbytes, cap
+
+    def update(self, probabilities, targets):
+        """probabilities fp32 [B, N], targets [B, N] (positive: > 0); device tensors, or host tensors uploaded without blocking.
+        Queues work on the current stream and returns: no host synchronisation."""
+        import ctypes
+        from . import _lib
+        p = probabilities.detach()
+        if p.device != self.device:
+            p = p.to(self.device, non_blocking=True)
+        p = p.to(torch.float32).contiguous()
+        y = targets.detach() if isinstance(targets, torch.Tensor) else torch.as_tensor(np.asarray(targets))
+        if y.device != self.device:
+            y = y.to(self.device, non_blocking=True)
+        if y.dtype == torch.bool:
+            y = y.view(torch.uint8)
+        elif y.dtype not in (torch.float32, torch.uint8):
+            y = (y > 0).view(torch.uint8)
+        y = y.contiguous()
+        if p.dim() != 2 or p.shape[1] != self.N or y.shape != p.shape:
+            raise ValueError(f"expected [B, {self.N}] probabilities and targets, got {tuple(p.shape)} and {tuple(y.shape)}")
+        dt = _lib.VT_U8 if y.dtype == torch.uint8 else _lib.VT_F32
+        for lo in range(0, p.shape[0], 4096):
+            pb, yb = p[lo:lo + 4096], y[lo:lo + 4096]
+            B = pb.shape[0]
+            if self.capacity and self.n_seen + B > self.capacity:
+                if not self.auto_grow:
+                    raise ValueError(f"evaluator capacity {self.capacity} exceeded by sample {self.n_seen + B}")
+                self._grow(self.n_seen + B)
+            self.ctx.call("vt_eval_update", ctypes.c_void_p(self._ptr), self._bytes, self.N, self.T, self.t_main, self.capacity,
+                          ctypes.c_void_p(pb.data_ptr()), ctypes.c_void_p(yb.data_ptr()), dt, B, self.n_seen, self._stream())
+            self.n_seen += B
+
+    def read_state(self, with_ap=True):
+        """(counts [N][T][2], support [N], row_stats [3], ap [N] or None, micro_ap or None) on the host: the one synchronisation."""
+        import ctypes
+        if self.n_seen == 0:
+            raise ValueError("no data: call update() first")
+        counts = torch.empty(self.N, self.T, 2, dtype=torch.int32, pin_memory=True)
+        support = torch.empty(self.N, dtype=torch.int32, pin_memory=True)
+        row_stats = torch.empty(3, dtype=torch.int64, pin_memory=True)
+        s = self._stream()
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self.ctx.call("vt_eval_read_counts", ctypes.c_void_p(self._ptr), self._bytes, self.N, self.T, self.capacity, vp(counts),
+                      counts.numel() * 4, vp(support), support.numel() * 4, vp(row_stats), 24, s)
+        ap_host = micro = None
+        keys_host = None
+        if with_ap and self.capacity:
+            ws_bytes = self.ctx.lib.vt_eval_ap_workspace_bytes(self.N, self.n_seen)
+            ap = torch.empty(self.N + 1, dtype=torch.float64, device=self.device)
+            if ws_bytes:
+                ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=self.device)
+                wp = ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256)
+                mp = ctypes.c_void_p(ap.data_ptr() + 8 * self.N)
+            else:                                           # n * c >= 2^31: the store comes back once and the host routine ranks it
+                wp, mp = ctypes.c_void_p(0), ctypes.c_void_p(0)
+            self.ctx.call("vt_eval_average_precision", ctypes.c_void_p(self._ptr), self._bytes, self.N, self.T, self.capacity, self.n_seen,
+                          vp(ap), self.N * 8, mp, wp, ws_bytes, s)
+            ap_host = torch.empty(self.N + 1, dtype=torch.float64, pin_memory=True)
+            ap_host.copy_(ap, non_blocking=True)
+            if not ws_bytes:
+                head = self.ctx.lib.vt_eval_state_bytes(self.N, self.T, 0)
+                off = self._ptr - self._buf.data_ptr() + head
+                keys_host = self._buf[off:off + self.N * self.capacity * 8].view(torch.int64).view(self.N, self.capacity)[:, :self.n_seen].cpu()
+        torch.cuda.current_stream(self.device).synchronize()
+        if ap_host is not None:
+            a = ap_host.numpy()
+            ap_host, micro = a[:self.N].copy(), float(a[self.N])
+            if keys_host is not None:
+                micro = self._host_micro_ap(keys_host.numpy().view(np.uint64))
+        return (counts.numpy().view(np.uint32).copy(), support.numpy().view(np.uint32).copy(), row_stats.numpy().view(np.uint64).copy(),
+                ap_host, micro)
+
+    @staticmethod
+    def _host_micro_ap(keys):
+        hi = (keys >> np.uint64(32)).astype(np.uint32)
+        bits = np.where(hi & np.uint32(0x80000000), hi & np.uint32(0x7fffffff), ~hi)
+        prob = bits.view(np.float32).reshape(-1, 1)
+        return float(_average_precision((keys & np.uint64(1)).reshape(-1, 1) > 0, prob)[0])
+
+    def compute_metrics(self, threshold=None):
+        """MultiLabelEvaluator.compute_metrics' dict at the constructor's `threshold`.  Without a key store (capacity 0) the AP keys are
+        left out rather than invented."""
+        if threshold is not None and np.float32(threshold) != np.float32(self.threshold):
+            raise ValueError(f"the counts were taken at threshold {self.threshold}; pass threshold= to the constructor")
+        counts, support, row_stats, ap, micro = self.read_state()
+        if ap is None:
+            import warnings
+            warnings.warn("DeviceMultiLabelEvaluator(capacity=0) keeps no ranking: mAP, mAP_micro, mAP_weighted and the per-class ap are omitted")
+        return finish_from_counts(counts, support, row_stats, self.n_seen, ap, micro, self.t_main, self.class_names)[0]
+
+    def optimal_thresholds(self):
+        """find_optimal_threshold's dict over the search grid."""
+        counts, support, row_stats, _, _ = self.read_state(with_ap=False)
+        search = [(t, k) for k, t in enumerate(self.grid)]
+        return finish_from_counts(counts, support, row_stats, self.n_seen, None, None, self.t_main, self.class_names, search)[1]
+
+
+def _raise_on_word(st):
+    if st & 1:
+        raise FloatingPointError("non-finite activations in the encoder: the fp16 residual-stream storage overflowed "
+                                 "(vt_set_flag(ctx, 4, 0) stores it as fp32) or the checkpoint holds inf / NaN")
+    if st & 2:
+        raise FloatingPointError("fp8 mode: activations exceeded the e4m3 range and were clamped (vt_set_flag(ctx, 11, 0) returns to bf16)")
+
+
+def _device_pass(model, decoder, loader, class_names, device, threshold, capacity=None):
+    """encode -> decoder -> sigmoid -> DeviceMultiLabelEvaluator.update, batch after batch without a host synchronisation: the encoder's
+    health word is copied in stream order into pinned memory (vt_status_async) and looked at one batch late and at the end."""
+    import ctypes
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    vae = getattr(model, "vae", model)
+    ctx = vae._context() if hasattr(vae, "_context") else None
+    if capacity is None and hasattr(loader, "dataset"):
+        try:
+            capacity = len(loader.dataset)
+        except TypeError:
+            capacity = None
+    ev = DeviceMultiLabelEvaluator(class_names, dev, threshold=threshold, capacity=capacity, context=ctx)
+    had_check = getattr(model, "check_finite", None)
+    if had_check is not None:
+        model.check_finite = False
+    # two pinned words and their numpy views, made before the loop: batch n's word is looked at while batch n + 1 is queued
+    words = [torch.zeros(1, dtype=torch.int32, pin_memory=True) for _ in range(2)] if ctx is not None else []
+    views = [w.numpy() for w in words]
+    pending, i = None, 0
+    try:
+        with torch.no_grad():
+            for batch in loader:
+                lat = model.encode(batch["pixel_values"].to(dev, non_blocking=True))
+                ev.update(torch.sigmoid(decoder(lat)), batch["labels"])
+                if ctx is not None:
+                    stream = torch.cuda.current_stream(dev)
+                    ctx.call("vt_status_async", 1, ctypes.c_void_p(words[i & 1].data_ptr()), ctypes.c_void_p(stream.cuda_stream))
+                    done = torch.cuda.Event()
+                    done.record(stream)
+                    if pending is not None:                  # batch n - 1's word: its event passed while batch n was queued
+                        pending[1].synchronize()
+                        _raise_on_word(int(pending[0][0]))
+                    pending = (views[i & 1], done)
+                    i += 1
+            if pending is not None:
+                pending[1].synchronize()
+                _raise_on_word(int(pending[0][0]))
+    finally:
+        if had_check is not None:
+            model.check_finite = had_check
+    return ev
