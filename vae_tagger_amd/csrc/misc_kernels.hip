@@ -595,7 +595,7 @@ hipError_t vt_launch_softmax_rows(const void* scores, int scores_f16, bf16_t* pr
                       : softmax_dispatch((const float*)scores, probs, rows, n, lds, ldp, s);
 }
 
-// ---- attention without a softmax pass (capi.hip run_attention) -------------------------------------------------------------
+// ---- attention without a softmax pass (attention.hip run_attention) -------------------------------------------------------------
 // softmax(s)_ij = exp(s_ij - c_i) / sum_j exp(s_ij - c_i) for ANY per-row c_i, so the Q.K^T epilogue can emit the
 // numerators directly once a c_i is known that keeps them inside the float range.  From the operands alone:
 // s_ij <= |q_i| max_j|k_j| alpha =: u_i (Cauchy-Schwarz) and max_j s_ij >= s_ii =: l_i (self-attention: the diagonal exists).

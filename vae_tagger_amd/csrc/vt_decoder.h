@@ -1,4 +1,4 @@
-// Decoder weight table (device fp32 pointers) + launch entry points, shared by decoder.hip and capi.hip.
+// Decoder weight table (device fp32 pointers) + launch entry points, shared by decoder.hip and the host side (vt_context.h, capi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,4 +1,4 @@
-// Internal launcher interface between the kernel translation units and the C-ABI (capi.hip).
+// Internal launcher interface between the kernel translation units and the host units behind the C ABI (weights.hip, encoder.hip, attention.hip, ops.hip, capi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vt_common.h"
@@ -27,7 +27,7 @@ struct ConvGemmArgs {
     int cout_keep;
     float post_scale, post_shift;
     int gn_cpg;             // channels per group for gn_partial (0 = off)
-    // row softmax pieces of the attention (capi.hip run_attention).  A (row, column slot) is one wave's 16*TC columns of a row:
+    // row softmax pieces of the attention (attention.hip run_attention).  A (row, column slot) is one wave's 16*TC columns of a row:
     // slot = column tile * WC + wave column, vt_conv_gemm_col_slots(a) of them.
     int row_mode;           // 0 off; 1 = no output, row_part = max over the slot of alpha*acc (columns >= Wrows excluded);
                             // 2 = the output is exp(alpha*acc - row_in[p]) (columns >= Wrows: 0), row_part = the slot's sum
@@ -334,4 +334,4 @@ hipError_t vt_launch_softmax_rows(const void* scores, int scores_f16, bf16_t* pr
                                   int ldp, hipStream_t s);
 
 // decoder (all fp32)
-struct DecoderWeights;   // defined in capi.hip
+struct DecoderWeights;   // defined in vt_decoder.h
