@@ -113,6 +113,24 @@ int vt_resize_table(int in_size, int out_size, int filter, int* table_out, int t
 int vt_resize_u8(vt_context* ctx, const uint8_t* src_hwc, int src_h, int src_w, int crop_left, int crop_top, int crop_w, int crop_h,
                  uint8_t* dst_hwc, int dst_h, int dst_w, int filter, void* workspace, size_t workspace_bytes, void* stream);
 
+/* vt_resize_normalize_batch: vt_resize_u8 + vt_preprocess_u8 for a whole batch in one call.  B source images (device, uint8 HWC
+ * RGB) of DIFFERENT sizes, each with its own crop box, are resized to one common dst_h x dst_w and written as the encoder's input:
+ *   out_u8_hwc[k] == vt_resize_u8 of item k, byte for byte (a pass is skipped when that axis keeps its size, as in Pillow);
+ *   out_nchw      == vt_preprocess_u8(out_u8_hwc), bit for bit.
+ * Either output may be NULL (not both); the uint8 batch image is not written unless asked for.  Two launches per call whatever B
+ * is: descriptors and per-image coefficient tables live in the workspace and the grid's z index selects the image.  The tables are
+ * built on the host (and remembered per (size, size, filter)) and staged through a small ring of pinned blocks owned by the context:
+ * the call does not wait for the GPU unless the ring has wrapped onto a block whose copy is still in flight.
+ * `items` is a HOST array.  Every size is checked before anything is launched: an undersized output or workspace gives
+ * VT_ERR_WORKSPACE, a NULL pointer, a crop box outside its source or an unsupported size VT_ERR_INVALID, and nothing is written.
+ * vt_resize_batch_workspace_bytes returns 0 for arguments the call would reject as invalid (source pointers are not looked at). */
+typedef struct { const uint8_t* src_hwc; int src_h, src_w, crop_left, crop_top, crop_w, crop_h; } vt_resize_item;
+size_t vt_resize_batch_workspace_bytes(const vt_resize_item* items /* host [B] */, int B, int dst_h, int dst_w, int filter);
+int vt_resize_normalize_batch(vt_context* ctx, const vt_resize_item* items /* host [B] */, int B, int dst_h, int dst_w, int filter,
+                              float* out_nchw /* [B,3,dst_h,dst_w], may be NULL */, size_t out_nchw_bytes,
+                              uint8_t* out_u8_hwc /* [B,dst_h,dst_w,3], may be NULL */, size_t out_u8_bytes,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- streaming multi-label evaluator <- MultiLabelEvaluator.compute_metrics / find_optimal_threshold, evaluation.py:13-275, without the
  * n x c host matrix: the state lives in ONE caller-owned device block and is fed batch by batch in stream order; no call below
  * synchronises the host.  The state remembers nothing about its own shape: every call takes (N classes, T thresholds, capacity)

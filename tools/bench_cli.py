@@ -6,7 +6,14 @@ encode + tag -> JSON, against the HBM-resident number bench.py reports for the s
 N synthetic 1024 x 1024 pictures (smooth fields + noise; 32 distinct ones, repeated under different names) are written to a temporary
 directory once as PNG and once as JPEG (quality 90); vae_tagger_amd.infer_full.main() runs over each directory (a short warm-up run first:
 code objects, allocator, clocks), and the loop's own wall time gives images/s.  Then the same pipeline object shape runs 10 HBM-resident
-steps (what bench.py times) for the comparison."""
+steps (what bench.py times) for the comparison.
+
+    python tools/bench_cli.py --bucketed [--n 512] [--batch 16] [--tags 10000] [--host_resize] [--host_metrics]
+
+The bucketed mode times vae_tagger_amd.evaluate.main() with --use_bucketing (512 / 1024 / 64, one pass: --threshold 0.5) over N labelled
+files of mixed aspect ratio (half PNG, half JPEG), and then replays the SAME sequence of batch shapes from HBM-resident tensors through the
+same encode -> decoder -> sigmoid -> evaluator-update loop: the ratio of the two is what the input side (decode threads, PCIe, the
+side stream's resize) costs."""
 import argparse, json, os, shutil, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import contextlib
@@ -29,10 +36,90 @@ ap.add_argument("--confidence_threshold", type=float, default=0.75,
 ap.add_argument("--host_resize", action="store_true")
 ap.add_argument("--serial", action="store_true")
 ap.add_argument("--src_res", type=int, default=0, help="size of the files' pictures (default: --res, i.e. no resize needed; e.g. 1536 exercises the device resize)")
+ap.add_argument("--bucketed", action="store_true", help="time the evaluate CLI with --use_bucketing instead of infer_full")
+ap.add_argument("--host_metrics", action="store_true", help="(--bucketed) the evaluate CLI's host evaluator")
 a = ap.parse_args()
+
+BUCKETED_SIZES = [(1024, 1024), (1216, 832), (832, 1216), (1344, 768), (768, 1344), (1536, 1024), (1000, 1500), (1152, 896), (1600, 1200),
+                  (900, 1200), (2048, 1024), (1024, 2048), (1280, 1280), (1100, 1000), (1920, 1080), (1080, 1920)]     # (w, h) of the files
+
+
+def bucketed_mode(tmp):
+    from vae_tagger_amd import evaluate
+    from vae_tagger_amd.evaluation import DeviceMultiLabelEvaluator
+    rng = np.random.default_rng(0)
+    t0 = time.perf_counter()
+    os.makedirs(os.path.join(tmp, "imgs"))
+    base = []
+    for i, (w, h) in enumerate(BUCKETED_SIZES * 2):
+        low = rng.random((12, 12, 3)).astype(np.float32)
+        img = np.asarray(Image.fromarray((low * 255).astype(np.uint8)).resize((w, h), Image.BICUBIC), dtype=np.float32) / 255.0
+        img = np.clip(img + 0.04 * rng.standard_normal((h, w, 3)).astype(np.float32), 0, 1)
+        fmt, kw = ("png", {}) if i % 2 else ("jpg", {"quality": 90})
+        path = os.path.join(tmp, "imgs", f"base{i:03d}.{fmt}")
+        Image.fromarray((img * 255).astype(np.uint8)).save(path, **kw)
+        base.append(path)
+    order = rng.permutation(a.n)                                       # (the buckets arrive interleaved, as in a real list)
+    data = {}
+    for k in order:
+        src = base[int(k) % len(base)]
+        path = os.path.join(tmp, "imgs", f"img{int(k):05d}{os.path.splitext(src)[1]}")
+        shutil.copyfile(src, path)
+        data[path] = ", ".join(f"tag_{int(t):05d}:{0.5 + 0.5 * (int(t) % 2)}" for t in rng.choice(a.tags, size=8, replace=False))
+    with open(os.path.join(tmp, "data.json"), "w") as f:
+        json.dump(data, f)
+    warm = dict(list(data.items())[: 3 * a.batch])
+    with open(os.path.join(tmp, "warm.json"), "w") as f:
+        json.dump(warm, f)
+    print(f"wrote {a.n} files of {len(BUCKETED_SIZES)} sizes in {time.perf_counter() - t0:.1f} s", flush=True)
+    save_file(synth.synth_state_dict(synth.encoder_manifest(), seed=0), os.path.join(tmp, "vae.safetensors"))
+    torch.save(synth.synth_state_dict(synth.attention_decoder_manifest(a.tags), seed=1), os.path.join(tmp, "dec.pth"))
+    with open(os.path.join(tmp, "tags.csv"), "w") as f:
+        f.write("name\n" + "\n".join(f"tag_{i:05d}" for i in range(a.tags)) + "\n")
+    common = ["--vae_checkpoint", os.path.join(tmp, "vae.safetensors"), "--decoder_checkpoint", os.path.join(tmp, "dec.pth"), "--tags_csv_path",
+              os.path.join(tmp, "tags.csv"), "--use_bucketing", "--batch_size", str(a.batch), "--workers", str(a.workers), "--threshold", "0.5",
+              "--output_dir", os.path.join(tmp, "out")]
+    common += (["--fp8"] if a.fp8 else []) + (["--host_resize"] if a.host_resize else []) + (["--host_metrics"] if a.host_metrics else [])
+    with contextlib.redirect_stdout(sys.stderr):
+        evaluate.main(common + ["--json_path", os.path.join(tmp, "warm.json")])
+        evaluate.main(common + ["--json_path", os.path.join(tmp, "data.json")])
+    st = dict(evaluate.LAST_RUN_STATS)
+    shapes = [s for _, s in st["batches"]]
+    cli = st["images"] / st["loop_seconds"]
+    # the same sequence of batch shapes, HBM-resident, through the same device loop
+    args = evaluate.build_parser().parse_args(common + ["--json_path", os.path.join(tmp, "data.json")])
+    with contextlib.redirect_stdout(sys.stderr):
+        vm, dec, tags = infer_full.load_models(args, torch.device("cuda", torch.cuda.current_device()))
+    vm.check_finite = False
+    if a.fp8: vm.vae._context().call("vt_set_flag", 11, 1)
+    xs = {s: synth.synth_images(s[0], s[2], s[3], seed=s[2] + s[3]).cuda() for s in set(shapes)}
+    ys = {b: (torch.rand(b, a.tags) > 0.999).float().cuda() for b in {s[0] for s in shapes}}
+
+    def replay():
+        ev = DeviceMultiLabelEvaluator(tags, "cuda", threshold=0.5, capacity=sum(s[0] for s in shapes), context=vm.vae._context())
+        for s in shapes:
+            ev.update(torch.sigmoid(dec(vm.encode(xs[s]))), ys[s[0]])
+        torch.cuda.synchronize()
+    replay()
+    t0 = time.perf_counter()
+    replay()
+    resident = sum(s[0] for s in shapes) / (time.perf_counter() - t0)
+    hist = {}
+    for s in shapes:
+        hist[f"{s[3]}x{s[2]}"] = hist.get(f"{s[3]}x{s[2]}", 0) + s[0]
+    print(json.dumps({"workload": f"evaluate CLI, --use_bucketing 512/1024/64, {a.n} files (png + jpg) of {len(BUCKETED_SIZES)} sizes, batch {a.batch}, "
+                                  f"{a.tags} tags, {'fp8' if a.fp8 else 'bf16'}{', host resize' if a.host_resize else ''}"
+                                  f"{', host metrics' if a.host_metrics else ''}, one pass (--threshold)",
+                      "cores_available": len(os.sched_getaffinity(0)), "batches": len(shapes), "short_batches": sum(1 for s in shapes if s[0] < a.batch),
+                      "images_per_bucket": hist, "cli_images_per_sec": round(cli, 1), "hbm_resident_images_per_sec_same_batches": round(resident, 1),
+                      "cli_fraction_of_resident": round(cli / resident, 3)}), flush=True)
+
 
 tmp = tempfile.mkdtemp(prefix="vt_bench_cli_")
 try:
+    if a.bucketed:
+        bucketed_mode(tmp)
+        sys.exit(0)
     rng = np.random.default_rng(0)
     src = a.src_res or a.res
     t0 = time.perf_counter()

@@ -17,6 +17,12 @@ ENCODE_MOMENTS, ENCODE_MODE, ENCODE_MODE_SCALED = 0, 1, 2
 _c = ctypes
 _vp, _i, _f, _sz, _ll = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t, _c.c_longlong
 
+
+class ResizeItem(_c.Structure):
+    """vt_resize_item: one source image (device uint8 HWC) and its crop box."""
+    _fields_ = [("src_hwc", _vp), ("src_h", _i), ("src_w", _i), ("crop_left", _i), ("crop_top", _i), ("crop_w", _i), ("crop_h", _i)]
+
+
 # name -> (restype, argtypes); every symbol include/vae_tagger_hip.h declares
 PROTOTYPES = {
     "vt_version": (_c.c_char_p, []),
@@ -42,6 +48,8 @@ PROTOTYPES = {
     "vt_resize_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "vt_resize_table": (_i, [_i, _i, _i, _c.POINTER(_i), _i]),
     "vt_resize_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "vt_resize_batch_workspace_bytes": (_sz, [_c.POINTER(ResizeItem), _i, _i, _i, _i]),
+    "vt_resize_normalize_batch": (_i, [_vp, _c.POINTER(ResizeItem), _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "vt_eval_state_bytes": (_sz, [_i, _i, _ll]),
     "vt_eval_reset": (_i, [_vp, _vp, _sz, _i, _i, _c.POINTER(_c.c_double), _i, _ll, _vp]),
     "vt_eval_update": (_i, [_vp, _vp, _sz, _i, _i, _i, _ll, _vp, _vp, _i, _i, _ll, _vp]),

@@ -55,6 +55,7 @@ void vt_destroy(vt_context* c) {
         if (c->op_scratch) (void)hipFree(c->op_scratch);
         if (c->rs_host) (void)hipHostFree(c->rs_host);
         if (c->rs_event) (void)hipEventDestroy(c->rs_event);
+        for (auto& sl : c->rs_ring) { if (sl.host) (void)hipHostFree(sl.host); if (sl.ev) (void)hipEventDestroy(sl.ev); }
         c->free_allocs(c->enc_allocs);
         c->free_allocs(c->dec_allocs);
         if (c->zeros) (void)hipFree(c->zeros);
@@ -412,6 +413,9 @@ double rs_filter(int kind, double x) {
     }
     return 0.0;
 }
+}  // namespace
+extern "C++" {
+namespace vt {
 int rs_ksize(int in_size, int out_size, int kind) {
     double fs = (double)in_size / out_size;
     if (fs < 1.0) fs = 1.0;
@@ -442,6 +446,9 @@ void rs_table(int in_size, int out_size, int kind, int* tab) {
         }
     }
 }
+}  // namespace vt
+}  // extern "C++"
+namespace {
 struct RsPlan { int kh, kv; size_t tab_h, tab_v, tmp, total; };   // table sizes in ints, tmp / total in bytes
 RsPlan rs_plan(int crop_h, int crop_w, int dst_h, int dst_w, int kind) {
     RsPlan p{};

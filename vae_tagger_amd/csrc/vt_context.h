@@ -5,6 +5,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <array>
 #include <map>
 #include <string>
 #include <vector>
@@ -105,6 +106,13 @@ struct vt_context {
     int s2_halo = 1;                // vt_set_flag(ctx, 13, v): stride-2 convs on the phase-plane halo kernel instead of the generic GEMM
     // vt_resize_u8: pinned staging of the coefficient tables + the event of the last H2D copy that read it
     int* rs_host = nullptr; size_t rs_host_ints = 0; hipEvent_t rs_event = nullptr;
+    // vt_resize_normalize_batch: a ring of pinned blocks (descriptors + coefficient tables of one call each), the event of the H2D copy that
+    // last read each, and the host tables already built, keyed (in size, out size, filter, transposed)
+    struct RsRingSlot { void* host = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool used = false; };
+    static constexpr int RS_RING = 4;
+    RsRingSlot rs_ring[RS_RING];
+    unsigned rs_ring_next = 0;
+    std::map<std::array<int, 4>, std::vector<int>> rs_tables;
     int conv_in_mfma = 1;           // vt_set_flag(ctx, 5, v): conv_in on the matrix cores (bf16 im2col), else exact fp32 VALU
     void* op_scratch = nullptr; size_t op_scratch_bytes = 0;
 
@@ -191,6 +199,10 @@ struct ConvE4m3 {
     std::vector<uint8_t> wp8s2;                               // conv3x3_s2_halo_fp8.hip's packing (scales: mult8g); only when asked for
 };
 ConvE4m3 pack_conv_e4m3(const float* w_oihw, int cout, int cin, bool s2_layout);
+
+// ---- capi.hip (Pillow's resample tables, shared with resize_batch.hip) ----------------------------
+int rs_ksize(int in_size, int out_size, int kind);
+void rs_table(int in_size, int out_size, int kind, int* tab);     // tab[out_size][2 + ksize] = (first, count, coefficients...)
 
 // ---- capi.hip (diagnostics) -----------------------------------------------------------------------
 void dbg_sum(vt_context* c, const void* p, size_t bytes, hipStream_t s);

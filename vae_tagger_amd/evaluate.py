@@ -1,0 +1,167 @@
+"""Dataset evaluation CLI: what the reference's train_decoder.py runs after training (train_decoder.py:266-278) --
+`find_optimal_threshold` over the labelled set, then `evaluate_model` at the global threshold -- as a command of its own, fed by the
+pipelined loader of prefetch.py instead of a torch DataLoader over PIL transforms.
+
+    python -m vae_tagger_amd.evaluate --vae_checkpoint ae.safetensors --decoder_checkpoint dec.pth --json_path data.json \
+        --tags_csv_path tags.csv --use_bucketing [--base_resolution 512 --max_resolution 1024 --bucket_step 64] [--batch_size 8]
+
+Writes `optimal_thresholds.json`, `evaluation_results.csv` and `evaluation_results_overall.json` into --output_dir, as the reference
+does.  With --use_bucketing every image is centre-cropped to the aspect-ratio bucket of its own size and LANCZOS-resized (the
+reference's SmartResize; on the GPU, Pillow's arithmetic bit for bit) and batches are formed per bucket; without it every image is
+squashed to --resolution squared, as the inference CLIs do.  The data set is read TWICE unless --threshold is given: once for the
+threshold search and once for the metrics at the threshold it found (the exact-match and Hamming counts exist for one operating
+point per pass).  Metrics are accumulated on the GPU (DeviceMultiLabelEvaluator); --host_metrics is the host evaluator, same files.
+Single process only.  Reference: modules.py:487-548 (the JSON format), evaluation.py:173-275, train_decoder.py:284-333 (flags).
+"""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+
+class TaggedImageList:
+    """The reference's training JSON, `{image path: "tag:weight, tag:weight"}`, against the tag vocabulary of a CSV's `name` column
+    (what TaggedImageDataset.__init__ reads): `labels[path]` is an fp32 row holding each known tag's weight (1.0 when the entry has
+    no weight or one that does not parse; an unknown tag is ignored; a repeated tag keeps its last weight).  Paths whose file does
+    not exist are listed in `missing` and left out of `image_paths` (the reference fails on them when the image is opened)."""
+
+    def __init__(self, json_path, tags_csv_path, check_files=True):
+        import pandas as pd
+        with open(json_path, "r", encoding="utf-8") as fh:
+            data = json.load(fh)
+        self.tags = [str(t) for t in pd.read_csv(tags_csv_path)["name"]]
+        self.tag_to_idx = {t: i for i, t in enumerate(self.tags)}
+        self.labels, self.image_paths, self.missing = {}, [], []
+        for path, prompt in data.items():
+            if check_files and not os.path.isfile(path):
+                self.missing.append(path)
+                continue
+            self.image_paths.append(path)
+            self.labels[path] = self.parse_prompt(prompt)
+
+    def parse_prompt(self, prompt):
+        row = np.zeros(len(self.tags), dtype=np.float32)
+        # (a prompt without a comma is one entry, with or without a weight: the same rule as for each entry of a list)
+        for entry in str(prompt).split(","):
+            tag, sep, weight = entry.strip().partition(":")
+            value = 1.0
+            if sep:
+                try:
+                    value = float(weight.strip())
+                except ValueError:
+                    value = 1.0
+            k = self.tag_to_idx.get(tag.strip())
+            if k is not None:
+                row[k] = value
+        return row
+
+    def __len__(self):
+        return len(self.image_paths)
+
+
+def build_loader(args, pipe, data):
+    from .modules import AspectRatioBucketing, get_image_transform
+    from .prefetch import FeederLoader
+    bucketing = AspectRatioBucketing(args.base_resolution, args.max_resolution, args.bucket_step) if args.use_bucketing else None
+    return FeederLoader(pipe, data.image_paths, data.labels, args.batch_size, args.resolution, workers=args.workers or None,
+                        host_resize=args.host_resize, transform=get_image_transform(args.resolution), bucketing=bucketing,
+                        max_pending=args.max_pending or None)
+
+
+LAST_RUN_STATS = {}    # seconds spent in the passes over the data and the images they covered (tools/bench_cli.py reads it)
+
+
+def evaluate(args):
+    import time
+    from .evaluation import evaluate_model, find_optimal_threshold
+    from .infer_full import load_models
+    from .pipeline import EncodeTagPipeline
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("vae_tagger_amd.evaluate runs in a single process: the metrics are accumulated on one GPU "
+                           "(start it without torchrun / with WORLD_SIZE=1)")
+    if not torch.cuda.is_available():
+        raise RuntimeError("vae_tagger_amd needs an MI355X (no HIP device visible; there is no CPU fallback)")
+    device = torch.device("cuda", torch.cuda.current_device())
+    vae_model, decoder, tag_names = load_models(args, device)
+    data = TaggedImageList(args.json_path, args.tags_csv_path)
+    for p in data.missing:
+        print(f"跳过图像 {p}，错误原因: 文件不存在")
+    if not data.image_paths:
+        raise RuntimeError(f"{args.json_path} 中没有可用的图像")
+    if args.fp8:
+        vae_model.vae._context().call("vt_set_flag", 11, 1)
+    elif args.fp16_operands:
+        vae_model.vae.set_fp16_operands(True)
+    pipe = EncodeTagPipeline.input_side(vae_model)
+    loader = build_loader(args, pipe, data)
+    device_metrics = not args.host_metrics
+    os.makedirs(args.output_dir, exist_ok=True)
+    t0 = time.perf_counter()
+    passes = 0
+    if args.threshold is None:
+        print("寻找最优分类阈值...")
+        optimal = find_optimal_threshold(vae_model, decoder, loader, tag_names, device, args.output_dir, device_metrics=device_metrics)
+        threshold = optimal["global_threshold"]
+        passes += 1
+    else:
+        optimal, threshold = None, float(args.threshold)
+    print("使用最优阈值进行最终评估...")
+    metrics = evaluate_model(vae_model, decoder, loader, tag_names, device, threshold, args.output_dir, device_metrics=device_metrics)
+    passes += 1
+    torch.cuda.synchronize()
+    LAST_RUN_STATS.update(loop_seconds=time.perf_counter() - t0, images=sum(len(n) for n, _ in loader.batches), passes=passes,
+                          batches=list(loader.batches))
+    for p, e in loader.failed:
+        print(f"跳过图像 {p}，错误原因: {e}")
+    print(f"评估完成！图像: {LAST_RUN_STATS['images']}, 跳过: {len(loader.failed) + len(data.missing)}, 阈值: {threshold:.3f}")
+    return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": len(loader.failed) + len(data.missing)}
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="在带标签的数据集上评估VAE + 分类解码器 (阈值搜索 + 多标签指标)。")
+    p.add_argument("--vae_checkpoint", type=str, required=True, help="预训练VAE模型文件路径 (.safetensors)")
+    p.add_argument("--vae_config_path", type=str, default=None, help="VAE配置文件路径 (JSON格式)")
+    p.add_argument("--decoder_checkpoint", type=str, required=True, help="Decoder模型文件路径 (.bin/.pth)")
+    p.add_argument("--json_path", type=str, required=True, help='{image path: "tag:weight, tag:weight"}')
+    p.add_argument("--tags_csv_path", type=str, required=True, help="包含所有分类头的CSV文件")
+    p.add_argument("--output_dir", type=str, default="decoder_output")
+    p.add_argument("--resolution", type=int, default=1024)
+    p.add_argument("--use_attention", action="store_true", default=True, help="启用注意力机制 (默认开启)")
+    p.add_argument("--no_attention", action="store_true", help="禁用注意力机制")
+    p.add_argument("--use_spatial_attention", action="store_true", default=True, help="启用空间注意力")
+    p.add_argument("--use_self_attention", action="store_true", default=True, help="启用自注意力")
+    p.add_argument("--use_cross_attention", action="store_true", help="启用交叉注意力")
+    p.add_argument("--attention_heads", type=int, default=8, help="注意力头数")
+    p.add_argument("--attention_dropout", type=float, default=0.1, help="注意力dropout率")
+    p.add_argument("--use_bucketing", action="store_true", help="启用长宽比分桶功能")
+    p.add_argument("--base_resolution", type=int, default=512, help="分桶的基础分辨率")
+    p.add_argument("--max_resolution", type=int, default=1024, help="分桶的最大分辨率")
+    p.add_argument("--bucket_step", type=int, default=64, help="分桶的步长")
+    p.add_argument("--batch_size", type=int, default=8, help="images per device batch (one bucket per batch with --use_bucketing)")
+    p.add_argument("--workers", type=int, default=0, help="image decode threads (0 = min(16, cores))")
+    p.add_argument("--max_pending", type=int, default=0,
+                   help="with --use_bucketing: images that may wait in partly filled buckets before the fullest one is sent short "
+                        "(0 = 4 x batch_size)")
+    p.add_argument("--host_resize", action="store_true",
+                   help="the reference's own input route: PIL transforms on the CPU, fp32 tensors over PCIe (same files, slower)")
+    p.add_argument("--fp16_operands", action="store_true", help="fp16 instead of bf16 MFMA operands for the convolutions")
+    p.add_argument("--fp8", action="store_true", help="3x3 convs of the encoder on fp8 (e4m3) operands")
+    p.add_argument("--host_metrics", action="store_true",
+                   help="accumulate the metrics on the host (the probabilities of every batch are copied back) instead of on the GPU")
+    p.add_argument("--threshold", type=float, default=None,
+                   help="skip the threshold search and evaluate at this threshold: ONE pass over the images instead of two "
+                        "(search pass + metrics pass at the threshold found)")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.no_attention:
+        args.use_attention = False
+    return evaluate(args)
+
+
+if __name__ == "__main__":
+    main()

@@ -37,6 +37,19 @@ class EncodeTagPipeline:
         self.latent_channels = vae.config.latent_channels
         self._nd = len(vae.config.block_out_channels) - 1
 
+    @classmethod
+    def input_side(cls, vae_model):
+        """The input-side methods only (load_batch, load_image, resize_u8, normalize_u8) on the context the encoder already owns: for
+        callers that run `model.encode` / `decoder(...)` themselves (evaluation.py) and need no second copy of the weights."""
+        vae = vae_model.vae if isinstance(vae_model, DiffusersVAEWrapper) else vae_model
+        if not isinstance(vae, AutoencoderKL):
+            raise TypeError("EncodeTagPipeline.input_side needs vae_tagger_amd's AutoencoderKL (or its wrapper)")
+        self = cls.__new__(cls)
+        self.vae, self.decoder = vae, None
+        self.ctx = vae._context()                  # (raises unless the model is on a HIP device)
+        self.device = next(vae.parameters()).device
+        return self
+
     def flops_per_image(self, H, W):
         return self.ctx.lib.vt_encoder_flops(self.ctx.handle, H, W)
 
@@ -182,6 +195,40 @@ class EncodeTagPipeline:
         self.ctx.call("vt_resize_u8", vp(src), H, W, left, top, cw, ch, vp(out), out_h, out_w, filt, ctypes.c_void_p(ptr), need,
                       stream_ptr(self.device))
         return out
+
+    @torch.no_grad()
+    def load_batch(self, raw_images, bucket=None, resolution=None, return_u8=False, tag="resize_batch"):
+        """The batch counterpart of `load_image`, in ONE C call (vt_resize_normalize_batch: two launches whatever the batch size):
+        `raw_images` are contiguous uint8 [h,w,3] DEVICE tensors of any sizes -> fp32 [B,3,H,W] in [-1,1] on the current stream.
+        bucket = (tw, th): SmartResize's centre crop (`smart_crop_box`) + LANCZOS to th x tw; otherwise the distorting bilinear
+        `Resize((resolution, resolution))`.  return_u8: also the uint8 [B,H,W,3] batch Pillow would have produced (tests, tools)."""
+        if not raw_images:
+            raise ValueError("load_batch: empty batch")
+        if bucket is not None:
+            tw, th = int(bucket[0]), int(bucket[1])
+            filt = self.FILTER_LANCZOS
+        elif resolution is not None:
+            tw = th = int(resolution)
+            filt = self.FILTER_BILINEAR
+        else:
+            raise ValueError("load_batch: give a bucket (w, h) or a resolution")
+        B = len(raw_images)
+        items = (_lib.ResizeItem * B)()
+        for k, t in enumerate(raw_images):
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 3 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"expected contiguous uint8 [h,w,3] tensors on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            H, W, _ = t.shape
+            left, top, cw, ch = smart_crop_box(W, H, tw, th) if bucket is not None else (0, 0, W, H)
+            items[k] = _lib.ResizeItem(t.data_ptr(), H, W, left, top, cw, ch)
+        need = self.ctx.lib.vt_resize_batch_workspace_bytes(items, B, th, tw, filt)
+        if need == 0:
+            raise _lib.VTError(f"unsupported batch resize to {tw}x{th}")
+        out = torch.empty(B, 3, th, tw, dtype=torch.float32, device=self.device)
+        u8 = torch.empty(B, th, tw, 3, dtype=torch.uint8, device=self.device) if return_u8 else None
+        ws, ptr = workspace(self.device, need, tag)
+        self.ctx.call("vt_resize_normalize_batch", items, B, th, tw, filt, vp(out), out.numel() * 4, vp(u8), u8.numel() if return_u8 else 0,
+                      ctypes.c_void_p(ptr), need, stream_ptr(self.device))
+        return (out, u8) if return_u8 else out
 
     def status_async(self, out, clear=True):
         """The context's health word copied (and cleared) in stream order into `out` (int32 [1], pinned host or device) without a host
