@@ -166,6 +166,29 @@ int vt_eval_read_counts(vt_context* ctx, const void* state, size_t state_bytes, 
                         size_t counts_bytes, uint32_t* support_out, size_t support_bytes, uint64_t* row_stats_out, size_t row_stats_bytes,
                         void* stream);
 
+/* ---- sharded evaluation: a state block as a wire format, and the merge of several blocks on one device.  Same contract as above:
+ * every size is checked on the host before anything is launched (undersized buffer: VT_ERR_WORKSPACE; null / misaligned pointer or
+ * out-of-range argument: VT_ERR_INVALID; nothing is written), no host synchronisation, work is queued on `stream`.
+ * vt_eval_export writes into out_state an ordinary state of capacity out_capacity (vt_eval_state_bytes(N, T, out_capacity) bytes) that
+ * holds the same statistics: thresholds, row_stats, support and counts copied, the row scratch zeroed, the first n_seen key columns of
+ * every class row copied and the padding columns zero-filled -- the block's bytes are a function of the data only.  out_capacity is
+ * >= n_seen (it may be SMALLER than capacity: unlike vt_eval_grow the export compacts) or 0 (head only, no keys).  Ranks with different
+ * n_seen and capacities that export at the maximum n_seen all get blocks of one size: what an all-gather moves.
+ * vt_eval_merge adds the W sources' support, counts and row_stats into dst (integers: bit-reproducible) and appends the first n_w keys
+ * of every class row of source w at column dst_n_seen + sum_{v<w} n_v, sources in the order given.  The sample index in a key's low
+ * word, (~i << 1) | label, is rebased by that column offset o -- the key minus (o << 1), which never borrows into the high word while
+ * i + o < 2^31 -- so the merged block is the state one evaluator fed every sample in that order would hold: it takes further
+ * vt_eval_update calls with n_seen = the total, and vt_eval_average_precision.  dst keeps its thresholds; equal threshold tables and
+ * t_main in the sources are the caller's contract.  Two launches whatever W is (the descriptors travel as a kernel argument).
+ * Refused with VT_ERR_INVALID: W < 1 or W > 64; a source that is dst or overlaps it; dst_capacity > 0 with a source of capacity 0 and
+ * n_seen > 0; dst_n_seen + sum n_w > dst_capacity when dst_capacity > 0; a total of 2^31 or more.  dst_capacity == 0 merges the head only.
+ * `sources` is a HOST array; a source's n_seen is the number of samples its block holds (its counts cover all of them). */
+typedef struct { const void* state; size_t state_bytes; long long capacity; long long n_seen; } vt_eval_source;
+int vt_eval_export(vt_context* ctx, const void* state, size_t state_bytes, int N, int T, long long capacity, long long n_seen,
+                   void* out_state, size_t out_bytes, long long out_capacity, void* stream);
+int vt_eval_merge(vt_context* ctx, void* dst, size_t dst_bytes, int N, int T, long long dst_capacity, long long dst_n_seen,
+                  const vt_eval_source* sources /* host [W] */, int W, void* stream);
+
 /* algorithmic FLOPs of one encoder forward at HxW -- for roofline reporting */
 double vt_encoder_flops(const vt_context* ctx, int H, int W);
 
@@ -237,6 +260,9 @@ double vt_encoder_flops(const vt_context* ctx, int H, int W);
  *         0 = NHWC.  Same arithmetic, same bits.
  * flag 20: 1 (default) = conv_out (512 -> 32 channels, the moments / mode() epilogue) on its own 32-cout halo tile (conv_out_halo.hip: the
  *         18 x 18 halo of a 16 x 16-pixel tile and the chunk's nine weight tiles staged once per 32-channel chunk); 0 = the generic GEMM.
+
+ * flag 21: 1 (default) = vt_eval_export / vt_eval_merge move the keys 16 B per lane on the 16-B aligned part of every destination run;
+ *         0 = 8 B per lane throughout.  Same bytes out (tools/bench_eval.py --merge times both).
  */
 int vt_set_flag(vt_context* ctx, int flag, int value);
 

@@ -3,9 +3,13 @@
     python tools/bench_eval.py --n 2048 --leg host      # one leg per process: a driver script interleaves the legs, each under its own time limit
     python tools/bench_eval.py --n 2048 --leg device
     python tools/bench_eval.py --n 2048                 # both legs, host first
+    python tools/bench_eval.py --merge 8                # sharded evaluation's merge: W synthetic shards on one GPU (no model is loaded)
 
 Per leg one JSON line: the loop's images/s (first batch requested -> last batch finished on the GPU, both passes) and the seconds between
-the last batch and the return of the two calls (the metric finish: host numpy, or the device kernels + the final reads)."""
+the last batch and the return of the two calls (the metric finish: host numpy, or the device kernels + the final reads).
+--merge W: at N = --tags and n = 2048 and 8192 samples per shard, event-timed milliseconds of the W exports, of the merge (head + key
+kernel) and of the finish (sort + AP) on the merged state, next to a torch device-to-device copy of the same key bytes in the same
+process -- the yardstick: the key kernel reads and writes every key once, 2 x key bytes -- with 16-B and with 8-B accesses (flag 21)."""
 import argparse
 import contextlib
 import io
@@ -62,6 +66,82 @@ def run_leg(leg, vae, dec, names, args):
             "global_f1": r["global_f1"]}
 
 
+def _timed(fn, reps):
+    """Best and median event-timed milliseconds of fn() over `reps` runs after one warm-up."""
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    ms.sort()
+    return ms[0], ms[len(ms) // 2]
+
+
+def run_merge(W, tags, reps):
+    import ctypes
+    from vae_tagger_amd.evaluation import DeviceMultiLabelEvaluator
+    names = [f"tag_{i:05d}" for i in range(tags)]
+    g = torch.Generator(device="cuda").manual_seed(1)
+    out = {"merge": W, "tags": tags, "reps": reps, "shards": []}
+    for n in (2048, 8192):
+        p = torch.rand(4096, tags, generator=g, device="cuda")
+        y = (torch.rand(4096, tags, generator=g, device="cuda") < 0.02).to(torch.uint8)
+        base = DeviceMultiLabelEvaluator(names, "cuda", capacity=n + 1)      # an odd pitch: the export compacts to n
+        for lo in range(0, n, 4096):
+            base.update(p[:min(4096, n - lo)], y[:min(4096, n - lo)])
+        parts = [base] * W                                                   # W sources with one content: the traffic is what is timed
+        key_bytes = W * n * tags * 8
+        res = {"n_per_shard": n, "key_bytes": key_bytes}
+        for vec in (1, 0):
+            base.ctx.call("vt_set_flag", 21, vec)
+            blocks = []
+
+            def export():
+                blocks.clear()
+                blocks.extend(e.export_state(n) for e in parts)
+            best_e, med_e = _timed(export, reps)
+            merged = DeviceMultiLabelEvaluator(names, "cuda", capacity=W * n, context=base.ctx)
+
+            def merge():
+                merged.n_seen = 0
+                merged.merge_from(blocks)
+            best_m, med_m = _timed(merge, reps)
+            # the timed runs added the counts reps + 1 times: start over and merge once, for the finish below
+            merged.ctx.call("vt_eval_reset", ctypes.c_void_p(merged._ptr), merged._bytes, merged.N, merged.T,
+                            (ctypes.c_double * merged.T)(*merged.thr.tolist()), merged.t_main, merged.capacity, merged._stream())
+            merge()
+            tag = "16B" if vec else "8B"
+            res[f"export_ms_{tag}"] = round(best_e, 3)
+            res[f"merge_ms_{tag}"] = round(best_m, 3)
+            res[f"merge_ms_median_{tag}"] = round(med_m, 3)
+            res[f"merge_key_bytes_per_s_{tag}"] = round(2 * key_bytes / (best_m * 1e-3), 0)       # read + write of every key
+        base.ctx.call("vt_set_flag", 21, 1)
+        src = torch.empty(key_bytes, dtype=torch.uint8, device="cuda")
+        dst = torch.empty_like(src)
+        best_c, med_c = _timed(lambda: dst.copy_(src), reps)
+        res["torch_copy_ms"] = round(best_c, 3)
+        res["torch_copy_bytes_per_s"] = round(2 * key_bytes / (best_c * 1e-3), 0)
+        res["merge_over_copy_16B"] = round(res["merge_ms_16B"] / best_c, 3)
+        res["merge_over_copy_8B"] = round(res["merge_ms_8B"] / best_c, 3)
+        del src, dst
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        m = merged.compute_metrics()                                         # the existing finish: sort + AP (+ the final reads)
+        b.record()
+        b.synchronize()
+        res["finish_ms"] = round(a.elapsed_time(b), 3)
+        res["mAP"] = m["mAP"]
+        out["shards"].append(res)
+        del merged, blocks, base, parts
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=2048)
@@ -69,7 +149,12 @@ def main():
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--tags", type=int, default=10000)
     ap.add_argument("--leg", choices=["host", "device", "both"], default="both")
+    ap.add_argument("--merge", type=int, default=0, help="time export / merge / finish of this many synthetic shards (1..64) and exit")
+    ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
+    if args.merge:
+        print(json.dumps(run_merge(args.merge, args.tags, args.reps)), flush=True)
+        return
     vae = load_diffusers_vae_from_config(get_diffusers_vae_config())
     vae.load_state_dict(synth.synth_state_dict(synth.encoder_manifest(), seed=0), strict=False)
     vae = DiffusersVAEWrapper(vae).to("cuda").eval()

@@ -23,6 +23,11 @@ class ResizeItem(_c.Structure):
     _fields_ = [("src_hwc", _vp), ("src_h", _i), ("src_w", _i), ("crop_left", _i), ("crop_top", _i), ("crop_w", _i), ("crop_h", _i)]
 
 
+class EvalSource(_c.Structure):
+    """vt_eval_source: one state block handed to vt_eval_merge."""
+    _fields_ = [("state", _vp), ("state_bytes", _sz), ("capacity", _ll), ("n_seen", _ll)]
+
+
 # name -> (restype, argtypes); every symbol include/vae_tagger_hip.h declares
 PROTOTYPES = {
     "vt_version": (_c.c_char_p, []),
@@ -57,6 +62,8 @@ PROTOTYPES = {
     "vt_eval_ap_workspace_bytes": (_sz, [_i, _ll]),
     "vt_eval_average_precision": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _vp, _sz, _vp, _vp, _sz, _vp]),
     "vt_eval_read_counts": (_i, [_vp, _vp, _sz, _i, _i, _ll, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "vt_eval_export": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _vp, _sz, _ll, _vp]),
+    "vt_eval_merge": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _c.POINTER(EvalSource), _i, _vp]),
     "vt_encoder_flops": (_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),

@@ -360,6 +360,63 @@ int vt_eval_read_counts(vt_context* c, const void* state, size_t state_bytes, in
     return VT_OK;
 }
 
+// ---- state blocks as a wire format: export at a common capacity, merge on one device -----------------------------------------------
+namespace {
+bool blocks_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+}  // namespace
+
+int vt_eval_export(vt_context* c, const void* state, size_t state_bytes, int N, int T, long long capacity, long long n_seen, void* out_state,
+                   size_t out_bytes, long long out_capacity, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = eval_check_state(c, "vt_eval_export (state)", state, state_bytes, N, T, capacity)) return r;
+    if (int r = eval_check_state(c, "vt_eval_export (out)", out_state, out_bytes, N, T, out_capacity)) return r;
+    if (n_seen < 0 || n_seen > VT_EVAL_MAX_N_SEEN || (capacity > 0 && n_seen > capacity))
+        return c->fail(VT_ERR_INVALID, "vt_eval_export: n_seen = %lld outside [0, capacity = %lld]", n_seen, capacity);
+    if (out_capacity != 0 && out_capacity < n_seen)
+        return c->fail(VT_ERR_INVALID, "vt_eval_export: out_capacity = %lld is neither 0 nor >= n_seen = %lld", out_capacity, n_seen);
+    if (out_capacity > 0 && capacity == 0 && n_seen > 0)
+        return c->fail(VT_ERR_INVALID, "vt_eval_export: the state keeps no keys (capacity 0) but out_capacity = %lld", out_capacity);
+    const EvalLayout l = vt_eval_layout(N, T, capacity), lo = vt_eval_layout(N, T, out_capacity);
+    if (blocks_overlap(state, l.total, out_state, lo.total)) return c->fail(VT_ERR_INVALID, "vt_eval_export: out_state overlaps the state");
+    HIPCK(c, vt_eval_launch_export(state, l, out_state, lo, N, capacity, n_seen, out_capacity, c->eval_merge_vec, (hipStream_t)stream), "eval_export");
+    return VT_OK;
+}
+
+int vt_eval_merge(vt_context* c, void* dst, size_t dst_bytes, int N, int T, long long dst_capacity, long long dst_n_seen,
+                  const vt_eval_source* sources, int W, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = eval_check_state(c, "vt_eval_merge (dst)", dst, dst_bytes, N, T, dst_capacity)) return r;
+    if (!sources || W < 1 || W > VT_EVAL_MAX_MERGE) return c->fail(VT_ERR_INVALID, "vt_eval_merge: null sources or W = %d outside [1, %d]", W, VT_EVAL_MAX_MERGE);
+    if (dst_n_seen < 0 || dst_n_seen > VT_EVAL_MAX_N_SEEN || (dst_capacity > 0 && dst_n_seen > dst_capacity))
+        return c->fail(VT_ERR_INVALID, "vt_eval_merge: dst_n_seen = %lld outside [0, capacity = %lld]", dst_n_seen, dst_capacity);
+    const EvalLayout l = vt_eval_layout(N, T, dst_capacity);
+    EvalMergeArg a;
+    a.W = W;
+    long long total = dst_n_seen;
+    for (int w = 0; w < W; ++w) {
+        const vt_eval_source& s = sources[w];
+        if (int r = eval_check_state(c, "vt_eval_merge (source)", s.state, s.state_bytes, N, T, s.capacity)) return r;
+        if (s.n_seen < 0 || s.n_seen > VT_EVAL_MAX_N_SEEN || (s.capacity > 0 && s.n_seen > s.capacity))
+            return c->fail(VT_ERR_INVALID, "vt_eval_merge: source %d has n_seen = %lld outside [0, capacity = %lld]", w, s.n_seen, s.capacity);
+        if (blocks_overlap(dst, l.total, s.state, vt_eval_layout(N, T, s.capacity).total))
+            return c->fail(VT_ERR_INVALID, "vt_eval_merge: source %d is dst or overlaps it", w);
+        if (dst_capacity > 0 && s.capacity == 0 && s.n_seen > 0)
+            return c->fail(VT_ERR_INVALID, "vt_eval_merge: source %d keeps no keys (capacity 0) for its %lld samples, dst does", w, s.n_seen);
+        a.src[w] = EvalMergeSrc{(const char*)s.state, s.capacity, s.n_seen, s.n_seen, total};
+        total += s.n_seen;
+        if (total > VT_EVAL_MAX_N_SEEN) return c->fail(VT_ERR_INVALID, "vt_eval_merge: %lld samples in all, 2^31 or more", total);
+    }
+    if (dst_capacity > 0 && total > dst_capacity)
+        return c->fail(VT_ERR_INVALID, "vt_eval_merge: dst_n_seen + the sources' samples = %lld exceeds the capacity %lld", total, dst_capacity);
+    HIPCK(c, vt_eval_launch_merge(dst, l, N, dst_capacity, a, c->eval_merge_vec, (hipStream_t)stream), "eval_merge");
+    return VT_OK;
+}
+
 int vt_set_flag(vt_context* c, int flag, int value) {
     if (!c) return VT_ERR_INVALID;
     if (flag == 0) { c->use_halo_conv = value != 0; return VT_OK; }
@@ -378,6 +435,7 @@ int vt_set_flag(vt_context* c, int flag, int value) {
     if (flag == 17) { c->attn_proj_kernel = value != 0; return VT_OK; }
     if (flag == 18) { c->f16_ops = value != 0; return VT_OK; }
     if (flag == 19) { c->s2_planar = value != 0; return VT_OK; }
+    if (flag == 21) { c->eval_merge_vec = value != 0; return VT_OK; }
     if (flag == 20) { c->conv_out_halo = value != 0; return VT_OK; }
     if (flag == 13) { c->s2_halo = value != 0; return VT_OK; }
     if (flag == 14) { c->attn_fp8 = value != 0; return VT_OK; }

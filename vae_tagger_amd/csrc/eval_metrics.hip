@@ -3,6 +3,8 @@
 // per (class, sample); at the end the class rows are ranked with the shared bitonic network (vt_sort_network.h) and one workgroup per
 // class sums the average precision in fp64 in a fixed order.  Every counter is an integer owned by one thread or reached by integer
 // atomics only, so the state is bit-reproducible whatever the launch timing.
+// Sharded evaluation: a state is exported as a compact block and several blocks are merged into one state (a head kernel adding the
+// integers, a key kernel appending the class rows with the sample index rebased) -- no atomics, no LDS.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -274,6 +276,78 @@ __global__ __launch_bounds__(256) void eval_flatten_kernel(const unsigned long l
     flat[i] = keys[c * capacity + s] & 0xffffffff00000001ull;
 }
 
+// ---- export / merge of state blocks (sharded evaluation) ---------------------------------------------------------------------------
+// Key kernel: a strided copy with one integer op per key.  Per class row, source w's first n keys go to destination columns
+// [off, off + n) with `sub` = off << 1 subtracted: the low word is (~i << 1) | label = 2^32 - 2 - 2 i + label, so the subtraction
+// turns sample i into sample i + off and stays inside the low word while i + off < 2^31 (the host checks the total).  Columns
+// [n, fill) of the destination are zero-filled (the export's padding; fill == n in a merge).  blockIdx.x = row * chunks + chunk,
+// blockIdx.y = source; a chunk is MERGE_CH keys of one row: consecutive lanes touch consecutive keys (VEC = 1: 8 B per lane) or
+// consecutive pairs (VEC = 2: 16 B per lane on the 16-B aligned part of the DESTINATION run, whose first key may sit at an odd
+// index; the source pair is read as one 16-B access when it has the same parity and as two 8-B ones when not).
+constexpr int MERGE_CH = 2048;
+
+template <int VEC>
+__global__ __launch_bounds__(256) void eval_merge_keys_kernel(EvalMergeArg a, size_t keys_at, unsigned long long* __restrict__ dst,
+                                                              long long dst_pitch, long long chunks) {
+    const EvalMergeSrc s = a.src[blockIdx.y];
+    const long long row = blockIdx.x / chunks, c0 = (long long)(blockIdx.x % chunks) * MERGE_CH;
+    if (c0 >= s.fill) return;
+    const unsigned long long sub = (unsigned long long)s.off << 1;
+    const unsigned long long* __restrict__ sk = (const unsigned long long*)(s.base + keys_at) + row * s.pitch;
+    unsigned long long* __restrict__ dk = dst + row * dst_pitch + s.off;
+    const int tid = threadIdx.x;
+    if (VEC == 1) {
+#pragma unroll
+        for (int k = 0; k < MERGE_CH / 256; ++k) {
+            const long long col = c0 + k * 256 + tid;
+            if (col < s.fill) dk[col] = col < s.n ? sk[col] - sub : 0ull;
+        }
+    } else {
+        const long long lead = (row * dst_pitch + s.off) & 1;           // keys in front of the first 16-B aligned destination pair
+        const bool src_pairs = ((row * s.pitch + lead) & 1) == 0;       // block-uniform: the source pairs are 16-B aligned too
+        if (c0 == 0 && lead && tid == 0) dk[0] = 0 < s.n ? sk[0] - sub : 0ull;
+#pragma unroll
+        for (int k = 0; k < MERGE_CH / 512; ++k) {
+            const long long col = lead + c0 + 2 * (k * 256 + tid);
+            if (col + 1 < s.fill) {
+                ulonglong2 v = make_ulonglong2(0ull, 0ull);
+                if (col + 1 < s.n) {
+                    if (src_pairs) v = *(const ulonglong2*)(sk + col);
+                    else { v.x = sk[col]; v.y = sk[col + 1]; }
+                    v.x -= sub; v.y -= sub;
+                } else if (col < s.n) {
+                    v.x = sk[col] - sub;
+                }
+                *(ulonglong2*)(dk + col) = v;
+            } else if (col < s.fill) {
+                dk[col] = col < s.n ? sk[col] - sub : 0ull;
+            }
+        }
+    }
+}
+
+// Head kernel: support and counts (one run of uint32 from the support section to the end of the head, the sections' zero padding
+// included) and row_stats of W sources added into the destination; every element is owned by one thread, sources in the order given.
+__global__ __launch_bounds__(256) void eval_merge_head_kernel(EvalMergeArg a, char* __restrict__ dst, size_t support, size_t row_stats,
+                                                              long long quads) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < quads) {
+        uint4* d = (uint4*)(dst + support) + i;
+        uint4 v = *d;
+        for (int w = 0; w < a.W; ++w) {
+            const uint4 x = ((const uint4*)(a.src[w].base + support))[i];
+            v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w;
+        }
+        *d = v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 3) {
+        unsigned long long* d = (unsigned long long*)(dst + row_stats) + threadIdx.x;
+        unsigned long long v = *d;
+        for (int w = 0; w < a.W; ++w) v += ((const unsigned long long*)(a.src[w].base + row_stats))[threadIdx.x];
+        *d = v;
+    }
+}
+
 #define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) return _e; } while (0)
 #define CKL() CK(hipGetLastError())
 
@@ -344,5 +418,41 @@ hipError_t vt_eval_launch_ap(void* state, const EvalLayout& l, int N, long long 
         CK(sort_rows(flat, 1, total, total, s));
         hipLaunchKernelGGL(eval_ap_kernel, dim3(1), dim3(1024), 0, s, flat, total, total, micro_ap); CKL();
     }
+    return hipSuccess;
+}
+
+namespace {
+hipError_t launch_merge_keys(const EvalMergeArg& a, size_t keys_at, unsigned long long* dst, long long dst_pitch, int N, int vec, hipStream_t s) {
+    long long widest = 0;
+    for (int w = 0; w < a.W; ++w) widest = a.src[w].fill > widest ? a.src[w].fill : widest;
+    if (widest == 0) return hipSuccess;
+    const long long chunks = (widest + MERGE_CH - 1) / MERGE_CH;
+    if ((long long)N * chunks > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((long long)N * chunks), (unsigned)a.W);
+    if (vec) hipLaunchKernelGGL(eval_merge_keys_kernel<2>, grid, dim3(256), 0, s, a, keys_at, dst, dst_pitch, chunks);
+    else hipLaunchKernelGGL(eval_merge_keys_kernel<1>, grid, dim3(256), 0, s, a, keys_at, dst, dst_pitch, chunks);
+    CKL();
+    return hipSuccess;
+}
+}  // namespace
+
+hipError_t vt_eval_launch_export(const void* state, const EvalLayout& l, void* out, const EvalLayout& lo, int N, long long capacity,
+                                 long long n_seen, long long out_capacity, int vec, hipStream_t s) {
+    CK(hipMemcpyAsync(out, state, l.head_bytes, hipMemcpyDeviceToDevice, s));
+    CK(hipMemsetAsync((char*)out + lo.row_scratch, 0, sizeof(uint32_t) * VT_EVAL_MAX_B, s));
+    if (out_capacity <= 0) return hipSuccess;
+    EvalMergeArg a;
+    a.W = 1;
+    a.src[0] = EvalMergeSrc{(const char*)state, capacity, n_seen, out_capacity, 0};
+    CK(launch_merge_keys(a, l.keys, (unsigned long long*)((char*)out + lo.keys), out_capacity, N, vec, s));
+    const size_t used = lo.keys + sizeof(uint64_t) * (size_t)N * (size_t)out_capacity;
+    if (lo.total > used) CK(hipMemsetAsync((char*)out + used, 0, lo.total - used, s));    // the section's alignment tail
+    return hipSuccess;
+}
+
+hipError_t vt_eval_launch_merge(void* dst, const EvalLayout& l, int N, long long dst_capacity, const EvalMergeArg& a, int vec, hipStream_t s) {
+    const long long quads = (long long)((l.head_bytes - l.support) / 16);
+    hipLaunchKernelGGL(eval_merge_head_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, a, (char*)dst, l.support, l.row_stats, quads); CKL();
+    if (dst_capacity > 0) CK(launch_merge_keys(a, l.keys, (unsigned long long*)((char*)dst + l.keys), dst_capacity, N, vec, s));
     return hipSuccess;
 }

@@ -98,6 +98,7 @@ struct vt_context {
     unsigned long long* dbg = nullptr; int dbg_n = 0; bool dbg_on = false;
     int conv_out_halo = 1;          // vt_set_flag(ctx, 20, v): conv_out on its 32-cout halo tile (conv_out_halo.hip) instead of the generic GEMM
     int s2_planar = 1;              // vt_set_flag(ctx, 19, v): the 16-bit / e4m3 copy of a stage's output that feeds its stride-2 conv is written chunk-planar
+    int eval_merge_vec = 1;         // vt_set_flag(ctx, 21, v): vt_eval_export / vt_eval_merge move keys 16 B per lane on the aligned part (0: 8 B)
                                     // ([C/32 or C/64][H][W][chunk]) so that both halves of every 128-B line are staged three K-steps apart, not nine
     int f16_ops = 0;                // vt_set_flag(ctx, 18, v): fp16 instead of bf16 operands for the convs (same 2 B, 11 significand bits instead of 8)
     int attn_proj_kernel = 1;       // vt_set_flag(ctx, 17, v): the bf16 q | k and v^T projections on attn_qk.hip's skeleton (mode 4) instead of the generic GEMM

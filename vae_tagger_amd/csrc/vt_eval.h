@@ -7,6 +7,7 @@
 constexpr int VT_EVAL_MAX_T = 32;          // thresholds per state
 constexpr int VT_EVAL_MAX_B = 4096;        // rows of one update (the per-row mismatch scratch)
 constexpr long long VT_EVAL_MAX_N_SEEN = 0x7fffffffLL;    // the sample index is 31 bits of the key's low word
+constexpr int VT_EVAL_MAX_MERGE = 64;       // sources of one merge (their descriptors travel as a kernel argument)
 constexpr long long VT_EVAL_MICRO_LIMIT = 0x7fffffffLL;   // micro AP on the device while n_seen * N < 2^31
 
 // One block, every section 256-B aligned:
@@ -38,3 +39,16 @@ hipError_t vt_eval_launch_update(void* state, const EvalLayout& l, const float* 
 // into `flat` (n_seen * N keys), sorts it and writes micro_ap[0]
 hipError_t vt_eval_launch_ap(void* state, const EvalLayout& l, int N, long long capacity, long long n_seen, double* ap, double* micro_ap,
                              unsigned long long* flat, hipStream_t s);
+
+// One source of the export / merge key kernel: the first n keys of every class row (row pitch `pitch`) of the block at `base` go to
+// destination columns [off, off + n) with off << 1 subtracted from each key (the sample index moves by off); columns [n, fill) are
+// zero-filled.  The head sections and the start of the keys sit at the destination's offsets: they do not depend on the capacity.
+struct EvalMergeSrc { const char* base; long long pitch, n, fill, off; };
+struct EvalMergeArg { EvalMergeSrc src[VT_EVAL_MAX_MERGE]; int W; };
+
+// copies a state into a block of capacity out_capacity (>= n_seen, or 0: head only): head copied, row scratch zeroed, the first n_seen
+// key columns copied, the padding columns and the key section's alignment tail zero-filled.  vec: 16-B accesses on the aligned part.
+hipError_t vt_eval_launch_export(const void* state, const EvalLayout& l, void* out, const EvalLayout& lo, int N, long long capacity,
+                                 long long n_seen, long long out_capacity, int vec, hipStream_t s);
+// adds the sources' support / counts / row_stats into dst and (dst_capacity > 0) appends their keys: two launches whatever a.W is
+hipError_t vt_eval_launch_merge(void* dst, const EvalLayout& l, int N, long long dst_capacity, const EvalMergeArg& a, int vec, hipStream_t s);

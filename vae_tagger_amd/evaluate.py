@@ -11,7 +11,8 @@ reference's SmartResize; on the GPU, Pillow's arithmetic bit for bit) and batche
 squashed to --resolution squared, as the inference CLIs do.  The data set is read TWICE unless --threshold is given: once for the
 threshold search and once for the metrics at the threshold it found (the exact-match and Hamming counts exist for one operating
 point per pass).  Metrics are accumulated on the GPU (DeviceMultiLabelEvaluator); --host_metrics is the host evaluator, same files.
-Single process only.  Reference: modules.py:487-548 (the JSON format), evaluation.py:173-275, train_decoder.py:284-333 (flags).
+One process by default; `torchrun ... -m vae_tagger_amd.evaluate ... --sharded` runs one rank per GPU: rank r takes paths[r::world], the
+evaluator states are merged on rank 0 (evaluation.merge_across_ranks) after each pass and rank 0 writes the files.  Reference: modules.py:487-548 (the JSON format), evaluation.py:173-275, train_decoder.py:284-333 (flags).
 """
 import argparse
 import json
@@ -73,23 +74,50 @@ def build_loader(args, pipe, data):
 LAST_RUN_STATS = {}    # seconds spent in the passes over the data and the images they covered (tools/bench_cli.py reads it)
 
 
+def shard_paths(paths, rank, world):
+    """Rank r's share of the image list: paths[r::world].  Over r the shares partition the list; deterministic, balanced in the number
+    of images (not in their cost: see DESIGN.md section 4.15)."""
+    return list(paths[rank::world])
+
+
+def check_mode(args, world_size):
+    """The flag combinations that are refused, before any GPU or process-group work."""
+    sharded = getattr(args, "sharded", False)
+    if sharded and args.host_metrics:
+        raise RuntimeError("--sharded merges the device evaluator's state; the host matrix of --host_metrics is not merged "
+                           "(drop one of the two flags)")
+    if world_size > 1 and not sharded:
+        raise RuntimeError("vae_tagger_amd.evaluate runs in a single process unless --sharded is given: the metrics are accumulated on "
+                           "one GPU (start it without torchrun / with WORLD_SIZE=1, or pass --sharded to merge the ranks' states)")
+
+
 def evaluate(args):
     import time
     from .evaluation import evaluate_model, find_optimal_threshold
     from .infer_full import load_models
     from .pipeline import EncodeTagPipeline
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("vae_tagger_amd.evaluate runs in a single process: the metrics are accumulated on one GPU "
-                           "(start it without torchrun / with WORLD_SIZE=1)")
+    check_mode(args, int(os.environ.get("WORLD_SIZE", "1")))
+    world, rank, dev_index, group = 1, 0, None, None
+    if getattr(args, "sharded", False):
+        from .infer_full import _dist_setup
+        world, rank, dev_index = _dist_setup()           # creates the process group BEFORE any GPU call of this process
+        if dev_index is not None:
+            import torch.distributed as dist
+            group = dist.group.WORLD
     if not torch.cuda.is_available():
         raise RuntimeError("vae_tagger_amd needs an MI355X (no HIP device visible; there is no CPU fallback)")
+    if dev_index is not None:
+        torch.cuda.set_device(dev_index)
     device = torch.device("cuda", torch.cuda.current_device())
     vae_model, decoder, tag_names = load_models(args, device)
     data = TaggedImageList(args.json_path, args.tags_csv_path)
-    for p in data.missing:
-        print(f"跳过图像 {p}，错误原因: 文件不存在")
+    if rank == 0:
+        for p in data.missing:
+            print(f"跳过图像 {p}，错误原因: 文件不存在")
     if not data.image_paths:
         raise RuntimeError(f"{args.json_path} 中没有可用的图像")
+    if group is not None:
+        data.image_paths = shard_paths(data.image_paths, rank, world)
     if args.fp8:
         vae_model.vae._context().call("vt_set_flag", 11, 1)
     elif args.fp16_operands:
@@ -101,25 +129,39 @@ def evaluate(args):
     t0 = time.perf_counter()
     passes = 0
     if args.threshold is None:
-        print("寻找最优分类阈值...")
-        optimal = find_optimal_threshold(vae_model, decoder, loader, tag_names, device, args.output_dir, device_metrics=device_metrics)
-        threshold = optimal["global_threshold"]
+        if rank == 0:
+            print("寻找最优分类阈值...")
+        optimal = find_optimal_threshold(vae_model, decoder, loader, tag_names, device, args.output_dir, device_metrics=device_metrics,
+                                         group=group)
+        threshold = optimal["global_threshold"]          # with a group: rank 0's dict, broadcast -- the same threshold on every rank
         passes += 1
     else:
         optimal, threshold = None, float(args.threshold)
-    print("使用最优阈值进行最终评估...")
-    metrics = evaluate_model(vae_model, decoder, loader, tag_names, device, threshold, args.output_dir, device_metrics=device_metrics)
+    if rank == 0:
+        print("使用最优阈值进行最终评估...")
+    metrics = evaluate_model(vae_model, decoder, loader, tag_names, device, threshold, args.output_dir, device_metrics=device_metrics,
+                             group=group)
     passes += 1
     torch.cuda.synchronize()
     LAST_RUN_STATS.update(loop_seconds=time.perf_counter() - t0, images=sum(len(n) for n, _ in loader.batches), passes=passes,
                           batches=list(loader.batches))
-    for p, e in loader.failed:
+    failed, images = [(p, str(e)) for p, e in loader.failed], LAST_RUN_STATS["images"]
+    if group is not None:
+        import torch.distributed as dist
+        objs = [None] * world if rank == 0 else None
+        dist.gather_object((failed, images), objs, dst=0, group=group)
+        if rank != 0:
+            return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": None}
+        failed = [f for part, _ in objs for f in part]   # every file belongs to one rank: each failure is counted once
+        images = sum(n for _, n in objs)
+    for p, e in failed:
         print(f"跳过图像 {p}，错误原因: {e}")
-    print(f"评估完成！图像: {LAST_RUN_STATS['images']}, 跳过: {len(loader.failed) + len(data.missing)}, 阈值: {threshold:.3f}")
-    return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": len(loader.failed) + len(data.missing)}
+    print(f"评估完成！图像: {images}, 跳过: {len(failed) + len(data.missing)}, 阈值: {threshold:.3f}")
+    return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": len(failed) + len(data.missing)}
 
 
-def build_parser():
+def build_parser(distributed=False):
+    """The single-process flag set; distributed=True (what `main` parses with) adds --sharded."""
     p = argparse.ArgumentParser(description="在带标签的数据集上评估VAE + 分类解码器 (阈值搜索 + 多标签指标)。")
     p.add_argument("--vae_checkpoint", type=str, required=True, help="预训练VAE模型文件路径 (.safetensors)")
     p.add_argument("--vae_config_path", type=str, default=None, help="VAE配置文件路径 (JSON格式)")
@@ -153,11 +195,15 @@ def build_parser():
     p.add_argument("--threshold", type=float, default=None,
                    help="skip the threshold search and evaluate at this threshold: ONE pass over the images instead of two "
                         "(search pass + metrics pass at the threshold found)")
+    if distributed:
+        p.add_argument("--sharded", action="store_true",
+                       help="under torchrun: one rank per GPU, rank r evaluates paths[r::world], the device evaluator's states are "
+                            "merged on rank 0, which writes the files (not with --host_metrics)")
     return p
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(distributed=True).parse_args(argv)
     if args.no_attention:
         args.use_attention = False
     return evaluate(args)

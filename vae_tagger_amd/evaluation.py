@@ -155,9 +155,21 @@ def _probabilities(model, decoder, loader, device):
     return np.vstack(probs), np.vstack(labels)
 
 
-def evaluate_model(model, decoder, test_loader, class_names, device="cuda", threshold=0.5, output_dir=None, device_metrics=False):
-    """device_metrics=True: the probabilities never leave the GPU (DeviceMultiLabelEvaluator); same dict, prints and files."""
+def evaluate_model(model, decoder, test_loader, class_names, device="cuda", threshold=0.5, output_dir=None, device_metrics=False,
+                   group=None):
+    """device_metrics=True: the probabilities never leave the GPU (DeviceMultiLabelEvaluator); same dict, prints and files.
+    group (with device_metrics only; torch.distributed.group.WORLD for the default group): `test_loader` is this rank's share; the
+    states are merged on rank 0, which finishes, prints and writes the files; every rank returns the same dict."""
     model.eval(); decoder.eval()
+    if device_metrics and group is not None and _use_group(group):
+        def finish(ev):
+            metrics = ev.compute_metrics()
+            ev.print_metrics(metrics)
+            if output_dir:
+                os.makedirs(output_dir, exist_ok=True)
+                ev.save_metrics(metrics, os.path.join(output_dir, "evaluation_results.csv"))
+            return metrics
+        return _finish_on_rank0(_sharded_device_pass(model, decoder, test_loader, class_names, device, threshold, group), group, finish)
     if device_metrics:
         ev = _device_pass(model, decoder, test_loader, class_names, device, threshold)
         metrics = ev.compute_metrics()
@@ -177,10 +189,21 @@ def evaluate_model(model, decoder, test_loader, class_names, device="cuda", thre
     return metrics
 
 
-def find_optimal_threshold(model, decoder, val_loader, class_names, device="cuda", output_dir=None, device_metrics=False):
+def find_optimal_threshold(model, decoder, val_loader, class_names, device="cuda", output_dir=None, device_metrics=False, group=None):
     """Per-class and global (macro-F1) threshold search over 0.10, 0.15 ... 0.85, all classes at once per threshold.
-    device_metrics=True: from the device evaluator's integer counts (counts only: no key store is kept)."""
+    device_metrics=True: from the device evaluator's integer counts (counts only: no key store is kept).
+    group: as in evaluate_model -- the counts are merged on rank 0, every rank returns the same dict."""
     model.eval(); decoder.eval()
+    if device_metrics and group is not None and _use_group(group):
+        def finish(ev):
+            results = ev.optimal_thresholds()
+            print(f"global threshold {results['global_threshold']:.3f} (macro F1 {results['global_f1']:.4f})")
+            if output_dir:
+                os.makedirs(output_dir, exist_ok=True)
+                with open(os.path.join(output_dir, "optimal_thresholds.json"), "w", encoding="utf-8") as fh:
+                    json.dump(results, fh, indent=2, ensure_ascii=False)
+            return results
+        return _finish_on_rank0(_sharded_device_pass(model, decoder, val_loader, class_names, device, 0.5, group, keys=False), group, finish)
     if device_metrics:
         results = _device_pass(model, decoder, val_loader, class_names, device, 0.5, capacity=0).optimal_thresholds()
         print(f"global threshold {results['global_threshold']:.3f} (macro F1 {results['global_f1']:.4f})")
@@ -286,6 +309,122 @@ def finish_from_counts(counts, support, row_stats, n, ap=None, micro_ap=None, t_
     return m, optimal
 
 
+class EvalStateBlock:
+    """An exported evaluator state: `data` is the block (uint8 device tensor, 256-B aligned, vt_eval_state_bytes(N, T, capacity) bytes),
+    `n_seen` the samples it holds, `thresholds` / `t_main` the table it was taken at (host values, compared before a merge)."""
+
+    def __init__(self, data, capacity, n_seen, thresholds, t_main):
+        self.data, self.capacity, self.n_seen = data, int(capacity), int(n_seen)
+        self.thresholds, self.t_main = np.asarray(thresholds, dtype=np.float64), int(t_main)
+
+
+def rank_descriptor(ev, error=None):
+    """What a rank tells the others before the merge: small, host-only, picklable."""
+    if ev is None:
+        return {"N": None, "T": None, "t_main": None, "thresholds": None, "keys": None, "n_seen": 0, "error": error or "no evaluator state"}
+    return {"N": ev.N, "T": ev.T, "t_main": ev.t_main, "thresholds": ev.thr.tobytes(), "keys": ev.capacity > 0, "n_seen": int(ev.n_seen),
+            "error": error}
+
+
+def check_rank_descriptors(descs):
+    """Pure function of the gathered descriptors (identical on every rank, so every rank raises the same exception or none): a rank
+    that carries an error, or ranks that disagree on the classes, the thresholds, the operating point or on keeping keys."""
+    bad = [(r, d["error"]) for r, d in enumerate(descs) if d["error"]]
+    if bad:
+        raise RuntimeError("sharded evaluation failed on " + "; ".join(f"rank {r}: {e}" for r, e in bad))
+    first = descs[0]
+    for key, what in (("N", "number of classes"), ("T", "number of thresholds"), ("t_main", "operating point"),
+                      ("thresholds", "threshold table"), ("keys", "key store (capacity 0 on some ranks only)")):
+        for r, d in enumerate(descs):
+            if d[key] != first[key]:
+                shown = "" if key == "thresholds" else f" ({first[key]} vs {d[key]})"
+                raise ValueError(f"sharded evaluation: rank {r} differs from rank 0 in the {what}{shown}")
+    if sum(d["n_seen"] for d in descs) > 0x7fffffff:
+        raise ValueError("sharded evaluation: 2^31 samples or more in all")
+
+
+def _use_group(group, force_collective=False):
+    import torch.distributed as dist
+    if not dist.is_available() or not dist.is_initialized():
+        return False
+    return dist.get_world_size(group) > 1 or force_collective
+
+
+def merge_across_ranks(ev, group=None, force_collective=False, error=None):
+    """Merge every rank's DeviceMultiLabelEvaluator on rank 0: returns the merged evaluator there (a fresh state of capacity sum n_r)
+    and None on the other ranks.  Without a process group, or on a one-rank group without `force_collective`, `ev` is returned.
+    `error`: what went wrong during this rank's pass (a string), or None -- it travels in the first exchange, so that every rank
+    raises the same exception instead of one rank leaving the others waiting in the collective.  Steps: all_gather_object of the host
+    descriptors (checked by check_rank_descriptors); every rank exports at the maximum n_seen, so all blocks have one size; ONE
+    all-gather of the blocks (all_gather_into_tensor; under gloo the list form, staged through the host); rank 0 merges in rank order.
+    Every rank receives the gather: world x block bytes beside its own state (and, on rank 0, the merged one)."""
+    import torch.distributed as dist
+    if not _use_group(group, force_collective):
+        if error:
+            raise RuntimeError(f"evaluation failed: {error}")
+        return ev
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    descs = [None] * world
+    dist.all_gather_object(descs, rank_descriptor(ev, error), group=group)
+    check_rank_descriptors(descs)
+    counts = [d["n_seen"] for d in descs]
+    cap = max(counts) if descs[0]["keys"] else 0
+    block = ev.export_state(cap)
+    nbytes = block.data.numel()
+    if dist.get_backend(group) == "gloo":                    # the rehearsal backend (ranks sharing a GPU) moves host memory
+        parts = [torch.empty(nbytes, dtype=torch.uint8) for _ in range(world)]
+        dist.all_gather(parts, block.data.cpu(), group=group)
+        if rank != 0:
+            return None
+        gathered = torch.empty(world * nbytes + 256, dtype=torch.uint8, device=ev.device)
+        off = -gathered.data_ptr() % 256
+        gathered = gathered[off:off + world * nbytes]
+        for r, part in enumerate(parts):
+            gathered[r * nbytes:(r + 1) * nbytes].copy_(part, non_blocking=False)
+    else:
+        gathered = torch.empty(world * nbytes + 256, dtype=torch.uint8, device=ev.device)
+        off = -gathered.data_ptr() % 256
+        gathered = gathered[off:off + world * nbytes]
+        dist.all_gather_into_tensor(gathered, block.data, group=group)
+        if rank != 0:
+            return None
+    merged = DeviceMultiLabelEvaluator(ev.class_names, ev.device, thresholds=ev.grid, threshold=ev.threshold,
+                                       capacity=sum(counts) if cap else 0, context=ev.ctx)
+    merged.merge_from([EvalStateBlock(gathered[r * nbytes:(r + 1) * nbytes], cap, counts[r], ev.thr, ev.t_main) for r in range(world)])
+    return merged
+
+
+def _finish_on_rank0(merged, group, finish):
+    """finish(merged) on rank 0 (merged is None elsewhere); its result -- or its exception -- reaches every rank."""
+    import torch.distributed as dist
+    box = [None, None]
+    if merged is not None:
+        try:
+            box[0] = finish(merged)
+        except Exception as e:  # noqa: BLE001 - carried to every rank, raised below
+            box[1] = f"{type(e).__name__}: {e}"
+    dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    if box[1]:
+        raise RuntimeError(f"sharded evaluation: the finish on rank 0 failed: {box[1]}")
+    return box[0]
+
+
+def _sharded_device_pass(model, decoder, loader, class_names, device, threshold, group, keys=True):
+    """This rank's pass + the merge.  An exception of the pass is held back until the first exchange (merge_across_ranks)."""
+    ev, error = None, None
+    try:
+        n = None
+        if hasattr(loader, "dataset"):
+            try:
+                n = max(1, len(loader.dataset))              # a rank without a sample still keeps a (one-column) key store
+            except TypeError:
+                n = None
+        ev = _device_pass(model, decoder, loader, class_names, device, threshold, capacity=(n if keys else 0))
+    except Exception as e:  # noqa: BLE001
+        error = f"{type(e).__name__}: {e}"
+    return merge_across_ranks(ev, group, error=error)
+
+
 class DeviceMultiLabelEvaluator(MultiLabelEvaluator):
     """MultiLabelEvaluator whose accumulation runs on the GPU (vt_eval_* of the C ABI).  `thresholds` is the search grid (default: the grid
     of find_optimal_threshold, compared in fp64 as numpy compares a float32 array with a float64 scalar); `threshold` is the operating
@@ -372,6 +511,39 @@ class DeviceMultiLabelEvaluator(MultiLabelEvaluator):
             self.ctx.call("vt_eval_update", ctypes.c_void_p(self._ptr), self._bytes, self.N, self.T, self.t_main, self.capacity,
                           ctypes.c_void_p(pb.data_ptr()), ctypes.c_void_p(yb.data_ptr()), dt, B, self.n_seen, self._stream())
             self.n_seen += B
+
+    def export_state(self, capacity=None):
+        """The state as a block of `capacity` key columns (default: n_seen; 0: head only, no keys) -- an EvalStateBlock whose bytes are
+        a function of the data only: what a rank sends to the merge.  Queued on the current stream; no host synchronisation."""
+        import ctypes
+        cap = (self.n_seen if self.capacity else 0) if capacity is None else int(capacity)
+        buf, ptr, nbytes = self._alloc(cap)
+        self.ctx.call("vt_eval_export", ctypes.c_void_p(self._ptr), self._bytes, self.N, self.T, self.capacity, self.n_seen,
+                      ctypes.c_void_p(ptr), nbytes, cap, self._stream())
+        off = ptr - buf.data_ptr()
+        return EvalStateBlock(buf[off:off + nbytes], cap, self.n_seen, self.thr, self.t_main)
+
+    def merge_from(self, blocks):
+        """Append the samples of `blocks` (EvalStateBlock, in the order given) to this state: counts, support and row statistics are
+        added, the keys appended with their sample indices moved behind this state's samples -- afterwards the state is what one
+        evaluator fed everything in that order would hold.  One vt_eval_merge call (two launches); no host synchronisation."""
+        import ctypes
+        from . import _lib
+        blocks = list(blocks)
+        for b in blocks:
+            if b.t_main != self.t_main or np.asarray(b.thresholds, dtype=np.float64).tobytes() != self.thr.tobytes():
+                raise ValueError("merge_from: a block was taken at other thresholds than this evaluator's")
+            if b.data.device != self.device or b.data.dtype != torch.uint8 or not b.data.is_contiguous() or b.data.data_ptr() % 256:
+                raise ValueError("merge_from: a block is a contiguous, 256-B aligned uint8 tensor on the evaluator's device")
+        total = self.n_seen + sum(b.n_seen for b in blocks)
+        if self.capacity and total > self.capacity:
+            if not self.auto_grow:
+                raise ValueError(f"evaluator capacity {self.capacity} exceeded by the merged {total} samples")
+            self._grow(total)
+        src = (_lib.EvalSource * len(blocks))(*[_lib.EvalSource(b.data.data_ptr(), b.data.numel(), b.capacity, b.n_seen) for b in blocks])
+        self.ctx.call("vt_eval_merge", ctypes.c_void_p(self._ptr), self._bytes, self.N, self.T, self.capacity, self.n_seen, src, len(blocks),
+                      self._stream())
+        self.n_seen = total
 
     def read_state(self, with_ap=True):
         """(counts [N][T][2], support [N], row_stats [3], ap [N] or None, micro_ap or None) on the host: the one synchronisation."""

@@ -295,7 +295,8 @@ class FeederLoader:
     """A BatchFeeder with labels, seen as the loader evaluation.py expects: iterating yields {"pixel_values": x, "labels": y} with the
     consumer's CURRENT stream made to wait for the side stream's work on the batch.  Every iteration is a fresh pass over the paths
     (find_optimal_threshold and evaluate_model each make one).  `failed` collects the (path, exception) pairs of the last pass and
-    `batches` its (names, shape) sequence; `len(loader.dataset)` bounds the number of samples (the evaluator sizes its store by it)."""
+    `batches` its (names, shape) sequence; `len(loader.dataset)` bounds the number of samples (the evaluator sizes its store by it).
+    An empty path list -- a rank without a share under `evaluate --sharded` -- yields no batch."""
 
     def __init__(self, pipe, paths, labels, batch_size, resolution, **feeder_kwargs):
         self.pipe, self.dataset, self.labels = pipe, list(paths), labels
