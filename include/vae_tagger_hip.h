@@ -69,6 +69,14 @@ int vt_decoder_finalize(vt_context* ctx);
  * vt_summarize_confidence <- the per-image summary loop of infer_full.py:106-125 on the sorted outputs: per image the
  *                       first K (confidence fp32, tag index int32; -1 / 0 beyond N) pairs and stats[4] = {number of tags with
  *                       confidence >= threshold, max confidence, (sum of the first five) / 5, number of non-finite confidences}
+ * vt_summarize_confidence_per_class  the same summary with one threshold PER TAG (device fp32 class_thresholds [N], e.g. the
+ *                       per_class_thresholds a threshold search wrote): tag idx passes when confidence >= class_thresholds[idx] -- the
+ *                       CLI's >= convention (the evaluator's vt_eval_* decide with a strict >, as the reference does in both places); a
+ *                       NaN confidence never passes.  The passing tags are no longer a prefix of the sorted list: per image the first K
+ *                       PASSING (confidence, tag index) pairs are written in sorted order (0 / -1 behind the last passing one) and
+ *                       stats[4] = {number of passing tags, max confidence, (sum of the first five of the sorted list) / 5, number of
+ *                       non-finite confidences}.  Any N the sort supports.  With all thresholds equal to t: the same stats and the same
+ *                       first min(count, K) pairs as vt_summarize_confidence at t.
  * vt_status          sticky device-side health word of the context (SYNCHRONISES `stream`): bit 0 (VT_STATUS_NONFINITE) =
  *                       some GroupNorm saw non-finite statistics since the last clear -- an activation left the fp16 range
  *                       of the residual-stream storage (rerun with vt_set_flag(ctx, 4, 0)) or the weights hold inf / NaN;
@@ -87,6 +95,9 @@ int vt_get_confidence(vt_context* ctx, const float* logits, int B, int N, float*
 int vt_summarize_confidence(vt_context* ctx, const float* conf_sorted, const int64_t* indices, int B, int N, float threshold,
                             int K, float* top_conf_out /* [B][K] */, int32_t* top_idx_out /* [B][K] */,
                             float* stats_out /* [B][4] */, void* stream);
+int vt_summarize_confidence_per_class(vt_context* ctx, const float* conf_sorted, const int64_t* indices, int B, int N,
+                                      const float* class_thresholds /* device [N] */, int K, float* top_conf_out /* [B][K] */,
+                                      int32_t* top_idx_out /* [B][K] */, float* stats_out /* [B][4] */, void* stream);
 enum { VT_STATUS_NONFINITE = 1, VT_STATUS_FP8_SATURATED = 2 };
 int vt_status(vt_context* ctx, int clear, int* status_out /* host */, void* stream);
 /* the same word WITHOUT a host synchronisation: copied (and optionally cleared) in stream order into `status_out`, which is pinned host
@@ -149,7 +160,17 @@ int vt_resize_normalize_batch(vt_context* ctx, const vt_resize_item* items /* ho
  * the first n_seen keys of every class row IN PLACE (the state stays valid for further updates) and writes AP per class as fp64
  * (NaN for a class without a positive; scikit-learn's step-wise definition, ties grouped); with micro_ap_out != NULL it also ranks the
  * flattened store in `workspace`.  The read call copies counts [N][T][2], support [N] and row_stats [3] in stream order into device or
- * pinned host memory: they are valid once `stream` has passed the call. */
+ * pinned host memory: they are valid once `stream` has passed the call.
+ * The recount call re-decides every stored prediction under ONE THRESHOLD PER CLASS (device fp64 class_thresholds [N]) from the first
+ * n_seen keys of every class row, without touching the state: the probability comes back from the key's high word (the sort-key map is
+ * a bijection on the fp32 bits; -0 reads as +0), label and sample index from the low word, and a prediction is
+ * (double)p > class_thresholds[j], the rule of vt_eval_update.  counts_out [N][2] = (tp, fp) per class; row_stats_out [3] = { rows whose
+ * prediction row equals the label row, mismatching elements, non-finite probabilities } -- the state's own row_stats when every class
+ * gets thresholds[t_main], its counts[:, t, :] when every class gets thresholds[t].  The per-sample mismatch tally is indexed by the
+ * sample index in the key, so the result is the same before and after vt_eval_average_precision has sorted the rows, and on a state
+ * vt_eval_merge produced.  Needs a key store: capacity == 0 with n_seen > 0, or n_seen > capacity, is VT_ERR_INVALID.  The workspace
+ * (vt_eval_recount_workspace_bytes; device memory, 256-B aligned) holds the integer accumulators and the tally and is zeroed by the
+ * call; sums are integers (vector atomics), so the outputs are bit-reproducible.  Outputs: device or pinned host memory. */
 size_t vt_eval_state_bytes(int N, int T, long long capacity);
 int vt_eval_reset(vt_context* ctx, void* state, size_t state_bytes, int N, int T, const double* thresholds /* host [T] */, int t_main,
                   long long capacity, void* stream);
@@ -165,6 +186,10 @@ int vt_eval_average_precision(vt_context* ctx, void* state, size_t state_bytes, 
 int vt_eval_read_counts(vt_context* ctx, const void* state, size_t state_bytes, int N, int T, long long capacity, uint32_t* counts_out,
                         size_t counts_bytes, uint32_t* support_out, size_t support_bytes, uint64_t* row_stats_out, size_t row_stats_bytes,
                         void* stream);
+size_t vt_eval_recount_workspace_bytes(int N, long long n_seen);
+int vt_eval_recount(vt_context* ctx, const void* state, size_t state_bytes, int N, int T, long long capacity, long long n_seen,
+                    const double* class_thresholds /* DEVICE [N] */, uint32_t* counts_out /* [N][2] = (tp, fp) */, size_t counts_bytes,
+                    uint64_t* row_stats_out /* [3] */, size_t row_stats_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- sharded evaluation: a state block as a wire format, and the merge of several blocks on one device.  Same contract as above:
  * every size is checked on the host before anything is launched (undersized buffer: VT_ERR_WORKSPACE; null / misaligned pointer or

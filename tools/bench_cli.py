@@ -13,7 +13,12 @@ steps (what bench.py times) for the comparison.
 The bucketed mode times vae_tagger_amd.evaluate.main() with --use_bucketing (512 / 1024 / 64, one pass: --threshold 0.5) over N labelled
 files of mixed aspect ratio (half PNG, half JPEG), and then replays the SAME sequence of batch shapes from HBM-resident tensors through the
 same encode -> decoder -> sigmoid -> evaluator-update loop: the ratio of the two is what the input side (decode threads, PCIe, the
-side stream's resize) costs."""
+side stream's resize) costs.
+
+    python tools/bench_cli.py --bucketed --single_pass [--n 512] [--batch 16] [--tags 10000]
+
+times the threshold search + evaluation of the same list twice: the two-pass run (search pass, metrics pass) and `--single_pass` (one
+pass, the metrics recounted on the GPU from the stored keys) -- loop seconds and images per second of each, and whether the files agree."""
 import argparse, json, os, shutil, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import contextlib
@@ -38,6 +43,7 @@ ap.add_argument("--serial", action="store_true")
 ap.add_argument("--src_res", type=int, default=0, help="size of the files' pictures (default: --res, i.e. no resize needed; e.g. 1536 exercises the device resize)")
 ap.add_argument("--bucketed", action="store_true", help="time the evaluate CLI with --use_bucketing instead of infer_full")
 ap.add_argument("--host_metrics", action="store_true", help="(--bucketed) the evaluate CLI's host evaluator")
+ap.add_argument("--single_pass", action="store_true", help="(--bucketed) the one-pass search + evaluation against the two-pass run of the same list")
 a = ap.parse_args()
 
 BUCKETED_SIZES = [(1024, 1024), (1216, 832), (832, 1216), (1344, 768), (768, 1344), (1536, 1024), (1000, 1500), (1152, 896), (1600, 1200),
@@ -77,9 +83,27 @@ def bucketed_mode(tmp):
     with open(os.path.join(tmp, "tags.csv"), "w") as f:
         f.write("name\n" + "\n".join(f"tag_{i:05d}" for i in range(a.tags)) + "\n")
     common = ["--vae_checkpoint", os.path.join(tmp, "vae.safetensors"), "--decoder_checkpoint", os.path.join(tmp, "dec.pth"), "--tags_csv_path",
-              os.path.join(tmp, "tags.csv"), "--use_bucketing", "--batch_size", str(a.batch), "--workers", str(a.workers), "--threshold", "0.5",
-              "--output_dir", os.path.join(tmp, "out")]
+              os.path.join(tmp, "tags.csv"), "--use_bucketing", "--batch_size", str(a.batch), "--workers", str(a.workers)]
     common += (["--fp8"] if a.fp8 else []) + (["--host_resize"] if a.host_resize else []) + (["--host_metrics"] if a.host_metrics else [])
+    search = list(common)                                              # (the search runs: no --threshold, an output directory per run)
+    common += ["--threshold", "0.5", "--output_dir", os.path.join(tmp, "out")]
+    if a.single_pass:
+        rows = {}
+        with contextlib.redirect_stdout(sys.stderr):
+            evaluate.main(search + ["--json_path", os.path.join(tmp, "warm.json"), "--output_dir", os.path.join(tmp, "out_warm"), "--single_pass"])
+            for name, extra in (("two_pass", []), ("single_pass", ["--single_pass"]), ("two_pass_again", []), ("single_pass_again", ["--single_pass"])):
+                evaluate.main(search + ["--json_path", os.path.join(tmp, "data.json"), "--output_dir", os.path.join(tmp, "out_" + name)] + extra)
+                st = dict(evaluate.LAST_RUN_STATS)
+                rows[name] = {"passes": st["passes"], "images": st["images"], "loop_seconds": round(st["loop_seconds"], 3),
+                              "distinct_images_per_sec": round(st["images"] / st["loop_seconds"], 1)}
+        same = all(open(os.path.join(tmp, "out_two_pass", f), "rb").read() == open(os.path.join(tmp, "out_single_pass", f), "rb").read()
+                   for f in ("optimal_thresholds.json", "evaluation_results.csv", "evaluation_results_overall.json"))
+        print(json.dumps({"workload": f"evaluate CLI, --use_bucketing 512/1024/64, threshold search + evaluation, {a.n} files, batch {a.batch}, "
+                                      f"{a.tags} tags, {'fp8' if a.fp8 else 'bf16'}", "cores_available": len(os.sched_getaffinity(0)), "runs": rows,
+                          "single_over_two_pass_loop_seconds": round(rows["single_pass"]["loop_seconds"] / rows["two_pass"]["loop_seconds"], 3),
+                          "single_over_two_pass_loop_seconds_again": round(rows["single_pass_again"]["loop_seconds"] / rows["two_pass_again"]["loop_seconds"], 3),
+                          "files_byte_identical": same}), flush=True)
+        return
     with contextlib.redirect_stdout(sys.stderr):
         evaluate.main(common + ["--json_path", os.path.join(tmp, "warm.json")])
         evaluate.main(common + ["--json_path", os.path.join(tmp, "data.json")])

@@ -5,11 +5,17 @@
     python tools/bench_eval.py --n 2048                 # both legs, host first
     python tools/bench_eval.py --merge 8                # sharded evaluation's merge: W synthetic shards on one GPU (no model is loaded)
 
+    python tools/bench_eval.py --recount                # vt_eval_recount on a synthetic --tags x --n store (default 10000 x 8192; no model)
+
 Per leg one JSON line: the loop's images/s (first batch requested -> last batch finished on the GPU, both passes) and the seconds between
 the last batch and the return of the two calls (the metric finish: host numpy, or the device kernels + the final reads).
 --merge W: at N = --tags and n = 2048 and 8192 samples per shard, event-timed milliseconds of the W exports, of the merge (head + key
 kernel) and of the finish (sort + AP) on the merged state, next to a torch device-to-device copy of the same key bytes in the same
-process -- the yardstick: the key kernel reads and writes every key once, 2 x key bytes -- with 16-B and with 8-B accesses (flag 21)."""
+process -- the yardstick: the key kernel reads and writes every key once, 2 x key bytes -- with 16-B and with 8-B accesses (flag 21).
+--recount: event-timed milliseconds of one vt_eval_recount call (the memset of its workspace, the key pass, the fold and the emit) on a store
+of --tags classes x --n samples, at a scalar and at a per-class threshold vector, on the unsorted store and again after
+vt_eval_average_precision has sorted the rows (the mismatch atomics then land scattered), next to a torch device-to-device copy of the
+same key bytes: the recount only reads them, the copy reads and writes them."""
 import argparse
 import contextlib
 import io
@@ -142,6 +148,53 @@ def run_merge(W, tags, reps):
     return out
 
 
+def run_recount(n, tags, reps):
+    import ctypes
+    import numpy as np
+    from vae_tagger_amd.evaluation import DeviceMultiLabelEvaluator
+    names = [f"tag_{i:05d}" for i in range(tags)]
+    g = torch.Generator(device="cuda").manual_seed(1)
+    ev = DeviceMultiLabelEvaluator(names, "cuda", capacity=n)
+    # what a trained tagger's outputs look like to the counter: ~2 % positives, few predictions above the threshold (squared uniforms)
+    for lo in range(0, n, 2048):
+        b = min(2048, n - lo)
+        ev.update(torch.rand(b, tags, generator=g, device="cuda") ** 6, (torch.rand(b, tags, generator=g, device="cuda") < 0.02).to(torch.uint8))
+    key_bytes = n * tags * 8
+    vec = np.random.default_rng(0).choice(ev.grid, size=tags)
+    res = {"recount": True, "n": n, "tags": tags, "reps": reps, "key_bytes": key_bytes}
+    first = {}
+    vp = ctypes.c_void_p                                                  # the C call itself is timed, on buffers allocated once
+    counts = torch.empty(tags, 2, dtype=torch.int32, device="cuda")
+    rows = torch.empty(3, dtype=torch.int64, device="cuda")
+    ws_bytes = ev.ctx.lib.vt_eval_recount_workspace_bytes(tags, n)
+    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device="cuda")
+    wp = (ws.data_ptr() + 255) // 256 * 256
+    for state in ("unsorted", "sorted"):
+        for name, thr in (("scalar", 0.5), ("per_class", vec), ("scalar_0.99", 0.99)):     # 0.99: few predictions, so few mismatch atomics
+            first.setdefault(name, ev.recount(thr))
+            again = ev.recount(thr)
+            assert all(np.array_equal(x, y) for x, y in zip(first[name], again)), "recount changed with the order of the keys"
+            thr_dev = torch.from_numpy(np.broadcast_to(np.asarray(thr, dtype=np.float64), (tags,)).copy()).cuda()
+            best, med = _timed(lambda: ev.ctx.call("vt_eval_recount", vp(ev._ptr), ev._bytes, ev.N, ev.T, ev.capacity, ev.n_seen, vp(thr_dev.data_ptr()),
+                                                   vp(counts.data_ptr()), counts.numel() * 4, vp(rows.data_ptr()), 24, vp(wp), ws_bytes, ev._stream()), reps)
+            assert np.array_equal(counts.cpu().numpy().view(np.uint32), first[name][0]) and np.array_equal(rows.cpu().numpy().view(np.uint64), first[name][1])
+            res[f"recount_ms_{state}_{name}"] = round(best, 3)
+            res[f"recount_ms_median_{state}_{name}"] = round(med, 3)
+            res[f"recount_read_bytes_per_s_{state}_{name}"] = round(key_bytes / (best * 1e-3), 0)
+        if state == "unsorted":
+            for name in first:
+                res[f"mismatching_elements_{name}"] = int(first[name][1][1])
+            ev.read_state(with_ap=True)                                      # sorts the class rows in place
+    src = torch.empty(key_bytes, dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(src)
+    best_c, med_c = _timed(lambda: dst.copy_(src), reps)
+    res["torch_copy_ms"] = round(best_c, 3)
+    res["torch_copy_bytes_per_s"] = round(2 * key_bytes / (best_c * 1e-3), 0)
+    for state in ("unsorted", "sorted"):
+        res[f"recount_over_copy_{state}_per_class"] = round(res[f"recount_ms_{state}_per_class"] / best_c, 3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=2048)
@@ -151,7 +204,11 @@ def main():
     ap.add_argument("--leg", choices=["host", "device", "both"], default="both")
     ap.add_argument("--merge", type=int, default=0, help="time export / merge / finish of this many synthetic shards (1..64) and exit")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--recount", action="store_true", help="time vt_eval_recount on a synthetic --tags x --n store (--n defaults to 8192 here) and exit")
     args = ap.parse_args()
+    if args.recount:
+        print(json.dumps(run_recount(8192 if args.n == 2048 else args.n, args.tags, args.reps)), flush=True)
+        return
     if args.merge:
         print(json.dumps(run_merge(args.merge, args.tags, args.reps)), flush=True)
         return

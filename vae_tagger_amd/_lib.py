@@ -45,6 +45,7 @@ PROTOTYPES = {
     "vt_decode_logits": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "vt_get_confidence": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "vt_summarize_confidence": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "vt_summarize_confidence_per_class": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "vt_status": (_i, [_vp, _i, _c.POINTER(_i), _vp]),
     "vt_status_async": (_i, [_vp, _i, _vp, _vp]),
     "vt_encode_tag_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
@@ -62,6 +63,8 @@ PROTOTYPES = {
     "vt_eval_ap_workspace_bytes": (_sz, [_i, _ll]),
     "vt_eval_average_precision": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _vp, _sz, _vp, _vp, _sz, _vp]),
     "vt_eval_read_counts": (_i, [_vp, _vp, _sz, _i, _i, _ll, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "vt_eval_recount_workspace_bytes": (_sz, [_i, _ll]),
+    "vt_eval_recount": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "vt_eval_export": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _vp, _sz, _ll, _vp]),
     "vt_eval_merge": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _c.POINTER(EvalSource), _i, _vp]),
     "vt_encoder_flops": (_c.c_double, [_vp, _i, _i]),

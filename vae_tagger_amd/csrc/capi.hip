@@ -225,6 +225,17 @@ int vt_summarize_confidence(vt_context* c, const float* conf, const int64_t* idx
     return VT_OK;
 }
 
+int vt_summarize_confidence_per_class(vt_context* c, const float* conf, const int64_t* idx, int B, int N, const float* class_thresholds,
+                                      int K, float* top_conf, int32_t* top_idx, float* stats, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!conf || !idx || !class_thresholds || !top_conf || !top_idx || !stats || B <= 0 || N <= 0 || K <= 0)
+        return c->fail(VT_ERR_INVALID, "vt_summarize_confidence_per_class: bad argument");
+    HIPCK(c, vt_decoder_summary_per_class(conf, (const long long*)idx, B, N, class_thresholds, K, top_conf, (int*)top_idx, stats,
+                                          (hipStream_t)stream), "decoder_summary_per_class");
+    return VT_OK;
+}
+
 int vt_status(vt_context* c, int clear, int* status_out, void* stream) {
     if (!c) return VT_ERR_INVALID;
     DeviceGuard guard(c);
@@ -251,6 +262,8 @@ int vt_status_async(vt_context* c, int clear, int* status_out, void* stream) {
 }
 
 // ---- streaming evaluator (eval_metrics.hip).  Every argument is checked on the host before anything is launched or written. ----
+// reset / update / grow feed the state; average_precision, read_counts and recount (per-class thresholds, from the keys) read it out;
+// export / merge move it between ranks.
 namespace {
 bool eval_dims_ok(int N, int T, long long capacity) {
     return N > 0 && T > 0 && T <= VT_EVAL_MAX_T && capacity >= 0 && capacity <= VT_EVAL_MAX_N_SEEN &&
@@ -357,6 +370,33 @@ int vt_eval_read_counts(vt_context* c, const void* state, size_t state_bytes, in
     HIPCK(c, hipMemcpyAsync(counts_out, st + l.counts, nc, hipMemcpyDefault, s), "eval_read counts");
     HIPCK(c, hipMemcpyAsync(support_out, st + l.support, ns, hipMemcpyDefault, s), "eval_read support");
     HIPCK(c, hipMemcpyAsync(row_stats_out, st + l.row_stats, nr, hipMemcpyDefault, s), "eval_read row_stats");
+    return VT_OK;
+}
+
+size_t vt_eval_recount_workspace_bytes(int N, long long n_seen) {
+    if (N <= 0 || n_seen < 0 || n_seen > VT_EVAL_MAX_N_SEEN) return 0;
+    return vt_eval_recount_ws_bytes(N, n_seen);
+}
+
+int vt_eval_recount(vt_context* c, const void* state, size_t state_bytes, int N, int T, long long capacity, long long n_seen,
+                    const double* class_thresholds, uint32_t* counts_out, size_t counts_bytes, uint64_t* row_stats_out,
+                    size_t row_stats_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = eval_check_state(c, "vt_eval_recount", state, state_bytes, N, T, capacity)) return r;
+    if (n_seen < 0 || n_seen > VT_EVAL_MAX_N_SEEN || n_seen > capacity)
+        return c->fail(VT_ERR_INVALID, "vt_eval_recount: n_seen = %lld outside [0, capacity = %lld]%s", n_seen, capacity,
+                       capacity == 0 ? " (the state keeps no keys)" : "");
+    if (!class_thresholds || ((uintptr_t)class_thresholds & 7)) return c->fail(VT_ERR_INVALID, "vt_eval_recount: class_thresholds is null or misaligned");
+    if (!counts_out || ((uintptr_t)counts_out & 3) || !row_stats_out || ((uintptr_t)row_stats_out & 7))
+        return c->fail(VT_ERR_INVALID, "vt_eval_recount: an output is null or misaligned");
+    if (!workspace || misaligned(workspace)) return c->fail(VT_ERR_INVALID, "vt_eval_recount: workspace is null or not 256-B aligned");
+    const size_t nc = (size_t)N * 2 * 4, nr = 3 * 8, need = vt_eval_recount_ws_bytes(N, n_seen);
+    if (counts_bytes < nc || row_stats_bytes < nr)
+        return c->fail(VT_ERR_WORKSPACE, "vt_eval_recount: outputs hold %zu / %zu bytes, %zu / %zu needed", counts_bytes, row_stats_bytes, nc, nr);
+    if (workspace_bytes < need) return c->fail(VT_ERR_WORKSPACE, "vt_eval_recount: workspace holds %zu bytes, %zu needed", workspace_bytes, need);
+    HIPCK(c, vt_eval_launch_recount(state, vt_eval_layout(N, T, capacity), N, capacity, n_seen, class_thresholds, counts_out,
+                                    (unsigned long long*)row_stats_out, workspace, (hipStream_t)stream), "eval_recount");
     return VT_OK;
 }
 

@@ -424,6 +424,78 @@ __global__ __launch_bounds__(256) void dec_summary_kernel(const float* __restric
     }
 }
 
+// ---- the same summary under one threshold per class: tag idx passes when conf >= thr[idx] (NaN never passes), so the passing tags are
+// no longer a prefix of the sorted list.  One workgroup per image walks the list in tiles of 256 x PC_ITEMS consecutive elements; an
+// exclusive scan of the threads' pass counts (shuffle scan inside a wave + the 4 wave totals in LDS) gives every passing element its
+// rank among the passing ones, in sorted order, and the first K of them are written (0 / -1 behind the last one).  Any N.
+// stats[b] = { passing tags, max confidence, top-5 sum / 5, number of non-finite confidences } -- entries 1 to 3 as dec_summary_kernel.
+constexpr int PC_ITEMS = 4;
+
+__global__ __launch_bounds__(256) void dec_summary_per_class_kernel(const float* __restrict__ conf, const long long* __restrict__ idx, int N,
+                                                                    const float* __restrict__ thr, int K, float* __restrict__ top_conf,
+                                                                    int* __restrict__ top_idx, float* __restrict__ stats) {
+    __shared__ int s_wave[4], s_bad;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const float* c = conf + (long long)b * N;
+    const long long* ix = idx + (long long)b * N;
+    float* tc = top_conf + (long long)b * K;
+    int* ti = top_idx + (long long)b * K;
+    if (tid == 0) s_bad = 0;
+    int base = 0, bad = 0;                                   // passing elements before this tile (block-uniform)
+    for (int t0 = 0; t0 < N; t0 += 256 * PC_ITEMS) {
+        const int i0 = t0 + tid * PC_ITEMS;
+        float v[PC_ITEMS];
+        int id[PC_ITEMS];
+        int mine = 0;
+        unsigned pass = 0;
+#pragma unroll
+        for (int e = 0; e < PC_ITEMS; ++e) {
+            const int i = i0 + e;
+            v[e] = 0.f; id[e] = -1;
+            if (i < N) {
+                v[e] = c[i];
+                const long long k = ix[i];
+                id[e] = (int)k;
+                bad += !(fabsf(v[e]) <= 3.0e38f);
+                if (k >= 0 && k < N && v[e] >= thr[k]) { pass |= 1u << e; ++mine; }
+            }
+        }
+        int inc = mine;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(inc, d);
+            if (lane >= d) inc += o;
+        }
+        __syncthreads();                                     // the previous tile's wave totals have been read
+        if (lane == 63) s_wave[w] = inc;
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int x = s_wave[i];
+            if (i < w) before += x;
+            all += x;
+        }
+        int pos = base + before + inc - mine;
+#pragma unroll
+        for (int e = 0; e < PC_ITEMS; ++e) {
+            if (pass & (1u << e)) {
+                if (pos < K) { tc[pos] = v[e]; ti[pos] = id[e]; }
+                ++pos;
+            }
+        }
+        base += all;
+    }
+    if (bad) atomicAdd(&s_bad, bad);
+    for (int i = base + tid; i < K; i += 256) { tc[i] = 0.f; ti[i] = -1; }
+    __syncthreads();
+    if (tid == 0) {
+        float s5 = 0.f;
+        for (int i = 0; i < 5 && i < N; ++i) s5 += c[i];
+        float* o = stats + (long long)b * 4;
+        o[0] = (float)base; o[1] = c[0]; o[2] = s5 / 5.0f; o[3] = (float)s_bad;
+    }
+}
+
 }  // namespace
 
 #define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) return _e; } while (0)
@@ -535,5 +607,12 @@ hipError_t vt_decoder_summary(const float* conf, const long long* idx, int B, in
                               int* top_idx, float* stats, hipStream_t s) {
     if (B <= 0 || N <= 0 || K <= 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dec_summary_kernel, dim3(B), dim3(256), 0, s, conf, idx, N, threshold, K, top_conf, top_idx, stats); CKL();
+    return hipSuccess;
+}
+
+hipError_t vt_decoder_summary_per_class(const float* conf, const long long* idx, int B, int N, const float* class_thresholds, int K,
+                                        float* top_conf, int* top_idx, float* stats, hipStream_t s) {
+    if (B <= 0 || N <= 0 || K <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dec_summary_per_class_kernel, dim3(B), dim3(256), 0, s, conf, idx, N, class_thresholds, K, top_conf, top_idx, stats); CKL();
     return hipSuccess;
 }

@@ -5,6 +5,8 @@
 // atomics only, so the state is bit-reproducible whatever the launch timing.
 // Sharded evaluation: a state is exported as a compact block and several blocks are merged into one state (a head kernel adding the
 // integers, a key kernel appending the class rows with the sample index rebased) -- no atomics, no LDS.
+// Recount: a read-only pass over the stored keys re-decides every prediction under one threshold per class (vt_eval_recount): the
+// metrics at another operating point, or under per-class thresholds, without feeding the samples again.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -348,6 +350,94 @@ __global__ __launch_bounds__(256) void eval_merge_head_kernel(EvalMergeArg a, ch
     }
 }
 
+// ---- recount under a per-class threshold vector, from the stored keys ---------------------------------------------------------------
+// A read-only pass over the first n keys of every class row.  blockIdx.x = row * chunks + chunk, a chunk is RC_CH keys of one row read
+// 16 B per lane on the 16-B aligned part of the row (a row's first key sits at an odd index when row * pitch is odd: lane 0 of chunk 0
+// takes it on its own).  Per key: the probability comes back from the high word (the inverse of vt_sort_key_hi), label and sample index
+// from the low word; prediction = (double)p > thr[row], strict, as eval_accumulate_kernel decides.  tp / fp / non-finite are summed per
+// workgroup and leave as one integer atomic each into the workspace head; a mismatching element adds 1 to tally[sample] (integer vector
+// atomic) -- indexed by the sample the key names, not by its column, so a row that vt_eval_average_precision has sorted counts the same.
+constexpr int RC_CH = 4096;
+
+struct RecountAcc { unsigned tp, fp, bad; };
+
+__device__ __forceinline__ void recount_key(unsigned long long k, double th, long long n, uint32_t* __restrict__ tally, RecountAcc& a) {
+    const float p = vt_sort_key_score((unsigned)(k >> 32));
+    const unsigned lo = (unsigned)k;
+    const unsigned y = lo & 1u;
+    const unsigned sample = (~lo) >> 1;
+    const unsigned pred = (double)p > th ? 1u : 0u;
+    a.tp += pred & y;
+    a.fp += pred & (y ^ 1u);
+    a.bad += !(fabsf(p) <= 3.0e38f) ? 1u : 0u;
+    if (pred != y && (long long)sample < n) atomicAdd(&tally[sample], 1u);      // (a key of a valid state never names a sample >= n)
+}
+
+__global__ __launch_bounds__(256) void eval_recount_kernel(const unsigned long long* __restrict__ keys, long long pitch, long long n,
+                                                           long long chunks, const double* __restrict__ thr,
+                                                           uint32_t* __restrict__ tally, uint32_t* __restrict__ acc_counts,
+                                                           unsigned long long* __restrict__ acc_bad) {
+    __shared__ unsigned s_red[4][3];
+    const long long row = blockIdx.x / chunks, c0 = (long long)(blockIdx.x % chunks) * RC_CH;
+    const unsigned long long* __restrict__ kb = keys + row * pitch;
+    const double th = thr[row];
+    const int tid = threadIdx.x;
+    const long long lead = (row * pitch) & 1;
+    RecountAcc a{0u, 0u, 0u};
+    if (c0 == 0 && lead && tid == 0 && n > 0) recount_key(kb[0], th, n, tally, a);
+#pragma unroll
+    for (int k = 0; k < RC_CH / 512; ++k) {
+        const long long col = lead + c0 + 2 * (k * 256 + tid);
+        if (col + 1 < n) {
+            const ulonglong2 v = *(const ulonglong2*)(kb + col);
+            recount_key(v.x, th, n, tally, a);
+            recount_key(v.y, th, n, tally, a);
+        } else if (col < n) {
+            recount_key(kb[col], th, n, tally, a);
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        a.tp += __shfl_down(a.tp, d); a.fp += __shfl_down(a.fp, d); a.bad += __shfl_down(a.bad, d);
+    }
+    if ((tid & 63) == 0) { s_red[tid >> 6][0] = a.tp; s_red[tid >> 6][1] = a.fp; s_red[tid >> 6][2] = a.bad; }
+    __syncthreads();
+    if (tid < 3) {
+        const unsigned v = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
+        if (v) {
+            if (tid < 2) atomicAdd(&acc_counts[row * 2 + tid], v);
+            else atomicAdd(acc_bad, (unsigned long long)v);
+        }
+    }
+}
+
+// tally[sample] = mismatching classes of that sample -> acc_rows = (exactly matching rows, mismatching elements)
+__global__ __launch_bounds__(256) void eval_recount_fold_kernel(const uint32_t* __restrict__ tally, long long n,
+                                                                unsigned long long* __restrict__ acc_rows) {
+    __shared__ unsigned long long s_red[4][2];
+    unsigned long long exact = 0, mis = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const uint32_t m = tally[i];
+        exact += m == 0;
+        mis += m;
+    }
+    for (int d = 32; d > 0; d >>= 1) { exact += __shfl_down(exact, d); mis += __shfl_down(mis, d); }
+    if ((threadIdx.x & 63) == 0) { s_red[threadIdx.x >> 6][0] = exact; s_red[threadIdx.x >> 6][1] = mis; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const unsigned long long v = s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x];
+        if (v) atomicAdd(&acc_rows[threadIdx.x], v);
+    }
+}
+
+// workspace accumulators -> the caller's outputs (device or pinned host memory: plain stores only)
+__global__ __launch_bounds__(256) void eval_recount_emit_kernel(const uint32_t* __restrict__ acc_counts, const unsigned long long* __restrict__ acc_stats,
+                                                                long long n2, uint32_t* __restrict__ counts_out,
+                                                                unsigned long long* __restrict__ row_stats_out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n2) counts_out[i] = acc_counts[i];
+    if (blockIdx.x == 0 && threadIdx.x < 3) row_stats_out[threadIdx.x] = acc_stats[threadIdx.x];
+}
+
 #define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) return _e; } while (0)
 #define CKL() CK(hipGetLastError())
 
@@ -454,5 +544,33 @@ hipError_t vt_eval_launch_merge(void* dst, const EvalLayout& l, int N, long long
     const long long quads = (long long)((l.head_bytes - l.support) / 16);
     hipLaunchKernelGGL(eval_merge_head_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, a, (char*)dst, l.support, l.row_stats, quads); CKL();
     if (dst_capacity > 0) CK(launch_merge_keys(a, l.keys, (unsigned long long*)((char*)dst + l.keys), dst_capacity, N, vec, s));
+    return hipSuccess;
+}
+
+size_t vt_eval_recount_ws_bytes(int N, long long n_seen) {
+    return vt_eval_align(sizeof(uint64_t) * 3) + vt_eval_align(sizeof(uint32_t) * 2 * (size_t)N) + vt_eval_align(sizeof(uint32_t) * (size_t)n_seen);
+}
+
+hipError_t vt_eval_launch_recount(const void* state, const EvalLayout& l, int N, long long capacity, long long n_seen, const double* thr,
+                                  uint32_t* counts_out, unsigned long long* row_stats_out, void* ws, hipStream_t s) {
+    // workspace: stats uint64 [3] = (exact rows, mismatching elements, non-finite) | counts uint32 [N][2] | tally uint32 [n_seen]
+    char* w = (char*)ws;
+    unsigned long long* acc_stats = (unsigned long long*)w;
+    uint32_t* acc_counts = (uint32_t*)(w + vt_eval_align(sizeof(uint64_t) * 3));
+    uint32_t* tally = acc_counts + vt_eval_align(sizeof(uint32_t) * 2 * (size_t)N) / sizeof(uint32_t);
+    CK(hipMemsetAsync(ws, 0, vt_eval_recount_ws_bytes(N, n_seen), s));
+    if (n_seen > 0) {
+        const long long chunks = (n_seen + RC_CH - 1) / RC_CH;
+        if ((long long)N * chunks > 0x7fffffffLL) return hipErrorInvalidValue;
+        const unsigned long long* keys = (const unsigned long long*)((const char*)state + l.keys);
+        hipLaunchKernelGGL(eval_recount_kernel, dim3((unsigned)((long long)N * chunks)), dim3(256), 0, s, keys, capacity, n_seen, chunks, thr, tally,
+                           acc_counts, acc_stats + 2); CKL();
+        long long fold_blocks = (n_seen + 255) / 256;
+        if (fold_blocks > 1024) fold_blocks = 1024;
+        hipLaunchKernelGGL(eval_recount_fold_kernel, dim3((unsigned)fold_blocks), dim3(256), 0, s, tally, n_seen, acc_stats); CKL();
+    }
+    const long long n2 = 2LL * N;
+    hipLaunchKernelGGL(eval_recount_emit_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, acc_counts, acc_stats, n2, counts_out,
+                       row_stats_out); CKL();
     return hipSuccess;
 }

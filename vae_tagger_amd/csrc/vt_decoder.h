@@ -32,3 +32,6 @@ size_t vt_decoder_workspace_floats(int B, int C, int H, int W);
 hipError_t vt_decoder_sort(const float* logits, int B, int N, float* conf, long long* idx, hipStream_t s);
 hipError_t vt_decoder_summary(const float* conf, const long long* idx, int B, int N, float threshold, int K, float* top_conf,
                               int* top_idx, float* stats, hipStream_t s);
+// the summary under one threshold per class (device class_thresholds [N]): the passing pairs are compacted in sorted order
+hipError_t vt_decoder_summary_per_class(const float* conf, const long long* idx, int B, int N, const float* class_thresholds, int K,
+                                        float* top_conf, int* top_idx, float* stats, hipStream_t s);

@@ -52,3 +52,10 @@ hipError_t vt_eval_launch_export(const void* state, const EvalLayout& l, void* o
                                  long long n_seen, long long out_capacity, int vec, hipStream_t s);
 // adds the sources' support / counts / row_stats into dst and (dst_capacity > 0) appends their keys: two launches whatever a.W is
 hipError_t vt_eval_launch_merge(void* dst, const EvalLayout& l, int N, long long dst_capacity, const EvalMergeArg& a, int vec, hipStream_t s);
+
+// recount under one threshold per class (DEVICE thr [N], fp64) from the first n_seen keys of every class row; the state is only read.
+// counts_out [N][2] = (tp, fp), row_stats_out [3] = (exactly matching rows, mismatching elements, non-finite probabilities); the
+// workspace (vt_eval_recount_ws_bytes) holds the accumulators and the per-sample mismatch tally, zeroed by the call itself.
+size_t vt_eval_recount_ws_bytes(int N, long long n_seen);
+hipError_t vt_eval_launch_recount(const void* state, const EvalLayout& l, int N, long long capacity, long long n_seen, const double* thr,
+                                  uint32_t* counts_out, unsigned long long* row_stats_out, void* ws, hipStream_t s);

@@ -8,9 +8,10 @@ pipelined loader of prefetch.py instead of a torch DataLoader over PIL transform
 Writes `optimal_thresholds.json`, `evaluation_results.csv` and `evaluation_results_overall.json` into --output_dir, as the reference
 does.  With --use_bucketing every image is centre-cropped to the aspect-ratio bucket of its own size and LANCZOS-resized (the
 reference's SmartResize; on the GPU, Pillow's arithmetic bit for bit) and batches are formed per bucket; without it every image is
-squashed to --resolution squared, as the inference CLIs do.  The data set is read TWICE unless --threshold is given: once for the
-threshold search and once for the metrics at the threshold it found (the exact-match and Hamming counts exist for one operating
-point per pass).  Metrics are accumulated on the GPU (DeviceMultiLabelEvaluator); --host_metrics is the host evaluator, same files.
+squashed to --resolution squared, as the inference CLIs do.  The data set is read TWICE unless --threshold or --single_pass is given:
+once for the threshold search and once for the metrics at the threshold it found.  --single_pass keeps one sort key per (class, image)
+on the GPU during the search pass and recounts the metrics at the threshold found from them (vt_eval_recount): same files, every image
+encoded once.  --per_class_thresholds adds the metrics under the searched per-class thresholds (evaluation_results_per_class_thresholds.csv).  Metrics are accumulated on the GPU (DeviceMultiLabelEvaluator); --host_metrics is the host evaluator, same files.
 One process by default; `torchrun ... -m vae_tagger_amd.evaluate ... --sharded` runs one rank per GPU: rank r takes paths[r::world], the
 evaluator states are merged on rank 0 (evaluation.merge_across_ranks) after each pass and rank 0 writes the files.  Reference: modules.py:487-548 (the JSON format), evaluation.py:173-275, train_decoder.py:284-333 (flags).
 """
@@ -86,6 +87,12 @@ def check_mode(args, world_size):
     if sharded and args.host_metrics:
         raise RuntimeError("--sharded merges the device evaluator's state; the host matrix of --host_metrics is not merged "
                            "(drop one of the two flags)")
+    if getattr(args, "single_pass", False) and args.threshold is not None:
+        raise RuntimeError("--single_pass merges the threshold search and the evaluation into one pass; with --threshold there is no "
+                           "search and the run is one pass already (drop one of the two flags)")
+    if getattr(args, "per_class_thresholds", False) and args.threshold is not None:
+        raise RuntimeError("--per_class_thresholds reports the metrics under the thresholds the search finds; with --threshold there "
+                           "is no search (drop one of the two flags)")
     if world_size > 1 and not sharded:
         raise RuntimeError("vae_tagger_amd.evaluate runs in a single process unless --sharded is given: the metrics are accumulated on "
                            "one GPU (start it without torchrun / with WORLD_SIZE=1, or pass --sharded to merge the ranks' states)")
@@ -93,7 +100,7 @@ def check_mode(args, world_size):
 
 def evaluate(args):
     import time
-    from .evaluation import evaluate_model, find_optimal_threshold
+    from .evaluation import evaluate_and_search, evaluate_model, find_optimal_threshold
     from .infer_full import load_models
     from .pipeline import EncodeTagPipeline
     check_mode(args, int(os.environ.get("WORLD_SIZE", "1")))
@@ -128,20 +135,32 @@ def evaluate(args):
     os.makedirs(args.output_dir, exist_ok=True)
     t0 = time.perf_counter()
     passes = 0
-    if args.threshold is None:
+    per_class = bool(getattr(args, "per_class_thresholds", False))
+    per_class_metrics = None
+    if getattr(args, "single_pass", False):
         if rank == 0:
-            print("寻找最优分类阈值...")
-        optimal = find_optimal_threshold(vae_model, decoder, loader, tag_names, device, args.output_dir, device_metrics=device_metrics,
-                                         group=group)
-        threshold = optimal["global_threshold"]          # with a group: rank 0's dict, broadcast -- the same threshold on every rank
+            print("寻找最优分类阈值并进行最终评估 (单次遍历)...")
+        optimal, metrics, per_class_metrics = evaluate_and_search(vae_model, decoder, loader, tag_names, device, args.output_dir,
+                                                                  device_metrics=device_metrics, group=group, per_class=per_class)
+        threshold = optimal["global_threshold"]
         passes += 1
     else:
-        optimal, threshold = None, float(args.threshold)
-    if rank == 0:
-        print("使用最优阈值进行最终评估...")
-    metrics = evaluate_model(vae_model, decoder, loader, tag_names, device, threshold, args.output_dir, device_metrics=device_metrics,
-                             group=group)
-    passes += 1
+        if args.threshold is None:
+            if rank == 0:
+                print("寻找最优分类阈值...")
+            optimal = find_optimal_threshold(vae_model, decoder, loader, tag_names, device, args.output_dir, device_metrics=device_metrics,
+                                             group=group)
+            threshold = optimal["global_threshold"]          # with a group: rank 0's dict, broadcast -- the same threshold on every rank
+            passes += 1
+        else:
+            optimal, threshold = None, float(args.threshold)
+        if rank == 0:
+            print("使用最优阈值进行最终评估...")
+        metrics = evaluate_model(vae_model, decoder, loader, tag_names, device, threshold, args.output_dir, device_metrics=device_metrics,
+                                 group=group, per_class_thresholds=optimal if per_class else None)
+        if per_class:
+            metrics, per_class_metrics = metrics
+        passes += 1
     torch.cuda.synchronize()
     LAST_RUN_STATS.update(loop_seconds=time.perf_counter() - t0, images=sum(len(n) for n, _ in loader.batches), passes=passes,
                           batches=list(loader.batches))
@@ -151,17 +170,20 @@ def evaluate(args):
         objs = [None] * world if rank == 0 else None
         dist.gather_object((failed, images), objs, dst=0, group=group)
         if rank != 0:
-            return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": None}
+            return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": None,
+                    **({"per_class_metrics": per_class_metrics} if per_class else {})}
         failed = [f for part, _ in objs for f in part]   # every file belongs to one rank: each failure is counted once
         images = sum(n for _, n in objs)
     for p, e in failed:
         print(f"跳过图像 {p}，错误原因: {e}")
     print(f"评估完成！图像: {images}, 跳过: {len(failed) + len(data.missing)}, 阈值: {threshold:.3f}")
-    return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": len(failed) + len(data.missing)}
+    return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": len(failed) + len(data.missing),
+            **({"per_class_metrics": per_class_metrics} if per_class else {})}
 
 
-def build_parser(distributed=False):
-    """The single-process flag set; distributed=True (what `main` parses with) adds --sharded."""
+def build_parser(distributed=False, recount=False):
+    """The single-process flag set; distributed=True adds --sharded, recount=True the flags that rest on the device recount
+    (--single_pass, --per_class_thresholds).  `main` parses with both."""
     p = argparse.ArgumentParser(description="在带标签的数据集上评估VAE + 分类解码器 (阈值搜索 + 多标签指标)。")
     p.add_argument("--vae_checkpoint", type=str, required=True, help="预训练VAE模型文件路径 (.safetensors)")
     p.add_argument("--vae_config_path", type=str, default=None, help="VAE配置文件路径 (JSON格式)")
@@ -195,6 +217,13 @@ def build_parser(distributed=False):
     p.add_argument("--threshold", type=float, default=None,
                    help="skip the threshold search and evaluate at this threshold: ONE pass over the images instead of two "
                         "(search pass + metrics pass at the threshold found)")
+    if recount:
+        p.add_argument("--single_pass", action="store_true",
+                       help="threshold search and evaluation in ONE pass over the images: the metrics at the threshold found are recounted "
+                            "on the GPU from the evaluator's stored keys (same files as the two-pass run; not with --threshold)")
+        p.add_argument("--per_class_thresholds", action="store_true",
+                       help="also report the metrics under the searched per-class thresholds and write them as "
+                            "evaluation_results_per_class_thresholds.csv / _overall.json (no extra pass over the images; not with --threshold)")
     if distributed:
         p.add_argument("--sharded", action="store_true",
                        help="under torchrun: one rank per GPU, rank r evaluates paths[r::world], the device evaluator's states are "
@@ -203,7 +232,7 @@ def build_parser(distributed=False):
 
 
 def main(argv=None):
-    args = build_parser(distributed=True).parse_args(argv)
+    args = build_parser(distributed=True, recount=True).parse_args(argv)
     if args.no_attention:
         args.use_attention = False
     return evaluate(args)

@@ -155,64 +155,47 @@ def _probabilities(model, decoder, loader, device):
     return np.vstack(probs), np.vstack(labels)
 
 
-def evaluate_model(model, decoder, test_loader, class_names, device="cuda", threshold=0.5, output_dir=None, device_metrics=False,
-                   group=None):
-    """device_metrics=True: the probabilities never leave the GPU (DeviceMultiLabelEvaluator); same dict, prints and files.
-    group (with device_metrics only; torch.distributed.group.WORLD for the default group): `test_loader` is this rank's share; the
-    states are merged on rank 0, which finishes, prints and writes the files; every rank returns the same dict."""
-    model.eval(); decoder.eval()
-    if device_metrics and group is not None and _use_group(group):
-        def finish(ev):
-            metrics = ev.compute_metrics()
-            ev.print_metrics(metrics)
-            if output_dir:
-                os.makedirs(output_dir, exist_ok=True)
-                ev.save_metrics(metrics, os.path.join(output_dir, "evaluation_results.csv"))
-            return metrics
-        return _finish_on_rank0(_sharded_device_pass(model, decoder, test_loader, class_names, device, threshold, group), group, finish)
-    if device_metrics:
-        ev = _device_pass(model, decoder, test_loader, class_names, device, threshold)
-        metrics = ev.compute_metrics()
-        ev.print_metrics(metrics)
-        if output_dir:
-            os.makedirs(output_dir, exist_ok=True)
-            ev.save_metrics(metrics, os.path.join(output_dir, "evaluation_results.csv"))
-        return metrics
-    y_prob, y_true = _probabilities(model, decoder, test_loader, device)
+RESULTS_CSV = "evaluation_results.csv"
+PER_CLASS_RESULTS_CSV = "evaluation_results_per_class_thresholds.csv"     # the metrics under the searched per-class thresholds
+
+
+def threshold_vector(per_class, class_names, default):
+    """fp64 [N] in class order from find_optimal_threshold's dict (or its `per_class_thresholds` entry, or a plain {name: threshold}
+    mapping); a class the mapping does not name gets `default`.  An array is returned as it is."""
+    if isinstance(per_class, dict):
+        per_class = per_class.get("per_class_thresholds", per_class)
+        out = np.full(len(class_names), np.float64(default))
+        for i, name in enumerate(class_names):
+            v = per_class.get(name)
+            if v is not None:
+                out[i] = float(v["threshold"]) if isinstance(v, dict) else float(v)
+        return out
+    out = np.asarray(per_class, dtype=np.float64)
+    if out.shape != (len(class_names),):
+        raise ValueError(f"expected {len(class_names)} per-class thresholds, got an array of shape {out.shape}")
+    return out
+
+
+def _host_metrics(y_prob, y_true, class_names, device, threshold):
+    """The host evaluator on the whole probability matrix: `threshold` is a Python float (compared as `y_prob > 0.5` is) or an fp64
+    vector with one entry per class (float32 matrix > float64 row: compared in fp64)."""
     ev = MultiLabelEvaluator(class_names, device)
     ev.update((y_prob > threshold).astype(np.float32), y_true, y_prob)
-    metrics = ev.compute_metrics(threshold)
+    return ev.compute_metrics()
+
+
+def _report(metrics, output_dir, filename):
+    """Print the metrics and write `<filename>` + its `_overall.json` (MultiLabelEvaluator's own formats)."""
+    ev = MultiLabelEvaluator.__new__(MultiLabelEvaluator)
     ev.print_metrics(metrics)
     if output_dir:
         os.makedirs(output_dir, exist_ok=True)
-        ev.save_metrics(metrics, os.path.join(output_dir, "evaluation_results.csv"))
+        ev.save_metrics(metrics, os.path.join(output_dir, filename))
     return metrics
 
 
-def find_optimal_threshold(model, decoder, val_loader, class_names, device="cuda", output_dir=None, device_metrics=False, group=None):
-    """Per-class and global (macro-F1) threshold search over 0.10, 0.15 ... 0.85, all classes at once per threshold.
-    device_metrics=True: from the device evaluator's integer counts (counts only: no key store is kept).
-    group: as in evaluate_model -- the counts are merged on rank 0, every rank returns the same dict."""
-    model.eval(); decoder.eval()
-    if device_metrics and group is not None and _use_group(group):
-        def finish(ev):
-            results = ev.optimal_thresholds()
-            print(f"global threshold {results['global_threshold']:.3f} (macro F1 {results['global_f1']:.4f})")
-            if output_dir:
-                os.makedirs(output_dir, exist_ok=True)
-                with open(os.path.join(output_dir, "optimal_thresholds.json"), "w", encoding="utf-8") as fh:
-                    json.dump(results, fh, indent=2, ensure_ascii=False)
-            return results
-        return _finish_on_rank0(_sharded_device_pass(model, decoder, val_loader, class_names, device, 0.5, group, keys=False), group, finish)
-    if device_metrics:
-        results = _device_pass(model, decoder, val_loader, class_names, device, 0.5, capacity=0).optimal_thresholds()
-        print(f"global threshold {results['global_threshold']:.3f} (macro F1 {results['global_f1']:.4f})")
-        if output_dir:
-            os.makedirs(output_dir, exist_ok=True)
-            with open(os.path.join(output_dir, "optimal_thresholds.json"), "w", encoding="utf-8") as fh:
-                json.dump(results, fh, indent=2, ensure_ascii=False)
-        return results
-    y_prob, y_true = _probabilities(model, decoder, val_loader, device)
+def _host_search(y_prob, y_true, class_names):
+    """find_optimal_threshold's search on the host matrix."""
     y_true = y_true > 0
     thresholds = np.arange(0.1, 0.9, 0.05)
     c = y_true.shape[1]
@@ -228,15 +211,96 @@ def find_optimal_threshold(model, decoder, val_loader, class_names, device="cuda
         best_f[better], best_t[better] = f[better], t
         if f.mean() > g_f:
             g_f, g_t = float(f.mean()), float(t)
-    results = {"global_threshold": g_t, "global_f1": g_f,
-               "per_class_thresholds": {n: {"threshold": float(best_t[i]), "f1_score": float(best_f[i])}
-                                        for i, n in enumerate(class_names)}}
-    print(f"global threshold {g_t:.3f} (macro F1 {g_f:.4f})")
+    return {"global_threshold": g_t, "global_f1": g_f,
+            "per_class_thresholds": {n: {"threshold": float(best_t[i]), "f1_score": float(best_f[i])}
+                                     for i, n in enumerate(class_names)}}
+
+
+def _report_search(results, output_dir):
+    print(f"global threshold {results['global_threshold']:.3f} (macro F1 {results['global_f1']:.4f})")
     if output_dir:
         os.makedirs(output_dir, exist_ok=True)
         with open(os.path.join(output_dir, "optimal_thresholds.json"), "w", encoding="utf-8") as fh:
             json.dump(results, fh, indent=2, ensure_ascii=False)
     return results
+
+
+def evaluate_model(model, decoder, test_loader, class_names, device="cuda", threshold=0.5, output_dir=None, device_metrics=False,
+                   group=None, per_class_thresholds=None):
+    """device_metrics=True: the probabilities never leave the GPU (DeviceMultiLabelEvaluator); same dict, prints and files.
+    group (with device_metrics only; torch.distributed.group.WORLD for the default group): `test_loader` is this rank's share; the
+    states are merged on rank 0, which finishes, prints and writes the files; every rank returns the same dict.
+    per_class_thresholds (find_optimal_threshold's dict, a {name: threshold} mapping or an fp64 vector; a class it does not name is
+    decided at `threshold`): the metrics under them are reported as well -- recounted from the same pass's key store on the device
+    routes -- and written as evaluation_results_per_class_thresholds.csv / _overall.json; the return value is then
+    (metrics, per_class_metrics)."""
+    model.eval(); decoder.eval()
+
+    def finish(ev):
+        metrics = _report(ev.compute_metrics(), output_dir, RESULTS_CSV)
+        if per_class_thresholds is None:
+            return metrics
+        vec = threshold_vector(per_class_thresholds, class_names, threshold)
+        return metrics, _report(ev.compute_metrics_at(vec), output_dir, PER_CLASS_RESULTS_CSV)
+    if device_metrics and group is not None and _use_group(group):
+        return _finish_on_rank0(_sharded_device_pass(model, decoder, test_loader, class_names, device, threshold, group), group, finish)
+    if device_metrics:
+        return finish(_device_pass(model, decoder, test_loader, class_names, device, threshold))
+    y_prob, y_true = _probabilities(model, decoder, test_loader, device)
+    metrics = _report(_host_metrics(y_prob, y_true, class_names, device, threshold), output_dir, RESULTS_CSV)
+    if per_class_thresholds is None:
+        return metrics
+    vec = threshold_vector(per_class_thresholds, class_names, threshold)
+    return metrics, _report(_host_metrics(y_prob, y_true, class_names, device, vec), output_dir, PER_CLASS_RESULTS_CSV)
+
+
+def find_optimal_threshold(model, decoder, val_loader, class_names, device="cuda", output_dir=None, device_metrics=False, group=None):
+    """Per-class and global (macro-F1) threshold search over 0.10, 0.15 ... 0.85, all classes at once per threshold.
+    device_metrics=True: from the device evaluator's integer counts (counts only: no key store is kept).
+    group: as in evaluate_model -- the counts are merged on rank 0, every rank returns the same dict."""
+    model.eval(); decoder.eval()
+    if device_metrics and group is not None and _use_group(group):
+        def finish(ev):
+            return _report_search(ev.optimal_thresholds(), output_dir)
+        return _finish_on_rank0(_sharded_device_pass(model, decoder, val_loader, class_names, device, 0.5, group, keys=False), group, finish)
+    if device_metrics:
+        return _report_search(_device_pass(model, decoder, val_loader, class_names, device, 0.5, capacity=0).optimal_thresholds(), output_dir)
+    y_prob, y_true = _probabilities(model, decoder, val_loader, device)
+    return _report_search(_host_search(y_prob, y_true, class_names), output_dir)
+
+
+def evaluate_and_search(model, decoder, loader, class_names, device="cuda", output_dir=None, device_metrics=True, group=None,
+                        per_class=False):
+    """find_optimal_threshold followed by evaluate_model at the threshold found, in ONE pass over `loader`: the key-keeping device
+    evaluator is fed once on the search grid, the search runs on its counts, and the metrics at the global threshold -- with
+    per_class=True also those under the searched per-class thresholds -- are recounted from the stored keys
+    (DeviceMultiLabelEvaluator.compute_metrics_at); the encoder, about 99 % of the work per image, runs once per image.  Prints and
+    writes what the two functions print and write (optimal_thresholds.json, evaluation_results.csv, evaluation_results_overall.json;
+    per_class: evaluation_results_per_class_thresholds.csv / _overall.json as well).  Returns (optimal, metrics, per_class_metrics or
+    None).  group: the sharded pass with keys, merged and finished on rank 0; every rank returns rank 0's dicts.
+    device_metrics=False: the one host probability matrix serves the search and both evaluations."""
+    model.eval(); decoder.eval()
+
+    def finish(ev):
+        optimal = _report_search(ev.optimal_thresholds(), output_dir)
+        metrics = _report(ev.compute_metrics_at(optimal["global_threshold"]), output_dir, RESULTS_CSV)
+        pc = None
+        if per_class:
+            vec = threshold_vector(optimal, class_names, optimal["global_threshold"])
+            pc = _report(ev.compute_metrics_at(vec), output_dir, PER_CLASS_RESULTS_CSV)
+        return optimal, metrics, pc
+    if device_metrics and group is not None and _use_group(group):
+        return tuple(_finish_on_rank0(_sharded_device_pass(model, decoder, loader, class_names, device, 0.5, group, keys=True), group, finish))
+    if device_metrics:
+        return finish(_device_pass(model, decoder, loader, class_names, device, 0.5))
+    y_prob, y_true = _probabilities(model, decoder, loader, device)
+    optimal = _report_search(_host_search(y_prob, y_true, class_names), output_dir)
+    metrics = _report(_host_metrics(y_prob, y_true, class_names, device, optimal["global_threshold"]), output_dir, RESULTS_CSV)
+    pc = None
+    if per_class:
+        vec = threshold_vector(optimal, class_names, optimal["global_threshold"])
+        pc = _report(_host_metrics(y_prob, y_true, class_names, device, vec), output_dir, PER_CLASS_RESULTS_CSV)
+    return optimal, metrics, pc
 
 
 # ---- device-side evaluator ---------------------------------------------------------------------------------------------------------
@@ -602,6 +666,51 @@ class DeviceMultiLabelEvaluator(MultiLabelEvaluator):
             import warnings
             warnings.warn("DeviceMultiLabelEvaluator(capacity=0) keeps no ranking: mAP, mAP_micro, mAP_weighted and the per-class ap are omitted")
         return finish_from_counts(counts, support, row_stats, self.n_seen, ap, micro, self.t_main, self.class_names)[0]
+
+    def _recount_async(self, thresholds):
+        """Queue vt_eval_recount on the current stream: (counts int32 [N][2], row_stats int64 [3]) pinned tensors, valid after a sync."""
+        import ctypes
+        if self.n_seen == 0:
+            raise ValueError("no data: call update() first")
+        if not self.capacity:
+            raise ValueError("recount needs the key store: this evaluator keeps counts only (capacity 0)")
+        thr = np.asarray(thresholds, dtype=np.float64)
+        if thr.ndim == 0:
+            thr = np.full(self.N, thr)
+        if thr.shape != (self.N,):
+            raise ValueError(f"expected a scalar or {self.N} thresholds, got an array of shape {thr.shape}")
+        thr_dev = torch.from_numpy(np.ascontiguousarray(thr)).to(self.device)
+        counts = torch.empty(self.N, 2, dtype=torch.int32, pin_memory=True)
+        row_stats = torch.empty(3, dtype=torch.int64, pin_memory=True)
+        ws_bytes = self.ctx.lib.vt_eval_recount_workspace_bytes(self.N, self.n_seen)
+        ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=self.device)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self.ctx.call("vt_eval_recount", ctypes.c_void_p(self._ptr), self._bytes, self.N, self.T, self.capacity, self.n_seen, vp(thr_dev),
+                      vp(counts), counts.numel() * 4, vp(row_stats), 24, ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256), ws_bytes,
+                      self._stream())
+        stream = torch.cuda.current_stream(self.device)
+        thr_dev.record_stream(stream); ws.record_stream(stream)
+        return counts, row_stats
+
+    def recount(self, thresholds):
+        """Re-decide every stored prediction as (double)p > thresholds[class] (a scalar serves every class; fp64, compared as given)
+        from the key store: (counts uint32 [N][2] = (tp, fp), row_stats uint64 [3] = (exactly matching rows, mismatching elements,
+        non-finite probabilities)).  The state is not modified; the result does not depend on whether the rows have been ranked."""
+        counts, row_stats = self._recount_async(thresholds)
+        torch.cuda.current_stream(self.device).synchronize()
+        return counts.numpy().view(np.uint32).copy(), row_stats.numpy().view(np.uint64).copy()
+
+    def compute_metrics_at(self, thresholds, with_ap=True):
+        """compute_metrics' dict at another operating point, recounted from the key store.  A scalar is an operating point as the
+        constructor's `threshold` is (compared in fp32, as `y_prob > 0.5` is: it is rounded to fp32 first); an array holds one
+        threshold per class, compared in fp64 as given (numpy's float32 matrix > float64 row)."""
+        thr = np.asarray(thresholds, dtype=np.float64)
+        if thr.ndim == 0:
+            thr = np.float64(np.float32(thr))
+        counts, row_stats = self._recount_async(thr)
+        _, support, _, ap, micro = self.read_state(with_ap=with_ap)          # (synchronises: the recount's outputs are final too)
+        counts = counts.numpy().view(np.uint32).reshape(self.N, 1, 2)
+        return finish_from_counts(counts, support, row_stats.numpy().view(np.uint64), self.n_seen, ap, micro, 0, self.class_names)[0]
 
     def optimal_thresholds(self):
         """find_optimal_threshold's dict over the search grid."""

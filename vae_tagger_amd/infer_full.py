@@ -100,8 +100,36 @@ def summarize(conf_row, idx_row, tag_names, threshold):
             "avg_confidence_top5": float(f"{sum(top5) / 5:.4f}")}      # always divides by 5, like the reference
 
 
-def _entries_from_summary(summary, conf, idx, tag_names, copy_stream=None):
+def summarize_per_class(conf_row, idx_row, tag_names, thresholds):
+    """`summarize` with one threshold per tag (`thresholds[i]` for tag i): a tag passes when its confidence >= its own threshold, so a
+    lower-ranked tag may pass where a higher-ranked one does not; the whole sorted list is looked at.  The host reference of
+    vt_summarize_confidence_per_class."""
+    predicted = []
+    for c, i in zip(conf_row, idx_row):
+        c = float(c)
+        if c >= float(thresholds[int(i)]):          # (a NaN confidence fails the test)
+            predicted.append({"tag": tag_names[int(i)], "confidence": float(f"{c:.4f}")})
+    top5 = [float(c) for c in conf_row[:5]]
+    return {"predicted_tags": predicted, "total_tags_above_threshold": len(predicted),
+            "max_confidence": float(f"{float(conf_row[0]):.4f}"),
+            "avg_confidence_top5": float(f"{sum(top5) / 5:.4f}")}
+
+
+def load_class_thresholds(path, tag_names, default):
+    """fp32 [N] from the `per_class_thresholds` of an optimal_thresholds.json (what the threshold search of vae_tagger_amd.evaluate, or
+    the reference's find_optimal_threshold, writes); a tag the file does not name uses `default` (--confidence_threshold)."""
+    import numpy as np
+    from .evaluation import threshold_vector
+    with open(path, "r", encoding="utf-8") as fh:
+        data = json.load(fh)
+    if not isinstance(data, dict) or not isinstance(data.get("per_class_thresholds"), dict):
+        raise ValueError(f"{path}: no per_class_thresholds mapping (expected the optimal_thresholds.json of a threshold search)")
+    return threshold_vector(data["per_class_thresholds"], tag_names, default).astype(np.float32)
+
+
+def _entries_from_summary(summary, conf, idx, tag_names, copy_stream=None, class_thresholds=None):
     """JSON entries from the host arrays of the device-side summary (formatting only).  Raises FloatingPointError on non-finite confidences.
+    `class_thresholds`: the host fp32 [N] copy of the per-tag thresholds the summary was taken under (None: one scalar threshold).
     `copy_stream`: the stream a longer prefix is fetched on (the pipelined loop passes one of its own, so that the copy of batch n's finished
     arrays does not queue behind batch n + 1's kernels on the compute stream)."""
     top_conf, top_idx, stats = summary
@@ -113,6 +141,11 @@ def _entries_from_summary(summary, conf, idx, tag_names, copy_stream=None):
                                      "or the checkpoint holds inf / NaN")
         if count <= top_conf.shape[1]:
             cs, ix = top_conf[b, :count], top_idx[b, :count]
+        elif class_thresholds is not None:          # rare, per-tag thresholds: the passing tags are no prefix -- the whole row, filtered here
+            with torch.cuda.stream(copy_stream) if copy_stream is not None else contextlib.nullcontext():
+                cs, ix = conf[b].cpu().numpy(), idx[b].cpu().numpy()
+            keep = cs >= class_thresholds[ix]
+            cs, ix = cs[keep], ix[keep]
         else:                                       # rare: more tags above the threshold than the summary carries
             with torch.cuda.stream(copy_stream) if copy_stream is not None else contextlib.nullcontext():
                 cs, ix = conf[b, :count].cpu().numpy(), idx[b, :count].cpu().numpy()
@@ -122,10 +155,11 @@ def _entries_from_summary(summary, conf, idx, tag_names, copy_stream=None):
     return out
 
 
-def summarize_batch(pipe, conf, idx, tag_names, threshold, top_k=TOP_K):
+def summarize_batch(pipe, conf, idx, tag_names, threshold, top_k=TOP_K, class_thresholds=None):
     """conf / idx: sorted device tensors [B,N] (pipe.tag).  Threshold count, top-k, max and top-5 mean come from the
-    device (vt_summarize_confidence): formatting only on the host.  Raises FloatingPointError on non-finite confidences."""
-    return _entries_from_summary(pipe.summarize(conf, idx, threshold, top_k), conf, idx, tag_names)
+    device (vt_summarize_confidence): formatting only on the host.  Raises FloatingPointError on non-finite confidences.
+    `threshold` may be a device fp32 [N] tensor of per-tag thresholds; `class_thresholds` is then its host copy (numpy)."""
+    return _entries_from_summary(pipe.summarize(conf, idx, threshold, top_k), conf, idx, tag_names, class_thresholds=class_thresholds)
 
 
 def _dist_setup():
@@ -176,8 +210,15 @@ class _Tagger:
     """The device leg of the loop: one batch -> JSON entries, with the health word's fall-backs (fp16 -> fp32 residual storage, fp8 -> bf16) and the
     reference's error granularity (a failure costs ONE image: infer_full.py:130-132)."""
 
-    def __init__(self, pipe, tag_names, threshold, fp8, f16=False):
+    def __init__(self, pipe, tag_names, threshold, fp8, f16=False, class_thresholds=None):
         self.pipe, self.tag_names, self.thr = pipe, tag_names, threshold
+        self.class_thr = None           # per-tag thresholds (host fp32 [N]); uploaded once, self.thr is then the device vector
+        if class_thresholds is not None:
+            import numpy as np
+            self.class_thr = np.ascontiguousarray(class_thresholds, dtype=np.float32)
+            if self.class_thr.shape != (len(tag_names),):
+                raise ValueError(f"expected {len(tag_names)} per-tag thresholds, got shape {self.class_thr.shape}")
+            self.thr = torch.from_numpy(self.class_thr).to(pipe.device)
         self.f16 = bool(f16)            # fp16 instead of bf16 conv operands (vt_set_flag 18): values must fit fp16
         self.fp8 = bool(fp8)            # current numeric mode of the context
         self.fp32_res = False
@@ -235,7 +276,7 @@ class _Tagger:
                         raise FloatingPointError("non-finite activations even with fp32 residual storage (inf / NaN pixels or weights?)")
                     print("警告: 激活值超出fp16范围，改用fp32残差存储")
                     self.fp32_res = True
-        return summarize_batch(pipe, conf, idx, self.tag_names, self.thr), self.fp8
+        return summarize_batch(pipe, conf, idx, self.tag_names, self.thr, class_thresholds=self.class_thr), self.fp8
 
     def clear_status(self):
         try:
@@ -290,7 +331,7 @@ class _Tagger:
                 try:
                     # (the event has passed: conf / idx are final, so a longer prefix can be copied on a stream that does not wait for batch n + 1)
                     entries = _entries_from_summary(self.pipe.unpack_summary(rec["host"], rec["K"]), rec["conf"], rec["idx"], self.tag_names,
-                                                    self.copy_stream)
+                                                    self.copy_stream, self.class_thr)
                     return [(p, e, rec["fp8"]) for p, e in zip(rec["names"], entries)], 0
                 except Exception:  # noqa: BLE001
                     pass
@@ -327,7 +368,11 @@ def infer_and_classify(args):
     f16 = bool(getattr(args, "fp16_operands", False)) and not getattr(args, "fp8", False)
     if f16:
         pipe.set_fp16_operands(True)
-    tg = _Tagger(pipe, tag_names, args.confidence_threshold, getattr(args, "fp8", False), f16)
+    class_thr = None
+    if getattr(args, "thresholds_json", None):
+        class_thr = load_class_thresholds(args.thresholds_json, tag_names, args.confidence_threshold)
+        print(f"使用每个标签各自的阈值: {args.thresholds_json}")
+    tg = _Tagger(pipe, tag_names, args.confidence_threshold, getattr(args, "fp8", False), f16, class_thresholds=class_thr)
     bs = max(1, int(getattr(args, "batch_size", 8)))
     host_resize = bool(getattr(args, "host_resize", False))
     serial = bool(getattr(args, "serial", False))
@@ -403,7 +448,8 @@ def infer_and_classify(args):
     return results
 
 
-def build_parser():
+def build_parser(per_class=False):
+    """per_class=True (what `main` parses with) adds --thresholds_json."""
     p = argparse.ArgumentParser(description="使用VAE和分类解码器进行图像分类。")
     p.add_argument("--vae_checkpoint", type=str, required=True, help="预训练VAE模型文件路径 (.safetensors)")
     p.add_argument("--vae_config_path", type=str, default=None, help="VAE配置文件路径 (JSON格式)")
@@ -413,6 +459,10 @@ def build_parser():
     p.add_argument("--output_dir", type=str, default="inference_output", help="结果保存目录")
     p.add_argument("--resolution", type=int, default=1024, help="模型训练时的分辨率")
     p.add_argument("--confidence_threshold", type=float, default=0.5, help="置信度阈值")
+    if per_class:
+        p.add_argument("--thresholds_json", type=str, default=None,
+                       help="optimal_thresholds.json of a threshold search: every tag is decided at its own per_class_thresholds entry "
+                            "(confidence >= threshold); tags the file does not name use --confidence_threshold (not in the reference)")
     p.add_argument("--use_attention", action="store_true", default=True, help="使用注意力机制 (默认开启)")
     p.add_argument("--no_attention", action="store_true", help="禁用注意力机制")
     p.add_argument("--use_spatial_attention", action="store_true", default=True, help="启用空间注意力")
@@ -440,7 +490,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(per_class=True).parse_args(argv)
     if args.no_attention:
         args.use_attention = False
     if args.model_checkpoint and (not args.vae_checkpoint or not args.decoder_checkpoint):

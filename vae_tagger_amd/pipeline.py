@@ -97,14 +97,22 @@ class EncodeTagPipeline:
     def summarize_async(self, conf, idx, threshold, top_k=64):
         """Device-side counterpart of the per-image loop of infer_full.py:106-125 on sorted (conf, idx), WITHOUT a host synchronisation:
         launches vt_summarize_confidence and an asynchronous copy of its B x (2K + 4) values into pinned host memory on the current stream.
-        Returns (packed pinned tensor, K); `unpack_summary` reads it once the stream has passed this point (an event / a sync)."""
+        Returns (packed pinned tensor, K); `unpack_summary` reads it once the stream has passed this point (an event / a sync).
+        `threshold`: a float, or a device fp32 [N] tensor of per-tag thresholds (vt_summarize_confidence_per_class: stats[:, 0] counts the
+        tags that pass their own threshold and the K pairs are the first K passing ones)."""
         B, N = conf.shape
         K = int(max(5, min(top_k, N)))
         tc = torch.empty(B, K, dtype=torch.float32, device=conf.device)
         ti = torch.empty(B, K, dtype=torch.int32, device=conf.device)
         st = torch.empty(B, 4, dtype=torch.float32, device=conf.device)
-        self.ctx.call("vt_summarize_confidence", vp(conf), vp(idx), B, N, float(threshold), K, vp(tc), vp(ti), vp(st),
-                      stream_ptr(conf.device))
+        if isinstance(threshold, torch.Tensor):          # one threshold per tag: the first K PASSING pairs, in sorted order
+            if threshold.dtype != torch.float32 or threshold.shape != (N,) or threshold.device != conf.device or not threshold.is_contiguous():
+                raise ValueError(f"per-class thresholds: a contiguous fp32 [{N}] tensor on {conf.device} expected")
+            self.ctx.call("vt_summarize_confidence_per_class", vp(conf), vp(idx), B, N, vp(threshold), K, vp(tc), vp(ti), vp(st),
+                          stream_ptr(conf.device))
+        else:
+            self.ctx.call("vt_summarize_confidence", vp(conf), vp(idx), B, N, float(threshold), K, vp(tc), vp(ti), vp(st),
+                          stream_ptr(conf.device))
         packed = torch.cat([tc, ti.view(torch.float32), st], dim=1)
         host = torch.empty(packed.shape, dtype=torch.float32, pin_memory=True)
         host.copy_(packed, non_blocking=True)                                         # one D2H copy
