@@ -214,6 +214,44 @@ int vt_eval_export(vt_context* ctx, const void* state, size_t state_bytes, int N
 int vt_eval_merge(vt_context* ctx, void* dst, size_t dst_bytes, int N, int T, long long dst_capacity, long long dst_n_seen,
                   const vt_eval_source* sources /* host [W] */, int W, void* stream);
 
+/* ---- streaming validation loss <- the validation loop of train_decoder.py:218-241 and the three losses it chooses from:
+ * nn.BCEWithLogitsLoss, FocalLoss and ClassBalancedLoss (improved_losses.py:39-72).  Forward only.  Same contract as vt_eval_*: ONE
+ * caller-owned device block (vt_loss_state_bytes(N) bytes, 256-B aligned) fed batch by batch in stream order; every byte size is
+ * checked on the host before anything is launched -- an undersized buffer is VT_ERR_WORKSPACE, a null / misaligned pointer or an
+ * out-of-range argument VT_ERR_INVALID, and nothing is written; no call synchronises the host.
+ * vt_loss_update takes the decoder's LOGITS fp32 [B][N] (not the sigmoid outputs, which saturate) and the labels: a VT_F32 label is
+ * used as its value (the `tag:weight` floats of the training JSON need not be 0 or 1), a VT_U8 label is 0 or 1.  Per element, in
+ * fp64 from the fp32 inputs:
+ *     bce   = max(x, 0) - x y + log1p(exp(-|x|))            (the stable form of binary_cross_entropy_with_logits)
+ *     focal = alpha (1 - exp(-bce))^gamma bce               (alpha, gamma stored at reset; gamma >= 0)
+ * Block layout (every section 256-B aligned):
+ *     params  { fp64 alpha, fp64 gamma, uint64 has_weights, uint64 N }
+ *   | totals  { fp64 [3] = sum over the updates of the PER-BATCH MEAN of bce, of focal and of weighted bce -- each
+ *               sum_j w_j (sum of class j over the batch) / (B N), w_j = 1 for the first two --, uint64 [3] = updates, elements,
+ *               non-finite logits }
+ *   | class weights fp64 [N] (1.0 when reset was given none)  | class sums fp64 [N][2] = (bce, focal) over every row seen
+ *   | the last update's partials, one { fp64 [3], uint64 } per 64 classes.
+ * totals[k] / updates is train_decoder.py's val_loss / val_steps for this batching; sum_j sums[j][k] / elements is the mean over all
+ * elements, independent of the batching.  A non-finite logit propagates into the sums as it would into the reference's loss; the
+ * counter says why.  An infinite class weight (a class without a sample, ClassBalancedLoss) makes the weighted sums infinite.
+ * Determinism: no floating-point atomic (no atomic at all); per update one thread owns a class, rows and classes are combined in an
+ * order fixed by (B, N) alone, so the state after a given call sequence is bit-identical from run to run.  B <= 4096 per update.
+ * vt_loss_reset clears the block; class_weights is a HOST fp64 [N] or NULL and is free again when the call returns.
+ * vt_loss_read copies the whole block as it stands, in stream order, into device or pinned host memory of vt_loss_state_bytes(N) bytes.
+ * vt_loss_merge adds the W sources into dst IN THE ORDER GIVEN (dst = ((dst + s_0) + s_1) + ...: reproducible for a given sharding);
+ * dst keeps its parameters.  The parameters every block was reset with are the caller's to state (HOST values, as (N, T, capacity)
+ * are for vt_eval_*): a source whose alpha, gamma or class weights differ bit-wise from dst's is VT_ERR_INVALID, as are W < 1, W > 64
+ * and a source that is dst or overlaps it. */
+typedef struct { const void* state; size_t state_bytes; double alpha; double gamma; const double* class_weights /* host [N] or NULL */; } vt_loss_source;
+size_t vt_loss_state_bytes(int N);
+int vt_loss_reset(vt_context* ctx, void* state, size_t state_bytes, int N, double alpha, double gamma,
+                  const double* class_weights /* host [N] or NULL */, void* stream);
+int vt_loss_update(vt_context* ctx, void* state, size_t state_bytes, int N, const float* logits /* [B][N] */,
+                   const void* labels /* [B][N] */, int labels_dtype /* VT_F32 | VT_U8 */, int B, void* stream);
+int vt_loss_read(vt_context* ctx, const void* state, size_t state_bytes, int N, void* out, size_t out_bytes, void* stream);
+int vt_loss_merge(vt_context* ctx, void* dst, size_t dst_bytes, int N, double alpha, double gamma,
+                  const double* class_weights /* host [N] or NULL */, const vt_loss_source* sources /* host [W] */, int W, void* stream);
+
 /* algorithmic FLOPs of one encoder forward at HxW -- for roofline reporting */
 double vt_encoder_flops(const vt_context* ctx, int H, int W);
 

@@ -6,6 +6,7 @@
     python tools/bench_eval.py --merge 8                # sharded evaluation's merge: W synthetic shards on one GPU (no model is loaded)
 
     python tools/bench_eval.py --recount                # vt_eval_recount on a synthetic --tags x --n store (default 10000 x 8192; no model)
+    python tools/bench_eval.py --sweep 10 --n 512       # the checkpoint sweep: K decoders per encode, interleaved with the one-decoder one-pass loop
 
 Per leg one JSON line: the loop's images/s (first batch requested -> last batch finished on the GPU, both passes) and the seconds between
 the last batch and the return of the two calls (the metric finish: host numpy, or the device kernels + the final reads).
@@ -15,7 +16,10 @@ process -- the yardstick: the key kernel reads and writes every key once, 2 x ke
 --recount: event-timed milliseconds of one vt_eval_recount call (the memset of its workspace, the key pass, the fold and the emit) on a store
 of --tags classes x --n samples, at a scalar and at a per-class threshold vector, on the unsorted store and again after
 vt_eval_average_precision has sorted the rows (the mismatch atomics then land scattered), next to a torch device-to-device copy of the
-same key bytes: the recount only reads them, the copy reads and writes them."""
+same key bytes: the recount only reads them, the copy reads and writes them.
+--sweep K: images/s of evaluation.sweep_checkpoints' loop over K decoders (seeds 1..K; loss accumulators on) and of the one-decoder one-pass loop
+(evaluate_and_search, the code of the single-checkpoint run), legs interleaved --reps times in one process; K x the one-decoder loop's time is what
+K separate runs cost.  Also the event-timed milliseconds of one vt_loss_update against one vt_eval_update at (--batch, --tags), each over 20 calls."""
 import argparse
 import contextlib
 import io
@@ -195,6 +199,63 @@ def run_recount(n, tags, reps):
     return res
 
 
+def run_sweep(K, vae, names, args):
+    import ctypes
+    from vae_tagger_amd.evaluation import DeviceMultiLabelEvaluator, evaluate_and_search, sweep_checkpoints
+    from vae_tagger_amd.losses import DeviceLossAccumulator, class_balanced_weights
+    decs = []
+    with contextlib.redirect_stdout(io.StringIO()):
+        for k in range(K):
+            d = create_attention_decoder(16, 16, 16, args.tags, {"use_spatial_attention": True, "use_self_attention": True})
+            d.load_state_dict(synth.synth_state_dict(synth.attention_decoder_manifest(args.tags), seed=1 + k), strict=False)
+            decs.append(d.to("cuda").eval())
+    x = synth.synth_images(args.batch, args.res, args.res, seed=0).cuda()
+    with torch.no_grad():
+        lat = vae.encode(x)
+        for d in decs:
+            torch.sigmoid(d(lat))
+    torch.cuda.synchronize()
+    weights = class_balanced_weights(torch.arange(1, args.tags + 1).numpy())
+    one_s, sweep_s = [], []
+    for _ in range(args.reps):                               # interleaved: one-decoder loop, sweep loop, ...
+        loader = Loader(args.n, args.batch, args.res, args.tags, "cuda")
+        with contextlib.redirect_stdout(io.StringIO()):
+            evaluate_and_search(vae, decs[0], loader, names, device="cuda")
+        one_s.append(loader.loop_s)
+        loader = Loader(args.n, args.batch, args.res, args.tags, "cuda")
+        with contextlib.redirect_stdout(io.StringIO()):
+            res = sweep_checkpoints(vae, decs, loader, names, device="cuda", class_weights=weights)
+        sweep_s.append(loader.loop_s)
+    one, sw = min(one_s), min(sweep_s)
+    out = {"sweep": K, "n": args.n, "tags": args.tags, "batch": args.batch, "res": args.res, "reps": args.reps,
+           "one_decoder_loop_images_per_s": round(args.n / one, 2), "sweep_loop_images_per_s": round(args.n / sw, 2),
+           "one_decoder_loop_s": [round(v, 4) for v in one_s], "sweep_loop_s": [round(v, 4) for v in sweep_s],
+           "sweep_over_one": round(sw / one, 4), "K_separate_runs_over_sweep": round(K * one / sw, 3),
+           "val_loss_bce": [r["loss"]["bce"]["mean_of_batch_means"] for r in res]}
+    # one vt_loss_update against one vt_eval_update at the same shape
+    logits = torch.randn(args.batch, args.tags, device="cuda") * 3
+    probs = torch.sigmoid(logits)
+    labels = (torch.rand(args.batch, args.tags, device="cuda") < 0.02).float()
+    acc = DeviceLossAccumulator(args.tags, "cuda", class_weights=weights)
+    ev = DeviceMultiLabelEvaluator(names, "cuda", capacity=args.batch * 21 * (args.reps + 1))
+    vp = ctypes.c_void_p
+
+    def loss_calls():
+        for _ in range(20):
+            acc.ctx.call("vt_loss_update", vp(acc._ptr), acc._bytes, acc.N, vp(logits.data_ptr()), vp(labels.data_ptr()), 0, args.batch, acc._stream())
+
+    def eval_calls():
+        for _ in range(20):
+            ev.ctx.call("vt_eval_update", vp(ev._ptr), ev._bytes, ev.N, ev.T, ev.t_main, ev.capacity, vp(probs.data_ptr()), vp(labels.data_ptr()), 0,
+                        args.batch, ev.n_seen, ev._stream())
+            ev.n_seen += args.batch
+    best_l, med_l = _timed(loss_calls, args.reps)
+    best_e, med_e = _timed(eval_calls, args.reps)
+    out.update(loss_update_ms=round(best_l / 20, 4), loss_update_ms_median=round(med_l / 20, 4), eval_update_ms=round(best_e / 20, 4),
+               eval_update_ms_median=round(med_e / 20, 4))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=2048)
@@ -204,6 +265,7 @@ def main():
     ap.add_argument("--leg", choices=["host", "device", "both"], default="both")
     ap.add_argument("--merge", type=int, default=0, help="time export / merge / finish of this many synthetic shards (1..64) and exit")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sweep", type=int, default=0, help="time the checkpoint sweep over this many decoders against the one-decoder one-pass loop and exit")
     ap.add_argument("--recount", action="store_true", help="time vt_eval_recount on a synthetic --tags x --n store (--n defaults to 8192 here) and exit")
     args = ap.parse_args()
     if args.recount:
@@ -220,6 +282,9 @@ def main():
     dec.load_state_dict(synth.synth_state_dict(synth.attention_decoder_manifest(args.tags), seed=1), strict=False)
     dec = dec.to("cuda").eval()
     names = [f"tag_{i:05d}" for i in range(args.tags)]
+    if args.sweep:
+        print(json.dumps(run_sweep(args.sweep, vae, names, args)), flush=True)
+        return
     with torch.no_grad():                                    # warm-up: weights uploaded, kernels loaded
         torch.sigmoid(dec(vae.encode(synth.synth_images(args.batch, args.res, args.res, seed=0).cuda())))
     torch.cuda.synchronize()

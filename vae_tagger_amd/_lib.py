@@ -28,6 +28,11 @@ class EvalSource(_c.Structure):
     _fields_ = [("state", _vp), ("state_bytes", _sz), ("capacity", _ll), ("n_seen", _ll)]
 
 
+class LossSource(_c.Structure):
+    """vt_loss_source: one state block handed to vt_loss_merge, with the (host) parameters it was reset with."""
+    _fields_ = [("state", _vp), ("state_bytes", _sz), ("alpha", _c.c_double), ("gamma", _c.c_double), ("class_weights", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/vae_tagger_hip.h declares
 PROTOTYPES = {
     "vt_version": (_c.c_char_p, []),
@@ -67,6 +72,11 @@ PROTOTYPES = {
     "vt_eval_recount": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "vt_eval_export": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _vp, _sz, _ll, _vp]),
     "vt_eval_merge": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _c.POINTER(EvalSource), _i, _vp]),
+    "vt_loss_state_bytes": (_sz, [_i]),
+    "vt_loss_reset": (_i, [_vp, _vp, _sz, _i, _c.c_double, _c.c_double, _vp, _vp]),
+    "vt_loss_update": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _i, _i, _vp]),
+    "vt_loss_read": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
+    "vt_loss_merge": (_i, [_vp, _vp, _sz, _i, _c.c_double, _c.c_double, _vp, _c.POINTER(LossSource), _i, _vp]),
     "vt_encoder_flops": (_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),

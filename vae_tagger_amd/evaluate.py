@@ -13,7 +13,11 @@ once for the threshold search and once for the metrics at the threshold it found
 on the GPU during the search pass and recounts the metrics at the threshold found from them (vt_eval_recount): same files, every image
 encoded once.  --per_class_thresholds adds the metrics under the searched per-class thresholds (evaluation_results_per_class_thresholds.csv).  Metrics are accumulated on the GPU (DeviceMultiLabelEvaluator); --host_metrics is the host evaluator, same files.
 One process by default; `torchrun ... -m vae_tagger_amd.evaluate ... --sharded` runs one rank per GPU: rank r takes paths[r::world], the
-evaluator states are merged on rank 0 (evaluation.merge_across_ranks) after each pass and rank 0 writes the files.  Reference: modules.py:487-548 (the JSON format), evaluation.py:173-275, train_decoder.py:284-333 (flags).
+evaluator states are merged on rank 0 (evaluation.merge_across_ranks) after each pass and rank 0 writes the files.
+--val_loss also reports the validation loss train_decoder.py keeps its best checkpoint by (BCE-with-logits, Focal and class-balanced
+BCE, accumulated on the GPU from the logits: validation_loss.json); --decoder_checkpoints A B C ... scores several checkpoints of one
+architecture in ONE pass -- every image is encoded once, each checkpoint's files go to output_dir/ckpt_<index>_<file stem>/ and
+output_dir/checkpoint_sweep.json ranks them.  Reference: modules.py:487-548 (the JSON format), evaluation.py:173-275, train_decoder.py:284-333 (flags).
 """
 import argparse
 import json
@@ -87,6 +91,15 @@ def check_mode(args, world_size):
     if sharded and args.host_metrics:
         raise RuntimeError("--sharded merges the device evaluator's state; the host matrix of --host_metrics is not merged "
                            "(drop one of the two flags)")
+    sweep = getattr(args, "decoder_checkpoints", None)
+    if (sweep or getattr(args, "val_loss", False)) and args.host_metrics:
+        raise RuntimeError("--val_loss and --decoder_checkpoints accumulate on the GPU (the loss from the logits, one evaluator per "
+                           "checkpoint); the host matrix of --host_metrics keeps neither (drop one of the flags)")
+    if sweep and args.threshold is not None:
+        raise RuntimeError("--decoder_checkpoints searches every checkpoint's own threshold in its one pass; with --threshold there is "
+                           "no search (drop one of the two flags)")
+    if sweep:
+        check_same_tag_count(sweep)
     if getattr(args, "single_pass", False) and args.threshold is not None:
         raise RuntimeError("--single_pass merges the threshold search and the evaluation into one pass; with --threshold there is no "
                            "search and the run is one pass already (drop one of the two flags)")
@@ -96,6 +109,89 @@ def check_mode(args, world_size):
     if world_size > 1 and not sharded:
         raise RuntimeError("vae_tagger_amd.evaluate runs in a single process unless --sharded is given: the metrics are accumulated on "
                            "one GPU (start it without torchrun / with WORLD_SIZE=1, or pass --sharded to merge the ranks' states)")
+
+
+def checkpoint_tag_count(path):
+    """The number of tags a decoder checkpoint scores: the rows of the classifier's last linear layer (the 2-D `classifier.<k>.weight`
+    of the highest k), read on the host."""
+    from .infer_full import load_state_dict_file
+    heads = {}
+    for k, v in load_state_dict_file(path).items():
+        parts = k.split(".")
+        if len(parts) == 3 and parts[0] == "classifier" and parts[2] == "weight" and parts[1].isdigit() and getattr(v, "ndim", 0) == 2:
+            heads[int(parts[1])] = int(v.shape[0])
+    if not heads:
+        raise RuntimeError(f"{path}: no classifier.<k>.weight matrix found, cannot tell the number of tags")
+    return heads[max(heads)]
+
+
+def check_same_tag_count(paths, count=checkpoint_tag_count):
+    """Refuse a sweep over checkpoints that score different numbers of tags (host only: before any GPU work)."""
+    for p in paths:
+        if not os.path.exists(p):
+            raise RuntimeError(f"解码器模型文件不存在: {p}")
+    counts = [count(p) for p in paths]
+    if len(set(counts)) > 1:
+        raise RuntimeError("--decoder_checkpoints: the checkpoints score different numbers of tags ("
+                           + ", ".join(f"{os.path.basename(str(p))}: {c}" for p, c in zip(paths, counts)) + ")")
+    return counts[0] if counts else None
+
+
+def _load_sweep_decoders(args, decoder, device):
+    """One decoder per checkpoint of --decoder_checkpoints, each with its own device context (the architecture of `decoder`)."""
+    import copy
+    from .infer_full import load_state_dict_file
+    decoders = []
+    for path in args.decoder_checkpoints:
+        ctx, decoder._ctx = getattr(decoder, "_ctx", None), None      # the copy gets a device context of its own on first use
+        try:
+            d = copy.deepcopy(decoder).cpu()
+        finally:
+            decoder._ctx = ctx
+        try:
+            d.load_state_dict(load_state_dict_file(path), strict=False)
+        except Exception as e:  # noqa: BLE001 - reference behaviour (load_models)
+            raise RuntimeError(f"无法加载Decoder模型: {e}")
+        decoders.append(d.to(device).eval())
+    return decoders
+
+
+def _run_val_loss(args, vae_model, decoder, tag_names, data, all_labels, loader, device, group, rank, per_class):
+    """--val_loss / --decoder_checkpoints: the passes that go through evaluation.sweep_checkpoints.  Returns (threshold, optimal,
+    metrics, per_class_metrics, passes, extra result keys)."""
+    from .evaluation import find_optimal_threshold, sweep_checkpoints
+    from .losses import class_balanced_weights, class_distribution, select_loss, sweep_dir_name, sweep_summary
+    selected = select_loss(args.use_class_balanced, args.use_focal_loss)
+    # class weights from the WHOLE JSON (every entry, as compute_class_distribution sees the dataset), before any sharding
+    weights = class_balanced_weights(class_distribution(all_labels, len(tag_names)))
+    kw = dict(group=group, focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, class_weights=weights, selected_loss=selected)
+    if args.decoder_checkpoints:
+        decoders = _load_sweep_decoders(args, decoder, device)
+        dirs = [os.path.join(args.output_dir, sweep_dir_name(i, p)) for i, p in enumerate(args.decoder_checkpoints)]
+        if rank == 0:
+            print(f"检查点扫描: {len(decoders)} 个解码器, 单次遍历...")
+        results = sweep_checkpoints(vae_model, decoders, loader, tag_names, device, dirs, per_class=per_class, **kw)
+        summary = sweep_summary([dict(r, path=p) for r, p in zip(results, args.decoder_checkpoints)], selected)
+        if rank == 0:
+            with open(os.path.join(args.output_dir, "checkpoint_sweep.json"), "w", encoding="utf-8") as fh:
+                json.dump(summary, fh, indent=2, ensure_ascii=False)
+            print(f"best_by_val_loss: {summary['best_by_val_loss']}  best_by_macro_f1: {summary['best_by_macro_f1']}")
+        best = results[summary["best_by_val_loss"]["index"] if summary["best_by_val_loss"] else 0]
+        return (best["optimal"]["global_threshold"], best["optimal"], best["metrics"], best["per_class_metrics"], 1,
+                {"sweep": summary, "checkpoints": results, "validation_loss": best["loss"]})
+    passes, optimal, threshold = 1, None, args.threshold
+    if not args.single_pass and args.threshold is None:
+        if rank == 0:
+            print("寻找最优分类阈值...")
+        optimal = find_optimal_threshold(vae_model, decoder, loader, tag_names, device, args.output_dir, device_metrics=True, group=group)
+        threshold, passes = optimal["global_threshold"], 2
+    if rank == 0:
+        print("寻找最优分类阈值并进行最终评估 (单次遍历)..." if args.single_pass else "使用最优阈值进行最终评估...")
+    r = sweep_checkpoints(vae_model, [decoder], loader, tag_names, device, [args.output_dir], threshold=None if args.single_pass else float(threshold),
+                          per_class=per_class, per_class_thresholds=optimal if (per_class and not args.single_pass) else None, **kw)[0]
+    if args.single_pass:
+        optimal, threshold = r["optimal"], r["optimal"]["global_threshold"]
+    return float(threshold), optimal, r["metrics"], r["per_class_metrics"], passes, {"validation_loss": r["loss"]}
 
 
 def evaluate(args):
@@ -118,6 +214,9 @@ def evaluate(args):
     device = torch.device("cuda", torch.cuda.current_device())
     vae_model, decoder, tag_names = load_models(args, device)
     data = TaggedImageList(args.json_path, args.tags_csv_path)
+    val_loss = bool(getattr(args, "val_loss", False) or getattr(args, "decoder_checkpoints", None))
+    # every entry of the JSON, as the reference's compute_class_distribution sees the dataset (a missing file is still an entry there)
+    all_labels = TaggedImageList(args.json_path, args.tags_csv_path, check_files=False).labels if val_loss else None
     if rank == 0:
         for p in data.missing:
             print(f"跳过图像 {p}，错误原因: 文件不存在")
@@ -137,7 +236,11 @@ def evaluate(args):
     passes = 0
     per_class = bool(getattr(args, "per_class_thresholds", False))
     per_class_metrics = None
-    if getattr(args, "single_pass", False):
+    extra = {}
+    if val_loss:
+        threshold, optimal, metrics, per_class_metrics, passes, extra = _run_val_loss(args, vae_model, decoder, tag_names, data, all_labels,
+                                                                                      loader, device, group, rank, per_class)
+    elif getattr(args, "single_pass", False):
         if rank == 0:
             print("寻找最优分类阈值并进行最终评估 (单次遍历)...")
         optimal, metrics, per_class_metrics = evaluate_and_search(vae_model, decoder, loader, tag_names, device, args.output_dir,
@@ -171,19 +274,20 @@ def evaluate(args):
         dist.gather_object((failed, images), objs, dst=0, group=group)
         if rank != 0:
             return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": None,
-                    **({"per_class_metrics": per_class_metrics} if per_class else {})}
+                    **({"per_class_metrics": per_class_metrics} if per_class else {}), **extra}
         failed = [f for part, _ in objs for f in part]   # every file belongs to one rank: each failure is counted once
         images = sum(n for _, n in objs)
     for p, e in failed:
         print(f"跳过图像 {p}，错误原因: {e}")
     print(f"评估完成！图像: {images}, 跳过: {len(failed) + len(data.missing)}, 阈值: {threshold:.3f}")
     return {"threshold": threshold, "optimal_thresholds": optimal, "metrics": metrics, "skipped": len(failed) + len(data.missing),
-            **({"per_class_metrics": per_class_metrics} if per_class else {})}
+            **({"per_class_metrics": per_class_metrics} if per_class else {}), **extra}
 
 
-def build_parser(distributed=False, recount=False):
+def build_parser(distributed=False, recount=False, val_loss=False):
     """The single-process flag set; distributed=True adds --sharded, recount=True the flags that rest on the device recount
-    (--single_pass, --per_class_thresholds).  `main` parses with both."""
+    (--single_pass, --per_class_thresholds), val_loss=True the validation loss and the checkpoint sweep (--val_loss, the loss flags of
+    train_decoder.py, --decoder_checkpoints).  `main` parses with all three."""
     p = argparse.ArgumentParser(description="在带标签的数据集上评估VAE + 分类解码器 (阈值搜索 + 多标签指标)。")
     p.add_argument("--vae_checkpoint", type=str, required=True, help="预训练VAE模型文件路径 (.safetensors)")
     p.add_argument("--vae_config_path", type=str, default=None, help="VAE配置文件路径 (JSON格式)")
@@ -224,6 +328,21 @@ def build_parser(distributed=False, recount=False):
         p.add_argument("--per_class_thresholds", action="store_true",
                        help="also report the metrics under the searched per-class thresholds and write them as "
                             "evaluation_results_per_class_thresholds.csv / _overall.json (no extra pass over the images; not with --threshold)")
+    if val_loss:
+        p.add_argument("--val_loss", action="store_true",
+                       help="also report the validation loss train_decoder.py selects checkpoints by -- BCE-with-logits, Focal and "
+                            "class-balanced BCE, accumulated on the GPU from the logits -- and write validation_loss.json "
+                            "(not with --host_metrics)")
+        p.add_argument("--use_focal_loss", action="store_true", help="使用Focal Loss处理类别不平衡 (selects the loss reported as val_loss)")
+        p.add_argument("--use_class_balanced", action="store_true", help="使用类别平衡损失 (selects the loss reported as val_loss)")
+        p.add_argument("--focal_alpha", type=float, default=1.0, help="Focal Loss的alpha参数")
+        p.add_argument("--focal_gamma", type=float, default=2.0, help="Focal Loss的gamma参数")
+        p.add_argument("--decoder_checkpoints", type=str, nargs="+", default=None,
+                       help="checkpoint sweep: score these decoder checkpoints (one architecture, one tag count) in ONE pass -- every "
+                            "image is encoded once; implies --single_pass and --val_loss; files go to output_dir/ckpt_<index>_<stem>/ "
+                            "and output_dir/checkpoint_sweep.json (not with --threshold or --host_metrics).  --decoder_checkpoint stays "
+                            "required and names the architecture's checkpoint.  Memory: every checkpoint keeps its own key store of "
+                            "tags x images x 8 bytes on the GPU -- 655 MB at 10 000 tags x 8 192 images, about 6.6 GB for ten checkpoints")
     if distributed:
         p.add_argument("--sharded", action="store_true",
                        help="under torchrun: one rank per GPU, rank r evaluates paths[r::world], the device evaluator's states are "
@@ -232,9 +351,11 @@ def build_parser(distributed=False, recount=False):
 
 
 def main(argv=None):
-    args = build_parser(distributed=True, recount=True).parse_args(argv)
+    args = build_parser(distributed=True, recount=True, val_loss=True).parse_args(argv)
     if args.no_attention:
         args.use_attention = False
+    if args.decoder_checkpoints:
+        args.single_pass = args.val_loss = True
     return evaluate(args)
 
 

@@ -771,3 +771,158 @@ def _device_pass(model, decoder, loader, class_names, device, threshold, capacit
         if had_check is not None:
             model.check_finite = had_check
     return ev
+
+
+# ---- checkpoint sweep: several decoders scored per encode, validation loss on the device --------------------------------------------
+VALIDATION_LOSS_JSON = "validation_loss.json"
+
+
+def _sweep_pass(model, decoders, loader, class_names, device, threshold, capacity, loss_kw):
+    """_device_pass for several decoders: per batch ONE model.encode, then per decoder its logits, one DeviceLossAccumulator.update on
+    them (loss_kw is not None) and one DeviceMultiLabelEvaluator.update on their sigmoid -- no host synchronisation per batch; the
+    encoder's health word is read one batch late, as in _device_pass.  Returns (evaluators, accumulators or Nones)."""
+    import ctypes
+    from .losses import DeviceLossAccumulator
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    vae = getattr(model, "vae", model)
+    ctx = vae._context() if hasattr(vae, "_context") else None
+    if capacity is None and hasattr(loader, "dataset"):
+        try:
+            capacity = len(loader.dataset)
+        except TypeError:
+            capacity = None
+    evs = [DeviceMultiLabelEvaluator(class_names, dev, threshold=threshold, capacity=capacity, context=ctx) for _ in decoders]
+    accs = [DeviceLossAccumulator(len(class_names), dev, context=ctx, **loss_kw) if loss_kw is not None else None for _ in decoders]
+    had_check = getattr(model, "check_finite", None)
+    if had_check is not None:
+        model.check_finite = False
+    words = [torch.zeros(1, dtype=torch.int32, pin_memory=True) for _ in range(2)] if ctx is not None else []
+    views = [w.numpy() for w in words]
+    pending, i = None, 0
+    try:
+        with torch.no_grad():
+            for batch in loader:
+                lat = model.encode(batch["pixel_values"].to(dev, non_blocking=True))
+                labels = batch["labels"]
+                if isinstance(labels, torch.Tensor) and labels.device != dev:
+                    labels = labels.to(dev, non_blocking=True)       # one upload for every decoder's two updates
+                for decoder, ev, acc in zip(decoders, evs, accs):
+                    logits = decoder(lat)
+                    if acc is not None:
+                        acc.update(logits, labels)
+                    ev.update(torch.sigmoid(logits), labels)
+                if ctx is not None:
+                    stream = torch.cuda.current_stream(dev)
+                    ctx.call("vt_status_async", 1, ctypes.c_void_p(words[i & 1].data_ptr()), ctypes.c_void_p(stream.cuda_stream))
+                    done = torch.cuda.Event()
+                    done.record(stream)
+                    if pending is not None:
+                        pending[1].synchronize()
+                        _raise_on_word(int(pending[0][0]))
+                    pending = (views[i & 1], done)
+                    i += 1
+            if pending is not None:
+                pending[1].synchronize()
+                _raise_on_word(int(pending[0][0]))
+    finally:
+        if had_check is not None:
+            model.check_finite = had_check
+    return evs, accs
+
+
+def _merge_losses_across_ranks(accs, group):
+    """ONE all-gather of this rank's loss blocks (every accumulator's block, concatenated); on rank 0 every accumulator's blocks are
+    merged IN RANK ORDER into a fresh accumulator, which is returned in its place; None on the other ranks."""
+    import torch.distributed as dist
+    from .losses import DeviceLossAccumulator, LossStateBlock, exchange_loss_blocks
+    blocks = [a.export_state() for a in accs]
+    nbytes = blocks[0].data.numel()                          # (a multiple of 256: the parts of the gather stay 256-B aligned)
+    parts = exchange_loss_blocks(torch.cat([b.data for b in blocks]), group)
+    if dist.get_rank(group) != 0:
+        return None
+    merged = []
+    for k, a in enumerate(accs):
+        m = DeviceLossAccumulator(a.N, a.device, a.alpha, a.gamma, a.class_weights, context=a.ctx)
+        stage = torch.empty(len(parts) * nbytes + 256, dtype=torch.uint8, device=a.device)
+        off = -stage.data_ptr() % 256
+        stage = stage[off:off + len(parts) * nbytes]
+        for r, part in enumerate(parts):
+            stage[r * nbytes:(r + 1) * nbytes].copy_(part[k * nbytes:(k + 1) * nbytes], non_blocking=False)
+        m.merge_from([LossStateBlock(stage[r * nbytes:(r + 1) * nbytes], a.alpha, a.gamma, a.class_weights) for r in range(len(parts))])
+        merged.append(m)
+    return merged
+
+
+def sweep_checkpoints(model, decoders, loader, class_names, device="cuda", output_dirs=None, threshold=None, per_class=False,
+                      per_class_thresholds=None, group=None, val_loss=True, focal_alpha=1.0, focal_gamma=2.0, class_weights=None,
+                      selected_loss="bce"):
+    """Score several decoders of one architecture in ONE pass over `loader`: the encoder -- nearly all of the work per image -- runs
+    once per batch, and every decoder gets its own key-keeping device evaluator and (val_loss) its own DeviceLossAccumulator, fed the
+    logits: train_decoder.py's validation loss (train_decoder.py:218-241) beside the metrics.
+    threshold=None: per decoder the one-pass finish of evaluate_and_search (search, metrics at the global threshold found, per_class:
+    also under the searched per-class thresholds); a float: evaluate_model's finish at that threshold (per_class_thresholds as there).
+    The files evaluate_and_search / evaluate_model write go to output_dirs[i], plus validation_loss.json (losses.loss_report;
+    `selected_loss` is the one the reference's rule picks: losses.select_loss).  class_weights: losses.class_balanced_weights(...) of
+    the WHOLE label set, or None (no class-balanced loss).  group: every rank passes its share of the data; the evaluators are merged
+    with merge_across_ranks, the loss blocks with one all-gather and vt_loss_merge in rank order, and rank 0 finishes; every rank
+    returns rank 0's result.  Returns one dict per decoder: optimal (None with a threshold), metrics, per_class_metrics (or None),
+    loss (losses.finish_state's dict, or None).  Memory: every decoder keeps its own key store of N x capacity x 8 bytes."""
+    from .losses import loss_report
+    model.eval()
+    for d in decoders:
+        d.eval()
+    decoders = list(decoders)
+    output_dirs = list(output_dirs) if output_dirs is not None else [None] * len(decoders)
+    if len(output_dirs) != len(decoders) or not decoders:
+        raise ValueError("sweep_checkpoints: one output directory (or None) per decoder, and at least one decoder")
+    loss_kw = {"alpha": focal_alpha, "gamma": focal_gamma, "class_weights": class_weights} if val_loss else None
+
+    def finish_one(ev, acc, output_dir):
+        if threshold is None:
+            optimal = _report_search(ev.optimal_thresholds(), output_dir)
+            metrics = _report(ev.compute_metrics_at(optimal["global_threshold"]), output_dir, RESULTS_CSV)
+            pc = None
+            if per_class:
+                pc = _report(ev.compute_metrics_at(threshold_vector(optimal, class_names, optimal["global_threshold"])), output_dir,
+                             PER_CLASS_RESULTS_CSV)
+        else:
+            optimal, pc = None, None
+            metrics = _report(ev.compute_metrics(), output_dir, RESULTS_CSV)
+            if per_class_thresholds is not None:
+                pc = _report(ev.compute_metrics_at(threshold_vector(per_class_thresholds, class_names, threshold)), output_dir,
+                             PER_CLASS_RESULTS_CSV)
+        loss = None
+        if acc is not None:
+            loss = acc.read(class_names)
+            report = loss_report(loss, selected_loss)
+            print(f"validation loss ({selected_loss}) {report['val_loss']:.6f} over {loss['steps']} batches"
+                  + (f"; {loss['non_finite']} non-finite logits" if loss["non_finite"] else ""))
+            if output_dir:
+                os.makedirs(output_dir, exist_ok=True)
+                with open(os.path.join(output_dir, VALIDATION_LOSS_JSON), "w", encoding="utf-8") as fh:
+                    json.dump(report, fh, indent=2, ensure_ascii=False)
+        return {"optimal": optimal, "metrics": metrics, "per_class_metrics": pc, "loss": loss}
+
+    def finish(pairs):
+        return [finish_one(ev, acc, d) for (ev, acc), d in zip(pairs, output_dirs)]
+    t = 0.5 if threshold is None else threshold
+    if group is not None and _use_group(group):
+        evs, accs, error = [None] * len(decoders), None, None
+        try:
+            n = None
+            if hasattr(loader, "dataset"):
+                try:
+                    n = max(1, len(loader.dataset))
+                except TypeError:
+                    n = None
+            evs, accs = _sweep_pass(model, decoders, loader, class_names, device, t, n, loss_kw)
+        except Exception as e:  # noqa: BLE001 - travels in the first exchange, so that every rank raises
+            error = f"{type(e).__name__}: {e}"
+        merged = [merge_across_ranks(ev, group, error=error) for ev in evs]
+        merged_accs = _merge_losses_across_ranks(accs, group) if loss_kw is not None else None
+        pairs = None if merged[0] is None else list(zip(merged, merged_accs if merged_accs is not None else [None] * len(merged)))
+        return _finish_on_rank0(pairs, group, finish)
+    evs, accs = _sweep_pass(model, decoders, loader, class_names, device, t, None, loss_kw)
+    return finish(list(zip(evs, accs)))
