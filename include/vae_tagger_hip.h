@@ -255,6 +255,60 @@ int vt_loss_merge(vt_context* ctx, void* dst, size_t dst_bytes, int N, double al
 /* algorithmic FLOPs of one encoder forward at HxW -- for roofline reporting */
 double vt_encoder_flops(const vt_context* ctx, int H, int W);
 
+/* ---- training the decoder's classifier head (train_decoder.py:173-263) --------------------------------------------------------
+ * vt_decode_logits = front + head.  The FRONT (ClassificationDecoder: the 4x4 adaptive pool; AttentionClassificationDecoder: spatial
+ * attention, feature_compress, self- / cross-attention) ends in one feature row per image, [B][F] fp32 with F = vt_decoder_feature_dim
+ * (256 plain, 512 attention) whatever the latent's size; the HEAD is `classifier.*`: Linear -> LayerNorm -> (Leaky)ReLU -> Dropout
+ * layers and Linear(256, N).  vt_decode_features runs the front alone (workspace: vt_decode_workspace_bytes); vt_head_forward on its
+ * rows gives vt_decode_logits' bits.  The front is frozen here (BatchNorm on its running statistics, no dropout), so an image's
+ * feature row never changes and can be cached across epochs.
+ *
+ * The trainer keeps everything in one caller-owned, 256-B aligned device block of vt_head_state_bytes(ctx) bytes (layout:
+ * csrc/vt_train.h): fp32 parameters, gradients, Adam m and v, the gradient norm / clip coefficient, and a ring of VT_HEAD_RING fp64
+ * loss values.  Every linear layer's INPUT width must be a multiple of 256 (the backward kernel's column block): true of both reference
+ * heads at latent_channels = 16 (F = 256 / 512, hidden 1024 / 512 / 256); otherwise vt_head_state_bytes returns 0.  fp32 storage, fp64 loss elements and scalar reductions, no atomics: every sum runs in an order fixed by the shapes, so
+ * the same call sequence leaves the same bits.  No call synchronises the host.  The decoder must be finalized; its shapes size the block.
+ *   vt_head_init      parameters <- the context's classifier tables; gradients, m, v, ring <- 0
+ *   vt_head_forward   eval-mode logits [B][N] of the state's parameters
+ *   vt_head_forward_backward   forward (train != 0: dropout at dropout_p[layer], HOST array of the hidden layers' rates, NULL = none;
+ *                     mask of element i of layer l at (seed, step): a counter-based hash, regenerated in backward; survivors scaled
+ *                     by 1 / (1 - p)), the loss, its gradient, backward through every layer, ADDED into the gradients.
+ *                     loss_kind 0: BCE-with-logits, mean over B N; 1: focal alpha (1 - e^-bce)^gamma bce; 2: class_weights[c] bce
+ *                     (device fp32 [N]: losses.class_balanced_weights).  labels [B][N]: VT_F32 used as its value, or VT_U8 (0 / 1).
+ *                     ring[step % VT_HEAD_RING] = loss_scale x loss; the gradients are those of loss_scale x loss.
+ *                     logits_out (may be NULL): the forward's logits.  masks_out (may be NULL): one byte per element and hidden layer,
+ *                     layer after layer, [B][d_l] each (1 = kept).  Workspace: vt_head_workspace_bytes(ctx, B).
+ *   vt_head_clip      clip_grad_norm_(max_norm): total L2 norm of the gradients forward_backward left (partials written by the
+ *                     kernels that wrote them, added in a fixed order), coef = min(1, max_norm / (norm + 1e-6)); the gradients are
+ *                     scaled in place when coef < 1 and keep their bits otherwise.  VT_HEAD_NORM reads { fp64 norm^2, fp32 norm, fp32 coef }.
+ *                     (Gradients set with vt_head_write are not in the norm until a forward_backward has added to them.)
+ *   vt_head_step      torch.optim.AdamW's update number t (1-based) with decoupled weight decay; zeroes the gradients in the same pass
+ *   vt_head_commit    the context's classifier tables <- parameters: vt_decode_logits and everything on it sees the trained head
+ *   vt_head_read / vt_head_write   one named tensor ("classifier.8.weight") of the parameters, gradients, m or v, the loss ring
+ *                     (fp64 [VT_HEAD_RING]) or the norm scalars, copied in stream order to / from device or pinned host memory
+ */
+enum { VT_HEAD_PARAM = 0, VT_HEAD_GRAD = 1, VT_HEAD_ADAM_M = 2, VT_HEAD_ADAM_V = 3, VT_HEAD_LOSS_RING = 4, VT_HEAD_NORM = 5 };
+enum { VT_HEAD_LOSS_BCE = 0, VT_HEAD_LOSS_FOCAL = 1, VT_HEAD_LOSS_CLASS_BALANCED = 2 };
+int vt_decoder_feature_dim(const vt_context* ctx);
+int vt_decode_features(vt_context* ctx, const float* latent_nchw, int B, int h, int w, float* features_out /* [B][F] */, void* workspace,
+                       size_t workspace_bytes, void* stream);
+size_t vt_head_state_bytes(const vt_context* ctx);
+size_t vt_head_workspace_bytes(const vt_context* ctx, int B);
+int vt_head_init(vt_context* ctx, void* state, size_t state_bytes, void* stream);
+int vt_head_forward(vt_context* ctx, const void* state, size_t state_bytes, const float* features, int B, float* logits_out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int vt_head_forward_backward(vt_context* ctx, void* state, size_t state_bytes, const float* features, const void* labels, int labels_dtype,
+                             int B, int loss_kind, double focal_alpha, double focal_gamma, const float* class_weights, double loss_scale,
+                             int train, const float* dropout_p /* host */, unsigned long long seed, unsigned long long step,
+                             float* logits_out, unsigned char* masks_out, void* workspace, size_t workspace_bytes, void* stream);
+int vt_head_clip(vt_context* ctx, void* state, size_t state_bytes, float max_norm, void* stream);
+int vt_head_step(vt_context* ctx, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, double weight_decay,
+                 long long t, void* stream);
+int vt_head_commit(vt_context* ctx, const void* state, size_t state_bytes, void* stream);
+int vt_head_read(vt_context* ctx, const void* state, size_t state_bytes, int kind, const char* name, void* out, size_t out_bytes, void* stream);
+int vt_head_write(vt_context* ctx, void* state, size_t state_bytes, int kind, const char* name, const void* src, size_t src_bytes,
+                  void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * flag 0: 1 (default) = 3x3 stride-1 convs use the halo-tile kernel (conv3x3_halo.hip),
  *         0 = every contraction uses the generic implicit-GEMM kernel (conv_gemm.hip).

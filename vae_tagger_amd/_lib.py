@@ -13,6 +13,9 @@ LIB_PATH = os.environ.get("VAE_TAGGER_HIP_LIB") or os.path.join(_HERE, "csrc", "
 VT_F32, VT_BF16, VT_F16, VT_U8 = 0, 1, 2, 3
 VT_STATUS_NONFINITE, VT_STATUS_FP8_SATURATED = 1, 2      # bits of vt_status (include/vae_tagger_hip.h)
 ENCODE_MOMENTS, ENCODE_MODE, ENCODE_MODE_SCALED = 0, 1, 2
+HEAD_PARAM, HEAD_GRAD, HEAD_ADAM_M, HEAD_ADAM_V, HEAD_LOSS_RING, HEAD_NORM = range(6)      # vt_head_read / vt_head_write kinds
+HEAD_LOSS_KINDS = {"bce": 0, "focal": 1, "class_balanced": 2}
+HEAD_RING = 256
 
 _c = ctypes
 _vp, _i, _f, _sz, _ll = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t, _c.c_longlong
@@ -77,6 +80,19 @@ PROTOTYPES = {
     "vt_loss_update": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _i, _i, _vp]),
     "vt_loss_read": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "vt_loss_merge": (_i, [_vp, _vp, _sz, _i, _c.c_double, _c.c_double, _vp, _c.POINTER(LossSource), _i, _vp]),
+    "vt_decoder_feature_dim": (_i, [_vp]),
+    "vt_decode_features": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "vt_head_state_bytes": (_sz, [_vp]),
+    "vt_head_workspace_bytes": (_sz, [_vp, _i]),
+    "vt_head_init": (_i, [_vp, _vp, _sz, _vp]),
+    "vt_head_forward": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp]),
+    "vt_head_forward_backward": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _i, _i, _c.c_double, _c.c_double, _vp, _c.c_double, _i,
+                                      _c.POINTER(_f), _c.c_ulonglong, _c.c_ulonglong, _vp, _vp, _vp, _sz, _vp]),
+    "vt_head_clip": (_i, [_vp, _vp, _sz, _f, _vp]),
+    "vt_head_step": (_i, [_vp, _vp, _sz, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _ll, _vp]),
+    "vt_head_commit": (_i, [_vp, _vp, _sz, _vp]),
+    "vt_head_read": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
+    "vt_head_write": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
     "vt_encoder_flops": (_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),

@@ -501,21 +501,32 @@ __global__ __launch_bounds__(256) void dec_summary_per_class_kernel(const float*
 #define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) return _e; } while (0)
 #define CKL() CK(hipGetLastError())
 
-hipError_t vt_decoder_forward(const DecoderWeights& w, const float* latent, int B, int H, int Wd, float* ws,
-                              float* logits, hipStream_t s) {
+// The classifier head's layout (modules.py:401-418 / :318-331): hidden widths, activation and the feature-row width F.
+DecHeadShape vt_decoder_head_shape(const DecoderWeights& w) {
+    DecHeadShape h;
+    const int C = w.latent_channels;
+    if (w.plain) { h.hidden = 2; h.dims[0] = C * 16; h.dims[1] = 512; h.dims[2] = 256; h.dims[3] = w.num_classes; h.dims[4] = 0; h.act = 1; }
+    else { h.hidden = 3; h.dims[0] = (C / 2) * 64; h.dims[1] = 1024; h.dims[2] = 512; h.dims[3] = 256; h.dims[4] = w.num_classes; h.act = 0; }
+    return h;
+}
+
+hipError_t vt_dec_linear(const float* x, const float* w, const float* bias, float* y, int B, int IN, int OUT, hipStream_t s) {
+    hipLaunchKernelGGL(dec_linear_kernel, dim3((OUT + 3) / 4), dim3(256), 0, s, x, w, bias, y, B, IN, OUT); CKL();
+    return hipSuccess;
+}
+hipError_t vt_dec_ln_act(float* y, const float* g, const float* b, int rows, int N, int act, hipStream_t s) {
+    hipLaunchKernelGGL(dec_ln_act_kernel, dim3(rows), dim3(256), 0, s, y, g, b, N, act); CKL();
+    return hipSuccess;
+}
+
+// front: latent -> the feature row [B][F] the classifier reads (plain: the 4x4 pool; attention: spatial attention, compress,
+// self- / cross-attention), written to `feat`; `ws` holds the front's scratch.
+hipError_t vt_decoder_front(const DecoderWeights& w, const float* latent, int B, int H, int Wd, float* ws, float* feat, hipStream_t s) {
     const int C = w.latent_channels, HW = H * Wd;
     if (B <= 0 || H <= 0 || Wd <= 0 || C <= 0 || C > 64) return hipErrorInvalidValue;
     if (w.plain) {
-        float* pooled = ws;                       // [B][C*16]
-        float* h0 = pooled + (size_t)B * C * 16;  // [B][512]
-        float* h1 = h0 + (size_t)B * 512;         // [B][256]
         const int n = C * 16;
-        hipLaunchKernelGGL(dec_adaptive_pool_kernel, dim3((n + 255) / 256, B), dim3(256), 0, s, latent, C, H, Wd, 4, 4, pooled); CKL();
-        hipLaunchKernelGGL(dec_linear_kernel, dim3((512 + 3) / 4), dim3(256), 0, s, pooled, w.cls_w[0], w.cls_b[0], h0, B, n, 512); CKL();
-        hipLaunchKernelGGL(dec_ln_act_kernel, dim3(B), dim3(256), 0, s, h0, w.cls_ln_w[0], w.cls_ln_b[0], 512, 1); CKL();
-        hipLaunchKernelGGL(dec_linear_kernel, dim3((256 + 3) / 4), dim3(256), 0, s, h0, w.cls_w[1], w.cls_b[1], h1, B, 512, 256); CKL();
-        hipLaunchKernelGGL(dec_ln_act_kernel, dim3(B), dim3(256), 0, s, h1, w.cls_ln_w[1], w.cls_ln_b[1], 256, 1); CKL();
-        hipLaunchKernelGGL(dec_linear_kernel, dim3((w.num_classes + 3) / 4), dim3(256), 0, s, h1, w.cls_w[2], w.cls_b[2], logits, B, 256, w.num_classes); CKL();
+        hipLaunchKernelGGL(dec_adaptive_pool_kernel, dim3((n + 255) / 256, B), dim3(256), 0, s, latent, C, H, Wd, 4, 4, feat); CKL();
         return hipSuccess;
     }
     const int CO = C / 2;
@@ -525,10 +536,6 @@ hipError_t vt_decoder_forward(const DecoderWeights& w, const float* latent, int 
     float* gate = p; p += (size_t)B * C;
     float* sp = p; p += (size_t)B * 2 * HW;
     float* sg = p; p += (size_t)B * HW;
-    float* feat = p; p += (size_t)B * CO * 64;      // [B][CO][64]  == flattened [B][512]
-    float* h0 = p; p += (size_t)B * 1024;
-    float* h1 = p; p += (size_t)B * 512;
-    float* h2 = p; p += (size_t)B * 256;
     float* cq = p; p += (size_t)B * 512;
     float* cqp = p; p += (size_t)B * 256;
     float* co = p; p += (size_t)B * 256;
@@ -560,14 +567,32 @@ hipError_t vt_decoder_forward(const DecoderWeights& w, const float* latent, int 
         hipLaunchKernelGGL(dec_add_kernel, dim3((B * 512 + 255) / 256), dim3(256), 0, s, cat, cq, (long long)B * 512); CKL();
         hipLaunchKernelGGL(dec_add_rowmean_kernel, dim3(B), dim3(256), 0, s, feat, cat, CO * 64, 512); CKL();
     }
-    hipLaunchKernelGGL(dec_linear_kernel, dim3(1024 / 4), dim3(256), 0, s, feat, w.cls_w[0], w.cls_b[0], h0, B, CO * 64, 1024); CKL();
-    hipLaunchKernelGGL(dec_ln_act_kernel, dim3(B), dim3(256), 0, s, h0, w.cls_ln_w[0], w.cls_ln_b[0], 1024, 0); CKL();
-    hipLaunchKernelGGL(dec_linear_kernel, dim3(512 / 4), dim3(256), 0, s, h0, w.cls_w[1], w.cls_b[1], h1, B, 1024, 512); CKL();
-    hipLaunchKernelGGL(dec_ln_act_kernel, dim3(B), dim3(256), 0, s, h1, w.cls_ln_w[1], w.cls_ln_b[1], 512, 0); CKL();
-    hipLaunchKernelGGL(dec_linear_kernel, dim3(256 / 4), dim3(256), 0, s, h1, w.cls_w[2], w.cls_b[2], h2, B, 512, 256); CKL();
-    hipLaunchKernelGGL(dec_ln_act_kernel, dim3(B), dim3(256), 0, s, h2, w.cls_ln_w[2], w.cls_ln_b[2], 256, 0); CKL();
-    hipLaunchKernelGGL(dec_linear_kernel, dim3((w.num_classes + 3) / 4), dim3(256), 0, s, h2, w.cls_w[3], w.cls_b[3], logits, B, 256, w.num_classes); CKL();
     return hipSuccess;
+}
+
+// head: Linear -> LayerNorm -> (Leaky)ReLU per hidden layer (dropout is the identity in eval mode), then Linear(256, N).
+// hbuf: B * (dims[1] + ... + dims[hidden]) floats.
+hipError_t vt_decoder_head(const DecHeadShape& h, const DecHeadParams& p, const float* feat, int B, float* hbuf, float* logits, hipStream_t s) {
+    const float* x = feat;
+    for (int i = 0; i < h.hidden; ++i) {
+        CK(vt_dec_linear(x, p.w[i], p.b[i], hbuf, B, h.dims[i], h.dims[i + 1], s));
+        CK(vt_dec_ln_act(hbuf, p.ln_w[i], p.ln_b[i], B, h.dims[i + 1], h.act, s));
+        x = hbuf; hbuf += (size_t)B * h.dims[i + 1];
+    }
+    return vt_dec_linear(x, p.w[h.hidden], p.b[h.hidden], logits, B, h.dims[h.hidden], h.dims[h.hidden + 1], s);
+}
+
+hipError_t vt_decoder_forward(const DecoderWeights& w, const float* latent, int B, int H, int Wd, float* ws,
+                              float* logits, hipStream_t s) {
+    const DecHeadShape h = vt_decoder_head_shape(w);
+    float* feat = ws;                                   // [B][F]
+    float* hbuf = feat + (size_t)B * h.dims[0];         // the head's hidden rows
+    float* front_ws = hbuf + (size_t)B * (1024 + 512 + 256);
+    CK(vt_decoder_front(w, latent, B, H, Wd, front_ws, feat, s));
+    DecHeadParams p;
+    for (int i = 0; i < 4; ++i) { p.w[i] = w.cls_w[i]; p.b[i] = w.cls_b[i]; }
+    for (int i = 0; i < 3; ++i) { p.ln_w[i] = w.cls_ln_w[i]; p.ln_b[i] = w.cls_ln_b[i]; }
+    return vt_decoder_head(h, p, feat, B, hbuf, logits, s);
 }
 
 size_t vt_decoder_workspace_floats(int B, int C, int H, int Wd) {

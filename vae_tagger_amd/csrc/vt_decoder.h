@@ -26,6 +26,17 @@ struct DecoderWeights {
     const float* cls_ln_b[3] = {nullptr, nullptr, nullptr};
 };
 
+// the classifier head: `hidden` Linear -> LayerNorm -> activation layers of widths dims[1..hidden] over a feature row of dims[0]
+// floats, then Linear(dims[hidden], dims[hidden + 1] = num_classes); act 0 = ReLU, 1 = LeakyReLU(0.2)
+struct DecHeadShape { int hidden = 0; int dims[5] = {0, 0, 0, 0, 0}; int act = 0; };
+struct DecHeadParams { const float* w[4]; const float* b[4]; const float* ln_w[3]; const float* ln_b[3]; };
+DecHeadShape vt_decoder_head_shape(const DecoderWeights& w);
+// the head's two kernels, as vt_decoder_forward launches them (train_head.hip's forward runs the same launches: same bits)
+hipError_t vt_dec_linear(const float* x, const float* w, const float* bias, float* y, int B, int IN, int OUT, hipStream_t s);
+hipError_t vt_dec_ln_act(float* y, const float* g, const float* b, int rows, int N, int act, hipStream_t s);
+// vt_decoder_forward = front (latent -> feature rows [B][dims[0]]) + head (feature rows -> logits)
+hipError_t vt_decoder_front(const DecoderWeights& w, const float* latent_nchw, int B, int H, int W, float* ws, float* feat, hipStream_t s);
+hipError_t vt_decoder_head(const DecHeadShape& h, const DecHeadParams& p, const float* feat, int B, float* hbuf, float* logits, hipStream_t s);
 hipError_t vt_decoder_forward(const DecoderWeights& w, const float* latent_nchw, int B, int H, int W, float* ws,
                               float* logits, hipStream_t s);
 size_t vt_decoder_workspace_floats(int B, int C, int H, int W);

@@ -1,0 +1,303 @@
+"""Decoder training CLI: the reference's train_decoder.py (train_decoder.py:30-278) with the classifier head trained on the GPU
+(train.HeadTrainer) behind the frozen encoder and the frozen decoder front.
+
+    python -m vae_tagger_amd.train_decoder --vae_checkpoint ae.safetensors --json_path data.json --tags_csv_path tags.csv \
+        --no_attention --num_epochs 10 --train_batch_size 16 [--use_bucketing] [--decoder_checkpoint start.bin]
+
+--no_attention trains ClassificationDecoder in full (its front is the parameter-free 4x4 pool).  An attention decoder is trained only
+with --freeze_front: its front (spatial attention, feature_compress, self- / cross-attention) runs as in inference and only
+`classifier.*` changes -- e.g. to adapt a trained checkpoint to a new tag list; backward through the front is not implemented.
+Epoch 1 encodes every image once and keeps the front's feature row and the labels of each on the GPU (train.FeatureCache); later epochs
+train from that cache without calling the encoder (--no_feature_cache re-encodes every epoch).  The dataset applies no random
+augmentation (modules.py:688-729), so a cached row is what a re-encode would give.
+Files, as the reference writes them: best_pytorch_model.bin (strictly lower validation loss), pytorch_model.bin (every --save_steps
+epochs), training_history.json, then the threshold search and the metrics on the validation set (optimal_thresholds.json,
+evaluation_results.csv, evaluation_results_overall.json); plus train_report.json (per epoch: seconds, images/s, encoder batches, steps).
+"""
+import argparse
+import json
+import os
+import time
+
+import torch
+
+IGNORED_ARGUMENTS = ("mixed_precision", "cudnn_benchmark", "cudnn_deterministic", "num_workers", "prefetch_factor", "use_safetensors")
+FRONT_MESSAGE = ("an attention decoder is trained with --freeze_front only: backward through the decoder front (BatchNorm in training "
+                 "mode, self-attention with dropout) is not implemented; --freeze_front trains classifier.* on the frozen front, "
+                 "--no_attention trains the plain decoder in full")
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="训练分类解码器 (classifier head on the GPU, frozen encoder and decoder front)")
+    p.add_argument("--vae_checkpoint", type=str, required=True, help="预训练VAE模型文件路径 (.safetensors)")
+    p.add_argument("--vae_config_path", type=str, default=None, help="VAE配置文件路径 (JSON格式)")
+    p.add_argument("--decoder_checkpoint", type=str, default=None, help="预训练Decoder模型文件路径 (.bin/.pth)")
+    p.add_argument("--json_path", type=str, required=True)
+    p.add_argument("--tags_csv_path", type=str, required=True)
+    p.add_argument("--output_dir", type=str, default="decoder_output")
+    p.add_argument("--resolution", type=int, default=1024)
+    p.add_argument("--train_batch_size", type=int, default=1)
+    p.add_argument("--num_epochs", type=int, default=10)
+    p.add_argument("--learning_rate", type=float, default=1e-3)
+    p.add_argument("--weight_decay", type=float, default=1e-6)
+    p.add_argument("--mixed_precision", type=str, default=None, help="ignored: the head trains in fp32")
+    p.add_argument("--use_attention", action="store_true", default=True, help="启用注意力机制 (默认开启)")
+    p.add_argument("--no_attention", action="store_true", help="禁用注意力机制")
+    p.add_argument("--use_spatial_attention", action="store_true", default=True, help="启用空间注意力")
+    p.add_argument("--use_self_attention", action="store_true", default=True, help="启用自注意力")
+    p.add_argument("--use_cross_attention", action="store_true", help="启用交叉注意力")
+    p.add_argument("--attention_heads", type=int, default=8, help="注意力头数")
+    p.add_argument("--attention_dropout", type=float, default=0.1, help="注意力dropout率")
+    p.add_argument("--use_simplified_decoder_loss", action="store_true", default=True, help="使用简化的解码器损失（推荐）")
+    p.add_argument("--use_focal_loss", action="store_true", help="使用Focal Loss处理类别不平衡")
+    p.add_argument("--use_class_balanced", action="store_true", help="使用类别平衡损失")
+    p.add_argument("--focal_alpha", type=float, default=1.0, help="Focal Loss的alpha参数")
+    p.add_argument("--focal_gamma", type=float, default=2.0, help="Focal Loss的gamma参数")
+    p.add_argument("--lr_scheduler_type", type=str, default="cosine", help="constant, constant_with_warmup, linear, cosine")
+    p.add_argument("--lr_warmup_steps", type=int, default=500, help="学习率预热步数")
+    p.add_argument("--max_grad_norm", type=float, default=1.0, help="梯度裁剪阈值")
+    p.add_argument("--logging_steps", type=int, default=100, help="日志记录间隔")
+    p.add_argument("--save_steps", type=int, default=5, help="模型保存间隔（epochs）")
+    p.add_argument("--use_quant_conv", action="store_true", help="VAE config: use_quant_conv")
+    p.add_argument("--use_post_quant_conv", action="store_true", help="VAE config: use_post_quant_conv")
+    p.add_argument("--use_safetensors", action="store_true", help="ignored: checkpoints are written with torch.save")
+    p.add_argument("--use_bucketing", action="store_true", help="启用长宽比分桶功能")
+    p.add_argument("--base_resolution", type=int, default=512, help="分桶的基础分辨率")
+    p.add_argument("--max_resolution", type=int, default=1024, help="分桶的最大分辨率")
+    p.add_argument("--bucket_step", type=int, default=64, help="分桶的步长")
+    p.add_argument("--num_workers", type=int, default=None, help="ignored: see --workers")
+    p.add_argument("--prefetch_factor", type=int, default=None, help="ignored: the feeder pipelines by itself")
+    p.add_argument("--gradient_accumulation_steps", type=int, default=1, help="梯度累积步数")
+    p.add_argument("--seed", type=int, default=42,
+                   help="随机种子: the validation split is the first max(1, int(0.1 n)) entries of torch.randperm(n) under a generator "
+                        "seeded with it, and every epoch's training order is drawn from it -- reproducible from the seed alone, NOT "
+                        "the permutation the reference's random_split draws from the global RNG")
+    p.add_argument("--cudnn_benchmark", action="store_true", default=None, help="ignored")
+    p.add_argument("--cudnn_deterministic", action="store_true", default=None, help="ignored: the training step is deterministic")
+    # this project's own
+    p.add_argument("--freeze_front", action="store_true",
+                   help="attention decoders: train classifier.* only, on the front as it runs in inference (required for them)")
+    p.add_argument("--no_feature_cache", action="store_true", help="re-encode every image every epoch instead of caching its feature row")
+    p.add_argument("--workers", type=int, default=0, help="image decode threads (0 = min(16, cores))")
+    p.add_argument("--max_pending", type=int, default=0, help="with --use_bucketing: images that may wait in partly filled buckets")
+    p.add_argument("--host_resize", action="store_true", help="PIL transforms on the CPU (the reference's input route)")
+    p.add_argument("--fp16_operands", action="store_true", help="fp16 instead of bf16 MFMA operands for the encoder's convolutions")
+    p.add_argument("--fp8", action="store_true", help="3x3 convs of the encoder on fp8 (e4m3) operands")
+    return p
+
+
+def ignored_arguments(args):
+    """The reference's arguments that were given and mean nothing here."""
+    return [k for k in IGNORED_ARGUMENTS if getattr(args, k, None) not in (None, False)]
+
+
+def check_args(args):
+    """What is refused, before any GPU work."""
+    from .train import SCHEDULES
+    if args.no_attention:
+        args.use_attention = False
+    if args.use_attention and not args.freeze_front:
+        raise RuntimeError(FRONT_MESSAGE)
+    if args.lr_scheduler_type not in SCHEDULES:
+        raise RuntimeError(f"--lr_scheduler_type {args.lr_scheduler_type}: one of {', '.join(SCHEDULES)} expected")
+    if args.train_batch_size < 1 or args.num_epochs < 1 or args.save_steps < 1 or args.logging_steps < 1:
+        raise RuntimeError("--train_batch_size, --num_epochs, --save_steps and --logging_steps must be at least 1")
+    return args
+
+
+def _load_models(args, device):
+    from .diffusers_vae_loader import DiffusersVAEWrapper, get_diffusers_vae_config, load_diffusers_vae_from_config
+    from .infer_full import create_vae_from_config_file, load_state_dict_file
+    from .modules import ClassificationDecoder, create_attention_decoder, get_vae_latent_info
+    import pandas as pd
+    if args.vae_config_path and os.path.exists(args.vae_config_path):
+        vae_model = create_vae_from_config_file(args.vae_config_path, args.vae_checkpoint)
+    elif args.vae_checkpoint and os.path.exists(args.vae_checkpoint):
+        vae_model = DiffusersVAEWrapper(load_diffusers_vae_from_config(get_diffusers_vae_config(), args.vae_checkpoint))
+    else:
+        raise RuntimeError("必须提供 VAE 模型检查点或配置文件")
+    vae_model.to(device).eval()
+    info = get_vae_latent_info(args.resolution)
+    tag_names = [str(t) for t in pd.read_csv(args.tags_csv_path)["name"]]
+    if args.use_attention:
+        decoder = create_attention_decoder(info["latent_channels"], info["latent_height"], info["latent_width"], len(tag_names),
+                                           {"use_spatial_attention": args.use_spatial_attention, "use_self_attention": args.use_self_attention,
+                                            "use_cross_attention": args.use_cross_attention, "attention_heads": args.attention_heads,
+                                            "attention_dropout": args.attention_dropout})
+    else:
+        print("使用标准分类解码器")
+        decoder = ClassificationDecoder(info["latent_channels"], info["latent_height"], info["latent_width"], len(tag_names))
+    if args.decoder_checkpoint and os.path.exists(args.decoder_checkpoint):
+        print(f"加载预训练Decoder: {args.decoder_checkpoint}")
+        try:
+            decoder.load_state_dict(load_state_dict_file(args.decoder_checkpoint), strict=False)
+        except Exception as e:  # noqa: BLE001 - reference behaviour (train_decoder.py:91-92)
+            print(f"Decoder模型加载失败，从零开始训练: {e}")
+    else:
+        print("从零开始训练Decoder")
+    return vae_model, decoder.to(device).eval(), tag_names
+
+
+class _LossReader:
+    """The per-step losses of the device ring, read only when asked (logging steps, the end of an epoch) or when the ring is full."""
+
+    def __init__(self, trainer, ring):
+        self.trainer, self.ring, self.read_to, self.values = trainer, ring, 0, []
+
+    def drain(self, upto):
+        if upto > self.read_to:
+            ring = self.trainer.losses()
+            self.values.extend(float(ring[s % self.ring]) for s in range(self.read_to, upto))
+            self.read_to = upto
+        return self.values
+
+    def before_step(self, step):
+        if step - self.read_to >= self.ring:
+            self.drain(step)
+
+
+def train(args):
+    """`args`: a namespace of build_parser() that has passed check_args (main does both)."""
+    from . import _lib
+    from .evaluate import TaggedImageList
+    from .evaluation import evaluate_and_search
+    from .losses import DeviceLossAccumulator, class_balanced_weights, class_distribution, loss_report, select_loss
+    from .modules import AspectRatioBucketing, get_image_transform
+    from .pipeline import EncodeTagPipeline
+    from .prefetch import FeederLoader
+    from .train import FeatureCache, HeadTrainer, epoch_order, lr_schedule, split_indices
+    ignored = ignored_arguments(args)
+    if ignored:
+        print("ignored arguments (no meaning here): " + ", ".join("--" + k for k in ignored))
+    if not torch.cuda.is_available():
+        raise RuntimeError("vae_tagger_amd needs an MI355X (no HIP device visible; there is no CPU fallback)")
+    device = torch.device("cuda", torch.cuda.current_device())
+    vae_model, decoder, tag_names = _load_models(args, device)
+    data = TaggedImageList(args.json_path, args.tags_csv_path)
+    for p in data.missing:
+        print(f"跳过图像 {p}，错误原因: 文件不存在")
+    train_idx, val_idx = split_indices(len(data.image_paths), args.seed)
+    train_paths, val_paths = [data.image_paths[i] for i in train_idx], [data.image_paths[i] for i in val_idx]
+    print(f"训练集大小: {len(train_paths)}, 验证集大小: {len(val_paths)}")
+    N = len(tag_names)
+    selected = select_loss(args.use_class_balanced, args.use_focal_loss)
+    weights = None
+    if args.use_class_balanced:
+        all_labels = TaggedImageList(args.json_path, args.tags_csv_path, check_files=False).labels
+        weights = class_balanced_weights(class_distribution(all_labels, N))
+    if args.fp8:
+        vae_model.vae._context().call("vt_set_flag", 11, 1)
+    elif args.fp16_operands:
+        vae_model.vae.set_fp16_operands(True)
+    vae_model.check_finite = False                     # the health word is read once per pass instead of once per batch
+    pipe = EncodeTagPipeline.input_side(vae_model)
+    bucketing = AspectRatioBucketing(args.base_resolution, args.max_resolution, args.bucket_step) if args.use_bucketing else None
+
+    def loader(paths):
+        return FeederLoader(pipe, paths, data.labels, args.train_batch_size, args.resolution, workers=args.workers or None,
+                            host_resize=args.host_resize, transform=get_image_transform(args.resolution), bucketing=bucketing,
+                            max_pending=args.max_pending or None)
+
+    trainer = HeadTrainer(decoder, loss=selected, focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, class_weights=weights,
+                          seed=args.seed)
+    cache = None if args.no_feature_cache else FeatureCache(len(data.image_paths), trainer.F, N, device)
+    acc = DeviceLossAccumulator(N, device, args.focal_alpha, args.focal_gamma, weights, context=decoder._context())
+    accum = max(1, args.gradient_accumulation_steps)
+    bs = args.train_batch_size
+    total_steps = args.num_epochs * ((len(train_paths) + bs - 1) // bs)
+    os.makedirs(args.output_dir, exist_ok=True)
+    history = {"train_loss": [], "val_loss": [], "learning_rates": []}
+    report = {"epochs": [], "feature_cache_bytes": cache.nbytes if cache is not None else 0, "feature_dim": trainer.F,
+              "train_images": len(train_paths), "val_images": len(val_paths)}
+    reader = _LossReader(trainer, _lib.HEAD_RING)
+    micro, sched, best, current_lr = 0, 0, float("inf"), args.learning_rate * lr_schedule(args.lr_scheduler_type, 0, args.lr_warmup_steps, total_steps)
+    val_batches = None                                 # the validation batches of the first pass, by name: every epoch scores the same ones
+
+    def encoded(paths, counter):
+        for batch in loader(paths):
+            feats = trainer.features(vae_model.encode(batch["pixel_values"]))
+            counter[0] += 1
+            if cache is not None:
+                cache.put(batch["names"], feats, batch["labels"])
+            yield batch["names"], feats, batch["labels"]
+
+    def cached(batches):
+        for names in batches:
+            names = [n for n in names if n in cache]
+            if names:
+                yield (names, *cache.gather(names))
+
+    for epoch in range(args.num_epochs):
+        t0, enc, first, images = time.perf_counter(), [0], micro, 0
+        order = [train_paths[i] for i in epoch_order(len(train_paths), args.seed, epoch)]
+        from_cache = cache is not None and epoch > 0
+        source = cached([order[i:i + bs] for i in range(0, len(order), bs)]) if from_cache else encoded(order, enc)
+        for step, (names, feats, labels) in enumerate(source):
+            reader.before_step(micro)
+            trainer.forward_backward(feats, labels, loss_scale=1.0 / accum, train=True, step=micro)
+            if args.max_grad_norm > 0:
+                trainer.clip(args.max_grad_norm)
+            if (step + 1) % accum == 0:
+                trainer.step(current_lr, args.weight_decay)
+                sched += 1
+                current_lr = args.learning_rate * lr_schedule(args.lr_scheduler_type, sched, args.lr_warmup_steps, total_steps)
+            micro += 1
+            images += len(names)
+            if step % args.logging_steps == 0:
+                vals = reader.drain(micro)[first:]
+                print(f"Epoch: {epoch}, Step: {step}, Loss: {vals[-1]:.4f}, Avg Loss: {sum(vals) / len(vals):.4f}, LR: {current_lr:.2e}")
+        train_steps = micro - first
+        # validation: head in eval mode on the frozen front's rows
+        acc.reset()
+        if val_batches is None or cache is None:
+            seen = []
+            for names, feats, labels in encoded(val_paths, enc):
+                acc.update(trainer.forward(feats), labels)
+                seen.append(list(names))
+            val_batches = seen
+        else:
+            for names, feats, labels in cached(val_batches):
+                acc.update(trainer.forward(feats), labels)
+        vae_model.vae.raise_on_status()                # the encoder's health word, once per epoch (synchronises)
+        vals = reader.drain(micro)[first:]
+        seconds = time.perf_counter() - t0
+        if not vals or not acc.steps:
+            raise RuntimeError("no image of the training or the validation set could be read")
+        val_loss = loss_report(acc.read(tag_names), selected)["val_loss"]
+        history["train_loss"].append(sum(vals) / len(vals))
+        history["val_loss"].append(val_loss)
+        history["learning_rates"].append(current_lr)
+        n_img = images + sum(len(b) for b in val_batches)
+        report["epochs"].append({"epoch": epoch, "seconds": seconds, "images_per_second": n_img / seconds, "images": n_img,
+                                 "encoder_batches": enc[0], "steps": train_steps, "optimizer_steps": sched})
+        print(f"Epoch {epoch} completed - Train Loss: {history['train_loss'][-1]:.4f}, Val Loss: {val_loss:.4f}")
+        if val_loss < best:
+            best = val_loss
+            print(f"New best validation loss: {best:.4f}")
+            torch.save(trainer.state_dict(), os.path.join(args.output_dir, "best_pytorch_model.bin"))
+        if (epoch + 1) % args.save_steps == 0:
+            torch.save(trainer.state_dict(), os.path.join(args.output_dir, "pytorch_model.bin"))
+    print("训练完成，开始最终评估...")
+    with open(os.path.join(args.output_dir, "training_history.json"), "w") as fh:
+        json.dump(history, fh, indent=2)
+    with open(os.path.join(args.output_dir, "train_report.json"), "w") as fh:
+        json.dump(report, fh, indent=2)
+    trainer.commit()
+    decoder.load_state_dict(trainer.state_dict(), strict=False)   # the module's own tensors follow the device tables
+    decoder.to(device).eval()
+    optimal, metrics, _ = evaluate_and_search(vae_model, decoder, loader(val_paths), tag_names, device, args.output_dir)
+    print("训练和评估完成！")
+    return {"history": history, "report": report, "optimal_thresholds": optimal, "metrics": metrics, "best_val_loss": best}
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    try:
+        check_args(args)
+    except RuntimeError as e:
+        raise SystemExit(str(e))
+    return train(args)
+
+
+if __name__ == "__main__":
+    main()
