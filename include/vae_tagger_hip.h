@@ -252,6 +252,57 @@ int vt_loss_read(vt_context* ctx, const void* state, size_t state_bytes, int N, 
 int vt_loss_merge(vt_context* ctx, void* dst, size_t dst_bytes, int N, double alpha, double gamma,
                   const double* class_weights /* host [N] or NULL */, const vt_loss_source* sources /* host [W] */, int W, void* stream);
 
+/* ---- per-image (example-based) metrics <- calculate_metrics, batch_inference_test.py:63-137: for every image precision_i =
+ * |true & pred| / |pred|, recall_i = |true & pred| / |true|, F1_i and the exact match, averaged over the images -- the reduction of
+ * the [B][N] matrix along the CLASSES, where vt_eval_* reduces it along the samples.  Same contract as vt_eval_* / vt_loss_*: ONE
+ * caller-owned device block (vt_sample_state_bytes(T, capacity) bytes, 256-B aligned) fed batch by batch in stream order; every size
+ * is checked on the host before anything is launched -- an undersized buffer is VT_ERR_WORKSPACE, a null / misaligned pointer or an
+ * out-of-range argument VT_ERR_INVALID, and nothing is written; no call synchronises the host.
+ * Block layout (every section 256-B aligned):
+ *     thresholds fp64 [32]
+ *   | totals { uint64 [32] = (rule, T, 0 ...), uint32 [4096]: non-finite probabilities seen in row b of every update }
+ *   | true uint32 [capacity]                       (an image's true tags: positive labels + true_extra)
+ *   | rows uint32 [capacity][T][2] = (tp, predicted)
+ * so a merge of shards is a concatenation of `true` and `rows` (and a sum of the 4096 slots).  T <= 32, B <= 4096 per update,
+ * n_seen + B <= capacity < 2^31.
+ *   - a prediction is (double)p > thresholds[t] (VT_SAMPLE_GT, the rule of vt_eval_update) or (double)p >= thresholds[t] (VT_SAMPLE_GE,
+ *     infer_full.py's conf_value >= confidence_threshold), decided in fp64; a NaN probability never predicts; a non-finite one is
+ *     counted; a label is positive when > 0 (VT_F32 or VT_U8 labels);
+ *   - vt_sample_update writes, for row b, true[n_seen + b] = (positive labels of the row) + true_extra[b] (device uint32 [B] or NULL:
+ *     the image's ground-truth tags that are not in the tag list -- the reference counts them in |true|, so they lower recall) and
+ *     (tp, predicted) for every threshold.  One launch, one workgroup per row, all T thresholds from one pass over the row, no atomics;
+ *   - vt_sample_from_keys fills a T = 1 state from the first n_seen keys of every class row of a vt_eval_* state (capacity > 0) under
+ *     ONE THRESHOLD PER CLASS (device fp64 class_thresholds [N]): the probability comes back from the key's high word as
+ *     vt_eval_recount recovers it, label and sample index from the low word, so the result is the same before and after
+ *     vt_eval_average_precision has sorted the rows and on a state vt_eval_merge produced.  true_extra: device uint32 [n_seen] or NULL.
+ *     The tallies go through integer vector atomics into rows the call zeroes itself: bit-reproducible.  The evaluator state is only read;
+ *   - vt_sample_finish writes vt_sample_finish_bytes(T) bytes into `out` (device or pinned host memory):
+ *         fp64 [T][3] = { sum precision_i, sum recall_i, sum F1_i } | uint64 [T][2] = { exact matches, images with no prediction }
+ *       | uint64 [2] = { images with no true tag, non-finite probabilities }
+ *     with the reference's conventions: precision 0 when nothing is predicted, recall 1 when the image has no true tag,
+ *     F1 = 2 P R / (P + R) from the fp64 P and R or 0 when P + R = 0, exact match when tp == predicted == true.  The sums run in
+ *     image order (the order of the reference's loop), without floating-point atomics: two runs give the same bits, and a host
+ *     loop over the same images gives them too.  (scikit-learn's
+ *     average="samples" recall is (sum recall_i - images with no true tag) / n.)
+ *   - vt_sample_read_rows copies true [n_seen] and rows [n_seen][T][2] in stream order into device or pinned host memory. */
+enum { VT_SAMPLE_GT = 0, VT_SAMPLE_GE = 1 };
+size_t vt_sample_state_bytes(int T, long long capacity);
+int vt_sample_reset(vt_context* ctx, void* state, size_t state_bytes, int T, const double* thresholds /* host [T] */, int rule,
+                    long long capacity, void* stream);
+int vt_sample_update(vt_context* ctx, void* state, size_t state_bytes, int T, long long capacity, const float* probs /* [B][N] */,
+                     const void* labels /* [B][N] */, int labels_dtype /* VT_F32 | VT_U8 */, const uint32_t* true_extra /* [B] or NULL */,
+                     int B, int N, long long n_seen /* samples of the earlier updates */, void* stream);
+int vt_sample_from_keys(vt_context* ctx, const void* eval_state, size_t eval_state_bytes, int N, int T_eval, long long capacity,
+                        long long n_seen, const double* class_thresholds /* DEVICE [N] */, int rule,
+                        const uint32_t* true_extra /* DEVICE [n_seen] or NULL */, void* sample_state /* T = 1 */, size_t sample_state_bytes,
+                        long long sample_capacity, void* stream);
+size_t vt_sample_finish_bytes(int T);
+int vt_sample_finish(vt_context* ctx, const void* state, size_t state_bytes, int T, long long capacity, long long n_seen, void* out,
+                     size_t out_bytes, void* stream);
+int vt_sample_read_rows(vt_context* ctx, const void* state, size_t state_bytes, int T, long long capacity, long long n_seen,
+                        uint32_t* true_out /* [n_seen] */, size_t true_bytes, uint32_t* rows_out /* [n_seen][T][2] */, size_t rows_bytes,
+                        void* stream);
+
 /* algorithmic FLOPs of one encoder forward at HxW -- for roofline reporting */
 double vt_encoder_flops(const vt_context* ctx, int H, int W);
 

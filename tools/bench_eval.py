@@ -7,6 +7,7 @@
 
     python tools/bench_eval.py --recount                # vt_eval_recount on a synthetic --tags x --n store (default 10000 x 8192; no model)
     python tools/bench_eval.py --sweep 10 --n 512       # the checkpoint sweep: K decoders per encode, interleaved with the one-decoder one-pass loop
+    python tools/bench_eval.py --samples                # per-image metrics: vt_sample_from_keys against vt_eval_recount on the same store, update, finish
 
 Per leg one JSON line: the loop's images/s (first batch requested -> last batch finished on the GPU, both passes) and the seconds between
 the last batch and the return of the two calls (the metric finish: host numpy, or the device kernels + the final reads).
@@ -19,7 +20,9 @@ vt_eval_average_precision has sorted the rows (the mismatch atomics then land sc
 same key bytes: the recount only reads them, the copy reads and writes them.
 --sweep K: images/s of evaluation.sweep_checkpoints' loop over K decoders (seeds 1..K; loss accumulators on) and of the one-decoder one-pass loop
 (evaluate_and_search, the code of the single-checkpoint run), legs interleaved --reps times in one process; K x the one-decoder loop's time is what
-K separate runs cost.  Also the event-timed milliseconds of one vt_loss_update against one vt_eval_update at (--batch, --tags), each over 20 calls."""
+K separate runs cost.  Also the event-timed milliseconds of one vt_loss_update against one vt_eval_update at (--batch, --tags), each over 20 calls.
+--samples: on the store of --recount, event-timed milliseconds of vt_sample_from_keys, of vt_eval_recount and of a torch copy of the key bytes,
+interleaved three times; of one vt_sample_update at B = 16, T = 19 (over 20 calls); and of vt_sample_finish at 8192 and 65536 images."""
 import argparse
 import contextlib
 import io
@@ -199,6 +202,81 @@ def run_recount(n, tags, reps):
     return res
 
 
+def run_samples(n, tags, reps):
+    """Per-image metrics: vt_sample_from_keys against vt_eval_recount and a torch copy on the same key store; vt_sample_update at
+    B = 16, T = 19; vt_sample_finish at 8192 and 65536 images."""
+    import ctypes
+    import numpy as np
+    from vae_tagger_amd.evaluation import DeviceMultiLabelEvaluator
+    from vae_tagger_amd.sample_metrics import SEARCH_GRID, DeviceSampleEvaluator
+    names = [f"tag_{i:05d}" for i in range(tags)]
+    g = torch.Generator(device="cuda").manual_seed(1)
+    ev = DeviceMultiLabelEvaluator(names, "cuda", capacity=n)
+    for lo in range(0, n, 2048):                                             # the store of run_recount
+        b = min(2048, n - lo)
+        ev.update(torch.rand(b, tags, generator=g, device="cuda") ** 6, (torch.rand(b, tags, generator=g, device="cuda") < 0.02).to(torch.uint8))
+    key_bytes = n * tags * 8
+    vec = np.random.default_rng(0).choice(ev.grid, size=tags)
+    res = {"samples": True, "n": n, "tags": tags, "reps": reps, "key_bytes": key_bytes}
+    vp = ctypes.c_void_p
+    counts = torch.empty(tags, 2, dtype=torch.int32, device="cuda")
+    rows = torch.empty(3, dtype=torch.int64, device="cuda")
+    ws_bytes = ev.ctx.lib.vt_eval_recount_workspace_bytes(tags, n)
+    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device="cuda")
+    wp = (ws.data_ptr() + 255) // 256 * 256
+    se = DeviceSampleEvaluator([float("nan")], "gt", "cuda", capacity=n, context=ev.ctx)
+    src = torch.empty(key_bytes, dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(src)
+    for state in ("unsorted", "sorted"):
+        for name, thr in (("scalar", 0.5), ("per_class", vec), ("scalar_0.99", 0.99)):
+            thr_dev = torch.from_numpy(np.broadcast_to(np.asarray(thr, dtype=np.float64), (tags,)).copy()).cuda()
+            rec = lambda: ev.ctx.call("vt_eval_recount", vp(ev._ptr), ev._bytes, ev.N, ev.T, ev.capacity, ev.n_seen, vp(thr_dev.data_ptr()),
+                                      vp(counts.data_ptr()), counts.numel() * 4, vp(rows.data_ptr()), 24, vp(wp), ws_bytes, ev._stream())
+            fk = lambda: ev.ctx.call("vt_sample_from_keys", vp(ev._ptr), ev._bytes, ev.N, ev.T, ev.capacity, ev.n_seen, vp(thr_dev.data_ptr()), 0,
+                                     None, vp(se._ptr), se._bytes, se.capacity, ev._stream())
+            r_ms, f_ms, c_ms = [], [], []
+            for _ in range(3):                                               # interleaved on one box
+                r_ms.append(_timed(rec, reps)[0]); f_ms.append(_timed(fk, reps)[0]); c_ms.append(_timed(lambda: dst.copy_(src), reps)[0])
+            res[f"recount_ms_{state}_{name}"] = round(min(r_ms), 3)
+            res[f"from_keys_ms_{state}_{name}"] = round(min(f_ms), 3)
+            res[f"torch_copy_ms_{state}_{name}"] = round(min(c_ms), 3)
+            res[f"from_keys_over_recount_{state}_{name}"] = round(min(f_ms) / min(r_ms), 4)
+            res[f"from_keys_read_bytes_per_s_{state}_{name}"] = round(key_bytes / (min(f_ms) * 1e-3), 0)
+        if state == "unsorted":
+            se.n_seen = n
+            first = se.read_rows()
+            ev.read_state(with_ap=True)                                      # sorts the class rows in place
+        else:
+            again = se.read_rows()
+            assert np.array_equal(first[0], again[0]) and np.array_equal(first[1], again[1]), "from_keys changed with the order of the keys"
+    del src, dst, ws
+    # one update at the CLI's shape under --search, and the finish
+    B, T = 16, len(SEARCH_GRID)
+    probs = torch.rand(B, tags, device="cuda") ** 6
+    labels = (torch.rand(B, tags, device="cuda") < 0.02).to(torch.uint8)
+    for cap in (8192, 65536):
+        su = DeviceSampleEvaluator(SEARCH_GRID, "ge", "cuda", capacity=cap)
+        for lo in range(0, cap, B):                                          # fill the state with real rows
+            su.ctx.call("vt_sample_update", vp(su._ptr), su._bytes, su.T, su.capacity, vp(probs.data_ptr()), vp(labels.data_ptr()), 3, None, B, tags,
+                        lo, su._stream())
+        su.n_seen = cap
+        if cap == 8192:
+            def updates():
+                for k in range(20):
+                    su.ctx.call("vt_sample_update", vp(su._ptr), su._bytes, su.T, su.capacity, vp(probs.data_ptr()), vp(labels.data_ptr()), 3, None, B,
+                                tags, k * B, su._stream())
+            best_u, med_u = _timed(updates, reps)
+            res.update(update_B=B, update_T=T, update_ms=round(best_u / 20, 4), update_ms_median=round(med_u / 20, 4),
+                       update_bytes=B * tags * 5 + B * (4 + 8 * T))
+        out = torch.empty(su.ctx.lib.vt_sample_finish_bytes(T), dtype=torch.uint8, device="cuda")
+        best_f, med_f = _timed(lambda: su.ctx.call("vt_sample_finish", vp(su._ptr), su._bytes, su.T, su.capacity, cap, vp(out.data_ptr()), out.numel(),
+                                                   su._stream()), reps)
+        res[f"finish_ms_{cap}"] = round(best_f, 4)
+        res[f"finish_ms_median_{cap}"] = round(med_f, 4)
+        res[f"finish_bytes_{cap}"] = cap * (4 + 8) * T                      # every workgroup reads `true` and its own column of the rows
+    return res
+
+
 def run_sweep(K, vae, names, args):
     import ctypes
     from vae_tagger_amd.evaluation import DeviceMultiLabelEvaluator, evaluate_and_search, sweep_checkpoints
@@ -267,7 +345,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sweep", type=int, default=0, help="time the checkpoint sweep over this many decoders against the one-decoder one-pass loop and exit")
     ap.add_argument("--recount", action="store_true", help="time vt_eval_recount on a synthetic --tags x --n store (--n defaults to 8192 here) and exit")
+    ap.add_argument("--samples", action="store_true",
+                    help="per-image metrics: time vt_sample_from_keys against vt_eval_recount and a torch copy on a synthetic --tags x --n store "
+                         "(--n defaults to 8192 here), vt_sample_update and vt_sample_finish, and exit")
     args = ap.parse_args()
+    if args.samples:
+        print(json.dumps(run_samples(8192 if args.n == 2048 else args.n, args.tags, args.reps)), flush=True)
+        return
     if args.recount:
         print(json.dumps(run_recount(8192 if args.n == 2048 else args.n, args.tags, args.reps)), flush=True)
         return

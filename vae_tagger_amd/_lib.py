@@ -16,6 +16,7 @@ ENCODE_MOMENTS, ENCODE_MODE, ENCODE_MODE_SCALED = 0, 1, 2
 HEAD_PARAM, HEAD_GRAD, HEAD_ADAM_M, HEAD_ADAM_V, HEAD_LOSS_RING, HEAD_NORM = range(6)      # vt_head_read / vt_head_write kinds
 HEAD_LOSS_KINDS = {"bce": 0, "focal": 1, "class_balanced": 2}
 HEAD_RING = 256
+VT_SAMPLE_GT, VT_SAMPLE_GE = 0, 1                        # vt_sample_reset / vt_sample_from_keys rules
 
 _c = ctypes
 _vp, _i, _f, _sz, _ll = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t, _c.c_longlong
@@ -80,6 +81,13 @@ PROTOTYPES = {
     "vt_loss_update": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _i, _i, _vp]),
     "vt_loss_read": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "vt_loss_merge": (_i, [_vp, _vp, _sz, _i, _c.c_double, _c.c_double, _vp, _c.POINTER(LossSource), _i, _vp]),
+    "vt_sample_state_bytes": (_sz, [_i, _ll]),
+    "vt_sample_reset": (_i, [_vp, _vp, _sz, _i, _c.POINTER(_c.c_double), _i, _ll, _vp]),
+    "vt_sample_update": (_i, [_vp, _vp, _sz, _i, _ll, _vp, _vp, _i, _vp, _i, _i, _ll, _vp]),
+    "vt_sample_from_keys": (_i, [_vp, _vp, _sz, _i, _i, _ll, _ll, _vp, _i, _vp, _vp, _sz, _ll, _vp]),
+    "vt_sample_finish_bytes": (_sz, [_i]),
+    "vt_sample_finish": (_i, [_vp, _vp, _sz, _i, _ll, _ll, _vp, _sz, _vp]),
+    "vt_sample_read_rows": (_i, [_vp, _vp, _sz, _i, _ll, _ll, _vp, _sz, _vp, _sz, _vp]),
     "vt_decoder_feature_dim": (_i, [_vp]),
     "vt_decode_features": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "vt_head_state_bytes": (_sz, [_vp]),
