@@ -311,8 +311,9 @@ double vt_encoder_flops(const vt_context* ctx, int H, int W);
  * attention, feature_compress, self- / cross-attention) ends in one feature row per image, [B][F] fp32 with F = vt_decoder_feature_dim
  * (256 plain, 512 attention) whatever the latent's size; the HEAD is `classifier.*`: Linear -> LayerNorm -> (Leaky)ReLU -> Dropout
  * layers and Linear(256, N).  vt_decode_features runs the front alone (workspace: vt_decode_workspace_bytes); vt_head_forward on its
- * rows gives vt_decode_logits' bits.  The front is frozen here (BatchNorm on its running statistics, no dropout), so an image's
- * feature row never changes and can be cached across epochs.
+ * rows gives vt_decode_logits' bits.  With these calls alone the front is frozen (BatchNorm on its running statistics, no dropout), so
+ * an image's feature row never changes and can be cached across epochs; the attention decoder's front is trained by vt_front_* below
+ * (not its cross-attention, which has no backward).
  *
  * The trainer keeps everything in one caller-owned, 256-B aligned device block of vt_head_state_bytes(ctx) bytes (layout:
  * csrc/vt_train.h): fp32 parameters, gradients, Adam m and v, the gradient norm / clip coefficient, and a ring of VT_HEAD_RING fp64
@@ -358,6 +359,53 @@ int vt_head_step(vt_context* ctx, void* state, size_t state_bytes, double lr, do
 int vt_head_commit(vt_context* ctx, const void* state, size_t state_bytes, void* stream);
 int vt_head_read(vt_context* ctx, const void* state, size_t state_bytes, int kind, const char* name, void* out, size_t out_bytes, void* stream);
 int vt_head_write(vt_context* ctx, void* state, size_t state_bytes, int kind, const char* name, const void* src, size_t src_bytes,
+                  void* stream);
+
+/* ---- training the attention decoder's front (csrc/train_front.hip) ------------------------------------------------------------
+ * spatial_attention.*, feature_compress.* and self_attention_post.* of AttentionClassificationDecoder at latent_channels = 16, heads in
+ * {1, 2, 4, 8}, each of spatial and self attention on or off.  Cross-attention is NOT covered: vt_front_state_bytes returns 0 with it
+ * (and for the plain decoder).  Same conventions as the head trainer: a caller-owned, 256-B aligned state block (layout: csrc/vt_train.h),
+ * fp32 storage, fp64 statistics and norm partials, no atomics, every sum in an order fixed by the shapes, no host synchronisation.  The
+ * gradient with respect to the latent is not computed (the encoder is frozen).
+ *   vt_front_init      parameters and BatchNorm running statistics <- the context's tables; gradients, m, v, num_batches_tracked <- 0
+ *   vt_front_forward   train = 0: the inference front on the state's parameters and running statistics (right after init or commit:
+ *                      vt_decode_features' bits).  train != 0: BatchNorm on the batch's statistics (biased variance over B h w, fp64
+ *                      partials per 256 pixels finished in order), running_mean / running_var updated with momentum 0.1 and the unbiased
+ *                      variance, num_batches_tracked + 1; dropout at attention_dropout on the softmax weights [B][heads][64][64], mask =
+ *                      the head trainer's hash of (seed, step, layer 8, element), survivors scaled by 1 / (1 - p); mask_out (may be
+ *                      NULL) receives it as bytes.  The workspace (vt_front_workspace_bytes) keeps what the backward of the SAME batch
+ *                      reads: pass the same latent, dropout arguments and workspace to vt_front_backward before the next forward.
+ *   vt_front_backward  d_features [B][F] -> gradients of every front tensor, ADDED into the state.  Channel max: the gradient goes to
+ *                      the arg-max channel, the lowest index on a tie; ReLU: derivative 0 at exactly 0.
+ *   vt_front_step      AdamW as vt_head_step.   vt_front_commit   the context's tables <- the state, the BatchNorm fold included
+ *   vt_front_read / vt_front_write   by state-dict key; kinds VT_HEAD_PARAM / GRAD / ADAM_M / ADAM_V / NORM, and the BatchNorm buffers
+ *                      VT_FRONT_BN_MEAN / VT_FRONT_BN_VAR (fp32 [8]) / VT_FRONT_BN_TRACKED (int64), for which `name` is ignored
+ *   vt_head_forward_backward_dx   vt_head_forward_backward (same bits in the state) + d_features [B][F] = d loss / d features
+ *   vt_train_clip      one clip_grad_norm_ over both blocks: norm^2 = the head's partials in order, then the front's; both blocks get
+ *                      the same { norm^2, norm, coef } and are scaled in place when coef < 1, untouched otherwise
+ */
+enum { VT_FRONT_BN_MEAN = 6, VT_FRONT_BN_VAR = 7, VT_FRONT_BN_TRACKED = 8 };
+size_t vt_front_state_bytes(const vt_context* ctx);
+size_t vt_front_workspace_bytes(const vt_context* ctx, int B, int h, int w);
+int vt_front_init(vt_context* ctx, void* state, size_t state_bytes, void* stream);
+int vt_front_forward(vt_context* ctx, void* state, size_t state_bytes, const float* latent_nchw, int B, int h, int w, int train,
+                     float attention_dropout, unsigned long long seed, unsigned long long step, float* features_out /* [B][F] */,
+                     unsigned char* mask_out, void* workspace, size_t workspace_bytes, void* stream);
+int vt_front_backward(vt_context* ctx, void* state, size_t state_bytes, const float* latent_nchw, const float* d_features /* [B][F] */, int B,
+                      int h, int w, float attention_dropout, unsigned long long seed, unsigned long long step, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int vt_front_step(vt_context* ctx, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, double weight_decay,
+                  long long t, void* stream);
+int vt_front_commit(vt_context* ctx, const void* state, size_t state_bytes, void* stream);
+int vt_front_read(vt_context* ctx, const void* state, size_t state_bytes, int kind, const char* name, void* out, size_t out_bytes, void* stream);
+int vt_front_write(vt_context* ctx, void* state, size_t state_bytes, int kind, const char* name, const void* src, size_t src_bytes,
+                   void* stream);
+int vt_head_forward_backward_dx(vt_context* ctx, void* state, size_t state_bytes, const float* features, const void* labels, int labels_dtype,
+                                int B, int loss_kind, double focal_alpha, double focal_gamma, const float* class_weights, double loss_scale,
+                                int train, const float* dropout_p /* host */, unsigned long long seed, unsigned long long step,
+                                float* logits_out, unsigned char* masks_out, float* d_features /* [B][F] */, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int vt_train_clip(vt_context* ctx, void* head_state, size_t head_state_bytes, void* front_state, size_t front_state_bytes, float max_norm,
                   void* stream);
 
 /* ---- options ---------------------------------------------------------------------------------

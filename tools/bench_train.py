@@ -14,7 +14,18 @@ Prints one JSON line.
 times the training CLI end to end on `--images` synthetic 1024 x 1024 JPEG files: first `evaluate --threshold 0.5` (ONE pass of encode ->
 decoder -> metrics; the evaluate path is the parent commit's, unchanged) over the same files for its images/s, then
 `train_decoder --no_attention` for `--epochs` epochs; reports epoch 1's images/s against evaluate's, and epoch 2's seconds against
-epoch 1's (train_report.json).  A short warm-up run of each on 2 batches comes first."""
+epoch 1's (train_report.json).  A short warm-up run of each on 2 batches comes first.
+
+    python tools/bench_train.py --front [--classes 10000] [--batch 16] [--latent 128] [--steps 100] [--rounds 5]
+
+One FULL step of the attention decoder (train.DecoderTrainer: front forward in training mode, head forward / loss / backward with
+d loss / d features, front backward, one clip over both blocks, AdamW on both) from a cached latent batch [batch][16][latent][latent],
+against the head-only step (train.HeadTrainer on cached feature rows: the step the trainer had before the front could be trained) and
+against the same full step in torch eager on the same GPU -- the three interleaved in one process, median round reported.
+
+    python tools/bench_train.py --cli --train_front [--images 256] ...
+
+times `train_decoder --train_front` (attention decoder from scratch): epoch 2's rate from the latent cache against epoch 1's."""
 import argparse
 import json
 import os
@@ -40,6 +51,116 @@ def torch_head(sd, plain, rates, device):
     head = nn.Sequential(*layers)
     head.load_state_dict({k[len("classifier."):]: v for k, v in sd.items() if k.startswith("classifier.")})
     return head.to(device).train()
+
+
+class TorchAttentionDecoder(torch.nn.Module):
+    """AttentionClassificationDecoder (spatial + self attention, no cross-attention) in torch, for the eager comparison."""
+
+    def __init__(self, N, heads=8, p=0.1):
+        import torch.nn as nn
+        super().__init__()
+        self.heads = heads
+        self.ca = nn.Sequential(nn.Conv2d(16, 2, 1, bias=False), nn.ReLU(), nn.Conv2d(2, 16, 1, bias=False))
+        self.sp = nn.Conv2d(2, 1, 7, padding=3, bias=False)
+        self.compress = nn.Sequential(nn.Conv2d(16, 8, 3, 1, 1), nn.BatchNorm2d(8), nn.ReLU(), nn.AdaptiveAvgPool2d((8, 8)))
+        self.norm, self.drop = nn.LayerNorm(8), nn.Dropout(p)
+        self.q, self.k, self.v, self.o = (nn.Linear(8, 8) for _ in range(4))
+        self.classifier = nn.Sequential(nn.Linear(512, 1024), nn.LayerNorm(1024), nn.ReLU(), nn.Dropout(0.3), nn.Linear(1024, 512), nn.LayerNorm(512),
+                                        nn.ReLU(), nn.Dropout(0.2), nn.Linear(512, 256), nn.LayerNorm(256), nn.ReLU(), nn.Dropout(0.1),
+                                        nn.Linear(256, N))
+
+    def forward(self, x):
+        import torch.nn.functional as F
+        x = x * torch.sigmoid(self.ca(F.adaptive_avg_pool2d(x, 1)) + self.ca(F.adaptive_max_pool2d(x, 1)))
+        x = x * torch.sigmoid(self.sp(torch.cat([x.mean(1, keepdim=True), x.max(1, keepdim=True)[0]], 1)))
+        y = self.compress(x)
+        B, hd = y.shape[0], 8 // self.heads
+        t = y.view(B, 8, 64).transpose(1, 2)
+        tn = self.norm(t)
+        q, k, v = (m(tn).view(B, 64, self.heads, hd).transpose(1, 2) for m in (self.q, self.k, self.v))
+        a = self.drop(torch.softmax(q @ k.transpose(-2, -1) / hd ** 0.5, dim=-1))
+        o = self.o((a @ v).transpose(1, 2).reshape(B, 64, 8)) + t
+        return self.classifier(o.transpose(1, 2).reshape(B, 512))
+
+
+def front_mode(args):
+    from vae_tagger_amd import synth
+    from vae_tagger_amd.modules import AttentionClassificationDecoder
+    from vae_tagger_amd.train import DecoderTrainer, HeadTrainer
+    dev = torch.device("cuda:0")
+    N, B, L = args.classes, args.batch, args.latent
+    sd = synth.synth_state_dict(synth.attention_decoder_manifest(N), seed=1)
+    dec = AttentionClassificationDecoder(16, L, L, N)
+    dec.load_state_dict(sd, strict=False)
+    dec = dec.to(dev).eval()
+    full, head = DecoderTrainer(dec), HeadTrainer(dec)
+    g = torch.Generator().manual_seed(0)
+    lat = (0.1 + 0.8 * torch.randn(B, 16, L, L, generator=g)).to(dev)
+    y = (torch.rand(B, N, generator=g) < 0.01).float().to(dev)
+    feats = head.features(lat)
+    ref = TorchAttentionDecoder(N).to(dev).train()
+    opt = torch.optim.AdamW(ref.parameters(), lr=1e-3, weight_decay=1e-6)
+    loss_fn = torch.nn.BCEWithLogitsLoss()
+
+    def step_full(n):
+        for _ in range(n):
+            full.forward_backward(lat, y)
+            full.clip(1.0)
+            full.step(1e-3, 1e-6)
+
+    def step_head(n):
+        for _ in range(n):
+            head.forward_backward(feats, y)
+            head.clip(1.0)
+            head.step(1e-3, 1e-6)
+
+    def step_torch(n):
+        for _ in range(n):
+            loss_fn(ref(lat), y).backward()
+            torch.nn.utils.clip_grad_norm_(ref.parameters(), 1.0)
+            opt.step()
+            opt.zero_grad()
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn(args.steps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / args.steps            # microseconds per step
+
+    fns = {"full": step_full, "head_only": step_head, "torch_full": step_torch}
+    for fn in fns.values():
+        fn(10)
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for k, fn in fns.items():
+            times[k].append(timed(fn))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"bench": "train_step_front", "classes": N, "batch": B, "latent": [L, L], "steps": args.steps, "rounds": args.rounds,
+           "full_us_per_step": med["full"], "head_only_us_per_step": med["head_only"], "torch_full_us_per_step": med["torch_full"],
+           "us_min_max": {k: [min(v), max(v)] for k, v in times.items()}, "full_over_head_only": med["full"] / med["head_only"],
+           "torch_over_full": med["torch_full"] / med["full"], "latent_batch_bytes": lat.numel() * 4}
+    print(json.dumps(out))
+    return out
+
+
+def cli_front_mode(args, tmp, common, trn):
+    from vae_tagger_amd import train_decoder
+    common = [a for a in common if a != "--no_attention"]
+    trn = [a for a in trn if a != "--no_attention"] + ["--train_front"]
+    train_decoder.main(trn + ["--json_path", os.path.join(tmp, "warm.json"), "--output_dir", os.path.join(tmp, "trf_warm"), "--num_epochs", "2"])
+    r = train_decoder.main(trn + ["--json_path", os.path.join(tmp, "data.json"), "--output_dir", os.path.join(tmp, "trf"),
+                                  "--num_epochs", str(args.epochs)])
+    ep = r["report"]["epochs"]
+    out = {"bench": "train_cli_front", "images": args.images, "classes": args.classes, "batch": args.batch,
+           "epoch_images_per_second": [e["images_per_second"] for e in ep], "epoch_seconds": [e["seconds"] for e in ep],
+           "epoch2_over_epoch1_rate": ep[1]["images_per_second"] / ep[0]["images_per_second"],
+           "encoder_batches": [e["encoder_batches"] for e in ep], "steps": [e["steps"] for e in ep], "latent_cache": r["report"]["latent_cache"],
+           "train_loss": r["history"]["train_loss"]}
+    print(json.dumps(out))
+    return out
 
 
 def cli_mode(args):
@@ -75,6 +196,8 @@ def cli_mode(args):
                   "--no_attention"]
         ev = common + ["--decoder_checkpoint", os.path.join(tmp, "dec.pth"), "--batch_size", str(args.batch), "--threshold", "0.5"]
         trn = common + ["--train_batch_size", str(args.batch), "--save_steps", "1000", "--lr_warmup_steps", "10"]
+        if args.train_front:
+            return cli_front_mode(args, tmp, common, trn)
         evaluate.main(ev + ["--json_path", os.path.join(tmp, "warm.json"), "--output_dir", os.path.join(tmp, "ev_warm")])
         evaluate.main(ev + ["--json_path", os.path.join(tmp, "data.json"), "--output_dir", os.path.join(tmp, "ev")])
         st = dict(evaluate.LAST_RUN_STATS)
@@ -97,6 +220,9 @@ def cli_mode(args):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cli", action="store_true", help="time the training CLI's epochs against the evaluate CLI on the same files")
+    ap.add_argument("--front", action="store_true", help="time the full attention-decoder step against the head-only step and torch eager")
+    ap.add_argument("--train_front", action="store_true", help="with --cli: time train_decoder --train_front (epoch 2 from the latent cache)")
+    ap.add_argument("--latent", type=int, default=128, help="with --front: the latent's height and width")
     ap.add_argument("--images", type=int, default=256)
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--classes", type=int, default=10000)
@@ -107,6 +233,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.cli:
         return cli_mode(args)
+    if args.front:
+        return front_mode(args)
     from vae_tagger_amd import synth
     from vae_tagger_amd.modules import AttentionClassificationDecoder, ClassificationDecoder
     from vae_tagger_amd.train import HeadTrainer, head_dropout_rates

@@ -14,6 +14,7 @@ VT_F32, VT_BF16, VT_F16, VT_U8 = 0, 1, 2, 3
 VT_STATUS_NONFINITE, VT_STATUS_FP8_SATURATED = 1, 2      # bits of vt_status (include/vae_tagger_hip.h)
 ENCODE_MOMENTS, ENCODE_MODE, ENCODE_MODE_SCALED = 0, 1, 2
 HEAD_PARAM, HEAD_GRAD, HEAD_ADAM_M, HEAD_ADAM_V, HEAD_LOSS_RING, HEAD_NORM = range(6)      # vt_head_read / vt_head_write kinds
+FRONT_BN_MEAN, FRONT_BN_VAR, FRONT_BN_TRACKED = 6, 7, 8                                    # vt_front_read / vt_front_write, besides the above
 HEAD_LOSS_KINDS = {"bce": 0, "focal": 1, "class_balanced": 2}
 HEAD_RING = 256
 VT_SAMPLE_GT, VT_SAMPLE_GE = 0, 1                        # vt_sample_reset / vt_sample_from_keys rules
@@ -101,6 +102,18 @@ PROTOTYPES = {
     "vt_head_commit": (_i, [_vp, _vp, _sz, _vp]),
     "vt_head_read": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
     "vt_head_write": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
+    "vt_front_state_bytes": (_sz, [_vp]),
+    "vt_front_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "vt_front_init": (_i, [_vp, _vp, _sz, _vp]),
+    "vt_front_forward": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _f, _c.c_ulonglong, _c.c_ulonglong, _vp, _vp, _vp, _sz, _vp]),
+    "vt_front_backward": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _i, _i, _f, _c.c_ulonglong, _c.c_ulonglong, _vp, _sz, _vp]),
+    "vt_front_step": (_i, [_vp, _vp, _sz, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _ll, _vp]),
+    "vt_front_commit": (_i, [_vp, _vp, _sz, _vp]),
+    "vt_front_read": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
+    "vt_front_write": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
+    "vt_head_forward_backward_dx": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _i, _i, _c.c_double, _c.c_double, _vp, _c.c_double, _i,
+                                         _c.POINTER(_f), _c.c_ulonglong, _c.c_ulonglong, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vt_train_clip": (_i, [_vp, _vp, _sz, _vp, _sz, _f, _vp]),
     "vt_encoder_flops": (_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),

@@ -156,7 +156,11 @@ int vt_decoder_finalize(vt_context* c) {
             }
             d.bn_scale = (const float*)c->upload(sc.data(), H * 4);
             d.bn_shift = (const float*)c->upload(sh.data(), H * 4);
-            if (!d.bn_scale || !d.bn_shift) return c->fail(VT_ERR_HIP, "upload failed for batch norm");
+            d.bn_w = (const float*)c->upload(g->v.data(), H * 4);
+            d.bn_b = (const float*)c->upload(b->v.data(), H * 4);
+            d.bn_mean = (const float*)c->upload(m->v.data(), H * 4);
+            d.bn_var = (const float*)c->upload(v->v.data(), H * 4);
+            if (!d.bn_scale || !d.bn_shift || !d.bn_w || !d.bn_b || !d.bn_mean || !d.bn_var) return c->fail(VT_ERR_HIP, "upload failed for batch norm");
         }
         if (d.use_self) {
             const char* p = "self_attention_post.";

@@ -1,7 +1,9 @@
 // Training of the decoder's classifier head on the device: what train_decoder.py's loop body (train_decoder.py:173-216) does to
 // `classifier.*` -- forward with dropout, BCE / Focal / class-balanced loss (improved_losses.py:39-72), backward, clip_grad_norm_
 // and AdamW -- on one caller-owned state block (vt_train.h) fed FEATURE ROWS [B][F]: the output of the decoder's front
-// (vt_decode_features), which is frozen here and therefore the same every epoch.
+// (vt_decode_features).  Alone, this unit leaves the front frozen (its rows are the same every epoch); the attention decoder's front
+// is trained by train_front.hip, which takes d loss / d features from vt_head_forward_backward_dx here and shares vt_train_clip (one
+// norm over both blocks) and the AdamW kernel.  Cross-attention has no backward anywhere.
 // fp32 parameters, gradients and moments; fp64 for the loss elements and every scalar reduction.  No atomics: every gradient element
 // is owned by one thread, sums over the batch run in ascending row order, sums over workgroups are written as partials and added in
 // workgroup order by a later launch -- the order of every sum is a function of the shapes alone, so a given call sequence leaves the
@@ -283,6 +285,37 @@ __global__ __launch_bounds__(256) VT_NO_PACKED_F32 void head_adamw_kernel(float4
     P[i] = p; G[i] = g; M[i] = m; V[i] = v;
 }
 
+// d_features[b][k] = sum of the first layer's G dX partials, g ascending
+__global__ __launch_bounds__(256) void head_dx_sum_kernel(const float* __restrict__ part, int G, long long n, float* __restrict__ dx) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float a = 0.f;
+    for (int g = 0; g < G; ++g) a += part[(long long)g * n + i];
+    dx[i] = a;
+}
+
+// one workgroup: the head's squared-norm partials in index order, then the front's -> one norm and one coefficient, written to both blocks
+__global__ __launch_bounds__(256) void train_clip_kernel(const double* __restrict__ head_part, int n_head, const double* __restrict__ front_part,
+                                                         int n_front, float max_norm, HeadScalars* __restrict__ sc_head,
+                                                         HeadScalars* __restrict__ sc_front) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n_head; i += 256) a += head_part[i];
+    const double th = block_sum_256d(a, red);
+    a = 0.0;
+    for (int i = threadIdx.x; i < n_front; i += 256) a += front_part[i];
+    const double tf = block_sum_256d(a, red);
+    if (threadIdx.x == 0) {
+        const double total = th + tf;
+        const float norm = (float)sqrt(total);
+        const float coef = max_norm / (norm + 1e-6f);
+        HeadScalars v;
+        v.sq = total; v.norm = norm; v.coef = coef < 1.0f ? coef : 1.0f;
+        *sc_head = v; *sc_front = v;
+    }
+}
+
 #define TCKL(c, what) HIPCK(c, hipGetLastError(), what)
 
 int head_check(vt_context* c, const char* who, const void* state, size_t state_bytes, HeadLayout* out) {
@@ -366,6 +399,15 @@ int head_check_batch(vt_context* c, const char* who, const HeadLayout& l, const 
 
 }  // namespace
 
+hipError_t vt_train_adamw_launch(float* P, float* G, float* M, float* V, long long n4, double lr, double beta1, double beta2, double eps,
+                                 double weight_decay, long long t, hipStream_t s) {
+    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
+    hipLaunchKernelGGL(head_adamw_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (float4*)P, (float4*)G, (float4*)M, (float4*)V, n4,
+                       (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2),
+                       (float)eps);
+    return hipGetLastError();
+}
+
 extern "C" {
 
 int vt_decoder_feature_dim(const vt_context* c) {
@@ -439,11 +481,11 @@ int vt_head_forward(vt_context* c, const void* state, size_t state_bytes, const 
     return VT_OK;
 }
 
-int vt_head_forward_backward(vt_context* c, void* state, size_t state_bytes, const float* features, const void* labels, int labels_dtype, int B,
-                             int loss_kind, double alpha, double gamma, const float* class_weights, double loss_scale, int train,
-                             const float* dropout_p, unsigned long long seed, unsigned long long step, float* logits_out, unsigned char* masks_out,
-                             void* ws, size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
+// vt_head_forward_backward, and with d_features its _dx form: the first layer's dX partials are kept and added in workgroup order
+static int head_forward_backward(vt_context* c, void* state, size_t state_bytes, const float* features, const void* labels, int labels_dtype, int B,
+                                 int loss_kind, double alpha, double gamma, const float* class_weights, double loss_scale, int train,
+                                 const float* dropout_p, unsigned long long seed, unsigned long long step, float* logits_out,
+                                 unsigned char* masks_out, float* d_features, void* ws, size_t ws_bytes, void* stream) {
     DeviceGuard guard(c);
     HeadLayout l;
     VTCK(head_check(c, "vt_head_forward_backward", state, state_bytes, &l));
@@ -494,7 +536,7 @@ int vt_head_forward_backward(vt_context* c, void* state, size_t state_bytes, con
         const bool hid = i < sh.hidden;
         hipLaunchKernelGGL(head_linear_bwd_kernel, dim3(l.groups[i], l.kblocks[i]), dim3(256), 0, s, dzl, x, p.w[i], const_cast<float*>(g.w[i]),
                            const_cast<float*>(g.b[i]), hid ? (const float*)(wsb + w.dt[i]) : nullptr, hid ? (const float*)(wsb + w.xh[i]) : nullptr,
-                           hid ? const_cast<float*>(g.ln_w[i]) : nullptr, hid ? const_cast<float*>(g.ln_b[i]) : nullptr, i > 0 ? part : nullptr,
+                           hid ? const_cast<float*>(g.ln_w[i]) : nullptr, hid ? const_cast<float*>(g.ln_b[i]) : nullptr, i > 0 || d_features ? part : nullptr,
                            normpart + l.part_base[i], B, sh.dims[i], sh.dims[i + 1], vt_head_rows(sh, i)); TCKL(c, "head linear backward");
         if (i == 0) break;
         const int j = i - 1, D = sh.dims[i];            // hidden layer j produced this linear's input
@@ -503,6 +545,53 @@ int vt_head_forward_backward(vt_context* c, void* state, size_t state_bytes, con
                            (float*)(wsb + w.xh[j]), (float*)(wsb + w.dz[j])); TCKL(c, "head layer norm backward");
         dzl = (const float*)(wsb + w.dz[j]);
     }
+    if (d_features) {
+        const long long n = (long long)B * sh.dims[0];
+        hipLaunchKernelGGL(head_dx_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, l.groups[0], n, d_features); TCKL(c, "head d features");
+    }
+    return VT_OK;
+}
+
+int vt_head_forward_backward(vt_context* c, void* state, size_t state_bytes, const float* features, const void* labels, int labels_dtype, int B,
+                             int loss_kind, double alpha, double gamma, const float* class_weights, double loss_scale, int train,
+                             const float* dropout_p, unsigned long long seed, unsigned long long step, float* logits_out, unsigned char* masks_out,
+                             void* ws, size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    return head_forward_backward(c, state, state_bytes, features, labels, labels_dtype, B, loss_kind, alpha, gamma, class_weights, loss_scale, train,
+                                 dropout_p, seed, step, logits_out, masks_out, nullptr, ws, ws_bytes, stream);
+}
+
+int vt_head_forward_backward_dx(vt_context* c, void* state, size_t state_bytes, const float* features, const void* labels, int labels_dtype, int B,
+                                int loss_kind, double alpha, double gamma, const float* class_weights, double loss_scale, int train,
+                                const float* dropout_p, unsigned long long seed, unsigned long long step, float* logits_out,
+                                unsigned char* masks_out, float* d_features, void* ws, size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    if (!d_features || ((uintptr_t)d_features & 3)) return c->fail(VT_ERR_INVALID, "vt_head_forward_backward_dx: d_features is null or misaligned");
+    return head_forward_backward(c, state, state_bytes, features, labels, labels_dtype, B, loss_kind, alpha, gamma, class_weights, loss_scale, train,
+                                 dropout_p, seed, step, logits_out, masks_out, d_features, ws, ws_bytes, stream);
+}
+
+// clip_grad_norm_ over the head's and the front's gradients together
+int vt_train_clip(vt_context* c, void* head_state, size_t head_bytes, void* front_state, size_t front_bytes, float max_norm, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    HeadLayout l;
+    VTCK(head_check(c, "vt_train_clip", head_state, head_bytes, &l));
+    if (!vt_front_trainable(c->dec)) return c->fail(VT_ERR_INVALID, "vt_train_clip: this decoder's front is not trainable");
+    const FrontLayout f = vt_front_layout(c->dec);
+    if (!front_state || ((uintptr_t)front_state & (ALIGN - 1)) || front_bytes < f.total)
+        return c->fail(VT_ERR_INVALID, "vt_train_clip: the front state is null, not 256-B aligned or shorter than %zu bytes", f.total);
+    if (!(max_norm > 0.f)) return c->fail(VT_ERR_INVALID, "vt_train_clip: max_norm = %g must be positive", max_norm);
+    hipStream_t s = (hipStream_t)stream;
+    char* hs = (char*)head_state;
+    char* fs = (char*)front_state;
+    HeadScalars* sch = (HeadScalars*)(hs + l.scalars);
+    HeadScalars* scf = (HeadScalars*)(fs + f.scalars);
+    hipLaunchKernelGGL(train_clip_kernel, dim3(1), dim3(256), 0, s, (const double*)(hs + l.normpart), l.norm_parts, (const double*)(fs + f.normpart),
+                       VT_FRONT_NORM_PARTS, max_norm, sch, scf); TCKL(c, "train clip");
+    const long long n4 = (long long)(l.P / 4), f4 = VT_FRONT_P / 4;
+    hipLaunchKernelGGL(head_scale_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (float4*)(hs + l.grads), n4, sch); TCKL(c, "train clip scale");
+    hipLaunchKernelGGL(head_scale_kernel, dim3((unsigned)((f4 + 255) / 256)), dim3(256), 0, s, (float4*)(fs + f.grads), f4, scf); TCKL(c, "train clip scale");
     return VT_OK;
 }
 
@@ -530,11 +619,8 @@ int vt_head_step(vt_context* c, void* state, size_t state_bytes, double lr, doub
     if (t < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !isfinite(lr) || !isfinite(weight_decay))
         return c->fail(VT_ERR_INVALID, "vt_head_step: t >= 1, betas in [0, 1), eps >= 0 and finite lr / weight_decay expected");
     char* st = (char*)state;
-    const long long n4 = (long long)(l.P / 4);
-    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
-    hipLaunchKernelGGL(head_adamw_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float4*)(st + l.params),
-                       (float4*)(st + l.grads), (float4*)(st + l.m), (float4*)(st + l.v), n4, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2), (float)eps); TCKL(c, "head step");
+    HIPCK(c, vt_train_adamw_launch((float*)(st + l.params), (float*)(st + l.grads), (float*)(st + l.m), (float*)(st + l.v), (long long)(l.P / 4), lr,
+                                   beta1, beta2, eps, weight_decay, t, (hipStream_t)stream), "head step");
     return VT_OK;
 }
 

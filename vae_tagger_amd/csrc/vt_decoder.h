@@ -16,6 +16,8 @@ struct DecoderWeights {
     int ca_hidden = 2;
     const float *ca_w0 = nullptr, *ca_w2 = nullptr, *sa_w = nullptr;
     const float *fc_w = nullptr, *fc_b = nullptr, *bn_scale = nullptr, *bn_shift = nullptr;
+    // the BatchNorm tensors bn_scale / bn_shift were folded from (the front trainer reads and writes them: train_front.hip)
+    const float *bn_w = nullptr, *bn_b = nullptr, *bn_mean = nullptr, *bn_var = nullptr;
     DecSelfAttnW sa{};
     const float *qg_w = nullptr, *qg_b = nullptr;
     const float *cx_q_w = nullptr, *cx_q_b = nullptr, *cx_k_w = nullptr, *cx_k_b = nullptr;

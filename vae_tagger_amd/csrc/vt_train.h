@@ -87,7 +87,7 @@ inline HeadWorkspace vt_head_workspace(const HeadLayout& l, int B) {
     w.logits = take(4 * (size_t)B * N);
     w.dy = take(4 * (size_t)B * N);
     size_t part = 0;
-    for (int i = 1; i <= s.hidden; ++i) {                      // (layer 0 reads the frozen features: no dX)
+    for (int i = 0; i <= s.hidden; ++i) {                      // (layer 0's are read by vt_head_forward_backward_dx only)
         const size_t p = (size_t)l.groups[i] * B * s.dims[i];
         if (p > part) part = p;
     }
@@ -115,3 +115,95 @@ VT_TRAIN_HD inline bool vt_head_keep(uint64_t seed, uint64_t step, int layer, ui
     x = vt_head_mix64(x ^ ((uint64_t)(layer + 1) << 56) ^ idx);
     return (float)(uint32_t)(x >> 40) * (1.0f / 16777216.0f) >= p;
 }
+
+// ---- front trainer (train_front.hip): spatial_attention.*, feature_compress.* and self_attention_post.* of the attention decoder ----
+// Parameter tensors at FIXED float offsets in each of the four arrays (a tensor of a piece that is switched off keeps its slot, all
+// zero); every tensor starts on a multiple of 64 floats and the padding stays zero.  Gradient GROUPS are reduced by one launch each.
+constexpr int VT_FRONT_TENSORS = 17;
+constexpr int VT_FRONT_P = 2240;            // floats of one parameter array
+constexpr int VT_FRONT_NORM_PARTS = 16;     // squared-norm partials: mlp 0 | 7x7 1 | conv 2..6 | batch norm 7 | self-attention 8..10
+constexpr int VT_FRONT_MAX_B = 1024;        // (grids carry B, and B x 16, in their y dimension)
+constexpr int VT_FRONT_DROPOUT_LAYER = 8;   // the attention dropout's layer id in vt_head_keep (the head's are 0..2)
+enum { VT_FG_MLP = 0, VT_FG_SP7 = 1, VT_FG_CONV = 2, VT_FG_BN = 3, VT_FG_SA = 4 };
+constexpr int VT_FG_START[5] = {0, 128, 256, 1472, 1600};       // first float of each group; the group ends where the next starts
+constexpr int VT_FG_END[5] = {128, 256, 1472, 1600, 2240};
+constexpr int VT_FG_SLOT[5] = {0, 1, 2, 7, 8};                  // first squared-norm partial of each group
+struct FrontTensor { const char* name; int off, numel, piece; };     // piece 0: spatial attention, 1: feature_compress, 2: self-attention
+constexpr FrontTensor VT_FRONT_TABLE[VT_FRONT_TENSORS] = {
+    {"spatial_attention.channel_att.0.weight", 0, 32, 0},   {"spatial_attention.channel_att.2.weight", 64, 32, 0},
+    {"spatial_attention.spatial_att.0.weight", 128, 98, 0}, {"feature_compress.0.weight", 256, 1152, 1},
+    {"feature_compress.0.bias", 1408, 8, 1},                {"feature_compress.1.weight", 1472, 8, 1},
+    {"feature_compress.1.bias", 1536, 8, 1},                {"self_attention_post.norm.weight", 1600, 8, 2},
+    {"self_attention_post.norm.bias", 1664, 8, 2},          {"self_attention_post.q_proj.weight", 1728, 64, 2},
+    {"self_attention_post.q_proj.bias", 1792, 8, 2},        {"self_attention_post.k_proj.weight", 1856, 64, 2},
+    {"self_attention_post.k_proj.bias", 1920, 8, 2},        {"self_attention_post.v_proj.weight", 1984, 64, 2},
+    {"self_attention_post.v_proj.bias", 2048, 8, 2},        {"self_attention_post.out_proj.weight", 2112, 64, 2},
+    {"self_attention_post.out_proj.bias", 2176, 8, 2},
+};
+enum { VT_FT_CA0 = 0, VT_FT_CA2, VT_FT_SP7, VT_FT_FCW, VT_FT_FCB, VT_FT_BNW, VT_FT_BNB, VT_FT_LNW, VT_FT_LNB, VT_FT_QW, VT_FT_QB, VT_FT_KW,
+       VT_FT_KB, VT_FT_VW, VT_FT_VB, VT_FT_OW, VT_FT_OB };
+
+// One block, every section 256-B aligned:
+//   params fp32 [P] | grads | adam m | adam v | batch norm buffers { running_mean fp32 [8], running_var fp32 [8], eval scale fp32 [8],
+//   eval shift fp32 [8] (the fold vt_decoder_finalize makes, redone whenever its inputs change), int64 num_batches_tracked at byte 128 } |
+//   scalars { fp64 squared norm, fp32 norm, fp32 clip coefficient } | squared-norm partials fp64 [VT_FRONT_NORM_PARTS]
+struct FrontLayout {
+    int use_spatial, use_self, heads;
+    size_t params, grads, m, v, bn, scalars, normpart, total;
+    bool present(int t) const { const int p = VT_FRONT_TABLE[t].piece; return p == 1 || (p == 0 ? use_spatial != 0 : use_self != 0); }
+};
+inline FrontLayout vt_front_layout(const DecoderWeights& d) {
+    FrontLayout l;
+    l.use_spatial = d.use_spatial; l.use_self = d.use_self; l.heads = d.heads;
+    const size_t a = vt_eval_align(4 * (size_t)VT_FRONT_P);
+    l.params = 0; l.grads = a; l.m = 2 * a; l.v = 3 * a; l.bn = 4 * a;
+    l.scalars = l.bn + 256;
+    l.normpart = l.scalars + 256;
+    l.total = l.normpart + vt_eval_align(sizeof(double) * VT_FRONT_NORM_PARTS);
+    return l;
+}
+// the front can be trained: the attention decoder at latent_channels 16 without cross-attention, heads in {1, 2, 4, 8}
+inline bool vt_front_trainable(const DecoderWeights& d) {
+    if (d.plain || d.use_cross || d.latent_channels != 16) return false;
+    return !d.use_self || d.heads == 1 || d.heads == 2 || d.heads == 4 || d.heads == 8;
+}
+
+// Workspace of a forward / backward pair (the backward reads what the training-mode forward of the same batch left), every section
+// 256-B aligned.  Pixel chunks: 256 pixels of one image (batch-norm partials); conv tiles: 16 rows x 64 columns; 7x7 tiles: 2 rows.
+constexpr int VT_FRONT_CONV_ROWS = 16, VT_FRONT_CONV_COLS = 64, VT_FRONT_SP_ROWS = 2;
+struct FrontWorkspace {
+    size_t eval;                                                     // vt_decoder_front's scratch (train = 0)
+    size_t pool, gate, sp, am, sg, xs, z, bnpart, bnstat, tin;      // forward
+    size_t dpool, dz, dxs, dpre, dsp, dgate, p_sa, p_conv, p_sp7, p_mlp;   // backward
+    int chunks, conv_parts, sp_parts;
+    size_t total;
+};
+inline FrontWorkspace vt_front_workspace(const FrontLayout& l, int B, int H, int W) {
+    FrontWorkspace w;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += vt_eval_align(bytes); return o; };
+    const size_t HW = (size_t)H * W, b = (size_t)B;
+    w.chunks = B * (int)((HW + 255) / 256);
+    w.conv_parts = B * ((H + VT_FRONT_CONV_ROWS - 1) / VT_FRONT_CONV_ROWS) * ((W + VT_FRONT_CONV_COLS - 1) / VT_FRONT_CONV_COLS);
+    w.sp_parts = B * ((H + VT_FRONT_SP_ROWS - 1) / VT_FRONT_SP_ROWS);
+    w.eval = take(4 * vt_decoder_workspace_floats(B, 16, H, W));
+    w.pool = take(4 * b * 32); w.gate = take(4 * b * 16); w.sp = take(4 * b * 2 * HW); w.am = take(b * HW); w.sg = take(4 * b * HW);
+    w.xs = take(l.use_spatial ? 4 * b * 16 * HW : 0);
+    w.z = take(4 * b * 8 * HW);
+    w.bnpart = take(sizeof(double) * (size_t)w.chunks * 16);
+    w.bnstat = take(sizeof(double) * 32);                            // per channel: mean, rstd, sum dy, sum dy xhat
+    w.tin = take(4 * b * 512);
+    w.dpool = take(4 * b * 512); w.dz = take(4 * b * 8 * HW);
+    w.dxs = take(l.use_spatial ? 4 * b * 16 * HW : 0);
+    w.dpre = take(4 * b * HW); w.dsp = take(4 * b * 2 * HW); w.dgate = take(sizeof(double) * b * 16);
+    w.p_sa = take(4 * b * 640);
+    w.p_conv = take(4 * (size_t)w.conv_parts * 1216);
+    w.p_sp7 = take(4 * (size_t)w.sp_parts * 128);
+    w.p_mlp = take(4 * b * 128);
+    w.total = off;
+    return w;
+}
+
+// shared launches of train_head.hip (the front's optimiser step is the head's kernel over the front's arrays)
+hipError_t vt_train_adamw_launch(float* P, float* G, float* M, float* V, long long n4, double lr, double beta1, double beta2, double eps,
+                                 double weight_decay, long long t, hipStream_t s);

@@ -5,9 +5,16 @@ reference's train_decoder.py (train_decoder.py:173-216) does to `classifier.*`.
   split_indices / epoch_order    the train / validation split and the per-epoch training order, from the seed alone
   FeatureCache   the decoder front's feature rows and the labels of every image, kept on the device after the first epoch
   HeadTrainer    the device state (parameters, gradients, Adam moments, loss ring) and its forward_backward / clip / step / commit
+  FrontTrainer   the same for the attention decoder's front (vt_front_*; csrc/train_front.hip): training-mode forward (BatchNorm on
+                 batch statistics, dropout on the softmax weights), backward from d loss / d features, AdamW, commit
+  DecoderTrainer front + head: one forward_backward, ONE clip_grad_norm_ over both blocks (vt_train_clip), one step / commit
+  LatentCache    the encoder's latents of every image in one flat device arena, so that later epochs skip the encoder
 
-The decoder's FRONT (everything before `classifier`) is frozen: for ClassificationDecoder it is the parameter-free 4x4 pool, so the
-head is the whole model; for AttentionClassificationDecoder it runs as in inference (BatchNorm on its running statistics).
+With HeadTrainer alone the decoder's FRONT (everything before `classifier`) is frozen: for ClassificationDecoder it is the
+parameter-free 4x4 pool, so the head is the whole model; for AttentionClassificationDecoder it runs as in inference (BatchNorm on its
+running statistics).  DecoderTrainer trains the attention decoder in full -- spatial_attention.*, feature_compress.* (running
+statistics included) and self_attention_post.* -- but not with cross-attention, whose backward does not exist.  The channel max of the
+spatial attention gives its gradient to the arg-max channel, the lowest index on a tie.
 """
 import ctypes
 import math
@@ -97,6 +104,89 @@ class FeatureCache:
     def gather(self, keys):
         idx = torch.as_tensor([self.slot[k] for k in keys], dtype=torch.long, device=self.features.device)
         return self.features.index_select(0, idx), self.labels.index_select(0, idx)
+
+
+class LatentCache:
+    """The encoder's latents [16][h][w] fp32 of the images, one after the other in ONE flat fp32 arena on `device`, with (offset, h, w)
+    per image, and their label rows -- what the full decoder trainer needs to skip the encoder after the first epoch (the front is
+    trained, so its feature rows change; the latents do not).  The arena is sized up front for `capacity` images of at most
+    `max_numel` floats each (16 (resolution / 8)^2: 1 MB at 1024 x 1024); `LatentCache.fits` is the memory rule: when that bound plus
+    the labels exceeds the budget NOTHING is cached and every epoch re-encodes.  Host tensors work too: the index logic is the same."""
+
+    def __init__(self, capacity, max_numel, num_classes, device="cuda", label_dtype=torch.float32):
+        self.max_numel = int(max_numel)
+        self.arena = torch.zeros(int(capacity) * self.max_numel, dtype=torch.float32, device=device)
+        self.labels = torch.zeros(int(capacity), int(num_classes), dtype=label_dtype, device=device)
+        self.entry, self.used = {}, 0                # key -> (slot, offset, C, h, w); floats of the arena in use
+
+    @staticmethod
+    def bytes_needed(capacity, max_numel, num_classes, label_bytes=4):
+        return int(capacity) * (int(max_numel) * 4 + int(num_classes) * int(label_bytes))
+
+    @classmethod
+    def fits(cls, capacity, max_numel, num_classes, budget_bytes, label_bytes=4):
+        return cls.bytes_needed(capacity, max_numel, num_classes, label_bytes) <= int(budget_bytes)
+
+    def __len__(self):
+        return len(self.entry)
+
+    def __contains__(self, key):
+        return key in self.entry
+
+    @property
+    def nbytes(self):
+        """Bytes in use: the latents stored so far and their label rows."""
+        return self.used * 4 + len(self.entry) * self.labels.shape[1] * self.labels.element_size()
+
+    def shape(self, key):
+        return self.entry[key][3:]
+
+    def put(self, keys, latents, labels):
+        keys = list(keys)
+        if latents.dim() != 4 or latents.shape[0] != len(keys) or labels.shape[0] != len(keys):
+            raise ValueError("LatentCache.put: latents [B, C, h, w] and one label row per key")
+        _, C, h, w = latents.shape
+        n = C * h * w
+        if n > self.max_numel:
+            raise ValueError(f"LatentCache.put: a latent of {n} floats exceeds the {self.max_numel} the arena was sized for")
+        lat = latents.detach().to(self.arena.device, torch.float32).reshape(len(keys), n)
+        for i, k in enumerate(keys):
+            if k in self.entry:
+                slot, off = self.entry[k][:2]
+                if self.entry[k][2:] != (C, h, w):
+                    raise ValueError(f"LatentCache.put: {k} was stored as {self.entry[k][2:]}, now {(C, h, w)}")
+            else:
+                if len(self.entry) >= self.labels.shape[0] or self.used + n > self.arena.numel():
+                    raise IndexError("LatentCache is full")
+                slot, off = len(self.entry), self.used
+                self.entry[k] = (slot, off, C, h, w)
+                self.used += n
+            self.arena[off:off + n].copy_(lat[i])
+            self.labels[slot].copy_(labels[i].to(self.labels.device, self.labels.dtype))
+
+    def gather(self, keys):
+        """(latents [B][C][h][w], labels [B][N]) of keys that share one latent shape, in that order."""
+        keys = list(keys)
+        shapes = {self.entry[k][2:] for k in keys}
+        if len(shapes) != 1:
+            raise ValueError(f"LatentCache.gather: one latent shape per batch expected, got {sorted(shapes)}")
+        (C, h, w), = shapes
+        n = C * h * w
+        lat = torch.stack([self.arena[self.entry[k][1]:self.entry[k][1] + n] for k in keys]).view(len(keys), C, h, w)
+        idx = torch.as_tensor([self.entry[k][0] for k in keys], dtype=torch.long, device=self.labels.device)
+        return lat, self.labels.index_select(0, idx)
+
+    def batches(self, order, batch_size):
+        """The keys of `order` that are cached, as batches of up to batch_size keys of ONE latent shape each (batch statistics need
+        one shape per batch): the bucket feeder's grouping (prefetch.BucketGrouper) keyed by (h, w), nothing forced out early."""
+        from .prefetch import BucketGrouper
+        keys = [k for k in order if k in self.entry]
+        grouper = BucketGrouper(batch_size, max(1, len(keys)))
+        out = []
+        for k in keys:
+            out.extend([key for key, _ in group] for _, group in grouper.add(k, self.shape(k), None))
+        out.extend([key for key, _ in group] for _, group in grouper.flush())
+        return out
 
 
 def head_dropout_rates(decoder):
@@ -269,3 +359,222 @@ class HeadTrainer:
     def state_dict(self):
         """The decoder's full state_dict with the trained head (export_state_dict)."""
         return export_state_dict(self.decoder, self.parameter)
+
+
+# ---- the attention decoder's front -------------------------------------------------------------------------------------------------
+FRONT_PREFIXES = ("spatial_attention.", "feature_compress.", "self_attention_post.")
+FRONT_BUFFERS = {"feature_compress.1.running_mean": _lib.FRONT_BN_MEAN, "feature_compress.1.running_var": _lib.FRONT_BN_VAR,
+                 "feature_compress.1.num_batches_tracked": _lib.FRONT_BN_TRACKED}
+
+
+def front_trainable(decoder):
+    """Can train.FrontTrainer train this decoder's front?  The attention decoder without cross-attention (vt_front_state_bytes)."""
+    plain, _, _, cross, _ = decoder._cfg
+    return not plain and not cross
+
+
+class FrontTrainer:
+    """Device state of the FRONT of an attention decoder (spatial_attention.*, feature_compress.*, self_attention_post.*; vt_front_* of
+    the C ABI, csrc/train_front.hip) and the calls that train it.  `forward(latent, train=True)` runs BatchNorm on the batch's
+    statistics (and updates the running ones) and drops softmax weights at `attention_dropout`; `backward(d_features)` belongs to the
+    last training-mode forward and ADDS the gradients of every front tensor.  The channel max of the spatial attention sends its
+    gradient to the arg-max channel, the lowest index on a tie.  Cross-attention is not covered."""
+
+    def __init__(self, decoder, attention_dropout=0.1, seed=0):
+        self.decoder = decoder
+        self.ctx = decoder._context()
+        self.device = next(decoder.parameters()).device
+        self.F = self.ctx.lib.vt_decoder_feature_dim(self.ctx.handle)
+        self.heads = decoder._cfg[4]
+        self.p = float(attention_dropout)
+        if not 0.0 <= self.p < 1.0:
+            raise ValueError(f"attention_dropout {attention_dropout} outside [0, 1)")
+        self.seed, self.calls, self.t = int(seed), 0, 0
+        self._bytes = self.ctx.lib.vt_front_state_bytes(self.ctx.handle)
+        if self._bytes == 0:
+            raise _lib.VTError("this decoder's front cannot be trained on the device: an attention decoder without cross-attention, "
+                               "latent_channels = 16 and attention_heads in {1, 2, 4, 8} is expected")
+        sd = decoder.state_dict()
+        self.shapes = {k: tuple(v.shape) for k, v in sd.items() if k.startswith(FRONT_PREFIXES) and k not in FRONT_BUFFERS}
+        self.buffers = {k: tuple(sd[k].shape) for k in FRONT_BUFFERS}
+        self._buf = torch.empty(self._bytes + 256, dtype=torch.uint8, device=self.device)
+        self._ptr = (self._buf.data_ptr() + 255) // 256 * 256
+        self._last = None
+        self.ctx.call("vt_front_init", ctypes.c_void_p(self._ptr), self._bytes, stream_ptr(self.device))
+        self.write_buffer("feature_compress.1.num_batches_tracked", sd["feature_compress.1.num_batches_tracked"])
+
+    def _state(self):
+        return ctypes.c_void_p(self._ptr), self._bytes
+
+    def _ws(self, B, h, w):
+        need = self.ctx.lib.vt_front_workspace_bytes(self.ctx.handle, int(B), int(h), int(w))
+        if need == 0:
+            raise _lib.VTError(f"unsupported front batch {B} x {h} x {w}")
+        _, ptr = workspace(self.device, need, "front")
+        return ctypes.c_void_p(ptr), need
+
+    def forward(self, latent, train=False, step=None, return_mask=False):
+        """Feature rows [B][F].  train=True keeps what backward() needs (until the next forward)."""
+        x = self.decoder._latent(latent)
+        B, _, h, w = x.shape
+        step = self.calls if step is None else int(step)
+        out = torch.empty(B, self.F, dtype=torch.float32, device=self.device)
+        mask = torch.empty(B, self.heads, 64, 64, dtype=torch.uint8, device=self.device) if return_mask and train else None
+        ws, need = self._ws(B, h, w)
+        self.ctx.call("vt_front_forward", *self._state(), vp(x), B, h, w, int(bool(train)), self.p, self.seed, step, vp(out), vp(mask), ws,
+                      need, stream_ptr(self.device))
+        self._last = (x, step) if train else None
+        if train:
+            self.calls = step + 1
+        return (out, mask) if return_mask else out
+
+    def backward(self, d_features):
+        if self._last is None:
+            raise RuntimeError("FrontTrainer.backward needs the training-mode forward of the same batch before it")
+        x, step = self._last
+        B, _, h, w = x.shape
+        d = d_features.detach().to(self.device, torch.float32).contiguous()
+        if tuple(d.shape) != (B, self.F):
+            raise ValueError(f"expected d_features [{B}, {self.F}], got {tuple(d.shape)}")
+        ws, need = self._ws(B, h, w)
+        self.ctx.call("vt_front_backward", *self._state(), vp(x), vp(d), B, h, w, self.p, self.seed, step, ws, need, stream_ptr(self.device))
+        self._last = None
+
+    def step(self, lr, weight_decay=0.0, betas=ADAM_BETAS, eps=ADAM_EPS):
+        self.t += 1
+        self.ctx.call("vt_front_step", *self._state(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), self.t,
+                      stream_ptr(self.device))
+
+    def commit(self):
+        """Write the parameters, the running statistics and their fold into the decoder's device tables."""
+        self.ctx.call("vt_front_commit", *self._state(), stream_ptr(self.device))
+
+    def _read(self, kind, name, shape, dtype):
+        out = torch.empty(shape, dtype=dtype, pin_memory=True)
+        self.ctx.call("vt_front_read", *self._state(), kind, name.encode() if name else None, ctypes.c_void_p(out.data_ptr()),
+                      out.numel() * out.element_size(), stream_ptr(self.device))
+        torch.cuda.current_stream(self.device).synchronize()
+        return out.clone()
+
+    def parameter(self, name):
+        return self._read(_lib.HEAD_PARAM, name, self.shapes[name], torch.float32)
+
+    def gradient(self, name):
+        return self._read(_lib.HEAD_GRAD, name, self.shapes[name], torch.float32)
+
+    def buffer(self, name):
+        """feature_compress.1.running_mean / running_var (fp32 [8]) or num_batches_tracked (int64 scalar)."""
+        tracked = FRONT_BUFFERS[name] == _lib.FRONT_BN_TRACKED
+        return self._read(FRONT_BUFFERS[name], None, self.buffers[name], torch.int64 if tracked else torch.float32)
+
+    def write(self, kind, name, tensor):
+        t = tensor.detach().to(self.device, torch.float32).contiguous()
+        if tuple(t.shape) != self.shapes[name]:
+            raise ValueError(f"{name}: expected {self.shapes[name]}, got {tuple(t.shape)}")
+        self.ctx.call("vt_front_write", *self._state(), kind, name.encode(), vp(t), t.numel() * 4, stream_ptr(self.device))
+        torch.cuda.current_stream(self.device).synchronize()        # (t may be freed when this returns)
+
+    def write_buffer(self, name, tensor):
+        tracked = FRONT_BUFFERS[name] == _lib.FRONT_BN_TRACKED
+        t = tensor.detach().to(self.device, torch.int64 if tracked else torch.float32).contiguous()
+        self.ctx.call("vt_front_write", *self._state(), FRONT_BUFFERS[name], None, vp(t), t.numel() * t.element_size(), stream_ptr(self.device))
+        torch.cuda.current_stream(self.device).synchronize()
+
+    def grad_norm(self):
+        """(total L2 norm, clip coefficient) of the last DecoderTrainer.clip()."""
+        raw = self._read(_lib.HEAD_NORM, None, (16,), torch.uint8).numpy()
+        return float(raw[8:12].view(np.float32)[0]), float(raw[12:16].view(np.float32)[0])
+
+    def tensors(self):
+        """Every front entry of the state_dict: parameters and the three BatchNorm buffers, host tensors."""
+        out = {k: self.parameter(k) for k in self.shapes}
+        out.update({k: self.buffer(k) for k in self.buffers})
+        return out
+
+    def state_dict(self):
+        """The decoder's full state_dict with the trained front (the reference's keys, the three BatchNorm buffers included); the head's
+        tensors are the decoder's own."""
+        trained = self.tensors()
+        return {k: (trained[k].to(v.dtype) if k in trained else v.detach().to("cpu")).clone() for k, v in self.decoder.state_dict().items()}
+
+    def state_bytes(self):
+        """The whole state block (for bit comparisons)."""
+        torch.cuda.current_stream(self.device).synchronize()
+        off = self._ptr - self._buf.data_ptr()
+        return self._buf[off:off + self._bytes].cpu()
+
+
+def export_full_state_dict(decoder, head, front):
+    """The decoder's state_dict with the head's and the front's tensors read from the device (the reference's keys and dtypes)."""
+    trained = front.tensors()
+    out = {}
+    for k, v in decoder.state_dict().items():
+        if k.startswith("classifier."):
+            t = head.parameter(k)
+        elif k in trained:
+            t = trained[k]
+        else:
+            out[k] = v.detach().to("cpu").clone()
+            continue
+        if tuple(t.shape) != tuple(v.shape):
+            raise ValueError(f"{k}: read {tuple(t.shape)}, the decoder holds {tuple(v.shape)}")
+        out[k] = t.detach().to("cpu", v.dtype).clone()
+    return out
+
+
+class DecoderTrainer:
+    """The attention decoder trained in full: FrontTrainer + HeadTrainer.  One forward_backward runs latent -> front (training mode) ->
+    head forward / loss / backward with d loss / d features -> front backward; clip() is ONE clip_grad_norm_ over both blocks."""
+
+    def __init__(self, decoder, loss="bce", focal_alpha=1.0, focal_gamma=2.0, class_weights=None, dropout=None, attention_dropout=0.1, seed=0):
+        self.decoder = decoder
+        self.head = HeadTrainer(decoder, loss, focal_alpha, focal_gamma, class_weights, dropout, seed)
+        self.front = FrontTrainer(decoder, attention_dropout, seed)
+        self.ctx, self.device, self.N, self.F = self.head.ctx, self.head.device, self.head.N, self.head.F
+
+    def forward(self, latent):
+        """Eval-mode logits: the front on its running statistics, no dropout (the reference's decoder.eval())."""
+        return self.head.forward(self.front.forward(latent, train=False))
+
+    def forward_backward(self, latent, labels, loss_scale=1.0, train=True, step=None, return_logits=False):
+        h = self.head
+        step = h.calls if step is None else int(step)
+        feats = self.front.forward(latent, train=True, step=step)
+        y = labels.detach().to(self.device)
+        if y.dtype == torch.bool:
+            y = y.view(torch.uint8)
+        elif y.dtype not in (torch.float32, torch.uint8):
+            y = y.to(torch.float32)
+        y = y.contiguous()
+        B = feats.shape[0]
+        if tuple(y.shape) != (B, self.N):
+            raise ValueError(f"expected labels [{B}, {self.N}], got {tuple(y.shape)}")
+        logits = torch.empty(B, self.N, dtype=torch.float32, device=self.device) if return_logits else None
+        d_feats = torch.empty(B, self.F, dtype=torch.float32, device=self.device)
+        ws, need = h._ws(B)
+        self.ctx.call("vt_head_forward_backward_dx", *h._state(), vp(feats), vp(y), _lib.VT_U8 if y.dtype == torch.uint8 else _lib.VT_F32, B,
+                      h.loss_kind, h.alpha, h.gamma, vp(h.class_weights), float(loss_scale), int(bool(train)), h.dropout, h.seed, step,
+                      vp(logits), None, vp(d_feats), ws, need, stream_ptr(self.device))
+        h.calls = step + 1
+        self.front.backward(d_feats)
+        return logits
+
+    def clip(self, max_norm):
+        self.ctx.call("vt_train_clip", *self.head._state(), *self.front._state(), float(max_norm), stream_ptr(self.device))
+
+    def step(self, lr, weight_decay=0.0, betas=ADAM_BETAS, eps=ADAM_EPS):
+        self.head.step(lr, weight_decay, betas, eps)
+        self.front.step(lr, weight_decay, betas, eps)
+
+    def commit(self):
+        self.front.commit()
+        self.head.commit()
+
+    def losses(self):
+        return self.head.losses()
+
+    def grad_norm(self):
+        return self.head.grad_norm()
+
+    def state_dict(self):
+        return export_full_state_dict(self.decoder, self.head, self.front)

@@ -1,15 +1,23 @@
-"""Decoder training CLI: the reference's train_decoder.py (train_decoder.py:30-278) with the classifier head trained on the GPU
-(train.HeadTrainer) behind the frozen encoder and the frozen decoder front.
+"""Decoder training CLI: the reference's train_decoder.py (train_decoder.py:30-278) with the decoder trained on the GPU behind the
+frozen encoder: the classifier head alone (train.HeadTrainer) or, with --train_front, the whole attention decoder (train.DecoderTrainer).
 
     python -m vae_tagger_amd.train_decoder --vae_checkpoint ae.safetensors --json_path data.json --tags_csv_path tags.csv \
         --no_attention --num_epochs 10 --train_batch_size 16 [--use_bucketing] [--decoder_checkpoint start.bin]
 
---no_attention trains ClassificationDecoder in full (its front is the parameter-free 4x4 pool).  An attention decoder is trained only
-with --freeze_front: its front (spatial attention, feature_compress, self- / cross-attention) runs as in inference and only
-`classifier.*` changes -- e.g. to adapt a trained checkpoint to a new tag list; backward through the front is not implemented.
+--no_attention trains ClassificationDecoder in full (its front is the parameter-free 4x4 pool).  An attention decoder needs one of
+two flags.  --freeze_front: its front (spatial attention, feature_compress, self- / cross-attention) runs as in inference and only
+`classifier.*` changes -- e.g. to adapt a trained checkpoint to a new tag list.  --train_front: the front is trained too, from scratch
+if no checkpoint is given: spatial_attention.*, feature_compress.* (BatchNorm on batch statistics, its running statistics updated) and
+self_attention_post.* with --attention_dropout on the softmax weights; validation runs the front in eval mode on the running
+statistics, as the reference's decoder.eval() does.  The channel max of the spatial attention passes its gradient to the arg-max
+channel, the lowest index on a tie.  Cross-attention has no backward: --use_cross_attention stays refused without --freeze_front.
 Epoch 1 encodes every image once and keeps the front's feature row and the labels of each on the GPU (train.FeatureCache); later epochs
 train from that cache without calling the encoder (--no_feature_cache re-encodes every epoch).  The dataset applies no random
-augmentation (modules.py:688-729), so a cached row is what a re-encode would give.
+augmentation (modules.py:688-729), so a cached row is what a re-encode would give.  With --train_front the feature rows change every
+step, so the encoder's LATENTS are cached instead (train.LatentCache: one flat fp32 arena, 16 (resolution / 8)^2 floats per image, 1 MB at
+1024 x 1024): if that bound for all training and validation images plus their labels exceeds --latent_cache_gb (default 16), nothing is
+cached and every epoch re-encodes; train_report.json records which happened and the bytes used.  Epochs from the cache form their
+batches from the epoch's order grouped by latent shape (batch statistics need one shape per batch).
 Files, as the reference writes them: best_pytorch_model.bin (strictly lower validation loss), pytorch_model.bin (every --save_steps
 epochs), training_history.json, then the threshold search and the metrics on the validation set (optimal_thresholds.json,
 evaluation_results.csv, evaluation_results_overall.json); plus train_report.json (per epoch: seconds, images/s, encoder batches, steps).
@@ -24,11 +32,12 @@ import torch
 IGNORED_ARGUMENTS = ("mixed_precision", "cudnn_benchmark", "cudnn_deterministic", "num_workers", "prefetch_factor", "use_safetensors")
 FRONT_MESSAGE = ("an attention decoder is trained with --freeze_front only: backward through the decoder front (BatchNorm in training "
                  "mode, self-attention with dropout) is not implemented; --freeze_front trains classifier.* on the frozen front, "
-                 "--no_attention trains the plain decoder in full")
+                 "--no_attention trains the plain decoder in full; --train_front trains the front as well (not with "
+                 "--use_cross_attention, whose backward does not exist)")
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="训练分类解码器 (classifier head on the GPU, frozen encoder and decoder front)")
+    p = argparse.ArgumentParser(description="训练分类解码器 (decoder on the GPU behind the frozen encoder; see --freeze_front / --train_front)")
     p.add_argument("--vae_checkpoint", type=str, required=True, help="预训练VAE模型文件路径 (.safetensors)")
     p.add_argument("--vae_config_path", type=str, default=None, help="VAE配置文件路径 (JSON格式)")
     p.add_argument("--decoder_checkpoint", type=str, default=None, help="预训练Decoder模型文件路径 (.bin/.pth)")
@@ -77,6 +86,12 @@ def build_parser():
     # this project's own
     p.add_argument("--freeze_front", action="store_true",
                    help="attention decoders: train classifier.* only, on the front as it runs in inference (required for them)")
+    p.add_argument("--train_front", action="store_true",
+                   help="attention decoders: train the front too (spatial attention, feature_compress, self-attention); not with "
+                        "--use_cross_attention")
+    p.add_argument("--latent_cache_gb", type=float, default=16.0,
+                   help="with --train_front: device memory for the cached latents and labels; if the set does not fit, or at 0, "
+                        "every epoch re-encodes")
     p.add_argument("--no_feature_cache", action="store_true", help="re-encode every image every epoch instead of caching its feature row")
     p.add_argument("--workers", type=int, default=0, help="image decode threads (0 = min(16, cores))")
     p.add_argument("--max_pending", type=int, default=0, help="with --use_bucketing: images that may wait in partly filled buckets")
@@ -96,7 +111,20 @@ def check_args(args):
     from .train import SCHEDULES
     if args.no_attention:
         args.use_attention = False
-    if args.use_attention and not args.freeze_front:
+    if args.train_front:
+        if not args.use_attention:
+            raise RuntimeError("--train_front trains the front of an attention decoder; with --no_attention there is none (the plain "
+                               "decoder is trained in full as it is)")
+        if args.freeze_front:
+            raise RuntimeError("--train_front and --freeze_front exclude each other")
+        if args.use_cross_attention:
+            raise RuntimeError("--train_front with --use_cross_attention: backward through cross-attention is not implemented; "
+                               "--freeze_front trains classifier.* on the frozen front")
+        if args.attention_heads not in (1, 2, 4, 8):
+            raise RuntimeError("--train_front: --attention_heads must be 1, 2, 4 or 8")
+        if not 0.0 <= args.attention_dropout < 1.0 or args.latent_cache_gb < 0:
+            raise RuntimeError("--attention_dropout must be in [0, 1) and --latent_cache_gb non-negative")
+    elif args.use_attention and not args.freeze_front:
         raise RuntimeError(FRONT_MESSAGE)
     if args.lr_scheduler_type not in SCHEDULES:
         raise RuntimeError(f"--lr_scheduler_type {args.lr_scheduler_type}: one of {', '.join(SCHEDULES)} expected")
@@ -165,7 +193,7 @@ def train(args):
     from .modules import AspectRatioBucketing, get_image_transform
     from .pipeline import EncodeTagPipeline
     from .prefetch import FeederLoader
-    from .train import FeatureCache, HeadTrainer, epoch_order, lr_schedule, split_indices
+    from .train import DecoderTrainer, FeatureCache, HeadTrainer, LatentCache, epoch_order, lr_schedule, split_indices
     ignored = ignored_arguments(args)
     if ignored:
         print("ignored arguments (no meaning here): " + ", ".join("--" + k for k in ignored))
@@ -198,24 +226,38 @@ def train(args):
                             host_resize=args.host_resize, transform=get_image_transform(args.resolution), bucketing=bucketing,
                             max_pending=args.max_pending or None)
 
-    trainer = HeadTrainer(decoder, loss=selected, focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, class_weights=weights,
-                          seed=args.seed)
-    cache = None if args.no_feature_cache else FeatureCache(len(data.image_paths), trainer.F, N, device)
+    full = bool(args.train_front)                      # the trainer's inputs are latents (full) or the frozen front's feature rows
+    if full:
+        trainer = DecoderTrainer(decoder, loss=selected, focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, class_weights=weights,
+                                 attention_dropout=args.attention_dropout, seed=args.seed)
+        side = (args.max_resolution if args.use_bucketing else args.resolution) // 8
+        latent_numel = 16 * side * side              # the largest latent: a bucket's area never exceeds max_resolution^2
+        budget = int(args.latent_cache_gb * (1 << 30))
+        fits = not args.no_feature_cache and LatentCache.fits(len(data.image_paths), latent_numel, N, budget)
+        cache = LatentCache(len(data.image_paths), latent_numel, N, device) if fits else None
+    else:
+        trainer = HeadTrainer(decoder, loss=selected, focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, class_weights=weights,
+                              seed=args.seed)
+        cache = None if args.no_feature_cache else FeatureCache(len(data.image_paths), trainer.F, N, device)
     acc = DeviceLossAccumulator(N, device, args.focal_alpha, args.focal_gamma, weights, context=decoder._context())
     accum = max(1, args.gradient_accumulation_steps)
     bs = args.train_batch_size
     total_steps = args.num_epochs * ((len(train_paths) + bs - 1) // bs)
     os.makedirs(args.output_dir, exist_ok=True)
     history = {"train_loss": [], "val_loss": [], "learning_rates": []}
-    report = {"epochs": [], "feature_cache_bytes": cache.nbytes if cache is not None else 0, "feature_dim": trainer.F,
+    report = {"epochs": [], "feature_cache_bytes": cache.nbytes if cache is not None and not full else 0, "feature_dim": trainer.F,
               "train_images": len(train_paths), "val_images": len(val_paths)}
+    if full:
+        report["latent_cache"] = {"cached": cache is not None, "budget_bytes": budget,
+                                  "bytes_needed": LatentCache.bytes_needed(len(data.image_paths), latent_numel, N), "bytes_used": 0}
     reader = _LossReader(trainer, _lib.HEAD_RING)
     micro, sched, best, current_lr = 0, 0, float("inf"), args.learning_rate * lr_schedule(args.lr_scheduler_type, 0, args.lr_warmup_steps, total_steps)
     val_batches = None                                 # the validation batches of the first pass, by name: every epoch scores the same ones
 
     def encoded(paths, counter):
         for batch in loader(paths):
-            feats = trainer.features(vae_model.encode(batch["pixel_values"]))
+            latent = vae_model.encode(batch["pixel_values"])
+            feats = latent if full else trainer.features(latent)
             counter[0] += 1
             if cache is not None:
                 cache.put(batch["names"], feats, batch["labels"])
@@ -231,7 +273,10 @@ def train(args):
         t0, enc, first, images = time.perf_counter(), [0], micro, 0
         order = [train_paths[i] for i in epoch_order(len(train_paths), args.seed, epoch)]
         from_cache = cache is not None and epoch > 0
-        source = cached([order[i:i + bs] for i in range(0, len(order), bs)]) if from_cache else encoded(order, enc)
+        if from_cache:
+            source = cached(cache.batches(order, bs) if full else [order[i:i + bs] for i in range(0, len(order), bs)])
+        else:
+            source = encoded(order, enc)
         for step, (names, feats, labels) in enumerate(source):
             reader.before_step(micro)
             trainer.forward_backward(feats, labels, loss_scale=1.0 / accum, train=True, step=micro)
@@ -247,7 +292,7 @@ def train(args):
                 vals = reader.drain(micro)[first:]
                 print(f"Epoch: {epoch}, Step: {step}, Loss: {vals[-1]:.4f}, Avg Loss: {sum(vals) / len(vals):.4f}, LR: {current_lr:.2e}")
         train_steps = micro - first
-        # validation: head in eval mode on the frozen front's rows
+        # validation: eval mode (the head on the frozen front's rows; with --train_front the front on its running statistics)
         acc.reset()
         if val_batches is None or cache is None:
             seen = []
@@ -280,6 +325,8 @@ def train(args):
     print("训练完成，开始最终评估...")
     with open(os.path.join(args.output_dir, "training_history.json"), "w") as fh:
         json.dump(history, fh, indent=2)
+    if full and cache is not None:
+        report["latent_cache"]["bytes_used"] = cache.nbytes
     with open(os.path.join(args.output_dir, "train_report.json"), "w") as fh:
         json.dump(report, fh, indent=2)
     trainer.commit()
