@@ -12,21 +12,6 @@
 
 namespace {
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float block_max_256(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // avg / max over H*W per (b, c)   (nn.AdaptiveAvgPool2d(1), nn.AdaptiveMaxPool2d(1))
 __global__ __launch_bounds__(256) void dec_pool_kernel(const float* __restrict__ x, int HW, float* __restrict__ pool) {
     __shared__ float red[4];
@@ -519,6 +504,20 @@ hipError_t vt_dec_ln_act(float* y, const float* g, const float* b, int rows, int
     return hipSuccess;
 }
 
+// SpatialAttention's pool, channel gate and spatial gate (train_front.hip's training-mode forward runs the same launches: same bits)
+hipError_t vt_dec_pool(const float* x, int B, int C, int HW, float* pool, hipStream_t s) {
+    hipLaunchKernelGGL(dec_pool_kernel, dim3(C, B), dim3(256), 0, s, x, HW, pool); CKL();
+    return hipSuccess;
+}
+hipError_t vt_dec_gate(const float* pool, const float* w0, const float* w2, int B, int C, int R, float* gate, hipStream_t s) {
+    hipLaunchKernelGGL(dec_gate_kernel, dim3(B), dim3(64), 0, s, pool, w0, w2, C, R, gate); CKL();
+    return hipSuccess;
+}
+hipError_t vt_dec_sgate(const float* sp, const float* w, int B, int H, int W, float* sg, hipStream_t s) {
+    hipLaunchKernelGGL(dec_sgate_kernel, dim3((H * W + 255) / 256, B), dim3(256), 0, s, sp, w, H, W, sg); CKL();
+    return hipSuccess;
+}
+
 // front: latent -> the feature row [B][F] the classifier reads (plain: the 4x4 pool; attention: spatial attention, compress,
 // self- / cross-attention), written to `feat`; `ws` holds the front's scratch.
 hipError_t vt_decoder_front(const DecoderWeights& w, const float* latent, int B, int H, int Wd, float* ws, float* feat, hipStream_t s) {
@@ -543,10 +542,10 @@ hipError_t vt_decoder_front(const DecoderWeights& w, const float* latent, int B,
     const float* gptr = nullptr;
     const float* sgptr = nullptr;
     if (w.use_spatial) {
-        hipLaunchKernelGGL(dec_pool_kernel, dim3(C, B), dim3(256), 0, s, latent, HW, pool); CKL();
-        hipLaunchKernelGGL(dec_gate_kernel, dim3(B), dim3(64), 0, s, pool, w.ca_w0, w.ca_w2, C, w.ca_hidden, gate); CKL();
+        CK(vt_dec_pool(latent, B, C, HW, pool, s));
+        CK(vt_dec_gate(pool, w.ca_w0, w.ca_w2, B, C, w.ca_hidden, gate, s));
         hipLaunchKernelGGL(dec_spmap_kernel, dim3((HW + 255) / 256, B), dim3(256), 0, s, latent, gate, C, HW, sp); CKL();
-        hipLaunchKernelGGL(dec_sgate_kernel, dim3((HW + 255) / 256, B), dim3(256), 0, s, sp, w.sa_w, H, Wd, sg); CKL();
+        CK(vt_dec_sgate(sp, w.sa_w, B, H, Wd, sg, s));
         gptr = gate; sgptr = sg;
     }
     hipLaunchKernelGGL((dec_compress_kernel<8>), dim3(64, B), dim3(256), (size_t)CO * C * 9 * sizeof(float), s, latent, gptr, sgptr,

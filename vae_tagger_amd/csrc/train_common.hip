@@ -1,0 +1,138 @@
+// What the trainers share (vt_train.h: TrainBlock): the kernels that work on any block -- the gradient norm and clip coefficient, the
+// gradient scale, AdamW -- and one host implementation of the state check, clip, step, the kind -> byte range dispatch of the four
+// parameter arrays and the scalars, and the read / write copies.  train_head.hip and train_front.hip call these with their own layout
+// and the name of the entry point they were reached through.  The conventions are theirs: fp32 storage, fp64 reductions in an order
+// fixed by the shapes, no atomics, nothing synchronises the host.
+#include <math.h>
+
+#include "vt_common.h"
+#include "vt_context.h"
+#include "vt_train.h"
+
+using namespace vt;
+
+namespace {
+
+// one workgroup: the squared-norm partials of block a in index order, then block b's (n_b may be 0: th + 0.0 has th's bits, th >= 0)
+// -> one norm and coef = min(1, max_norm / (norm + 1e-6))  (clip_grad_norm_), written to both blocks (sc_b may be sc_a)
+__global__ __launch_bounds__(256) void train_clip_kernel(const double* __restrict__ part_a, int n_a, const double* __restrict__ part_b, int n_b,
+                                                         float max_norm, TrainScalars* sc_a, TrainScalars* sc_b) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n_a; i += 256) a += part_a[i];
+    const double th = block_sum_256d(a, red);
+    a = 0.0;
+    for (int i = threadIdx.x; i < n_b; i += 256) a += part_b[i];
+    const double tf = block_sum_256d(a, red);
+    if (threadIdx.x == 0) {
+        const double total = th + tf;
+        const float norm = (float)sqrt(total);
+        const float coef = max_norm / (norm + 1e-6f);
+        TrainScalars v;
+        v.sq = total; v.norm = norm; v.coef = coef < 1.0f ? coef : 1.0f;
+        *sc_a = v; *sc_b = v;
+    }
+}
+
+// g *= coef when coef < 1 (a gradient inside the bound keeps its bits: nothing is written)
+__global__ __launch_bounds__(256) VT_NO_PACKED_F32 void train_scale_kernel(float4* __restrict__ g, long long n4, const TrainScalars* __restrict__ sc) {
+    const float coef = sc->coef;
+    if (!(coef < 1.0f)) return;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    float4 v = g[i];
+    v.x *= coef; v.y *= coef; v.z *= coef; v.w *= coef;
+    g[i] = v;
+}
+
+// (VT_NO_PACKED_F32: the compiler would pair these float4 lanes into packed fp32 ops with a source op_sel -- vt_common.h)
+// torch.optim.AdamW (single-tensor path): p *= 1 - lr wd; m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g g;
+// p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps); g = 0
+__device__ __forceinline__ void adamw_one(float& p, float& g, float& m, float& v, float decay, float w1, float beta2, float w2, float step_size,
+                                          float rbc2, float eps) {
+#pragma clang fp contract(off)
+    p = p * decay;
+    m = m + w1 * (g - m);
+    v = v * beta2 + w2 * (g * g);
+    const float denom = sqrtf(v) / rbc2 + eps;
+    p = p - step_size * (m / denom);
+    g = 0.f;
+}
+__global__ __launch_bounds__(256) VT_NO_PACKED_F32 void train_adamw_kernel(float4* __restrict__ P, float4* __restrict__ G, float4* __restrict__ M, float4* __restrict__ V,
+                                                          long long n4, float decay, float w1, float beta2, float w2, float step_size, float rbc2,
+                                                          float eps) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    float4 p = P[i], g = G[i], m = M[i], v = V[i];
+    adamw_one(p.x, g.x, m.x, v.x, decay, w1, beta2, w2, step_size, rbc2, eps);
+    adamw_one(p.y, g.y, m.y, v.y, decay, w1, beta2, w2, step_size, rbc2, eps);
+    adamw_one(p.z, g.z, m.z, v.z, decay, w1, beta2, w2, step_size, rbc2, eps);
+    adamw_one(p.w, g.w, m.w, v.w, decay, w1, beta2, w2, step_size, rbc2, eps);
+    P[i] = p; G[i] = g; M[i] = m; V[i] = v;
+}
+
+}  // namespace
+
+int vt_train_check(vt_context* c, const char* who, const TrainBlock& b, const void* state, size_t state_bytes) {
+    if (!state || ((uintptr_t)state & (ALIGN - 1))) return c->fail(VT_ERR_INVALID, "%s: state is null or not 256-B aligned", who);
+    if (state_bytes < b.total) return c->fail(VT_ERR_WORKSPACE, "%s: state holds %zu bytes, %zu needed", who, state_bytes, b.total);
+    return VT_OK;
+}
+
+int vt_train_clip_blocks(vt_context* c, const char* who, const TrainBlock& a, void* sa, const TrainBlock* b, void* sb, float max_norm,
+                         hipStream_t s) {
+    if (!(max_norm > 0.f)) return c->fail(VT_ERR_INVALID, "%s: max_norm = %g must be positive", who, max_norm);
+    char* pa = (char*)sa;
+    char* pb = b ? (char*)sb : pa;
+    const TrainBlock& bb = b ? *b : a;
+    TrainScalars* sca = (TrainScalars*)(pa + a.scalars);
+    TrainScalars* scb = (TrainScalars*)(pb + bb.scalars);
+    hipLaunchKernelGGL(train_clip_kernel, dim3(1), dim3(256), 0, s, (const double*)(pa + a.normpart), a.norm_parts,
+                       (const double*)(pb + bb.normpart), b ? bb.norm_parts : 0, max_norm, sca, scb);
+    HIPCK(c, hipGetLastError(), who);
+    const long long a4 = (long long)(a.P / 4), b4 = (long long)(bb.P / 4);
+    hipLaunchKernelGGL(train_scale_kernel, dim3((unsigned)((a4 + 255) / 256)), dim3(256), 0, s, (float4*)(pa + a.grads), a4, sca);
+    HIPCK(c, hipGetLastError(), who);
+    if (b) {
+        hipLaunchKernelGGL(train_scale_kernel, dim3((unsigned)((b4 + 255) / 256)), dim3(256), 0, s, (float4*)(pb + bb.grads), b4, scb);
+        HIPCK(c, hipGetLastError(), who);
+    }
+    return VT_OK;
+}
+
+int vt_train_step(vt_context* c, const char* who, const TrainBlock& b, void* state, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, long long t, hipStream_t s) {
+    if (t < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !isfinite(lr) || !isfinite(weight_decay))
+        return c->fail(VT_ERR_INVALID, "%s: t >= 1, betas in [0, 1), eps >= 0 and finite lr / weight_decay expected", who);
+    char* st = (char*)state;
+    const long long n4 = (long long)(b.P / 4);
+    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
+    hipLaunchKernelGGL(train_adamw_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (float4*)(st + b.params), (float4*)(st + b.grads),
+                       (float4*)(st + b.m), (float4*)(st + b.v), n4, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2,
+                       (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2), (float)eps);
+    HIPCK(c, hipGetLastError(), who);
+    return VT_OK;
+}
+
+int vt_train_section(vt_context* c, const char* who, const TrainBlock& b, int kind, size_t toff, size_t numel, size_t* off, size_t* bytes) {
+    if (kind >= VT_HEAD_PARAM && kind <= VT_HEAD_ADAM_V) {
+        const size_t base = kind == VT_HEAD_PARAM ? b.params : kind == VT_HEAD_GRAD ? b.grads : kind == VT_HEAD_ADAM_M ? b.m : b.v;
+        *off = base + 4 * toff; *bytes = 4 * numel;
+        return VT_OK;
+    }
+    if (kind == VT_HEAD_NORM) { *off = b.scalars; *bytes = sizeof(TrainScalars); return VT_OK; }
+    return c->fail(VT_ERR_INVALID, "%s: unknown kind %d", who, kind);
+}
+
+int vt_train_read(vt_context* c, const char* who, const void* state, size_t off, size_t bytes, void* out, size_t out_bytes, hipStream_t s) {
+    if (!out || out_bytes < bytes) return c->fail(VT_ERR_WORKSPACE, "%s: out is null or holds %zu bytes, %zu needed", who, out_bytes, bytes);
+    HIPCK(c, hipMemcpyAsync(out, (const char*)state + off, bytes, hipMemcpyDefault, s), who);
+    return VT_OK;
+}
+
+int vt_train_write(vt_context* c, const char* who, void* state, size_t off, size_t bytes, const void* src, size_t src_bytes, hipStream_t s) {
+    if (!src || src_bytes != bytes) return c->fail(VT_ERR_INVALID, "%s: src is null or holds %zu bytes, %zu expected", who, src_bytes, bytes);
+    HIPCK(c, hipMemcpyAsync((char*)state + off, src, bytes, hipMemcpyDefault, s), who);
+    return VT_OK;
+}

@@ -3,8 +3,11 @@
 // and self attention on or off; cross-attention is not covered (vt_front_state_bytes returns 0 with it).  One caller-owned state block
 // (vt_train.h), the head trainer's conventions: fp32 storage; fp64 statistics and norm partials; no atomics; every sum in an order
 // fixed by the shapes; nothing synchronises the host.  The gradient with respect to the latent is not computed (the encoder is frozen).
+// State check, AdamW step, the parameter kinds of read / write and the scalars are train_common.hip's; this file keeps the front's
+// kernels and its own kinds (the BatchNorm buffers and the re-fold after a write).
 //   forward, train = 0   vt_decoder_front on the state's tensors: the inference kernels, BatchNorm folded from the running statistics
-//   forward, train != 0  pool / gate / spmap / sgate (SpatialAttention) -> xs = (x gate) sgate -> conv3x3 -> z; batch statistics of z
+//   forward, train != 0  pool / gate / sgate (decoder.hip's launches: same bits) and spmap (SpatialAttention) -> xs = (x gate) sgate
+//                        -> conv3x3 -> z; batch statistics of z
 //                        (fp64 partials per 256 pixels, finished in chunk order; running statistics updated as nn.BatchNorm2d does);
 //                        BatchNorm + ReLU + adaptive pool 8x8; self-attention with dropout on the softmax weights (vt_head_keep,
 //                        layer VT_FRONT_DROPOUT_LAYER, element ((b heads + head) 64 + query) 64 + key)
@@ -26,70 +29,13 @@ namespace {
 
 #define FRONT_KERNEL(n) __global__ __launch_bounds__(n) VT_NO_PACKED_F32
 
-struct FrontScalars { double sq; float norm; float coef; };
+// float offset of tensor T inside the partial row of its gradient group (a row starts at the group's first float)
+template <int T> constexpr int SA_ROW = VT_FRONT_TABLE[T].off - VT_FG_START[VT_FG_SA];
+template <int T> constexpr int MLP_ROW = VT_FRONT_TABLE[T].off - VT_FG_START[VT_FG_MLP];
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;                                // (lane 0 holds the sum)
-}
-__device__ __forceinline__ double block_sum_256d(double v, double* red) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float block_max_256(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
-// is float `e` of a parameter array an element of a tensor (not padding)?  (the fixed table of vt_train.h)
-__device__ __forceinline__ bool front_real(int e) {
-    if (e < 256) return e < 32 || (e >= 64 && e < 96) || (e >= 128 && e < 226);
-    if (e < 1408) return true;
-    const int slot = (e - 1408) >> 6, r = e & 63;          // fc_b bn_w bn_b ln_w ln_b q_w q_b k_w k_b v_w v_b o_w o_b
-    return slot == 5 || slot == 7 || slot == 9 || slot == 11 || r < 8;
-}
-
-// ---- SpatialAttention forward (decoder.hip's kernels; spmap also records the arg-max channel) -----------------------------------------
-FRONT_KERNEL(256) void front_pool_kernel(const float* __restrict__ x, int HW, float* __restrict__ pool) {
-    __shared__ float red[4];
-    const int c = blockIdx.x, b = blockIdx.y, C = gridDim.x;
-    const float* xp = x + ((long long)b * C + c) * HW;
-    float s = 0.f, m = -INFINITY;
-    for (int i = threadIdx.x; i < HW; i += 256) { const float v = xp[i]; s += v; m = fmaxf(m, v); }
-    s = block_sum_256(s, red);
-    m = block_max_256(m, red);
-    if (threadIdx.x == 0) { pool[(b * C + c) * 2] = s / (float)HW; pool[(b * C + c) * 2 + 1] = m; }
-}
-
-FRONT_KERNEL(64) void front_gate_kernel(const float* __restrict__ pool, const float* __restrict__ w0, const float* __restrict__ w2,
-                                        float* __restrict__ gate) {
-    const int b = blockIdx.x, c = threadIdx.x;
-    if (c >= 16) return;
-    float out = 0.f;
-    for (int which = 0; which < 2; ++which)
-        for (int r = 0; r < 2; ++r) {
-            float h = 0.f;
-            for (int i = 0; i < 16; ++i) h = fmaf(w0[r * 16 + i], pool[(b * 16 + i) * 2 + which], h);
-            h = fmaxf(h, 0.f);
-            out = fmaf(w2[c * 2 + r], h, out);
-        }
-    gate[b * 16 + c] = vt_sigmoid_accurate(out);
-}
-
-// mean / max over channels of x gate -> sp[b][2][HW]; am[b][p] = the channel of the max, the lowest on a tie
+// ---- SpatialAttention forward: pool, channel gate and spatial gate are decoder.hip's launches (vt_dec_pool / _gate / _sgate) ----------
+// mean / max over channels of x gate -> sp[b][2][HW]; am[b][p] = the channel of the max, the lowest on a tie.  Not dec_spmap_kernel:
+// it records the arg-max channel, and its `if (v > m)` is not fmaxf on a tie of +0 and -0 (fmaxf may return either zero)
 FRONT_KERNEL(256) void front_spmap_kernel(const float* __restrict__ x, const float* __restrict__ gate, int HW, float* __restrict__ sp,
                                           unsigned char* __restrict__ am) {
     const int b = blockIdx.y;
@@ -105,28 +51,6 @@ FRONT_KERNEL(256) void front_spmap_kernel(const float* __restrict__ x, const flo
     sp[((long long)b * 2) * HW + p] = s / 16.0f;
     sp[((long long)b * 2 + 1) * HW + p] = m;
     am[(long long)b * HW + p] = (unsigned char)a;
-}
-
-FRONT_KERNEL(256) void front_sgate_kernel(const float* __restrict__ sp, const float* __restrict__ w, int H, int W, float* __restrict__ sg) {
-    __shared__ float sw[98];
-    if (threadIdx.x < 98) sw[threadIdx.x] = w[threadIdx.x];
-    __syncthreads();
-    const int b = blockIdx.y, HW = H * W;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= HW) return;
-    const int y = p / W, x = p - y * W;
-    float acc = 0.f;
-    for (int c = 0; c < 2; ++c)
-        for (int ky = 0; ky < 7; ++ky) {
-            const int iy = y + ky - 3;
-            if (iy < 0 || iy >= H) continue;
-            for (int kx = 0; kx < 7; ++kx) {
-                const int ix = x + kx - 3;
-                if (ix < 0 || ix >= W) continue;
-                acc = fmaf(sw[(c * 7 + ky) * 7 + kx], sp[((long long)b * 2 + c) * HW + iy * W + ix], acc);
-            }
-        }
-    sg[(long long)b * HW + p] = vt_sigmoid_accurate(acc);
 }
 
 // xs = (x gate[c]) sg[p]: the conv's input, kept for the backward
@@ -485,14 +409,20 @@ FRONT_KERNEL(64) void front_sa_bwd_kernel(const float* __restrict__ t, const flo
     for (int e = 0; e < 8; ++e) {
         const double a = wave_sum_d(dxn[e] * xh[e]), c = wave_sum_d(dxn[e]);
         const double sqb = wave_sum_d(dq[e]), skb = wave_sum_d(dk[e]), svb = wave_sum_d(dv[e]), sob = wave_sum_d(dout[e]);
-        if (lead) { row[e] = (float)a; row[64 + e] = (float)c; row[192 + e] = (float)sqb; row[320 + e] = (float)skb; row[448 + e] = (float)svb; row[576 + e] = (float)sob; }
+        if (lead) {
+            row[SA_ROW<VT_FT_LNW> + e] = (float)a; row[SA_ROW<VT_FT_LNB> + e] = (float)c; row[SA_ROW<VT_FT_QB> + e] = (float)sqb; row[SA_ROW<VT_FT_KB> + e] = (float)skb;
+            row[SA_ROW<VT_FT_VB> + e] = (float)svb; row[SA_ROW<VT_FT_OB> + e] = (float)sob;
+        }
     }
 #pragma unroll
     for (int o = 0; o < 8; ++o)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const double a = wave_sum_d(dq[o] * xn[e]), c = wave_sum_d(dk[o] * xn[e]), d = wave_sum_d(dv[o] * xn[e]), f = wave_sum_d(dout[o] * att[e]);
-            if (lead) { row[128 + o * 8 + e] = (float)a; row[256 + o * 8 + e] = (float)c; row[384 + o * 8 + e] = (float)d; row[512 + o * 8 + e] = (float)f; }
+            if (lead) {
+                row[SA_ROW<VT_FT_QW> + o * 8 + e] = (float)a; row[SA_ROW<VT_FT_KW> + o * 8 + e] = (float)c; row[SA_ROW<VT_FT_VW> + o * 8 + e] = (float)d;
+                row[SA_ROW<VT_FT_OW> + o * 8 + e] = (float)f;
+            }
         }
 }
 
@@ -715,7 +645,7 @@ FRONT_KERNEL(256) void front_dgate_kernel(const float* __restrict__ dxs, const f
 }
 
 // the channel gate's MLP (bias-free 16 -> 2 -> 16, applied to the average and to the max pool) for image b: part[b][128],
-// w0[r][i] at r 16 + i, w2[c][r] at 64 + c 2 + r
+// w0[r][i] at r 16 + i, w2[c][r] at its table offset in the group + c 2 + r
 FRONT_KERNEL(64) void front_mlp_bwd_kernel(const float* __restrict__ pool, const float* __restrict__ gate, const double* __restrict__ dgate,
                                            const float* __restrict__ w0, const float* __restrict__ w2, float* __restrict__ part) {
     __shared__ double s_h[2][2], s_do[16], s_dh[2];
@@ -740,10 +670,10 @@ FRONT_KERNEL(64) void front_mlp_bwd_kernel(const float* __restrict__ pool, const
         double a = 0.0;
         for (int which = 0; which < 2; ++which)
             if (s_h[which][r] > 0.0) a += s_dh[r] * (double)pool[(b * 16 + i) * 2 + which];
-        row[t] = (float)a;
+        row[MLP_ROW<VT_FT_CA0> + t] = (float)a;
     } else {
         const int c = (t - 32) >> 1, r = (t - 32) & 1;
-        row[64 + (t - 32)] = (float)(s_do[c] * (fmax(s_h[0][r], 0.0) + fmax(s_h[1][r], 0.0)));
+        row[MLP_ROW<VT_FT_CA2> + (t - 32)] = (float)(s_do[c] * (fmax(s_h[0][r], 0.0) + fmax(s_h[1][r], 0.0)));
     }
 }
 
@@ -755,7 +685,7 @@ FRONT_KERNEL(256) void front_reduce_kernel(const float* __restrict__ part, int n
     __shared__ double red[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     double sq = 0.0;
-    if (i < n && front_real(e0 + i)) {
+    if (i < n && vt_front_real(e0 + i)) {
         double a = 0.0;
         for (int r = 0; r < nparts; ++r) a += (double)part[(long long)r * stride + i];
         const float g = grads[e0 + i] + (float)a;
@@ -766,10 +696,6 @@ FRONT_KERNEL(256) void front_reduce_kernel(const float* __restrict__ part, int n
     if (threadIdx.x == 0) normpart[slot + blockIdx.x] = total;
 }
 
-FRONT_KERNEL(64) void front_scalars_init_kernel(FrontScalars* __restrict__ sc) {
-    if (threadIdx.x == 0) { sc->sq = 0.0; sc->norm = 0.f; sc->coef = 1.0f; }
-}
-
 #define TCKL(c, what) HIPCK(c, hipGetLastError(), what)
 
 int front_check(vt_context* c, const char* who, const void* state, size_t state_bytes, FrontLayout* out) {
@@ -778,9 +704,7 @@ int front_check(vt_context* c, const char* who, const void* state, size_t state_
         return c->fail(VT_ERR_INVALID, "%s: the front of this decoder cannot be trained on the device (attention decoder without cross-attention, "
                                        "heads in {1, 2, 4, 8} expected)", who);
     *out = vt_front_layout(c->dec);
-    if (!state || ((uintptr_t)state & (ALIGN - 1))) return c->fail(VT_ERR_INVALID, "%s: state is null or not 256-B aligned", who);
-    if (state_bytes < out->total) return c->fail(VT_ERR_WORKSPACE, "%s: state holds %zu bytes, %zu needed", who, state_bytes, out->total);
-    return VT_OK;
+    return vt_train_check(c, who, *out, state, state_bytes);
 }
 
 int front_check_batch(vt_context* c, const char* who, const FrontLayout& l, const void* latent, int B, int h, int w, const void* ws, size_t ws_bytes) {
@@ -866,8 +790,7 @@ int vt_front_init(vt_context* c, void* state, size_t state_bytes, void* stream) 
     HIPCK(c, hipMemcpyAsync(bn + 8, c->dec.bn_var, 32, hipMemcpyDeviceToDevice, s), "front_init copy");
     HIPCK(c, hipMemcpyAsync(bn + 16, c->dec.bn_scale, 32, hipMemcpyDeviceToDevice, s), "front_init copy");
     HIPCK(c, hipMemcpyAsync(bn + 24, c->dec.bn_shift, 32, hipMemcpyDeviceToDevice, s), "front_init copy");
-    hipLaunchKernelGGL(front_scalars_init_kernel, dim3(1), dim3(64), 0, s, (FrontScalars*)(st + l.scalars)); TCKL(c, "front_init scalars");
-    return VT_OK;
+    return vt_train_clip_blocks(c, "vt_front_init", l, st, nullptr, nullptr, 1.0f, s);     // over the zeroed block: norm 0, coefficient 1
 }
 
 int vt_front_commit(vt_context* c, const void* state, size_t state_bytes, void* stream) {
@@ -922,10 +845,10 @@ int vt_front_forward(vt_context* c, void* state, size_t state_bytes, const float
     const float* xs = latent;
     if (l.use_spatial) {
         float* pool = (float*)(wsb + k.pool); float* gate = (float*)(wsb + k.gate); float* sp = (float*)(wsb + k.sp); float* sg = (float*)(wsb + k.sg);
-        hipLaunchKernelGGL(front_pool_kernel, dim3(16, B), dim3(256), 0, s, latent, HW, pool); TCKL(c, "front pool");
-        hipLaunchKernelGGL(front_gate_kernel, dim3(B), dim3(64), 0, s, pool, T(VT_FT_CA0), T(VT_FT_CA2), gate); TCKL(c, "front gate");
+        HIPCK(c, vt_dec_pool(latent, B, 16, HW, pool, s), "front pool");
+        HIPCK(c, vt_dec_gate(pool, T(VT_FT_CA0), T(VT_FT_CA2), B, 16, 2, gate, s), "front gate");
         hipLaunchKernelGGL(front_spmap_kernel, px, dim3(256), 0, s, latent, gate, HW, sp, (unsigned char*)(wsb + k.am)); TCKL(c, "front spmap");
-        hipLaunchKernelGGL(front_sgate_kernel, px, dim3(256), 0, s, sp, T(VT_FT_SP7), h, w, sg); TCKL(c, "front sgate");
+        HIPCK(c, vt_dec_sgate(sp, T(VT_FT_SP7), B, h, w, sg, s), "front sgate");
         hipLaunchKernelGGL(front_xs_kernel, dim3((HW + 255) / 256, B * 16), dim3(256), 0, s, latent, gate, sg, HW, (float*)(wsb + k.xs)); TCKL(c, "front xs");
         xs = (const float*)(wsb + k.xs);
     }
@@ -1011,27 +934,19 @@ int vt_front_step(vt_context* c, void* state, size_t state_bytes, double lr, dou
     DeviceGuard guard(c);
     FrontLayout l;
     VTCK(front_check(c, "vt_front_step", state, state_bytes, &l));
-    if (t < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !isfinite(lr) || !isfinite(weight_decay))
-        return c->fail(VT_ERR_INVALID, "vt_front_step: t >= 1, betas in [0, 1), eps >= 0 and finite lr / weight_decay expected");
-    char* st = (char*)state;
-    HIPCK(c, vt_train_adamw_launch((float*)(st + l.params), (float*)(st + l.grads), (float*)(st + l.m), (float*)(st + l.v), VT_FRONT_P / 4, lr, beta1,
-                                   beta2, eps, weight_decay, t, (hipStream_t)stream), "front step");
-    return front_fold(c, l, st, (hipStream_t)stream);
+    VTCK(vt_train_step(c, "vt_front_step", l, state, lr, beta1, beta2, eps, weight_decay, t, (hipStream_t)stream));
+    return front_fold(c, l, (char*)state, (hipStream_t)stream);
 }
 
+// the front's own kinds (the BatchNorm buffers); the parameter arrays of a named tensor and the scalars are the common layer's
 static int front_section(vt_context* c, const char* who, const FrontLayout& l, int kind, const char* name, size_t* off, size_t* bytes) {
-    if (kind >= VT_HEAD_PARAM && kind <= VT_HEAD_ADAM_V) {
-        const int i = front_find(c, who, l, name);
-        if (i < 0) return VT_ERR_INVALID;
-        const size_t base = kind == VT_HEAD_PARAM ? l.params : kind == VT_HEAD_GRAD ? l.grads : kind == VT_HEAD_ADAM_M ? l.m : l.v;
-        *off = base + 4 * (size_t)VT_FRONT_TABLE[i].off; *bytes = 4 * (size_t)VT_FRONT_TABLE[i].numel;
-        return VT_OK;
-    }
-    if (kind == VT_HEAD_NORM) { *off = l.scalars; *bytes = sizeof(FrontScalars); return VT_OK; }
     if (kind == VT_FRONT_BN_MEAN) { *off = l.bn; *bytes = 32; return VT_OK; }
     if (kind == VT_FRONT_BN_VAR) { *off = l.bn + 32; *bytes = 32; return VT_OK; }
     if (kind == VT_FRONT_BN_TRACKED) { *off = l.bn + 128; *bytes = 8; return VT_OK; }
-    return c->fail(VT_ERR_INVALID, "%s: unknown kind %d", who, kind);
+    if (kind < VT_HEAD_PARAM || kind > VT_HEAD_ADAM_V) return vt_train_section(c, who, l, kind, 0, 0, off, bytes);    // no tensor is meant
+    const int i = front_find(c, who, l, name);
+    if (i < 0) return VT_ERR_INVALID;
+    return vt_train_section(c, who, l, kind, VT_FRONT_TABLE[i].off, VT_FRONT_TABLE[i].numel, off, bytes);
 }
 
 int vt_front_read(vt_context* c, const void* state, size_t state_bytes, int kind, const char* name, void* out, size_t out_bytes, void* stream) {
@@ -1041,9 +956,7 @@ int vt_front_read(vt_context* c, const void* state, size_t state_bytes, int kind
     VTCK(front_check(c, "vt_front_read", state, state_bytes, &l));
     size_t off = 0, bytes = 0;
     VTCK(front_section(c, "vt_front_read", l, kind, name, &off, &bytes));
-    if (!out || out_bytes < bytes) return c->fail(VT_ERR_WORKSPACE, "vt_front_read: out is null or holds %zu bytes, %zu needed", out_bytes, bytes);
-    HIPCK(c, hipMemcpyAsync(out, (const char*)state + off, bytes, hipMemcpyDefault, (hipStream_t)stream), "front_read");
-    return VT_OK;
+    return vt_train_read(c, "vt_front_read", state, off, bytes, out, out_bytes, (hipStream_t)stream);
 }
 
 int vt_front_write(vt_context* c, void* state, size_t state_bytes, int kind, const char* name, const void* src, size_t src_bytes, void* stream) {
@@ -1054,8 +967,7 @@ int vt_front_write(vt_context* c, void* state, size_t state_bytes, int kind, con
     if (kind == VT_HEAD_NORM) return c->fail(VT_ERR_INVALID, "vt_front_write: kind %d cannot be written", kind);
     size_t off = 0, bytes = 0;
     VTCK(front_section(c, "vt_front_write", l, kind, name, &off, &bytes));
-    if (!src || src_bytes != bytes) return c->fail(VT_ERR_INVALID, "vt_front_write: src is null or holds %zu bytes, %zu expected", src_bytes, bytes);
-    HIPCK(c, hipMemcpyAsync((char*)state + off, src, bytes, hipMemcpyDefault, (hipStream_t)stream), "front_write");
+    VTCK(vt_train_write(c, "vt_front_write", state, off, bytes, src, src_bytes, (hipStream_t)stream));
     if (kind == VT_HEAD_PARAM || kind == VT_FRONT_BN_MEAN || kind == VT_FRONT_BN_VAR) return front_fold(c, l, (char*)state, (hipStream_t)stream);
     return VT_OK;
 }

@@ -2,8 +2,9 @@
 // `classifier.*` -- forward with dropout, BCE / Focal / class-balanced loss (improved_losses.py:39-72), backward, clip_grad_norm_
 // and AdamW -- on one caller-owned state block (vt_train.h) fed FEATURE ROWS [B][F]: the output of the decoder's front
 // (vt_decode_features).  Alone, this unit leaves the front frozen (its rows are the same every epoch); the attention decoder's front
-// is trained by train_front.hip, which takes d loss / d features from vt_head_forward_backward_dx here and shares vt_train_clip (one
-// norm over both blocks) and the AdamW kernel.  Cross-attention has no backward anywhere.
+// is trained by train_front.hip, which takes d loss / d features from vt_head_forward_backward_dx here.  What the two trainers have in
+// common -- the state check, clip over one or both blocks, the AdamW step, the parameter kinds of read / write -- is train_common.hip;
+// this file keeps the head's forward, loss and backward and its own kind (the loss ring).  Cross-attention has no backward anywhere.
 // fp32 parameters, gradients and moments; fp64 for the loss elements and every scalar reduction.  No atomics: every gradient element
 // is owned by one thread, sums over the batch run in ascending row order, sums over workgroups are written as partials and added in
 // workgroup order by a later launch -- the order of every sum is a function of the shapes alone, so a given call sequence leaves the
@@ -13,8 +14,8 @@
 //   backward   head_linear_bwd_kernel per linear layer: reads each weight row once for dW (a rank-B update) AND the dX partials, adds
 //              into the gradient and takes the squared norm of what it wrote; head_ln_bwd_kernel per hidden layer: adds the dX
 //              partials, backs through dropout (same generator), activation and LayerNorm
-//   clip       head_clip_kernel: partials -> norm, coefficient; head_scale_kernel scales in place when the coefficient is below 1
-//   step       head_adamw_kernel: decoupled AdamW as torch.optim.AdamW, zeroes the gradients in the same pass
+//   clip, step train_common.hip: partials -> norm, coefficient, scale in place when the coefficient is below 1; decoupled AdamW as
+//              torch.optim.AdamW, zeroing the gradients in the same pass
 #include <math.h>
 #include <string.h>
 
@@ -27,21 +28,6 @@ using namespace vt;
 namespace {
 
 constexpr int HB_BT = 16;                   // batch rows of one pass of the backward kernel over its weight rows
-
-struct HeadScalars { double sq; float norm; float coef; };
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;                                // (lane 0 holds the sum)
-}
-// sum over 256 threads, waves added in wave order; every thread gets the result
-__device__ __forceinline__ double block_sum_256d(double v, double* red) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // in place: a = keep ? a / (1 - p) : 0   (nn.Dropout in training mode); optionally the mask bytes
 __global__ __launch_bounds__(256) void head_dropout_kernel(float* __restrict__ a, long long n, float p, float scale, unsigned long long seed,
@@ -234,57 +220,6 @@ __global__ __launch_bounds__(256) void head_ln_bwd_kernel(const float* __restric
     }
 }
 
-// one workgroup: the squared-norm partials in index order -> norm, coef = min(1, max_norm / (norm + 1e-6))  (clip_grad_norm_)
-__global__ __launch_bounds__(256) void head_clip_kernel(const double* __restrict__ normpart, int n, float max_norm, HeadScalars* __restrict__ sc) {
-#pragma clang fp contract(off)
-    __shared__ double red[4];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) a += normpart[i];
-    const double total = block_sum_256d(a, red);
-    if (threadIdx.x == 0) {
-        const float norm = (float)sqrt(total);
-        const float coef = max_norm / (norm + 1e-6f);
-        sc->sq = total; sc->norm = norm; sc->coef = coef < 1.0f ? coef : 1.0f;
-    }
-}
-
-// g *= coef when coef < 1 (a gradient inside the bound keeps its bits: nothing is written)
-__global__ __launch_bounds__(256) VT_NO_PACKED_F32 void head_scale_kernel(float4* __restrict__ g, long long n4, const HeadScalars* __restrict__ sc) {
-    const float coef = sc->coef;
-    if (!(coef < 1.0f)) return;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    float4 v = g[i];
-    v.x *= coef; v.y *= coef; v.z *= coef; v.w *= coef;
-    g[i] = v;
-}
-
-// (VT_NO_PACKED_F32: the compiler would pair these float4 lanes into packed fp32 ops with a source op_sel -- vt_common.h)
-// torch.optim.AdamW (single-tensor path): p *= 1 - lr wd; m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g g;
-// p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps); g = 0
-__device__ __forceinline__ void adamw_one(float& p, float& g, float& m, float& v, float decay, float w1, float beta2, float w2, float step_size,
-                                          float rbc2, float eps) {
-#pragma clang fp contract(off)
-    p = p * decay;
-    m = m + w1 * (g - m);
-    v = v * beta2 + w2 * (g * g);
-    const float denom = sqrtf(v) / rbc2 + eps;
-    p = p - step_size * (m / denom);
-    g = 0.f;
-}
-__global__ __launch_bounds__(256) VT_NO_PACKED_F32 void head_adamw_kernel(float4* __restrict__ P, float4* __restrict__ G, float4* __restrict__ M, float4* __restrict__ V,
-                                                         long long n4, float decay, float w1, float beta2, float w2, float step_size, float rbc2,
-                                                         float eps) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    float4 p = P[i], g = G[i], m = M[i], v = V[i];
-    adamw_one(p.x, g.x, m.x, v.x, decay, w1, beta2, w2, step_size, rbc2, eps);
-    adamw_one(p.y, g.y, m.y, v.y, decay, w1, beta2, w2, step_size, rbc2, eps);
-    adamw_one(p.z, g.z, m.z, v.z, decay, w1, beta2, w2, step_size, rbc2, eps);
-    adamw_one(p.w, g.w, m.w, v.w, decay, w1, beta2, w2, step_size, rbc2, eps);
-    P[i] = p; G[i] = g; M[i] = m; V[i] = v;
-}
-
 // d_features[b][k] = sum of the first layer's G dX partials, g ascending
 __global__ __launch_bounds__(256) void head_dx_sum_kernel(const float* __restrict__ part, int G, long long n, float* __restrict__ dx) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -292,28 +227,6 @@ __global__ __launch_bounds__(256) void head_dx_sum_kernel(const float* __restric
     float a = 0.f;
     for (int g = 0; g < G; ++g) a += part[(long long)g * n + i];
     dx[i] = a;
-}
-
-// one workgroup: the head's squared-norm partials in index order, then the front's -> one norm and one coefficient, written to both blocks
-__global__ __launch_bounds__(256) void train_clip_kernel(const double* __restrict__ head_part, int n_head, const double* __restrict__ front_part,
-                                                         int n_front, float max_norm, HeadScalars* __restrict__ sc_head,
-                                                         HeadScalars* __restrict__ sc_front) {
-#pragma clang fp contract(off)
-    __shared__ double red[4];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n_head; i += 256) a += head_part[i];
-    const double th = block_sum_256d(a, red);
-    a = 0.0;
-    for (int i = threadIdx.x; i < n_front; i += 256) a += front_part[i];
-    const double tf = block_sum_256d(a, red);
-    if (threadIdx.x == 0) {
-        const double total = th + tf;
-        const float norm = (float)sqrt(total);
-        const float coef = max_norm / (norm + 1e-6f);
-        HeadScalars v;
-        v.sq = total; v.norm = norm; v.coef = coef < 1.0f ? coef : 1.0f;
-        *sc_head = v; *sc_front = v;
-    }
 }
 
 #define TCKL(c, what) HIPCK(c, hipGetLastError(), what)
@@ -324,9 +237,7 @@ int head_check(vt_context* c, const char* who, const void* state, size_t state_b
     for (int i = 0; i <= s.hidden; ++i)
         if (s.dims[i] % 256) return c->fail(VT_ERR_INVALID, "%s: the head's input widths must be multiples of 256 (one backward thread per column of a 256-column block); this head has %d", who, s.dims[i]);
     *out = vt_head_layout(s);
-    if (!state || ((uintptr_t)state & (ALIGN - 1))) return c->fail(VT_ERR_INVALID, "%s: state is null or not 256-B aligned", who);
-    if (state_bytes < out->total) return c->fail(VT_ERR_WORKSPACE, "%s: state holds %zu bytes, %zu needed", who, state_bytes, out->total);
-    return VT_OK;
+    return vt_train_check(c, who, *out, state, state_bytes);
 }
 
 // the context's table entry of tensor t (a device pointer the context owns)
@@ -399,15 +310,6 @@ int head_check_batch(vt_context* c, const char* who, const HeadLayout& l, const 
 
 }  // namespace
 
-hipError_t vt_train_adamw_launch(float* P, float* G, float* M, float* V, long long n4, double lr, double beta1, double beta2, double eps,
-                                 double weight_decay, long long t, hipStream_t s) {
-    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
-    hipLaunchKernelGGL(head_adamw_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (float4*)P, (float4*)G, (float4*)M, (float4*)V, n4,
-                       (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2),
-                       (float)eps);
-    return hipGetLastError();
-}
-
 extern "C" {
 
 int vt_decoder_feature_dim(const vt_context* c) {
@@ -449,9 +351,7 @@ int vt_head_init(vt_context* c, void* state, size_t state_bytes, void* stream) {
     for (int i = 0; i < l.ntensors; ++i)
         HIPCK(c, hipMemcpyAsync((float*)(st + l.params) + l.t[i].off, head_ctx_tensor(c->dec, l.t[i]), 4 * l.t[i].numel, hipMemcpyDeviceToDevice, s),
               "head_init copy");
-    hipLaunchKernelGGL(head_clip_kernel, dim3(1), dim3(256), 0, s, (const double*)(st + l.normpart), l.norm_parts, 1.0f, (HeadScalars*)(st + l.scalars));
-    TCKL(c, "head_init scalars");            // (norm 0, coefficient 1)
-    return VT_OK;
+    return vt_train_clip_blocks(c, "vt_head_init", l, st, nullptr, nullptr, 1.0f, s);      // over the zeroed block: norm 0, coefficient 1
 }
 
 int vt_head_commit(vt_context* c, const void* state, size_t state_bytes, void* stream) {
@@ -579,20 +479,8 @@ int vt_train_clip(vt_context* c, void* head_state, size_t head_bytes, void* fron
     VTCK(head_check(c, "vt_train_clip", head_state, head_bytes, &l));
     if (!vt_front_trainable(c->dec)) return c->fail(VT_ERR_INVALID, "vt_train_clip: this decoder's front is not trainable");
     const FrontLayout f = vt_front_layout(c->dec);
-    if (!front_state || ((uintptr_t)front_state & (ALIGN - 1)) || front_bytes < f.total)
-        return c->fail(VT_ERR_INVALID, "vt_train_clip: the front state is null, not 256-B aligned or shorter than %zu bytes", f.total);
-    if (!(max_norm > 0.f)) return c->fail(VT_ERR_INVALID, "vt_train_clip: max_norm = %g must be positive", max_norm);
-    hipStream_t s = (hipStream_t)stream;
-    char* hs = (char*)head_state;
-    char* fs = (char*)front_state;
-    HeadScalars* sch = (HeadScalars*)(hs + l.scalars);
-    HeadScalars* scf = (HeadScalars*)(fs + f.scalars);
-    hipLaunchKernelGGL(train_clip_kernel, dim3(1), dim3(256), 0, s, (const double*)(hs + l.normpart), l.norm_parts, (const double*)(fs + f.normpart),
-                       VT_FRONT_NORM_PARTS, max_norm, sch, scf); TCKL(c, "train clip");
-    const long long n4 = (long long)(l.P / 4), f4 = VT_FRONT_P / 4;
-    hipLaunchKernelGGL(head_scale_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (float4*)(hs + l.grads), n4, sch); TCKL(c, "train clip scale");
-    hipLaunchKernelGGL(head_scale_kernel, dim3((unsigned)((f4 + 255) / 256)), dim3(256), 0, s, (float4*)(fs + f.grads), f4, scf); TCKL(c, "train clip scale");
-    return VT_OK;
+    VTCK(vt_train_check(c, "vt_train_clip (front)", f, front_state, front_bytes));
+    return vt_train_clip_blocks(c, "vt_train_clip", l, head_state, &f, front_state, max_norm, (hipStream_t)stream);
 }
 
 int vt_head_clip(vt_context* c, void* state, size_t state_bytes, float max_norm, void* stream) {
@@ -600,14 +488,7 @@ int vt_head_clip(vt_context* c, void* state, size_t state_bytes, float max_norm,
     DeviceGuard guard(c);
     HeadLayout l;
     VTCK(head_check(c, "vt_head_clip", state, state_bytes, &l));
-    if (!(max_norm > 0.f)) return c->fail(VT_ERR_INVALID, "vt_head_clip: max_norm = %g must be positive", max_norm);
-    hipStream_t s = (hipStream_t)stream;
-    char* st = (char*)state;
-    HeadScalars* sc = (HeadScalars*)(st + l.scalars);
-    hipLaunchKernelGGL(head_clip_kernel, dim3(1), dim3(256), 0, s, (const double*)(st + l.normpart), l.norm_parts, max_norm, sc); TCKL(c, "head clip");
-    const long long n4 = (long long)(l.P / 4);
-    hipLaunchKernelGGL(head_scale_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (float4*)(st + l.grads), n4, sc); TCKL(c, "head clip scale");
-    return VT_OK;
+    return vt_train_clip_blocks(c, "vt_head_clip", l, state, nullptr, nullptr, max_norm, (hipStream_t)stream);
 }
 
 int vt_head_step(vt_context* c, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, double weight_decay, long long t,
@@ -616,25 +497,16 @@ int vt_head_step(vt_context* c, void* state, size_t state_bytes, double lr, doub
     DeviceGuard guard(c);
     HeadLayout l;
     VTCK(head_check(c, "vt_head_step", state, state_bytes, &l));
-    if (t < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !isfinite(lr) || !isfinite(weight_decay))
-        return c->fail(VT_ERR_INVALID, "vt_head_step: t >= 1, betas in [0, 1), eps >= 0 and finite lr / weight_decay expected");
-    char* st = (char*)state;
-    HIPCK(c, vt_train_adamw_launch((float*)(st + l.params), (float*)(st + l.grads), (float*)(st + l.m), (float*)(st + l.v), (long long)(l.P / 4), lr,
-                                   beta1, beta2, eps, weight_decay, t, (hipStream_t)stream), "head step");
-    return VT_OK;
+    return vt_train_step(c, "vt_head_step", l, state, lr, beta1, beta2, eps, weight_decay, t, (hipStream_t)stream);
 }
 
+// the head's own kind (the loss ring); the parameter arrays of a named tensor and the scalars are the common layer's
 static int head_section(vt_context* c, const char* who, const HeadLayout& l, int kind, const char* name, size_t* off, size_t* bytes) {
-    if (kind >= VT_HEAD_PARAM && kind <= VT_HEAD_ADAM_V) {
-        const int i = head_find(c, who, l, name);
-        if (i < 0) return VT_ERR_INVALID;
-        const size_t base = kind == VT_HEAD_PARAM ? l.params : kind == VT_HEAD_GRAD ? l.grads : kind == VT_HEAD_ADAM_M ? l.m : l.v;
-        *off = base + 4 * l.t[i].off; *bytes = 4 * l.t[i].numel;
-        return VT_OK;
-    }
     if (kind == VT_HEAD_LOSS_RING) { *off = l.ring; *bytes = sizeof(double) * VT_HEAD_RING; return VT_OK; }
-    if (kind == VT_HEAD_NORM) { *off = l.scalars; *bytes = sizeof(HeadScalars); return VT_OK; }
-    return c->fail(VT_ERR_INVALID, "%s: unknown kind %d", who, kind);
+    if (kind < VT_HEAD_PARAM || kind > VT_HEAD_ADAM_V) return vt_train_section(c, who, l, kind, 0, 0, off, bytes);    // no tensor is meant
+    const int i = head_find(c, who, l, name);
+    if (i < 0) return VT_ERR_INVALID;
+    return vt_train_section(c, who, l, kind, l.t[i].off, l.t[i].numel, off, bytes);
 }
 
 int vt_head_read(vt_context* c, const void* state, size_t state_bytes, int kind, const char* name, void* out, size_t out_bytes, void* stream) {
@@ -644,9 +516,7 @@ int vt_head_read(vt_context* c, const void* state, size_t state_bytes, int kind,
     VTCK(head_check(c, "vt_head_read", state, state_bytes, &l));
     size_t off = 0, bytes = 0;
     VTCK(head_section(c, "vt_head_read", l, kind, name, &off, &bytes));
-    if (!out || out_bytes < bytes) return c->fail(VT_ERR_WORKSPACE, "vt_head_read: out is null or holds %zu bytes, %zu needed", out_bytes, bytes);
-    HIPCK(c, hipMemcpyAsync(out, (const char*)state + off, bytes, hipMemcpyDefault, (hipStream_t)stream), "head_read");
-    return VT_OK;
+    return vt_train_read(c, "vt_head_read", state, off, bytes, out, out_bytes, (hipStream_t)stream);
 }
 
 int vt_head_write(vt_context* c, void* state, size_t state_bytes, int kind, const char* name, const void* src, size_t src_bytes, void* stream) {
@@ -657,9 +527,7 @@ int vt_head_write(vt_context* c, void* state, size_t state_bytes, int kind, cons
     if (kind < VT_HEAD_PARAM || kind > VT_HEAD_ADAM_V) return c->fail(VT_ERR_INVALID, "vt_head_write: kind %d is not a parameter array", kind);
     size_t off = 0, bytes = 0;
     VTCK(head_section(c, "vt_head_write", l, kind, name, &off, &bytes));
-    if (!src || src_bytes != bytes) return c->fail(VT_ERR_INVALID, "vt_head_write: src is null or holds %zu bytes, %zu expected", src_bytes, bytes);
-    HIPCK(c, hipMemcpyAsync((char*)state + off, src, bytes, hipMemcpyDefault, (hipStream_t)stream), "head_write");
-    return VT_OK;
+    return vt_train_write(c, "vt_head_write", state, off, bytes, src, src_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

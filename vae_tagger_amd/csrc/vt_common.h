@@ -51,6 +51,33 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+__device__ __forceinline__ double wave_sum_d(double v) {
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+    return v;                                // (lane 0 holds the sum)
+}
+// sum over 256 threads, waves added in wave order; every thread gets the result
+__device__ __forceinline__ double block_sum_256d(double v, double* red) {
+    v = wave_sum_d(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float block_max_256(float v, float* red) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
 // Bijective XCD-aware remap: hardware deals consecutive workgroup ids round-robin over the 8 XCDs
 // (blocks b and b+8 share an L2).  Give each XCD a contiguous run of logical tiles so tiles that
 // share operand panels hit the same L2.  Speed only; any placement is correct.

@@ -36,6 +36,11 @@ DecHeadShape vt_decoder_head_shape(const DecoderWeights& w);
 // the head's two kernels, as vt_decoder_forward launches them (train_head.hip's forward runs the same launches: same bits)
 hipError_t vt_dec_linear(const float* x, const float* w, const float* bias, float* y, int B, int IN, int OUT, hipStream_t s);
 hipError_t vt_dec_ln_act(float* y, const float* g, const float* b, int rows, int N, int act, hipStream_t s);
+// SpatialAttention's pool [B][C][2], channel gate [B][C] and spatial gate [B][HW], as vt_decoder_front launches them (train_front.hip's
+// training-mode forward runs the same launches: same bits)
+hipError_t vt_dec_pool(const float* x, int B, int C, int HW, float* pool, hipStream_t s);
+hipError_t vt_dec_gate(const float* pool, const float* w0, const float* w2, int B, int C, int R, float* gate, hipStream_t s);
+hipError_t vt_dec_sgate(const float* sp, const float* w, int B, int H, int W, float* sg, hipStream_t s);
 // vt_decoder_forward = front (latent -> feature rows [B][dims[0]]) + head (feature rows -> logits)
 hipError_t vt_decoder_front(const DecoderWeights& w, const float* latent_nchw, int B, int H, int W, float* ws, float* feat, hipStream_t s);
 hipError_t vt_decoder_head(const DecHeadShape& h, const DecHeadParams& p, const float* feat, int B, float* hbuf, float* logits, hipStream_t s);

@@ -1,11 +1,39 @@
-// Classifier-head trainer: layout of the caller-owned state block and of the per-call workspace, and the dropout generator
-// (train_head.hip; mirrored by vae_tagger_amd/train.py).
+// The trainers: what every caller-owned state block has and the host layer over it (train_common.hip), then the layouts of the
+// classifier head's block and per-call workspace and the dropout generator (train_head.hip), then the front's (train_front.hip).
+// These tables are the only place a layout is written: vae_tagger_amd/train.py goes through vt_*_read / vt_*_write by kind and name
+// and mirrors nothing but the 16 bytes of TrainScalars (grad_norm).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include "vt_decoder.h"
 #include "vt_eval.h"
+
+struct vt_context;
+
+// ---- what every trainer block has ---------------------------------------------------------------------------------------------------
+// the scalars of the last clip: fp64 squared norm, fp32 norm, fp32 clip coefficient
+struct TrainScalars { double sq; float norm; float coef; };
+// byte offsets of the sections (each 256-B aligned) that the shared layer touches, the floats of one parameter array (padded) and the
+// number of squared-norm partials (fp64, one per workgroup of the kernels that write gradients)
+struct TrainBlock {
+    size_t P;
+    size_t params, grads, m, v, scalars, normpart, total;
+    int norm_parts;
+};
+// Host layer of train_common.hip; `who` is the entry point the caller was reached through (error messages name it).
+int vt_train_check(vt_context* c, const char* who, const TrainBlock& b, const void* state, size_t state_bytes);   // null, alignment, size
+// clip_grad_norm_ over block a, or over a and b together (b may be null): one norm and one coefficient, written to every block
+int vt_train_clip_blocks(vt_context* c, const char* who, const TrainBlock& a, void* sa, const TrainBlock* b, void* sb, float max_norm,
+                         hipStream_t s);
+int vt_train_step(vt_context* c, const char* who, const TrainBlock& b, void* state, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, long long t, hipStream_t s);
+// VT_HEAD_PARAM .. VT_HEAD_ADAM_V of the tensor at float offset `toff` with `numel` floats, or VT_HEAD_NORM -> byte range of the block
+int vt_train_section(vt_context* c, const char* who, const TrainBlock& b, int kind, size_t toff, size_t numel, size_t* off, size_t* bytes);
+int vt_train_read(vt_context* c, const char* who, const void* state, size_t off, size_t bytes, void* out, size_t out_bytes, hipStream_t s);
+int vt_train_write(vt_context* c, const char* who, void* state, size_t off, size_t bytes, const void* src, size_t src_bytes, hipStream_t s);
+
+// ---- head trainer (train_head.hip) ----------------------------------------------------------------------------------------------------
 
 constexpr int VT_HEAD_RING = 256;           // per-step loss values kept: slot = step % VT_HEAD_RING
 constexpr int VT_HEAD_MAX_B = 4096;
@@ -21,14 +49,12 @@ struct HeadTensor { int module; int is_bias; size_t off, numel; };      // name 
 // One block, every section 256-B aligned:
 //   params fp32 [P] | grads fp32 [P] | adam m fp32 [P] | adam v fp32 [P] | scalars { fp64 squared norm, fp32 norm, fp32 clip coefficient } |
 //   loss ring fp64 [VT_HEAD_RING] | squared-norm partials fp64 [norm_parts]: one per workgroup of the kernels that write gradients
-struct HeadLayout {
+struct HeadLayout : TrainBlock {
     DecHeadShape shape;
     int ntensors;
     HeadTensor t[VT_HEAD_TENSORS];
-    size_t P;                                // floats of one parameter array (padded)
-    size_t params, grads, m, v, scalars, ring, normpart, total;
+    size_t ring;
     int groups[4], kblocks[4], part_base[4]; // backward grid of linear layer l and its first squared-norm partial
-    int norm_parts;
 };
 
 inline int vt_head_rows(const DecHeadShape& s, int l) { return l == s.hidden ? VT_HEAD_ROWS_LAST : VT_HEAD_ROWS_HIDDEN; }
@@ -121,13 +147,9 @@ VT_TRAIN_HD inline bool vt_head_keep(uint64_t seed, uint64_t step, int layer, ui
 // zero); every tensor starts on a multiple of 64 floats and the padding stays zero.  Gradient GROUPS are reduced by one launch each.
 constexpr int VT_FRONT_TENSORS = 17;
 constexpr int VT_FRONT_P = 2240;            // floats of one parameter array
-constexpr int VT_FRONT_NORM_PARTS = 16;     // squared-norm partials: mlp 0 | 7x7 1 | conv 2..6 | batch norm 7 | self-attention 8..10
+constexpr int VT_FRONT_NORM_PARTS = 16;     // squared-norm partials: mlp 0 | 7x7 1 | conv 2..6 | batch norm 7 | self-attention 8..10 | 5 spare
 constexpr int VT_FRONT_MAX_B = 1024;        // (grids carry B, and B x 16, in their y dimension)
 constexpr int VT_FRONT_DROPOUT_LAYER = 8;   // the attention dropout's layer id in vt_head_keep (the head's are 0..2)
-enum { VT_FG_MLP = 0, VT_FG_SP7 = 1, VT_FG_CONV = 2, VT_FG_BN = 3, VT_FG_SA = 4 };
-constexpr int VT_FG_START[5] = {0, 128, 256, 1472, 1600};       // first float of each group; the group ends where the next starts
-constexpr int VT_FG_END[5] = {128, 256, 1472, 1600, 2240};
-constexpr int VT_FG_SLOT[5] = {0, 1, 2, 7, 8};                  // first squared-norm partial of each group
 struct FrontTensor { const char* name; int off, numel, piece; };     // piece 0: spatial attention, 1: feature_compress, 2: self-attention
 constexpr FrontTensor VT_FRONT_TABLE[VT_FRONT_TENSORS] = {
     {"spatial_attention.channel_att.0.weight", 0, 32, 0},   {"spatial_attention.channel_att.2.weight", 64, 32, 0},
@@ -142,19 +164,50 @@ constexpr FrontTensor VT_FRONT_TABLE[VT_FRONT_TENSORS] = {
 };
 enum { VT_FT_CA0 = 0, VT_FT_CA2, VT_FT_SP7, VT_FT_FCW, VT_FT_FCB, VT_FT_BNW, VT_FT_BNB, VT_FT_LNW, VT_FT_LNB, VT_FT_QW, VT_FT_QB, VT_FT_KW,
        VT_FT_KB, VT_FT_VW, VT_FT_VB, VT_FT_OW, VT_FT_OB };
+enum { VT_FG_MLP = 0, VT_FG_SP7 = 1, VT_FG_CONV = 2, VT_FG_BN = 3, VT_FG_SA = 4 };
+constexpr int VT_FG_FIRST[5] = {VT_FT_CA0, VT_FT_SP7, VT_FT_FCW, VT_FT_BNW, VT_FT_LNW};     // first tensor of each group
+constexpr int VT_FG_START[5] = {0, 128, 256, 1472, 1600};       // first float of each group; the group ends where the next starts
+constexpr int VT_FG_END[5] = {128, 256, 1472, 1600, 2240};
+constexpr int VT_FG_SLOT[5] = {0, 1, 2, 7, 8};                  // first squared-norm partial of each group
+// is float `e` of a parameter array an element of a tensor (not padding)?  always_inline: the kernels that call it carry
+// VT_NO_PACKED_F32, a target attribute, and the compiler does not inline a callee whose target attributes differ from its caller's
+// unless the callee is always_inline -- without it the kernel makes a real function call per thread.  Inlined, the loop unrolls over
+// the constant table into a chain of comparisons against literals.
+VT_TRAIN_HD constexpr __attribute__((always_inline)) bool vt_front_real(int e) {
+    for (int t = 0; t < VT_FRONT_TENSORS; ++t)
+        if (e >= VT_FRONT_TABLE[t].off && e < VT_FRONT_TABLE[t].off + VT_FRONT_TABLE[t].numel) return true;
+    return false;
+}
+// the literals above against the table: a changed offset that they do not follow does not compile
+constexpr int vt_fg_blocks(int g) { return (VT_FG_END[g] - VT_FG_START[g] + 255) / 256; }   // workgroups of the group's reduce launch
+constexpr bool vt_fg_starts_ok() {
+    for (int g = 0; g < 5; ++g)
+        if (VT_FG_START[g] != VT_FRONT_TABLE[VT_FG_FIRST[g]].off || VT_FG_END[g] != (g < 4 ? VT_FG_START[g + 1] : VT_FRONT_P)) return false;
+    return true;
+}
+constexpr bool vt_fg_slots_ok() {
+    for (int g = 0; g < 5; ++g)
+        if (VT_FG_SLOT[g] != (g ? VT_FG_SLOT[g - 1] + vt_fg_blocks(g - 1) : 0)) return false;
+    return VT_FG_SLOT[4] + vt_fg_blocks(4) <= VT_FRONT_NORM_PARTS;
+}
+static_assert(vt_fg_starts_ok(), "a gradient group starts at its first tensor's offset and ends where the next group starts");
+static_assert(VT_FRONT_P == VT_FRONT_TABLE[VT_FRONT_TENSORS - 1].off + (VT_FRONT_TABLE[VT_FRONT_TENSORS - 1].numel + 63) / 64 * 64,
+              "VT_FRONT_P is the end of the last tensor's 64-float slot");
+static_assert(vt_fg_slots_ok(), "VT_FG_SLOT counts one squared-norm partial per reduce workgroup, all inside VT_FRONT_NORM_PARTS");
 
 // One block, every section 256-B aligned:
 //   params fp32 [P] | grads | adam m | adam v | batch norm buffers { running_mean fp32 [8], running_var fp32 [8], eval scale fp32 [8],
 //   eval shift fp32 [8] (the fold vt_decoder_finalize makes, redone whenever its inputs change), int64 num_batches_tracked at byte 128 } |
 //   scalars { fp64 squared norm, fp32 norm, fp32 clip coefficient } | squared-norm partials fp64 [VT_FRONT_NORM_PARTS]
-struct FrontLayout {
+struct FrontLayout : TrainBlock {
     int use_spatial, use_self, heads;
-    size_t params, grads, m, v, bn, scalars, normpart, total;
+    size_t bn;
     bool present(int t) const { const int p = VT_FRONT_TABLE[t].piece; return p == 1 || (p == 0 ? use_spatial != 0 : use_self != 0); }
 };
 inline FrontLayout vt_front_layout(const DecoderWeights& d) {
     FrontLayout l;
     l.use_spatial = d.use_spatial; l.use_self = d.use_self; l.heads = d.heads;
+    l.P = VT_FRONT_P; l.norm_parts = VT_FRONT_NORM_PARTS;
     const size_t a = vt_eval_align(4 * (size_t)VT_FRONT_P);
     l.params = 0; l.grads = a; l.m = 2 * a; l.v = 3 * a; l.bn = 4 * a;
     l.scalars = l.bn + 256;
@@ -203,7 +256,3 @@ inline FrontWorkspace vt_front_workspace(const FrontLayout& l, int B, int H, int
     w.total = off;
     return w;
 }
-
-// shared launches of train_head.hip (the front's optimiser step is the head's kernel over the front's arrays)
-hipError_t vt_train_adamw_launch(float* P, float* G, float* M, float* V, long long n4, double lr, double beta1, double beta2, double eps,
-                                 double weight_decay, long long t, hipStream_t s);

@@ -5,6 +5,7 @@ reference's train_decoder.py (train_decoder.py:173-216) does to `classifier.*`.
   split_indices / epoch_order    the train / validation split and the per-epoch training order, from the seed alone
   FeatureCache   the decoder front's feature rows and the labels of every image, kept on the device after the first epoch
   HeadTrainer    the device state (parameters, gradients, Adam moments, loss ring) and its forward_backward / clip / step / commit
+                 (what it shares with FrontTrainer -- the state block, step, commit, read, write -- is _BlockTrainer)
   FrontTrainer   the same for the attention decoder's front (vt_front_*; csrc/train_front.hip): training-mode forward (BatchNorm on
                  batch statistics, dropout on the softmax weights), backward from d loss / d features, AdamW, commit
   DecoderTrainer front + head: one forward_backward, ONE clip_grad_norm_ over both blocks (vt_train_clip), one step / commit
@@ -198,13 +199,15 @@ def head_parameter_names(decoder):
     return [k for k in decoder.state_dict() if k.startswith("classifier.")]
 
 
-def export_state_dict(decoder, read_parameter):
-    """The decoder's full state_dict with every `classifier.*` tensor replaced by read_parameter(name) (a host fp32 tensor of the same
-    shape): the keys torch.save writes for a checkpoint; the frozen tensors are the decoder's own, unchanged."""
+def export_state_dict(decoder, read, names=None):
+    """The decoder's full state_dict with every tensor of `names` (default: `classifier.*`) replaced by read(name) (a host tensor of the
+    same shape): the keys torch.save writes for a checkpoint, in the decoder's order and dtypes; the other tensors are the decoder's
+    own, unchanged."""
+    names = set(head_parameter_names(decoder) if names is None else names)
     out = {}
     for k, v in decoder.state_dict().items():
-        if k.startswith("classifier."):
-            t = read_parameter(k)
+        if k in names:
+            t = read(k)
             if tuple(t.shape) != tuple(v.shape):
                 raise ValueError(f"{k}: read {tuple(t.shape)}, the decoder holds {tuple(v.shape)}")
             out[k] = t.detach().to("cpu", v.dtype).clone()
@@ -213,16 +216,81 @@ def export_state_dict(decoder, read_parameter):
     return out
 
 
-class HeadTrainer:
-    """Device state of the classifier head of `decoder` (on a HIP device) and the calls that train it.  Every method queues work on the
-    current stream and returns; `losses()`, `grad_norm()`, `parameter()` and `gradient()` synchronise."""
+class _BlockTrainer:
+    """What HeadTrainer and FrontTrainer share: one 256-B aligned device state block (parameters, gradients, Adam moments, the clip
+    scalars) behind the entries `PREFIX + init / step / commit / read / write` of the C ABI.  A subclass sets PREFIX and `shapes`
+    ({parameter name: shape}) and calls `_allocate`."""
+    PREFIX = None
 
-    def __init__(self, decoder, loss="bce", focal_alpha=1.0, focal_gamma=2.0, class_weights=None, dropout=None, seed=0):
+    def __init__(self, decoder, seed):
         self.decoder = decoder
         self.ctx = decoder._context()
         self.device = next(decoder.parameters()).device
-        self.N = decoder.num_classes
         self.F = self.ctx.lib.vt_decoder_feature_dim(self.ctx.handle)
+        self.seed, self.calls, self.t = int(seed), 0, 0
+
+    def _allocate(self, unsupported):
+        self._bytes = getattr(self.ctx.lib, self.PREFIX + "state_bytes")(self.ctx.handle)
+        if self._bytes == 0:
+            raise _lib.VTError(unsupported)
+        self._buf = torch.empty(self._bytes + 256, dtype=torch.uint8, device=self.device)
+        self._ptr = (self._buf.data_ptr() + 255) // 256 * 256
+        self._call("init")
+
+    def _state(self):
+        return ctypes.c_void_p(self._ptr), self._bytes
+
+    def _call(self, entry, *args):
+        self.ctx.call(self.PREFIX + entry, *self._state(), *args, stream_ptr(self.device))
+
+    def step(self, lr, weight_decay=0.0, betas=ADAM_BETAS, eps=ADAM_EPS):
+        self.t += 1
+        self._call("step", float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), self.t)
+
+    def commit(self):
+        """Write the state's tensors into the decoder's device tables: decoder(latent) then runs what was trained."""
+        self._call("commit")
+
+    def _read(self, kind, name, shape, dtype):
+        out = torch.empty(shape, dtype=dtype, pin_memory=True)
+        self._call("read", kind, name.encode() if name else None, ctypes.c_void_p(out.data_ptr()), out.numel() * out.element_size())
+        torch.cuda.current_stream(self.device).synchronize()
+        return out.clone()
+
+    def parameter(self, name):
+        return self._read(_lib.HEAD_PARAM, name, self.shapes[name], torch.float32)
+
+    def gradient(self, name):
+        return self._read(_lib.HEAD_GRAD, name, self.shapes[name], torch.float32)
+
+    def write(self, kind, name, tensor):
+        t = tensor.detach().to(self.device, torch.float32).contiguous()
+        if tuple(t.shape) != self.shapes[name]:
+            raise ValueError(f"{name}: expected {self.shapes[name]}, got {tuple(t.shape)}")
+        self._call("write", kind, name.encode(), vp(t), t.numel() * 4)
+        torch.cuda.current_stream(self.device).synchronize()        # (t may be freed when this returns)
+
+    def grad_norm(self):
+        """(total L2 norm, clip coefficient) of the last clip(): bytes 8..16 of the block's scalars { fp64 squared norm, fp32 norm,
+        fp32 coefficient } (TrainScalars of csrc/vt_train.h, the one layout fact this module repeats)."""
+        raw = self._read(_lib.HEAD_NORM, None, (16,), torch.uint8).numpy()
+        return float(raw[8:12].view(np.float32)[0]), float(raw[12:16].view(np.float32)[0])
+
+    def state_bytes(self):
+        """The whole state block (for bit comparisons)."""
+        torch.cuda.current_stream(self.device).synchronize()
+        off = self._ptr - self._buf.data_ptr()
+        return self._buf[off:off + self._bytes].cpu()
+
+
+class HeadTrainer(_BlockTrainer):
+    """Device state of the classifier head of `decoder` (on a HIP device) and the calls that train it.  Every method queues work on the
+    current stream and returns; `losses()`, `grad_norm()`, `parameter()` and `gradient()` synchronise."""
+    PREFIX = "vt_head_"
+
+    def __init__(self, decoder, loss="bce", focal_alpha=1.0, focal_gamma=2.0, class_weights=None, dropout=None, seed=0):
+        super().__init__(decoder, seed)
+        self.N = decoder.num_classes
         if loss not in _lib.HEAD_LOSS_KINDS:
             raise ValueError(f"loss {loss!r}: one of {', '.join(_lib.HEAD_LOSS_KINDS)} expected")
         self.loss_kind, self.alpha, self.gamma = _lib.HEAD_LOSS_KINDS[loss], float(focal_alpha), float(focal_gamma)
@@ -237,18 +305,9 @@ class HeadTrainer:
         if len(rates) != len(head_dropout_rates(decoder)):
             raise ValueError(f"{len(head_dropout_rates(decoder))} dropout rates expected")
         self.dropout = (ctypes.c_float * len(rates))(*rates)
-        self.seed, self.calls, self.t = int(seed), 0, 0
         self.shapes = {k: tuple(v.shape) for k, v in decoder.state_dict().items() if k.startswith("classifier.")}
-        self._bytes = self.ctx.lib.vt_head_state_bytes(self.ctx.handle)
-        if self._bytes == 0:
-            raise _lib.VTError("this decoder's head cannot be trained on the device: every linear layer's input width must be a multiple "
-                               f"of 256 (feature width {self.F}; latent_channels = 16 gives 256 / 512)")
-        self._buf = torch.empty(self._bytes + 256, dtype=torch.uint8, device=self.device)
-        self._ptr = (self._buf.data_ptr() + 255) // 256 * 256
-        self.ctx.call("vt_head_init", ctypes.c_void_p(self._ptr), self._bytes, stream_ptr(self.device))
-
-    def _state(self):
-        return ctypes.c_void_p(self._ptr), self._bytes
+        self._allocate("this decoder's head cannot be trained on the device: every linear layer's input width must be a multiple "
+                       f"of 256 (feature width {self.F}; latent_channels = 16 gives 256 / 512)")
 
     def _ws(self, B):
         need = self.ctx.lib.vt_head_workspace_bytes(self.ctx.handle, int(B))
@@ -277,13 +336,14 @@ class HeadTrainer:
         """Eval-mode logits [B][N] of the state's parameters."""
         f = self._features_in(features)
         out = torch.empty(f.shape[0], self.N, dtype=torch.float32, device=self.device)
-        ws, need = self._ws(f.shape[0])
-        self.ctx.call("vt_head_forward", *self._state(), vp(f), f.shape[0], vp(out), ws, need, stream_ptr(self.device))
+        self._call("forward", vp(f), f.shape[0], vp(out), *self._ws(f.shape[0]))
         return out
 
-    def forward_backward(self, features, labels, loss_scale=1.0, train=True, step=None, return_logits=False, return_masks=False):
+    def forward_backward(self, features, labels, loss_scale=1.0, train=True, step=None, return_logits=False, return_masks=False,
+                         return_d_features=False):
         """One micro-batch: forward (train: with dropout), loss, backward, gradients ADDED to the state's.  loss_scale x loss goes
-        into the ring at slot step % HEAD_RING; `step` (default: the number of calls so far) also keys the dropout masks."""
+        into the ring at slot step % HEAD_RING; `step` (default: the number of calls so far) also keys the dropout masks.  Returns
+        those of (logits, masks, d loss / d features) that were asked for: None, the one, or a tuple in this order."""
         f = self._features_in(features)
         y = labels.detach().to(self.device)
         if y.dtype == torch.bool:
@@ -300,10 +360,11 @@ class HeadTrainer:
         if return_masks:
             widths = [self.shapes[f"classifier.{4 * i}.bias"][0] for i in range(len(self.dropout))]
             masks = torch.empty(B * sum(widths), dtype=torch.uint8, device=self.device)
-        ws, need = self._ws(B)
-        self.ctx.call("vt_head_forward_backward", *self._state(), vp(f), vp(y), _lib.VT_U8 if y.dtype == torch.uint8 else _lib.VT_F32, B,
-                      self.loss_kind, self.alpha, self.gamma, vp(self.class_weights), float(loss_scale), int(bool(train)), self.dropout,
-                      self.seed, step, vp(logits), vp(masks), ws, need, stream_ptr(self.device))
+        d = torch.empty(B, self.F, dtype=torch.float32, device=self.device) if return_d_features else None
+        self._call("forward_backward_dx" if return_d_features else "forward_backward", vp(f), vp(y),
+                   _lib.VT_U8 if y.dtype == torch.uint8 else _lib.VT_F32, B, self.loss_kind, self.alpha, self.gamma, vp(self.class_weights),
+                   float(loss_scale), int(bool(train)), self.dropout, self.seed, step, vp(logits), vp(masks),
+                   *([vp(d)] if return_d_features else []), *self._ws(B))
         self.calls = step + 1
         if return_masks:
             out, off = [], 0
@@ -311,54 +372,19 @@ class HeadTrainer:
                 out.append(masks[off:off + B * wd].view(B, wd))
                 off += B * wd
             masks = out
-        if return_logits and return_masks:
-            return logits, masks
-        return logits if return_logits else masks
+        asked = [v for v, want in ((logits, return_logits), (masks, return_masks), (d, return_d_features)) if want]
+        return None if not asked else asked[0] if len(asked) == 1 else tuple(asked)
 
     def clip(self, max_norm):
-        self.ctx.call("vt_head_clip", *self._state(), float(max_norm), stream_ptr(self.device))
-
-    def step(self, lr, weight_decay=0.0, betas=ADAM_BETAS, eps=ADAM_EPS):
-        self.t += 1
-        self.ctx.call("vt_head_step", *self._state(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), self.t,
-                      stream_ptr(self.device))
-
-    def commit(self):
-        """Write the parameters into the decoder's device tables: decoder(latent) then runs the trained head."""
-        self.ctx.call("vt_head_commit", *self._state(), stream_ptr(self.device))
-
-    def _read(self, kind, name, shape, dtype):
-        out = torch.empty(shape, dtype=dtype, pin_memory=True)
-        self.ctx.call("vt_head_read", *self._state(), kind, name.encode() if name else None, ctypes.c_void_p(out.data_ptr()),
-                      out.numel() * out.element_size(), stream_ptr(self.device))
-        torch.cuda.current_stream(self.device).synchronize()
-        return out.clone()
-
-    def parameter(self, name):
-        return self._read(_lib.HEAD_PARAM, name, self.shapes[name], torch.float32)
-
-    def gradient(self, name):
-        return self._read(_lib.HEAD_GRAD, name, self.shapes[name], torch.float32)
-
-    def write(self, kind, name, tensor):
-        t = tensor.detach().to(self.device, torch.float32).contiguous()
-        if tuple(t.shape) != self.shapes[name]:
-            raise ValueError(f"{name}: expected {self.shapes[name]}, got {tuple(t.shape)}")
-        self.ctx.call("vt_head_write", *self._state(), kind, name.encode(), vp(t), t.numel() * 4, stream_ptr(self.device))
-        torch.cuda.current_stream(self.device).synchronize()        # (t may be freed when this returns)
+        self._call("clip", float(max_norm))
 
     def losses(self):
         """The loss ring, fp64 [HEAD_RING]: slot s holds loss_scale x loss of the last call whose step % HEAD_RING was s."""
         return self._read(_lib.HEAD_LOSS_RING, None, (_lib.HEAD_RING,), torch.float64)
 
-    def grad_norm(self):
-        """(total L2 norm, clip coefficient) of the last clip()."""
-        raw = self._read(_lib.HEAD_NORM, None, (16,), torch.uint8).numpy()
-        return float(raw[8:12].view(np.float32)[0]), float(raw[12:16].view(np.float32)[0])
-
     def state_dict(self):
         """The decoder's full state_dict with the trained head (export_state_dict)."""
-        return export_state_dict(self.decoder, self.parameter)
+        return export_state_dict(self.decoder, self.parameter, self.shapes)
 
 
 # ---- the attention decoder's front -------------------------------------------------------------------------------------------------
@@ -373,38 +399,28 @@ def front_trainable(decoder):
     return not plain and not cross
 
 
-class FrontTrainer:
+class FrontTrainer(_BlockTrainer):
     """Device state of the FRONT of an attention decoder (spatial_attention.*, feature_compress.*, self_attention_post.*; vt_front_* of
     the C ABI, csrc/train_front.hip) and the calls that train it.  `forward(latent, train=True)` runs BatchNorm on the batch's
     statistics (and updates the running ones) and drops softmax weights at `attention_dropout`; `backward(d_features)` belongs to the
     last training-mode forward and ADDS the gradients of every front tensor.  The channel max of the spatial attention sends its
-    gradient to the arg-max channel, the lowest index on a tie.  Cross-attention is not covered."""
+    gradient to the arg-max channel, the lowest index on a tie.  Cross-attention is not covered.  grad_norm() is that of the last
+    DecoderTrainer.clip()."""
+    PREFIX = "vt_front_"
 
     def __init__(self, decoder, attention_dropout=0.1, seed=0):
-        self.decoder = decoder
-        self.ctx = decoder._context()
-        self.device = next(decoder.parameters()).device
-        self.F = self.ctx.lib.vt_decoder_feature_dim(self.ctx.handle)
+        super().__init__(decoder, seed)
         self.heads = decoder._cfg[4]
         self.p = float(attention_dropout)
         if not 0.0 <= self.p < 1.0:
             raise ValueError(f"attention_dropout {attention_dropout} outside [0, 1)")
-        self.seed, self.calls, self.t = int(seed), 0, 0
-        self._bytes = self.ctx.lib.vt_front_state_bytes(self.ctx.handle)
-        if self._bytes == 0:
-            raise _lib.VTError("this decoder's front cannot be trained on the device: an attention decoder without cross-attention, "
-                               "latent_channels = 16 and attention_heads in {1, 2, 4, 8} is expected")
         sd = decoder.state_dict()
         self.shapes = {k: tuple(v.shape) for k, v in sd.items() if k.startswith(FRONT_PREFIXES) and k not in FRONT_BUFFERS}
         self.buffers = {k: tuple(sd[k].shape) for k in FRONT_BUFFERS}
-        self._buf = torch.empty(self._bytes + 256, dtype=torch.uint8, device=self.device)
-        self._ptr = (self._buf.data_ptr() + 255) // 256 * 256
         self._last = None
-        self.ctx.call("vt_front_init", ctypes.c_void_p(self._ptr), self._bytes, stream_ptr(self.device))
+        self._allocate("this decoder's front cannot be trained on the device: an attention decoder without cross-attention, "
+                       "latent_channels = 16 and attention_heads in {1, 2, 4, 8} is expected")
         self.write_buffer("feature_compress.1.num_batches_tracked", sd["feature_compress.1.num_batches_tracked"])
-
-    def _state(self):
-        return ctypes.c_void_p(self._ptr), self._bytes
 
     def _ws(self, B, h, w):
         need = self.ctx.lib.vt_front_workspace_bytes(self.ctx.handle, int(B), int(h), int(w))
@@ -420,9 +436,7 @@ class FrontTrainer:
         step = self.calls if step is None else int(step)
         out = torch.empty(B, self.F, dtype=torch.float32, device=self.device)
         mask = torch.empty(B, self.heads, 64, 64, dtype=torch.uint8, device=self.device) if return_mask and train else None
-        ws, need = self._ws(B, h, w)
-        self.ctx.call("vt_front_forward", *self._state(), vp(x), B, h, w, int(bool(train)), self.p, self.seed, step, vp(out), vp(mask), ws,
-                      need, stream_ptr(self.device))
+        self._call("forward", vp(x), B, h, w, int(bool(train)), self.p, self.seed, step, vp(out), vp(mask), *self._ws(B, h, w))
         self._last = (x, step) if train else None
         if train:
             self.calls = step + 1
@@ -436,90 +450,28 @@ class FrontTrainer:
         d = d_features.detach().to(self.device, torch.float32).contiguous()
         if tuple(d.shape) != (B, self.F):
             raise ValueError(f"expected d_features [{B}, {self.F}], got {tuple(d.shape)}")
-        ws, need = self._ws(B, h, w)
-        self.ctx.call("vt_front_backward", *self._state(), vp(x), vp(d), B, h, w, self.p, self.seed, step, ws, need, stream_ptr(self.device))
+        self._call("backward", vp(x), vp(d), B, h, w, self.p, self.seed, step, *self._ws(B, h, w))
         self._last = None
-
-    def step(self, lr, weight_decay=0.0, betas=ADAM_BETAS, eps=ADAM_EPS):
-        self.t += 1
-        self.ctx.call("vt_front_step", *self._state(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), self.t,
-                      stream_ptr(self.device))
-
-    def commit(self):
-        """Write the parameters, the running statistics and their fold into the decoder's device tables."""
-        self.ctx.call("vt_front_commit", *self._state(), stream_ptr(self.device))
-
-    def _read(self, kind, name, shape, dtype):
-        out = torch.empty(shape, dtype=dtype, pin_memory=True)
-        self.ctx.call("vt_front_read", *self._state(), kind, name.encode() if name else None, ctypes.c_void_p(out.data_ptr()),
-                      out.numel() * out.element_size(), stream_ptr(self.device))
-        torch.cuda.current_stream(self.device).synchronize()
-        return out.clone()
-
-    def parameter(self, name):
-        return self._read(_lib.HEAD_PARAM, name, self.shapes[name], torch.float32)
-
-    def gradient(self, name):
-        return self._read(_lib.HEAD_GRAD, name, self.shapes[name], torch.float32)
 
     def buffer(self, name):
         """feature_compress.1.running_mean / running_var (fp32 [8]) or num_batches_tracked (int64 scalar)."""
         tracked = FRONT_BUFFERS[name] == _lib.FRONT_BN_TRACKED
         return self._read(FRONT_BUFFERS[name], None, self.buffers[name], torch.int64 if tracked else torch.float32)
 
-    def write(self, kind, name, tensor):
-        t = tensor.detach().to(self.device, torch.float32).contiguous()
-        if tuple(t.shape) != self.shapes[name]:
-            raise ValueError(f"{name}: expected {self.shapes[name]}, got {tuple(t.shape)}")
-        self.ctx.call("vt_front_write", *self._state(), kind, name.encode(), vp(t), t.numel() * 4, stream_ptr(self.device))
-        torch.cuda.current_stream(self.device).synchronize()        # (t may be freed when this returns)
-
     def write_buffer(self, name, tensor):
         tracked = FRONT_BUFFERS[name] == _lib.FRONT_BN_TRACKED
         t = tensor.detach().to(self.device, torch.int64 if tracked else torch.float32).contiguous()
-        self.ctx.call("vt_front_write", *self._state(), FRONT_BUFFERS[name], None, vp(t), t.numel() * t.element_size(), stream_ptr(self.device))
+        self._call("write", FRONT_BUFFERS[name], None, vp(t), t.numel() * t.element_size())
         torch.cuda.current_stream(self.device).synchronize()
 
-    def grad_norm(self):
-        """(total L2 norm, clip coefficient) of the last DecoderTrainer.clip()."""
-        raw = self._read(_lib.HEAD_NORM, None, (16,), torch.uint8).numpy()
-        return float(raw[8:12].view(np.float32)[0]), float(raw[12:16].view(np.float32)[0])
-
-    def tensors(self):
-        """Every front entry of the state_dict: parameters and the three BatchNorm buffers, host tensors."""
-        out = {k: self.parameter(k) for k in self.shapes}
-        out.update({k: self.buffer(k) for k in self.buffers})
-        return out
+    def tensor(self, name):
+        """A front entry of the state_dict, parameter or BatchNorm buffer, as a host tensor."""
+        return self.buffer(name) if name in self.buffers else self.parameter(name)
 
     def state_dict(self):
         """The decoder's full state_dict with the trained front (the reference's keys, the three BatchNorm buffers included); the head's
         tensors are the decoder's own."""
-        trained = self.tensors()
-        return {k: (trained[k].to(v.dtype) if k in trained else v.detach().to("cpu")).clone() for k, v in self.decoder.state_dict().items()}
-
-    def state_bytes(self):
-        """The whole state block (for bit comparisons)."""
-        torch.cuda.current_stream(self.device).synchronize()
-        off = self._ptr - self._buf.data_ptr()
-        return self._buf[off:off + self._bytes].cpu()
-
-
-def export_full_state_dict(decoder, head, front):
-    """The decoder's state_dict with the head's and the front's tensors read from the device (the reference's keys and dtypes)."""
-    trained = front.tensors()
-    out = {}
-    for k, v in decoder.state_dict().items():
-        if k.startswith("classifier."):
-            t = head.parameter(k)
-        elif k in trained:
-            t = trained[k]
-        else:
-            out[k] = v.detach().to("cpu").clone()
-            continue
-        if tuple(t.shape) != tuple(v.shape):
-            raise ValueError(f"{k}: read {tuple(t.shape)}, the decoder holds {tuple(v.shape)}")
-        out[k] = t.detach().to("cpu", v.dtype).clone()
-    return out
+        return export_state_dict(self.decoder, self.tensor, [*self.shapes, *self.buffers])
 
 
 class DecoderTrainer:
@@ -537,25 +489,10 @@ class DecoderTrainer:
         return self.head.forward(self.front.forward(latent, train=False))
 
     def forward_backward(self, latent, labels, loss_scale=1.0, train=True, step=None, return_logits=False):
-        h = self.head
-        step = h.calls if step is None else int(step)
+        step = self.head.calls if step is None else int(step)
         feats = self.front.forward(latent, train=True, step=step)
-        y = labels.detach().to(self.device)
-        if y.dtype == torch.bool:
-            y = y.view(torch.uint8)
-        elif y.dtype not in (torch.float32, torch.uint8):
-            y = y.to(torch.float32)
-        y = y.contiguous()
-        B = feats.shape[0]
-        if tuple(y.shape) != (B, self.N):
-            raise ValueError(f"expected labels [{B}, {self.N}], got {tuple(y.shape)}")
-        logits = torch.empty(B, self.N, dtype=torch.float32, device=self.device) if return_logits else None
-        d_feats = torch.empty(B, self.F, dtype=torch.float32, device=self.device)
-        ws, need = h._ws(B)
-        self.ctx.call("vt_head_forward_backward_dx", *h._state(), vp(feats), vp(y), _lib.VT_U8 if y.dtype == torch.uint8 else _lib.VT_F32, B,
-                      h.loss_kind, h.alpha, h.gamma, vp(h.class_weights), float(loss_scale), int(bool(train)), h.dropout, h.seed, step,
-                      vp(logits), None, vp(d_feats), ws, need, stream_ptr(self.device))
-        h.calls = step + 1
+        out = self.head.forward_backward(feats, labels, loss_scale, train, step, return_logits, return_d_features=True)
+        logits, d_feats = out if return_logits else (None, out)
         self.front.backward(d_feats)
         return logits
 
@@ -577,4 +514,6 @@ class DecoderTrainer:
         return self.head.grad_norm()
 
     def state_dict(self):
-        return export_full_state_dict(self.decoder, self.head, self.front)
+        """The decoder's full state_dict with the head's and the front's tensors read from the device."""
+        return export_state_dict(self.decoder, lambda k: self.head.parameter(k) if k in self.head.shapes else self.front.tensor(k),
+                                 [*self.head.shapes, *self.front.shapes, *self.front.buffers])
