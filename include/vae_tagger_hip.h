@@ -312,8 +312,8 @@ double vt_encoder_flops(const vt_context* ctx, int H, int W);
  * (256 plain, 512 attention) whatever the latent's size; the HEAD is `classifier.*`: Linear -> LayerNorm -> (Leaky)ReLU -> Dropout
  * layers and Linear(256, N).  vt_decode_features runs the front alone (workspace: vt_decode_workspace_bytes); vt_head_forward on its
  * rows gives vt_decode_logits' bits.  With these calls alone the front is frozen (BatchNorm on its running statistics, no dropout), so
- * an image's feature row never changes and can be cached across epochs; the attention decoder's front is trained by vt_front_* below
- * (not its cross-attention, which has no backward).
+ * an image's feature row never changes and can be cached across epochs; the attention decoder's front is trained by vt_front_* and its
+ * cross-attention by vt_cross_* below.
  *
  * The trainer keeps everything in one caller-owned, 256-B aligned device block of vt_head_state_bytes(ctx) bytes (layout:
  * csrc/vt_train.h): fp32 parameters, gradients, Adam m and v, the gradient norm / clip coefficient, and a ring of VT_HEAD_RING fp64
@@ -363,10 +363,12 @@ int vt_head_write(vt_context* ctx, void* state, size_t state_bytes, int kind, co
 
 /* ---- training the attention decoder's front (csrc/train_front.hip) ------------------------------------------------------------
  * spatial_attention.*, feature_compress.* and self_attention_post.* of AttentionClassificationDecoder at latent_channels = 16, heads in
- * {1, 2, 4, 8}, each of spatial and self attention on or off.  Cross-attention is NOT covered: vt_front_state_bytes returns 0 with it
- * (and for the plain decoder).  Same conventions as the head trainer: a caller-owned, 256-B aligned state block (layout: csrc/vt_train.h),
- * fp32 storage, fp64 statistics and norm partials, no atomics, every sum in an order fixed by the shapes, no host synchronisation.  The
- * gradient with respect to the latent is not computed (the encoder is frozen).
+ * {1, 2, 4, 8}, each of spatial and self attention on or off (vt_front_state_bytes returns 0 otherwise, and for the plain decoder).  On a
+ * decoder with cross-attention these calls train the same 17 tensors and vt_front_forward yields, in both modes, the rows cross-attention
+ * reads (modules.py:448), not the head's feature rows: vt_cross_* below is the piece between the two.  Same conventions as the head
+ * trainer: a caller-owned, 256-B aligned state block (layout: csrc/vt_train.h), fp32 storage, fp64 statistics and norm partials, no
+ * atomics, every sum in an order fixed by the shapes, no host synchronisation.  The gradient with respect to the latent is not
+ * computed (the encoder is frozen).
  *   vt_front_init      parameters and BatchNorm running statistics <- the context's tables; gradients, m, v, num_batches_tracked <- 0
  *   vt_front_forward   train = 0: the inference front on the state's parameters and running statistics (right after init or commit:
  *                      vt_decode_features' bits).  train != 0: BatchNorm on the batch's statistics (biased variance over B h w, fp64
@@ -407,6 +409,40 @@ int vt_head_forward_backward_dx(vt_context* ctx, void* state, size_t state_bytes
                                 size_t workspace_bytes, void* stream);
 int vt_train_clip(vt_context* ctx, void* head_state, size_t head_state_bytes, void* front_state, size_t front_state_bytes, float max_norm,
                   void* stream);
+
+/* ---- training the attention decoder's cross-attention (csrc/train_cross.hip) ---------------------------------------------------
+ * query_generator.* and cross_attention.* (ten tensors, 530 176 parameters; modules.py:105-124, :451-459): the piece between the rows
+ * x [B][512] vt_front_forward yields on a decoder with cross-attention and the feature rows the head reads.  A third caller-owned,
+ * 256-B aligned state block with the conventions above (layout: csrc/vt_train.h).  vt_cross_state_bytes is non-zero exactly for an
+ * attention decoder with cross-attention, latent_channels = 16 and heads in {1, 2, 4, 8}; B <= 1024.  The piece has no dropout and no
+ * normalisation layer: training and eval forward are the same function.
+ *   vt_cross_init      parameters <- the context's tables; gradients, m, v <- 0
+ *   vt_cross_forward   features_out = x + mean(out_proj(attention(q_proj(q), k / v of x's 64 tokens)) + q), q = query_generator(x): the
+ *                      inference launches on the state's tensors (after the front's eval forward: vt_decode_features' bits).
+ *                      features_out may not alias x_in.  The workspace (vt_cross_workspace_bytes) keeps what the backward of the SAME
+ *                      batch reads: pass the same x_in and workspace to vt_cross_backward before the next forward.
+ *   vt_cross_backward  d_features [B][512] -> gradients of all ten tensors, ADDED into the state, and d_x_out [B][512] = d loss / d x
+ *                      (d_features + the piece's own part), which vt_front_backward takes as its d_features.  d_x_out may be d_features.
+ *   vt_cross_step      AdamW as vt_head_step.   vt_cross_commit   the context's tables <- the state
+ *   vt_cross_read / vt_cross_write   by state-dict key; kinds VT_HEAD_PARAM / GRAD / ADAM_M / ADAM_V, and VT_HEAD_NORM (read only)
+ *   vt_train_clip3     vt_train_clip over three blocks: norm^2 = the head's partials in order, then the front's, then the cross
+ *                      block's; the same { norm^2, norm, coef } is written to all three
+ */
+size_t vt_cross_state_bytes(const vt_context* ctx);
+size_t vt_cross_workspace_bytes(const vt_context* ctx, int B);
+int vt_cross_init(vt_context* ctx, void* state, size_t state_bytes, void* stream);
+int vt_cross_forward(vt_context* ctx, void* state, size_t state_bytes, const float* x_in /* [B][512] */, int B, float* features_out /* [B][512] */,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int vt_cross_backward(vt_context* ctx, void* state, size_t state_bytes, const float* x_in, const float* d_features /* [B][512] */, int B,
+                      float* d_x_out /* [B][512] */, void* workspace, size_t workspace_bytes, void* stream);
+int vt_cross_step(vt_context* ctx, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, double weight_decay,
+                  long long t, void* stream);
+int vt_cross_commit(vt_context* ctx, const void* state, size_t state_bytes, void* stream);
+int vt_cross_read(vt_context* ctx, const void* state, size_t state_bytes, int kind, const char* name, void* out, size_t out_bytes, void* stream);
+int vt_cross_write(vt_context* ctx, void* state, size_t state_bytes, int kind, const char* name, const void* src, size_t src_bytes,
+                   void* stream);
+int vt_train_clip3(vt_context* ctx, void* head_state, size_t head_state_bytes, void* front_state, size_t front_state_bytes, void* cross_state,
+                   size_t cross_state_bytes, float max_norm, void* stream);
 
 /* ---- options ---------------------------------------------------------------------------------
  * flag 0: 1 (default) = 3x3 stride-1 convs use the halo-tile kernel (conv3x3_halo.hip),

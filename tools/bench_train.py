@@ -23,11 +23,17 @@ d loss / d features, front backward, one clip over both blocks, AdamW on both) f
 against the head-only step (train.HeadTrainer on cached feature rows: the step the trainer had before the front could be trained) and
 against the same full step in torch eager on the same GPU -- the three interleaved in one process, median round reported.
 
+    python tools/bench_train.py --front --cross [--classes 10000] [--batch 16] [--latent 128] [--steps 50] [--rounds 5]
+
+The full step of a decoder WITH cross-attention (front, cross-attention, head; one clip over three blocks, AdamW on three) against the
+full step of the decoder without it and against the same cross-attention step in torch eager, interleaved in one process as above.
+
     python tools/bench_train.py --cli --train_front [--images 256] ...
 
 times `train_decoder --train_front` (attention decoder from scratch): epoch 2's rate from the latent cache against epoch 1's."""
 import argparse
 import json
+import math
 import os
 import statistics
 import sys
@@ -54,12 +60,15 @@ def torch_head(sd, plain, rates, device):
 
 
 class TorchAttentionDecoder(torch.nn.Module):
-    """AttentionClassificationDecoder (spatial + self attention, no cross-attention) in torch, for the eager comparison."""
+    """AttentionClassificationDecoder (spatial + self attention, cross-attention on request) in torch, for the eager comparison."""
 
-    def __init__(self, N, heads=8, p=0.1):
+    def __init__(self, N, heads=8, p=0.1, cross=False):
         import torch.nn as nn
         super().__init__()
-        self.heads = heads
+        self.heads, self.cross = heads, cross
+        if cross:
+            self.qg, self.cq, self.co = nn.Linear(512, 512), nn.Linear(512, 256), nn.Linear(256, 512)
+            self.ck, self.cv = nn.Linear(8, 256), nn.Linear(8, 256)
         self.ca = nn.Sequential(nn.Conv2d(16, 2, 1, bias=False), nn.ReLU(), nn.Conv2d(2, 16, 1, bias=False))
         self.sp = nn.Conv2d(2, 1, 7, padding=3, bias=False)
         self.compress = nn.Sequential(nn.Conv2d(16, 8, 3, 1, 1), nn.BatchNorm2d(8), nn.ReLU(), nn.AdaptiveAvgPool2d((8, 8)))
@@ -80,7 +89,17 @@ class TorchAttentionDecoder(torch.nn.Module):
         q, k, v = (m(tn).view(B, 64, self.heads, hd).transpose(1, 2) for m in (self.q, self.k, self.v))
         a = self.drop(torch.softmax(q @ k.transpose(-2, -1) / hd ** 0.5, dim=-1))
         o = self.o((a @ v).transpose(1, 2).reshape(B, 64, 8)) + t
-        return self.classifier(o.transpose(1, 2).reshape(B, 512))
+        flat = o.transpose(1, 2).reshape(B, 512)
+        if self.cross:
+            hd = 256 // self.heads
+            query = self.qg(flat)
+            tok = flat.view(B, 8, 64).transpose(1, 2)
+            u = self.cq(query).view(B, 1, self.heads, hd).transpose(1, 2)
+            k, v = (m(tok).view(B, 64, self.heads, hd).transpose(1, 2) for m in (self.ck, self.cv))
+            w = torch.softmax(u @ k.transpose(-2, -1) / hd ** 0.5, dim=-1)
+            att = self.co((w @ v).transpose(1, 2).reshape(B, 256)) + query
+            flat = flat + att.mean(dim=1, keepdim=True)
+        return self.classifier(flat)
 
 
 def front_mode(args):
@@ -94,11 +113,16 @@ def front_mode(args):
     dec.load_state_dict(sd, strict=False)
     dec = dec.to(dev).eval()
     full, head = DecoderTrainer(dec), HeadTrainer(dec)
+    full_cross = None
+    if args.cross:
+        dec_x = AttentionClassificationDecoder(16, L, L, N, True, True, True, 8)
+        dec_x.load_state_dict(synth.synth_state_dict(synth.attention_decoder_manifest(N, 16, True, True, True), seed=1), strict=False)
+        full_cross = DecoderTrainer(dec_x.to(dev).eval())
     g = torch.Generator().manual_seed(0)
     lat = (0.1 + 0.8 * torch.randn(B, 16, L, L, generator=g)).to(dev)
     y = (torch.rand(B, N, generator=g) < 0.01).float().to(dev)
     feats = head.features(lat)
-    ref = TorchAttentionDecoder(N).to(dev).train()
+    ref = TorchAttentionDecoder(N, cross=args.cross).to(dev).train()
     opt = torch.optim.AdamW(ref.parameters(), lr=1e-3, weight_decay=1e-6)
     loss_fn = torch.nn.BCEWithLogitsLoss()
 
@@ -107,6 +131,12 @@ def front_mode(args):
             full.forward_backward(lat, y)
             full.clip(1.0)
             full.step(1e-3, 1e-6)
+
+    def step_full_cross(n):
+        for _ in range(n):
+            full_cross.forward_backward(lat, y)
+            full_cross.clip(1.0)
+            full_cross.step(1e-3, 1e-6)
 
     def step_head(n):
         for _ in range(n):
@@ -130,6 +160,8 @@ def front_mode(args):
         return e0.elapsed_time(e1) * 1e3 / args.steps            # microseconds per step
 
     fns = {"full": step_full, "head_only": step_head, "torch_full": step_torch}
+    if args.cross:
+        fns = {"full_cross": step_full_cross, "full": step_full, "torch_full_cross": step_torch}
     for fn in fns.values():
         fn(10)
     torch.cuda.synchronize()
@@ -138,6 +170,14 @@ def front_mode(args):
         for k, fn in fns.items():
             times[k].append(timed(fn))
     med = {k: statistics.median(v) for k, v in times.items()}
+    if args.cross:
+        out = {"bench": "train_step_cross", "classes": N, "batch": B, "latent": [L, L], "steps": args.steps, "rounds": args.rounds,
+               "full_cross_us_per_step": med["full_cross"], "full_us_per_step": med["full"], "torch_full_cross_us_per_step": med["torch_full_cross"],
+               "us_min_max": {k: [min(v), max(v)] for k, v in times.items()}, "full_cross_over_full": med["full_cross"] / med["full"],
+               "torch_over_full_cross": med["torch_full_cross"] / med["full_cross"], "cross_parameters": sum(math.prod(v) for v in full_cross.cross.shapes.values()),
+               "latent_batch_bytes": lat.numel() * 4}
+        print(json.dumps(out))
+        return out
     out = {"bench": "train_step_front", "classes": N, "batch": B, "latent": [L, L], "steps": args.steps, "rounds": args.rounds,
            "full_us_per_step": med["full"], "head_only_us_per_step": med["head_only"], "torch_full_us_per_step": med["torch_full"],
            "us_min_max": {k: [min(v), max(v)] for k, v in times.items()}, "full_over_head_only": med["full"] / med["head_only"],
@@ -221,6 +261,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cli", action="store_true", help="time the training CLI's epochs against the evaluate CLI on the same files")
     ap.add_argument("--front", action="store_true", help="time the full attention-decoder step against the head-only step and torch eager")
+    ap.add_argument("--cross", action="store_true", help="with --front: the full step WITH cross-attention against the step without it and torch eager")
     ap.add_argument("--train_front", action="store_true", help="with --cli: time train_decoder --train_front (epoch 2 from the latent cache)")
     ap.add_argument("--latent", type=int, default=128, help="with --front: the latent's height and width")
     ap.add_argument("--images", type=int, default=256)

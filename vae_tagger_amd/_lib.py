@@ -114,6 +114,16 @@ PROTOTYPES = {
     "vt_head_forward_backward_dx": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _i, _i, _c.c_double, _c.c_double, _vp, _c.c_double, _i,
                                          _c.POINTER(_f), _c.c_ulonglong, _c.c_ulonglong, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vt_train_clip": (_i, [_vp, _vp, _sz, _vp, _sz, _f, _vp]),
+    "vt_cross_state_bytes": (_sz, [_vp]),
+    "vt_cross_workspace_bytes": (_sz, [_vp, _i]),
+    "vt_cross_init": (_i, [_vp, _vp, _sz, _vp]),
+    "vt_cross_forward": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp]),
+    "vt_cross_backward": (_i, [_vp, _vp, _sz, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "vt_cross_step": (_i, [_vp, _vp, _sz, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _ll, _vp]),
+    "vt_cross_commit": (_i, [_vp, _vp, _sz, _vp]),
+    "vt_cross_read": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
+    "vt_cross_write": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
+    "vt_train_clip3": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _f, _vp]),
     "vt_encoder_flops": (_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),

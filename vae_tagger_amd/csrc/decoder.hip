@@ -518,6 +518,20 @@ hipError_t vt_dec_sgate(const float* sp, const float* w, int B, int H, int W, fl
     return hipSuccess;
 }
 
+// cross-attention over the rows x [B][512] the front produced (modules.py:451-459): query = query_generator(x) -> cq;
+// attended = out_proj(attn(q_proj(query) -> cqp, k / v(x as 64 tokens of 8)) -> co) + query -> cat; feat += mean(attended).  `feat` holds
+// x on entry (it may be x itself: every read of x is queued before the last launch writes feat).  train_cross.hip's forward runs the
+// same launches: same bits.
+hipError_t vt_dec_cross(const DecoderWeights& w, const float* x, int B, float* cq, float* cqp, float* co, float* cat, float* feat, hipStream_t s) {
+    hipLaunchKernelGGL(dec_linear_kernel, dim3(512 / 4), dim3(256), 0, s, x, w.qg_w, w.qg_b, cq, B, 512, 512); CKL();
+    hipLaunchKernelGGL(dec_linear_kernel, dim3(256 / 4), dim3(256), 0, s, cq, w.cx_q_w, w.cx_q_b, cqp, B, 512, 256); CKL();
+    hipLaunchKernelGGL(dec_cross_attn_kernel, dim3(B), dim3(64), 0, s, cqp, x, w.cx_k_w, w.cx_k_b, w.cx_v_w, w.cx_v_b, 8, 256, w.heads, co); CKL();
+    hipLaunchKernelGGL(dec_linear_kernel, dim3(512 / 4), dim3(256), 0, s, co, w.cx_o_w, w.cx_o_b, cat, B, 256, 512); CKL();
+    hipLaunchKernelGGL(dec_add_kernel, dim3((B * 512 + 255) / 256), dim3(256), 0, s, cat, cq, (long long)B * 512); CKL();
+    hipLaunchKernelGGL(dec_add_rowmean_kernel, dim3(B), dim3(256), 0, s, feat, cat, 512, 512); CKL();
+    return hipSuccess;
+}
+
 // front: latent -> the feature row [B][F] the classifier reads (plain: the 4x4 pool; attention: spatial attention, compress,
 // self- / cross-attention), written to `feat`; `ws` holds the front's scratch.
 hipError_t vt_decoder_front(const DecoderWeights& w, const float* latent, int B, int H, int Wd, float* ws, float* feat, hipStream_t s) {
@@ -556,16 +570,7 @@ hipError_t vt_decoder_front(const DecoderWeights& w, const float* latent, int B,
         else hipLaunchKernelGGL((dec_self_attn_kernel<0, 0>), dim3(B), dim3(64), 0, s, feat, w.sa, CO, w.heads);
         CKL();
     }
-    if (w.use_cross) {
-        // query = query_generator(flat); attended = out_proj(attn(q_proj(query), k/v(spatial))) + query;
-        // flat += mean(attended)   (modules.py:451-459)
-        hipLaunchKernelGGL(dec_linear_kernel, dim3(512 / 4), dim3(256), 0, s, feat, w.qg_w, w.qg_b, cq, B, CO * 64, 512); CKL();
-        hipLaunchKernelGGL(dec_linear_kernel, dim3(256 / 4), dim3(256), 0, s, cq, w.cx_q_w, w.cx_q_b, cqp, B, 512, 256); CKL();
-        hipLaunchKernelGGL(dec_cross_attn_kernel, dim3(B), dim3(64), 0, s, cqp, feat, w.cx_k_w, w.cx_k_b, w.cx_v_w, w.cx_v_b, CO, 256, w.heads, co); CKL();
-        hipLaunchKernelGGL(dec_linear_kernel, dim3(512 / 4), dim3(256), 0, s, co, w.cx_o_w, w.cx_o_b, cat, B, 256, 512); CKL();
-        hipLaunchKernelGGL(dec_add_kernel, dim3((B * 512 + 255) / 256), dim3(256), 0, s, cat, cq, (long long)B * 512); CKL();
-        hipLaunchKernelGGL(dec_add_rowmean_kernel, dim3(B), dim3(256), 0, s, feat, cat, CO * 64, 512); CKL();
-    }
+    if (w.use_cross) CK(vt_dec_cross(w, feat, B, cq, cqp, co, cat, feat, s));
     return hipSuccess;
 }
 

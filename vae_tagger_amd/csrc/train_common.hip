@@ -1,6 +1,6 @@
 // What the trainers share (vt_train.h: TrainBlock): the kernels that work on any block -- the gradient norm and clip coefficient, the
 // gradient scale, AdamW -- and one host implementation of the state check, clip, step, the kind -> byte range dispatch of the four
-// parameter arrays and the scalars, and the read / write copies.  train_head.hip and train_front.hip call these with their own layout
+// parameter arrays and the scalars, and the read / write copies.  train_head.hip, train_front.hip and train_cross.hip call these with their own layout
 // and the name of the entry point they were reached through.  The conventions are theirs: fp32 storage, fp64 reductions in an order
 // fixed by the shapes, no atomics, nothing synchronises the host.
 #include <math.h>
@@ -13,25 +13,29 @@ using namespace vt;
 
 namespace {
 
-// one workgroup: the squared-norm partials of block a in index order, then block b's (n_b may be 0: th + 0.0 has th's bits, th >= 0)
-// -> one norm and coef = min(1, max_norm / (norm + 1e-6))  (clip_grad_norm_), written to both blocks (sc_b may be sc_a)
-__global__ __launch_bounds__(256) void train_clip_kernel(const double* __restrict__ part_a, int n_a, const double* __restrict__ part_b, int n_b,
-                                                         float max_norm, TrainScalars* sc_a, TrainScalars* sc_b) {
+// one workgroup: the squared-norm partials of block 0 in index order, then block 1's, ... (an unused entry has n = 0: t + 0.0 has t's
+// bits, t >= 0) -> one norm and coef = min(1, max_norm / (norm + 1e-6))  (clip_grad_norm_), written to every block
+struct ClipBlocks { const double* part[VT_CLIP_MAX_BLOCKS]; int n[VT_CLIP_MAX_BLOCKS]; TrainScalars* sc[VT_CLIP_MAX_BLOCKS]; int count; };
+__global__ __launch_bounds__(256) void train_clip_kernel(ClipBlocks blocks, float max_norm) {
 #pragma clang fp contract(off)
     __shared__ double red[4];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n_a; i += 256) a += part_a[i];
-    const double th = block_sum_256d(a, red);
-    a = 0.0;
-    for (int i = threadIdx.x; i < n_b; i += 256) a += part_b[i];
-    const double tf = block_sum_256d(a, red);
+    double total = 0.0;
+#pragma unroll
+    for (int k = 0; k < VT_CLIP_MAX_BLOCKS; ++k) {
+        const double* __restrict__ part = blocks.part[k];
+        double a = 0.0;
+        for (int i = threadIdx.x; i < blocks.n[k]; i += 256) a += part[i];
+        const double t = block_sum_256d(a, red);
+        total = k ? total + t : t;
+    }
     if (threadIdx.x == 0) {
-        const double total = th + tf;
         const float norm = (float)sqrt(total);
         const float coef = max_norm / (norm + 1e-6f);
         TrainScalars v;
         v.sq = total; v.norm = norm; v.coef = coef < 1.0f ? coef : 1.0f;
-        *sc_a = v; *sc_b = v;
+#pragma unroll
+        for (int k = 0; k < VT_CLIP_MAX_BLOCKS; ++k)
+            if (k < blocks.count) *blocks.sc[k] = v;
     }
 }
 
@@ -80,22 +84,23 @@ int vt_train_check(vt_context* c, const char* who, const TrainBlock& b, const vo
     return VT_OK;
 }
 
-int vt_train_clip_blocks(vt_context* c, const char* who, const TrainBlock& a, void* sa, const TrainBlock* b, void* sb, float max_norm,
-                         hipStream_t s) {
+int vt_train_clip_blocks(vt_context* c, const char* who, const TrainBlockRef* blocks, int n, float max_norm, hipStream_t s) {
     if (!(max_norm > 0.f)) return c->fail(VT_ERR_INVALID, "%s: max_norm = %g must be positive", who, max_norm);
-    char* pa = (char*)sa;
-    char* pb = b ? (char*)sb : pa;
-    const TrainBlock& bb = b ? *b : a;
-    TrainScalars* sca = (TrainScalars*)(pa + a.scalars);
-    TrainScalars* scb = (TrainScalars*)(pb + bb.scalars);
-    hipLaunchKernelGGL(train_clip_kernel, dim3(1), dim3(256), 0, s, (const double*)(pa + a.normpart), a.norm_parts,
-                       (const double*)(pb + bb.normpart), b ? bb.norm_parts : 0, max_norm, sca, scb);
+    if (n < 1 || n > VT_CLIP_MAX_BLOCKS) return c->fail(VT_ERR_INVALID, "%s: %d blocks, 1 to %d expected", who, n, VT_CLIP_MAX_BLOCKS);
+    ClipBlocks k;
+    for (int i = 0; i < VT_CLIP_MAX_BLOCKS; ++i) {
+        const TrainBlockRef& b = blocks[i < n ? i : 0];
+        k.part[i] = (const double*)((char*)b.state + b.layout->normpart);
+        k.n[i] = i < n ? b.layout->norm_parts : 0;
+        k.sc[i] = (TrainScalars*)((char*)b.state + b.layout->scalars);
+    }
+    k.count = n;
+    hipLaunchKernelGGL(train_clip_kernel, dim3(1), dim3(256), 0, s, k, max_norm);
     HIPCK(c, hipGetLastError(), who);
-    const long long a4 = (long long)(a.P / 4), b4 = (long long)(bb.P / 4);
-    hipLaunchKernelGGL(train_scale_kernel, dim3((unsigned)((a4 + 255) / 256)), dim3(256), 0, s, (float4*)(pa + a.grads), a4, sca);
-    HIPCK(c, hipGetLastError(), who);
-    if (b) {
-        hipLaunchKernelGGL(train_scale_kernel, dim3((unsigned)((b4 + 255) / 256)), dim3(256), 0, s, (float4*)(pb + bb.grads), b4, scb);
+    for (int i = 0; i < n; ++i) {
+        const long long n4 = (long long)(blocks[i].layout->P / 4);
+        hipLaunchKernelGGL(train_scale_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
+                           (float4*)((char*)blocks[i].state + blocks[i].layout->grads), n4, k.sc[i]);
         HIPCK(c, hipGetLastError(), who);
     }
     return VT_OK;

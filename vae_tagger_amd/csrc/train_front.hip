@@ -1,6 +1,7 @@
 // Training of the attention decoder's FRONT on the device: spatial_attention.*, feature_compress.* and self_attention_post.* of
 // AttentionClassificationDecoder (modules.py:36-47, :66-91, :377-382) at latent_channels = 16, heads in {1, 2, 4, 8}, each of spatial
-// and self attention on or off; cross-attention is not covered (vt_front_state_bytes returns 0 with it).  One caller-owned state block
+// and self attention on or off.  On a decoder with cross-attention the front ends in the rows cross-attention reads (modules.py:448),
+// in both modes; query_generator.* and cross_attention.* are train_cross.hip's.  One caller-owned state block
 // (vt_train.h), the head trainer's conventions: fp32 storage; fp64 statistics and norm partials; no atomics; every sum in an order
 // fixed by the shapes; nothing synchronises the host.  The gradient with respect to the latent is not computed (the encoder is frozen).
 // State check, AdamW step, the parameter kinds of read / write and the scalars are train_common.hip's; this file keeps the front's
@@ -117,13 +118,18 @@ FRONT_KERNEL(256) void front_bn_stats_kernel(const float* __restrict__ z, int HW
     chunk_sums_16(v, part + ((long long)b * gridDim.x + blockIdx.x) * 16);
 }
 
-// eval-mode fold of BatchNorm, as vt_decoder_finalize computes it on the host (fp32): scale = gamma / sqrt(var + eps), shift = beta - mean scale
+// eval-mode fold of BatchNorm, as vt_decoder_finalize computes it on the host (fp32): scale = gamma / sqrt(var + eps), shift = beta - mean scale.
+// The host rounds the product mean scale before it subtracts.  The pragma alone does not keep the device from fusing the two into one
+// multiply-add (the build's -ffp-contract=fast lets the backend fuse whatever the source says), which made the shift differ by an ulp
+// from the one a decoder loaded from the trainer's checkpoint computes; the empty asm pins the rounded product in a register.
 __device__ __forceinline__ void bn_fold_one(const float* __restrict__ params, float* __restrict__ bn, int o) {
 #pragma clang fp contract(off)
     const float inv = 1.0f / sqrtf(bn[8 + o] + 1e-5f);
     const float sc = params[VT_FRONT_TABLE[VT_FT_BNW].off + o] * inv;
+    float prod = bn[o] * sc;
+    asm volatile("" : "+v"(prod));
     bn[16 + o] = sc;
-    bn[24 + o] = params[VT_FRONT_TABLE[VT_FT_BNB].off + o] - bn[o] * sc;
+    bn[24 + o] = params[VT_FRONT_TABLE[VT_FT_BNB].off + o] - prod;
 }
 FRONT_KERNEL(64) void front_bn_fold_kernel(const float* __restrict__ params, float* __restrict__ bn) {
     if (threadIdx.x < 8) bn_fold_one(params, bn, threadIdx.x);
@@ -701,7 +707,7 @@ FRONT_KERNEL(256) void front_reduce_kernel(const float* __restrict__ part, int n
 int front_check(vt_context* c, const char* who, const void* state, size_t state_bytes, FrontLayout* out) {
     if (!c->dec_finalized) return c->fail(VT_ERR_STATE, "%s: decoder weights not finalized", who);
     if (!vt_front_trainable(c->dec))
-        return c->fail(VT_ERR_INVALID, "%s: the front of this decoder cannot be trained on the device (attention decoder without cross-attention, "
+        return c->fail(VT_ERR_INVALID, "%s: the front of this decoder cannot be trained on the device (attention decoder at latent_channels 16, "
                                        "heads in {1, 2, 4, 8} expected)", who);
     *out = vt_front_layout(c->dec);
     return vt_train_check(c, who, *out, state, state_bytes);
@@ -790,7 +796,8 @@ int vt_front_init(vt_context* c, void* state, size_t state_bytes, void* stream) 
     HIPCK(c, hipMemcpyAsync(bn + 8, c->dec.bn_var, 32, hipMemcpyDeviceToDevice, s), "front_init copy");
     HIPCK(c, hipMemcpyAsync(bn + 16, c->dec.bn_scale, 32, hipMemcpyDeviceToDevice, s), "front_init copy");
     HIPCK(c, hipMemcpyAsync(bn + 24, c->dec.bn_shift, 32, hipMemcpyDeviceToDevice, s), "front_init copy");
-    return vt_train_clip_blocks(c, "vt_front_init", l, st, nullptr, nullptr, 1.0f, s);     // over the zeroed block: norm 0, coefficient 1
+    const TrainBlockRef blocks[1] = {{&l, st}};
+    return vt_train_clip_blocks(c, "vt_front_init", blocks, 1, 1.0f, s);     // over the zeroed block: norm 0, coefficient 1
 }
 
 int vt_front_commit(vt_context* c, const void* state, size_t state_bytes, void* stream) {
@@ -835,6 +842,7 @@ int vt_front_forward(vt_context* c, void* state, size_t state_bytes, const float
         for (int i = 0; i < VT_FRONT_TENSORS; ++i)
             if (l.present(i)) *front_ctx_slot(d, i) = T(i);
         d.bn_scale = bn + 16; d.bn_shift = bn + 24;
+        d.use_cross = 0;                              // the front ends in front of cross-attention (vt_cross_forward runs that piece)
         HIPCK(c, vt_decoder_front(d, latent, B, h, w, (float*)(wsb + k.eval), features_out, s), "decoder_front");
         return VT_OK;
     }

@@ -351,7 +351,8 @@ int vt_head_init(vt_context* c, void* state, size_t state_bytes, void* stream) {
     for (int i = 0; i < l.ntensors; ++i)
         HIPCK(c, hipMemcpyAsync((float*)(st + l.params) + l.t[i].off, head_ctx_tensor(c->dec, l.t[i]), 4 * l.t[i].numel, hipMemcpyDeviceToDevice, s),
               "head_init copy");
-    return vt_train_clip_blocks(c, "vt_head_init", l, st, nullptr, nullptr, 1.0f, s);      // over the zeroed block: norm 0, coefficient 1
+    const TrainBlockRef blocks[1] = {{&l, st}};
+    return vt_train_clip_blocks(c, "vt_head_init", blocks, 1, 1.0f, s);      // over the zeroed block: norm 0, coefficient 1
 }
 
 int vt_head_commit(vt_context* c, const void* state, size_t state_bytes, void* stream) {
@@ -480,7 +481,24 @@ int vt_train_clip(vt_context* c, void* head_state, size_t head_bytes, void* fron
     if (!vt_front_trainable(c->dec)) return c->fail(VT_ERR_INVALID, "vt_train_clip: this decoder's front is not trainable");
     const FrontLayout f = vt_front_layout(c->dec);
     VTCK(vt_train_check(c, "vt_train_clip (front)", f, front_state, front_bytes));
-    return vt_train_clip_blocks(c, "vt_train_clip", l, head_state, &f, front_state, max_norm, (hipStream_t)stream);
+    const TrainBlockRef blocks[2] = {{&l, head_state}, {&f, front_state}};
+    return vt_train_clip_blocks(c, "vt_train_clip", blocks, 2, max_norm, (hipStream_t)stream);
+}
+
+// the same over the head's, the front's and the cross-attention's gradients
+int vt_train_clip3(vt_context* c, void* head_state, size_t head_bytes, void* front_state, size_t front_bytes, void* cross_state, size_t cross_bytes,
+                   float max_norm, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    HeadLayout l;
+    VTCK(head_check(c, "vt_train_clip3", head_state, head_bytes, &l));
+    if (!vt_cross_trainable(c->dec)) return c->fail(VT_ERR_INVALID, "vt_train_clip3: this decoder has no trainable cross-attention");
+    const FrontLayout f = vt_front_layout(c->dec);
+    const CrossLayout x = vt_cross_layout(c->dec);
+    VTCK(vt_train_check(c, "vt_train_clip3 (front)", f, front_state, front_bytes));
+    VTCK(vt_train_check(c, "vt_train_clip3 (cross)", x, cross_state, cross_bytes));
+    const TrainBlockRef blocks[3] = {{&l, head_state}, {&f, front_state}, {&x, cross_state}};
+    return vt_train_clip_blocks(c, "vt_train_clip3", blocks, 3, max_norm, (hipStream_t)stream);
 }
 
 int vt_head_clip(vt_context* c, void* state, size_t state_bytes, float max_norm, void* stream) {
@@ -488,7 +506,8 @@ int vt_head_clip(vt_context* c, void* state, size_t state_bytes, float max_norm,
     DeviceGuard guard(c);
     HeadLayout l;
     VTCK(head_check(c, "vt_head_clip", state, state_bytes, &l));
-    return vt_train_clip_blocks(c, "vt_head_clip", l, state, nullptr, nullptr, max_norm, (hipStream_t)stream);
+    const TrainBlockRef blocks[1] = {{&l, state}};
+    return vt_train_clip_blocks(c, "vt_head_clip", blocks, 1, max_norm, (hipStream_t)stream);
 }
 
 int vt_head_step(vt_context* c, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, double weight_decay, long long t,

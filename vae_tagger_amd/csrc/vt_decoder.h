@@ -41,6 +41,9 @@ hipError_t vt_dec_ln_act(float* y, const float* g, const float* b, int rows, int
 hipError_t vt_dec_pool(const float* x, int B, int C, int HW, float* pool, hipStream_t s);
 hipError_t vt_dec_gate(const float* pool, const float* w0, const float* w2, int B, int C, int R, float* gate, hipStream_t s);
 hipError_t vt_dec_sgate(const float* sp, const float* w, int B, int H, int W, float* sg, hipStream_t s);
+// the cross-attention piece over the front's rows x [B][512], as vt_decoder_front launches it (train_cross.hip's forward runs the same
+// launches: same bits); feat holds x on entry (or is x) and ends as the feature rows; cq / cqp / co keep q, q_proj(q) and the attention output
+hipError_t vt_dec_cross(const DecoderWeights& w, const float* x, int B, float* cq, float* cqp, float* co, float* cat, float* feat, hipStream_t s);
 // vt_decoder_forward = front (latent -> feature rows [B][dims[0]]) + head (feature rows -> logits)
 hipError_t vt_decoder_front(const DecoderWeights& w, const float* latent_nchw, int B, int H, int W, float* ws, float* feat, hipStream_t s);
 hipError_t vt_decoder_head(const DecHeadShape& h, const DecHeadParams& p, const float* feat, int B, float* hbuf, float* logits, hipStream_t s);

@@ -1,5 +1,6 @@
 // The trainers: what every caller-owned state block has and the host layer over it (train_common.hip), then the layouts of the
-// classifier head's block and per-call workspace and the dropout generator (train_head.hip), then the front's (train_front.hip).
+// classifier head's block and per-call workspace and the dropout generator (train_head.hip), then the front's (train_front.hip) and
+// the cross-attention's (train_cross.hip).
 // These tables are the only place a layout is written: vae_tagger_amd/train.py goes through vt_*_read / vt_*_write by kind and name
 // and mirrors nothing but the 16 bytes of TrainScalars (grad_norm).
 #pragma once
@@ -23,9 +24,11 @@ struct TrainBlock {
 };
 // Host layer of train_common.hip; `who` is the entry point the caller was reached through (error messages name it).
 int vt_train_check(vt_context* c, const char* who, const TrainBlock& b, const void* state, size_t state_bytes);   // null, alignment, size
-// clip_grad_norm_ over block a, or over a and b together (b may be null): one norm and one coefficient, written to every block
-int vt_train_clip_blocks(vt_context* c, const char* who, const TrainBlock& a, void* sa, const TrainBlock* b, void* sb, float max_norm,
-                         hipStream_t s);
+// clip_grad_norm_ over n blocks together (1 <= n <= VT_CLIP_MAX_BLOCKS): the squared-norm partials of block 0 in index order, then
+// block 1's, ...; one norm and one coefficient, written to every block
+constexpr int VT_CLIP_MAX_BLOCKS = 3;
+struct TrainBlockRef { const TrainBlock* layout; void* state; };
+int vt_train_clip_blocks(vt_context* c, const char* who, const TrainBlockRef* blocks, int n, float max_norm, hipStream_t s);
 int vt_train_step(vt_context* c, const char* who, const TrainBlock& b, void* state, double lr, double beta1, double beta2, double eps,
                   double weight_decay, long long t, hipStream_t s);
 // VT_HEAD_PARAM .. VT_HEAD_ADAM_V of the tensor at float offset `toff` with `numel` floats, or VT_HEAD_NORM -> byte range of the block
@@ -215,9 +218,10 @@ inline FrontLayout vt_front_layout(const DecoderWeights& d) {
     l.total = l.normpart + vt_eval_align(sizeof(double) * VT_FRONT_NORM_PARTS);
     return l;
 }
-// the front can be trained: the attention decoder at latent_channels 16 without cross-attention, heads in {1, 2, 4, 8}
+// the front can be trained: the attention decoder at latent_channels 16, heads in {1, 2, 4, 8} (with cross-attention the front ends
+// in the rows cross-attention reads; that piece is the cross block's, below)
 inline bool vt_front_trainable(const DecoderWeights& d) {
-    if (d.plain || d.use_cross || d.latent_channels != 16) return false;
+    if (d.plain || d.latent_channels != 16) return false;
     return !d.use_self || d.heads == 1 || d.heads == 2 || d.heads == 4 || d.heads == 8;
 }
 
@@ -253,6 +257,76 @@ inline FrontWorkspace vt_front_workspace(const FrontLayout& l, int B, int H, int
     w.p_conv = take(4 * (size_t)w.conv_parts * 1216);
     w.p_sp7 = take(4 * (size_t)w.sp_parts * 128);
     w.p_mlp = take(4 * b * 128);
+    w.total = off;
+    return w;
+}
+
+// ---- cross-attention trainer (train_cross.hip): query_generator.* and cross_attention.* of the attention decoder ---------------------
+// Ten tensors at fixed float offsets in each of the four arrays; every numel is a multiple of 64, so there is no padding.  The weight
+// gradients of the three large layers are written by tiles of VT_CROSS_TILE_ROWS rows x VT_CROSS_TILE_COLS columns, one workgroup and
+// one squared-norm partial each (the workgroups of column tile 0 also own the bias entries of their rows); k_proj / v_proj (one
+// contiguous range of 4608 floats) are reduced from one partial row per image by 256-float workgroups.
+constexpr int VT_CROSS_TENSORS = 10;
+constexpr int VT_CROSS_P = 530176;          // floats of one parameter array
+constexpr int VT_CROSS_TILE_ROWS = 8, VT_CROSS_TILE_COLS = 256;
+struct CrossTensor { const char* name; int off, numel; };
+constexpr CrossTensor VT_CROSS_TABLE[VT_CROSS_TENSORS] = {
+    {"query_generator.weight", 0, 262144},             {"query_generator.bias", 262144, 512},
+    {"cross_attention.q_proj.weight", 262656, 131072}, {"cross_attention.q_proj.bias", 393728, 256},
+    {"cross_attention.k_proj.weight", 393984, 2048},   {"cross_attention.k_proj.bias", 396032, 256},
+    {"cross_attention.v_proj.weight", 396288, 2048},   {"cross_attention.v_proj.bias", 398336, 256},
+    {"cross_attention.out_proj.weight", 398592, 131072}, {"cross_attention.out_proj.bias", 529664, 512},
+};
+enum { VT_CT_GW = 0, VT_CT_GB, VT_CT_QW, VT_CT_QB, VT_CT_KW, VT_CT_KB, VT_CT_VW, VT_CT_VB, VT_CT_OW, VT_CT_OB };
+constexpr int VT_CROSS_KV_ROW = 4608;       // floats of one image's partial row: k_proj.weight | k_proj.bias | v_proj.weight | v_proj.bias
+constexpr int vt_cross_tiles(int rows, int cols) { return (rows / VT_CROSS_TILE_ROWS) * (cols / VT_CROSS_TILE_COLS); }
+// first squared-norm partial of: query_generator [512 x 512] | q_proj [256 x 512] | out_proj [512 x 256] | the k / v range
+constexpr int VT_CROSS_SLOT_G = 0;
+constexpr int VT_CROSS_SLOT_Q = VT_CROSS_SLOT_G + vt_cross_tiles(512, 512);
+constexpr int VT_CROSS_SLOT_O = VT_CROSS_SLOT_Q + vt_cross_tiles(256, 512);
+constexpr int VT_CROSS_SLOT_KV = VT_CROSS_SLOT_O + vt_cross_tiles(512, 256);
+constexpr int VT_CROSS_NORM_PARTS = VT_CROSS_SLOT_KV + VT_CROSS_KV_ROW / 256;
+constexpr bool vt_cross_table_ok() {
+    int off = 0;
+    for (int t = 0; t < VT_CROSS_TENSORS; ++t) {
+        if (VT_CROSS_TABLE[t].off != off || VT_CROSS_TABLE[t].numel % 64) return false;
+        off += VT_CROSS_TABLE[t].numel;
+    }
+    return off == VT_CROSS_P;
+}
+static_assert(vt_cross_table_ok(), "the cross tensors follow each other without padding and end at VT_CROSS_P");
+static_assert(VT_CROSS_TABLE[VT_CT_VB].off + VT_CROSS_TABLE[VT_CT_VB].numel - VT_CROSS_TABLE[VT_CT_KW].off == VT_CROSS_KV_ROW,
+              "k_proj and v_proj are one contiguous range of VT_CROSS_KV_ROW floats");
+static_assert(VT_CROSS_NORM_PARTS == 274, "one squared-norm partial per workgroup that writes gradients: 128 + 64 + 64 tiles + 18");
+
+// One block, every section 256-B aligned: params fp32 [P] | grads | adam m | adam v | scalars | squared-norm partials fp64
+struct CrossLayout : TrainBlock { int heads; };
+inline CrossLayout vt_cross_layout(const DecoderWeights& d) {
+    CrossLayout l;
+    l.heads = d.heads;
+    l.P = VT_CROSS_P; l.norm_parts = VT_CROSS_NORM_PARTS;
+    const size_t a = vt_eval_align(4 * (size_t)VT_CROSS_P);
+    l.params = 0; l.grads = a; l.m = 2 * a; l.v = 3 * a;
+    l.scalars = 4 * a;
+    l.normpart = l.scalars + 256;
+    l.total = l.normpart + vt_eval_align(sizeof(double) * VT_CROSS_NORM_PARTS);
+    return l;
+}
+inline bool vt_cross_trainable(const DecoderWeights& d) { return vt_front_trainable(d) && d.use_cross && (d.heads == 1 || d.heads == 2 || d.heads == 4 || d.heads == 8); }
+
+// Workspace of a forward / backward pair, every section 256-B aligned (floats unless noted).  The forward leaves q (query_generator's
+// output), u (q_proj's) and o (the attention output) for the backward of the same batch.
+struct CrossWorkspace { size_t q, u, o, a, g, colsum, d_o, du, dq, dt, part, total; };
+inline CrossWorkspace vt_cross_workspace(int B) {
+    CrossWorkspace w;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += vt_eval_align(bytes); return o; };
+    const size_t b = (size_t)B;
+    w.q = take(4 * b * 512); w.u = take(4 * b * 256); w.o = take(4 * b * 256); w.a = take(4 * b * 512);
+    w.g = take(sizeof(double) * b);                 // fp64 g[b] = sum_f dY[b][f] / 512: every entry of d a
+    w.colsum = take(sizeof(double) * 256);          // fp64 column sums of out_proj.weight (one per backward, whatever B)
+    w.d_o = take(4 * b * 256); w.du = take(4 * b * 256); w.dq = take(4 * b * 512); w.dt = take(4 * b * 512);
+    w.part = take(4 * b * VT_CROSS_KV_ROW);
     w.total = off;
     return w;
 }

@@ -8,14 +8,17 @@ reference's train_decoder.py (train_decoder.py:173-216) does to `classifier.*`.
                  (what it shares with FrontTrainer -- the state block, step, commit, read, write -- is _BlockTrainer)
   FrontTrainer   the same for the attention decoder's front (vt_front_*; csrc/train_front.hip): training-mode forward (BatchNorm on
                  batch statistics, dropout on the softmax weights), backward from d loss / d features, AdamW, commit
-  DecoderTrainer front + head: one forward_backward, ONE clip_grad_norm_ over both blocks (vt_train_clip), one step / commit
+  CrossTrainer   the same for query_generator.* / cross_attention.* (vt_cross_*; csrc/train_cross.hip): the piece between the front's
+                 rows and the head's feature rows of a decoder with cross-attention
+  DecoderTrainer front (+ cross-attention) + head: one forward_backward, ONE clip_grad_norm_ over all blocks (vt_train_clip /
+                 vt_train_clip3), one step / commit
   LatentCache    the encoder's latents of every image in one flat device arena, so that later epochs skip the encoder
 
 With HeadTrainer alone the decoder's FRONT (everything before `classifier`) is frozen: for ClassificationDecoder it is the
 parameter-free 4x4 pool, so the head is the whole model; for AttentionClassificationDecoder it runs as in inference (BatchNorm on its
 running statistics).  DecoderTrainer trains the attention decoder in full -- spatial_attention.*, feature_compress.* (running
-statistics included) and self_attention_post.* -- but not with cross-attention, whose backward does not exist.  The channel max of the
-spatial attention gives its gradient to the arg-max channel, the lowest index on a tie.
+statistics included), self_attention_post.* and, on a decoder with cross-attention, query_generator.* and cross_attention.*.  The channel
+max of the spatial attention gives its gradient to the arg-max channel, the lowest index on a tie.
 """
 import ctypes
 import math
@@ -393,10 +396,13 @@ FRONT_BUFFERS = {"feature_compress.1.running_mean": _lib.FRONT_BN_MEAN, "feature
                  "feature_compress.1.num_batches_tracked": _lib.FRONT_BN_TRACKED}
 
 
+CROSS_PREFIXES = ("query_generator.", "cross_attention.")
+
+
 def front_trainable(decoder):
-    """Can train.FrontTrainer train this decoder's front?  The attention decoder without cross-attention (vt_front_state_bytes)."""
-    plain, _, _, cross, _ = decoder._cfg
-    return not plain and not cross
+    """Can train.FrontTrainer train this decoder's front?  The attention decoder, with or without cross-attention (vt_front_state_bytes);
+    with it, train.CrossTrainer trains the piece behind the front."""
+    return not decoder._cfg[0]
 
 
 class FrontTrainer(_BlockTrainer):
@@ -404,7 +410,9 @@ class FrontTrainer(_BlockTrainer):
     the C ABI, csrc/train_front.hip) and the calls that train it.  `forward(latent, train=True)` runs BatchNorm on the batch's
     statistics (and updates the running ones) and drops softmax weights at `attention_dropout`; `backward(d_features)` belongs to the
     last training-mode forward and ADDS the gradients of every front tensor.  The channel max of the spatial attention sends its
-    gradient to the arg-max channel, the lowest index on a tie.  Cross-attention is not covered.  grad_norm() is that of the last
+    gradient to the arg-max channel, the lowest index on a tie.  On a decoder with cross-attention the same 17 tensors are trained and
+    the rows `forward` returns, in both modes, are the rows cross-attention reads (CrossTrainer.forward turns them into the head's feature
+    rows), and `backward` takes the gradient with respect to those rows (CrossTrainer.backward's result).  grad_norm() is that of the last
     DecoderTrainer.clip()."""
     PREFIX = "vt_front_"
 
@@ -418,8 +426,8 @@ class FrontTrainer(_BlockTrainer):
         self.shapes = {k: tuple(v.shape) for k, v in sd.items() if k.startswith(FRONT_PREFIXES) and k not in FRONT_BUFFERS}
         self.buffers = {k: tuple(sd[k].shape) for k in FRONT_BUFFERS}
         self._last = None
-        self._allocate("this decoder's front cannot be trained on the device: an attention decoder without cross-attention, "
-                       "latent_channels = 16 and attention_heads in {1, 2, 4, 8} is expected")
+        self._allocate("this decoder's front cannot be trained on the device: an attention decoder with latent_channels = 16 and "
+                       "attention_heads in {1, 2, 4, 8} is expected")
         self.write_buffer("feature_compress.1.num_batches_tracked", sd["feature_compress.1.num_batches_tracked"])
 
     def _ws(self, B, h, w):
@@ -474,37 +482,104 @@ class FrontTrainer(_BlockTrainer):
         return export_state_dict(self.decoder, self.tensor, [*self.shapes, *self.buffers])
 
 
+class CrossTrainer(_BlockTrainer):
+    """Device state of query_generator.* and cross_attention.* of an attention decoder with cross-attention (vt_cross_* of the C ABI,
+    csrc/train_cross.hip) and the calls that train it.  `forward(x)` takes the front's rows [B][512] (FrontTrainer.forward) and returns
+    the head's feature rows; the piece has no dropout and no normalisation layer, so there is one mode.  `backward(d_features)` belongs
+    to the last forward, ADDS the gradients of the ten tensors and returns d loss / d x for FrontTrainer.backward.  The workspace that
+    carries q, u and o from forward to backward is this trainer's own, so several trainers on one device may interleave their calls."""
+    PREFIX = "vt_cross_"
+
+    def __init__(self, decoder, seed=0):
+        super().__init__(decoder, seed)
+        self.shapes = {k: tuple(v.shape) for k, v in decoder.state_dict().items() if k.startswith(CROSS_PREFIXES)}
+        self._last, self._wsbuf = None, None
+        self._allocate("this decoder has no cross-attention that can be trained on the device: an attention decoder with cross-attention, "
+                       "latent_channels = 16 and attention_heads in {1, 2, 4, 8} is expected")
+
+    def _ws(self, B):
+        need = self.ctx.lib.vt_cross_workspace_bytes(self.ctx.handle, int(B))
+        if need == 0:
+            raise _lib.VTError(f"unsupported cross-attention batch size {B}")
+        if self._wsbuf is None or self._wsbuf.numel() < need + 256:     # this trainer's own: backward reads what ITS forward left
+            self._wsbuf = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
+        return ctypes.c_void_p((self._wsbuf.data_ptr() + 255) // 256 * 256), need
+
+    def _rows(self, t, what):
+        r = t.detach().to(self.device, torch.float32).contiguous()
+        if r.dim() != 2 or r.shape[1] != self.F:
+            raise ValueError(f"expected {what} [B, {self.F}], got {tuple(r.shape)}")
+        return r
+
+    def forward(self, x):
+        """Feature rows [B][F] of the front's rows x; keeps what backward() needs (until the next forward)."""
+        x = self._rows(x, "x")
+        out = torch.empty_like(x)
+        self._call("forward", vp(x), x.shape[0], vp(out), *self._ws(x.shape[0]))
+        self._last = x
+        return out
+
+    def backward(self, d_features):
+        if self._last is None:
+            raise RuntimeError("CrossTrainer.backward needs the forward of the same batch before it")
+        x = self._last
+        d = self._rows(d_features, "d_features")
+        if d.shape != x.shape:
+            raise ValueError(f"expected d_features {tuple(x.shape)}, got {tuple(d.shape)}")
+        d_x = torch.empty_like(x)
+        self._call("backward", vp(x), vp(d), x.shape[0], vp(d_x), *self._ws(x.shape[0]))
+        self._last = None
+        return d_x
+
+    def state_dict(self):
+        """The decoder's full state_dict with the trained cross-attention tensors; the others are the decoder's own."""
+        return export_state_dict(self.decoder, self.parameter, self.shapes)
+
+
 class DecoderTrainer:
-    """The attention decoder trained in full: FrontTrainer + HeadTrainer.  One forward_backward runs latent -> front (training mode) ->
-    head forward / loss / backward with d loss / d features -> front backward; clip() is ONE clip_grad_norm_ over both blocks."""
+    """The attention decoder trained in full: FrontTrainer + HeadTrainer, and CrossTrainer between them when the decoder has
+    cross-attention.  One forward_backward runs latent -> front (training mode) [-> cross-attention] -> head forward / loss / backward
+    with d loss / d features [-> cross-attention backward] -> front backward; clip() is ONE clip_grad_norm_ over all blocks."""
 
     def __init__(self, decoder, loss="bce", focal_alpha=1.0, focal_gamma=2.0, class_weights=None, dropout=None, attention_dropout=0.1, seed=0):
         self.decoder = decoder
         self.head = HeadTrainer(decoder, loss, focal_alpha, focal_gamma, class_weights, dropout, seed)
         self.front = FrontTrainer(decoder, attention_dropout, seed)
+        self.cross = CrossTrainer(decoder, seed) if decoder._cfg[3] else None
         self.ctx, self.device, self.N, self.F = self.head.ctx, self.head.device, self.head.N, self.head.F
 
     def forward(self, latent):
         """Eval-mode logits: the front on its running statistics, no dropout (the reference's decoder.eval())."""
-        return self.head.forward(self.front.forward(latent, train=False))
+        rows = self.front.forward(latent, train=False)
+        return self.head.forward(rows if self.cross is None else self.cross.forward(rows))
 
     def forward_backward(self, latent, labels, loss_scale=1.0, train=True, step=None, return_logits=False):
         step = self.head.calls if step is None else int(step)
         feats = self.front.forward(latent, train=True, step=step)
+        if self.cross is not None:
+            feats = self.cross.forward(feats)
         out = self.head.forward_backward(feats, labels, loss_scale, train, step, return_logits, return_d_features=True)
         logits, d_feats = out if return_logits else (None, out)
-        self.front.backward(d_feats)
+        self.front.backward(d_feats if self.cross is None else self.cross.backward(d_feats))
         return logits
 
     def clip(self, max_norm):
-        self.ctx.call("vt_train_clip", *self.head._state(), *self.front._state(), float(max_norm), stream_ptr(self.device))
+        if self.cross is None:
+            self.ctx.call("vt_train_clip", *self.head._state(), *self.front._state(), float(max_norm), stream_ptr(self.device))
+        else:
+            self.ctx.call("vt_train_clip3", *self.head._state(), *self.front._state(), *self.cross._state(), float(max_norm),
+                          stream_ptr(self.device))
 
     def step(self, lr, weight_decay=0.0, betas=ADAM_BETAS, eps=ADAM_EPS):
         self.head.step(lr, weight_decay, betas, eps)
         self.front.step(lr, weight_decay, betas, eps)
+        if self.cross is not None:
+            self.cross.step(lr, weight_decay, betas, eps)
 
     def commit(self):
         self.front.commit()
+        if self.cross is not None:
+            self.cross.commit()
         self.head.commit()
 
     def losses(self):
@@ -513,7 +588,14 @@ class DecoderTrainer:
     def grad_norm(self):
         return self.head.grad_norm()
 
+    def _tensor(self, k):
+        if k in self.head.shapes:
+            return self.head.parameter(k)
+        if self.cross is not None and k in self.cross.shapes:
+            return self.cross.parameter(k)
+        return self.front.tensor(k)
+
     def state_dict(self):
-        """The decoder's full state_dict with the head's and the front's tensors read from the device."""
-        return export_state_dict(self.decoder, lambda k: self.head.parameter(k) if k in self.head.shapes else self.front.tensor(k),
-                                 [*self.head.shapes, *self.front.shapes, *self.front.buffers])
+        """The decoder's full state_dict with the head's, the front's and the cross-attention's tensors read from the device."""
+        names = [*self.head.shapes, *self.front.shapes, *self.front.buffers, *(self.cross.shapes if self.cross is not None else ())]
+        return export_state_dict(self.decoder, self._tensor, names)

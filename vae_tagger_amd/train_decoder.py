@@ -1,5 +1,6 @@
 """Decoder training CLI: the reference's train_decoder.py (train_decoder.py:30-278) with the decoder trained on the GPU behind the
-frozen encoder: the classifier head alone (train.HeadTrainer) or, with --train_front, the whole attention decoder (train.DecoderTrainer).
+frozen encoder: the classifier head alone (train.HeadTrainer) or, with --train_front, the whole attention decoder (train.DecoderTrainer),
+cross-attention included under --train_cross_attention.
 
     python -m vae_tagger_amd.train_decoder --vae_checkpoint ae.safetensors --json_path data.json --tags_csv_path tags.csv \
         --no_attention --num_epochs 10 --train_batch_size 16 [--use_bucketing] [--decoder_checkpoint start.bin]
@@ -10,7 +11,10 @@ two flags.  --freeze_front: its front (spatial attention, feature_compress, self
 if no checkpoint is given: spatial_attention.*, feature_compress.* (BatchNorm on batch statistics, its running statistics updated) and
 self_attention_post.* with --attention_dropout on the softmax weights; validation runs the front in eval mode on the running
 statistics, as the reference's decoder.eval() does.  The channel max of the spatial attention passes its gradient to the arg-max
-channel, the lowest index on a tie.  Cross-attention has no backward: --use_cross_attention stays refused without --freeze_front.
+channel, the lowest index on a tie.  With --use_cross_attention, --train_front needs --train_cross_attention as well: query_generator.*
+and cross_attention.* are then trained too (train.CrossTrainer) and the decoder is trained in full; without the flag the combination
+stays refused, with a message that names it.  (The refusal is a pinned behaviour of this CLI; folding --train_cross_attention into
+--use_cross_attention under --train_front is a later change that may edit the test that pins it.)
 Epoch 1 encodes every image once and keeps the front's feature row and the labels of each on the GPU (train.FeatureCache); later epochs
 train from that cache without calling the encoder (--no_feature_cache re-encodes every epoch).  The dataset applies no random
 augmentation (modules.py:688-729), so a cached row is what a re-encode would give.  With --train_front the feature rows change every
@@ -30,10 +34,10 @@ import time
 import torch
 
 IGNORED_ARGUMENTS = ("mixed_precision", "cudnn_benchmark", "cudnn_deterministic", "num_workers", "prefetch_factor", "use_safetensors")
-FRONT_MESSAGE = ("an attention decoder is trained with --freeze_front only: backward through the decoder front (BatchNorm in training "
-                 "mode, self-attention with dropout) is not implemented; --freeze_front trains classifier.* on the frozen front, "
-                 "--no_attention trains the plain decoder in full; --train_front trains the front as well (not with "
-                 "--use_cross_attention, whose backward does not exist)")
+FRONT_MESSAGE = ("an attention decoder needs --freeze_front or --train_front: training the decoder front without a choice between them is "
+                 "not implemented; --freeze_front trains classifier.* on the frozen front, --no_attention trains the plain decoder in "
+                 "full; --train_front trains the front as well (with --use_cross_attention add --train_cross_attention, which trains "
+                 "query_generator.* and cross_attention.* too)")
 
 
 def build_parser():
@@ -87,8 +91,10 @@ def build_parser():
     p.add_argument("--freeze_front", action="store_true",
                    help="attention decoders: train classifier.* only, on the front as it runs in inference (required for them)")
     p.add_argument("--train_front", action="store_true",
-                   help="attention decoders: train the front too (spatial attention, feature_compress, self-attention); not with "
-                        "--use_cross_attention")
+                   help="attention decoders: train the front too (spatial attention, feature_compress, self-attention); with "
+                        "--use_cross_attention it needs --train_cross_attention")
+    p.add_argument("--train_cross_attention", action="store_true",
+                   help="with --train_front --use_cross_attention: train query_generator.* and cross_attention.* too (the whole decoder)")
     p.add_argument("--latent_cache_gb", type=float, default=16.0,
                    help="with --train_front: device memory for the cached latents and labels; if the set does not fit, or at 0, "
                         "every epoch re-encodes")
@@ -111,15 +117,23 @@ def check_args(args):
     from .train import SCHEDULES
     if args.no_attention:
         args.use_attention = False
+    if args.train_cross_attention:
+        if args.freeze_front:
+            raise RuntimeError("--train_cross_attention and --freeze_front exclude each other: --freeze_front trains classifier.* alone")
+        if not args.train_front:
+            raise RuntimeError("--train_cross_attention needs --train_front: cross-attention is trained together with the front")
+        if not args.use_cross_attention:
+            raise RuntimeError("--train_cross_attention needs --use_cross_attention: the decoder has no cross-attention without it")
     if args.train_front:
         if not args.use_attention:
             raise RuntimeError("--train_front trains the front of an attention decoder; with --no_attention there is none (the plain "
                                "decoder is trained in full as it is)")
         if args.freeze_front:
             raise RuntimeError("--train_front and --freeze_front exclude each other")
-        if args.use_cross_attention:
-            raise RuntimeError("--train_front with --use_cross_attention: backward through cross-attention is not implemented; "
-                               "--freeze_front trains classifier.* on the frozen front")
+        if args.use_cross_attention and not args.train_cross_attention:
+            raise RuntimeError("--train_front with --use_cross_attention: backward through cross-attention is not implemented without "
+                               "--train_cross_attention, which trains query_generator.* and cross_attention.* too; --freeze_front "
+                               "trains classifier.* on the frozen front")
         if args.attention_heads not in (1, 2, 4, 8):
             raise RuntimeError("--train_front: --attention_heads must be 1, 2, 4 or 8")
         if not 0.0 <= args.attention_dropout < 1.0 or args.latent_cache_gb < 0:
