@@ -444,6 +444,32 @@ int vt_cross_write(vt_context* ctx, void* state, size_t state_bytes, int kind, c
 int vt_train_clip3(vt_context* ctx, void* head_state, size_t head_state_bytes, void* front_state, size_t front_state_bytes, void* cross_state,
                    size_t cross_state_bytes, float max_norm, void* stream);
 
+/* ---- sharded training: the gradient exchange (csrc/train_common.hip) ------------------------------------------------------------
+ * Data-parallel ranks all-gather their gradients and every rank merges them itself, in rank order, on the device: no atomics, the
+ * same bits on every rank and run to run, so the ranks' parameters and Adam moments never drift apart and nothing is broadcast.
+ * The same three calls exist for each trainer block (vt_head_ / vt_front_ / vt_cross_):
+ *   grads_floats   P: the floats of the block's gradient section, padding included (0 where state_bytes is 0)
+ *   grads_export   dst (device, 16-B aligned, dst_bytes >= 4 P) <- the gradient section, in stream order
+ *   grads_merge    gradient[e] = (float) sum over r = 0 .. K-1, in that order, of weights[r] * (double)src[r * stride_floats + e]: fp64,
+ *                  the multiply and the add rounded separately, one final cast.  src: device, 16-B aligned, not inside the state;
+ *                  stride_floats a multiple of 4 and >= P (several blocks may sit side by side in one gathered buffer); 1 <= K <= 64;
+ *                  weights: HOST array of K finite, non-negative values (n_r / sum n: the merged gradient is then the concatenated
+ *                  batch's); a rank whose weight is 0 is still read.  The same launch rewrites every squared-norm partial of the block
+ *                  from the merged values, so clip and step follow as after a backward.
+ */
+size_t vt_head_grads_floats(const vt_context* ctx);
+int vt_head_grads_export(vt_context* ctx, const void* state, size_t state_bytes, void* dst, size_t dst_bytes, void* stream);
+int vt_head_grads_merge(vt_context* ctx, void* state, size_t state_bytes, const float* src, size_t stride_floats, int K, const double* weights,
+                        void* stream);
+size_t vt_front_grads_floats(const vt_context* ctx);
+int vt_front_grads_export(vt_context* ctx, const void* state, size_t state_bytes, void* dst, size_t dst_bytes, void* stream);
+int vt_front_grads_merge(vt_context* ctx, void* state, size_t state_bytes, const float* src, size_t stride_floats, int K, const double* weights,
+                         void* stream);
+size_t vt_cross_grads_floats(const vt_context* ctx);
+int vt_cross_grads_export(vt_context* ctx, const void* state, size_t state_bytes, void* dst, size_t dst_bytes, void* stream);
+int vt_cross_grads_merge(vt_context* ctx, void* state, size_t state_bytes, const float* src, size_t stride_floats, int K, const double* weights,
+                         void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * flag 0: 1 (default) = 3x3 stride-1 convs use the halo-tile kernel (conv3x3_halo.hip),
  *         0 = every contraction uses the generic implicit-GEMM kernel (conv_gemm.hip).

@@ -30,7 +30,13 @@ full step of the decoder without it and against the same cross-attention step in
 
     python tools/bench_train.py --cli --train_front [--images 256] ...
 
-times `train_decoder --train_front` (attention decoder from scratch): epoch 2's rate from the latent cache against epoch 1's."""
+times `train_decoder --train_front` (attention decoder from scratch): epoch 2's rate from the latent cache against epoch 1's.
+
+    python tools/bench_train.py --merge 8 [--classes 10000] [--batch 16] [--latent 128] [--steps 50] [--rounds 5]
+
+The gradient exchange of `train_decoder --sharded` on one GPU: export + merge (+ clip) of the three blocks over K synthetic gradient sets
+against a torch device-to-device copy of the same K x P_total x 4 bytes, and the full step with a forced exchange on a one-rank RCCL
+group against the plain step.  No multi-GPU figure can come from it."""
 import argparse
 import json
 import math
@@ -186,6 +192,93 @@ def front_mode(args):
     return out
 
 
+def merge_mode(args):
+    """--merge K: the gradient exchange of sharded training on ONE GPU.  (a) export + merge + clip, and the merge alone, of the three
+    blocks of the decoder with cross-attention over K synthetic gradient sets [K][P_total], against a torch device-to-device copy of the
+    same K P_total 4 bytes; (b) the full step with a forced exchange on a ONE-rank RCCL group (export, all_gather_into_tensor, the read
+    of the count, merge of K = 1) against the plain step.  No collective between GPUs runs here: nothing about scaling follows."""
+    import torch.distributed as dist
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", str(29800 + os.getpid() % 100))
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    dev = torch.device("cuda:0")
+    dist.init_process_group("nccl", world_size=1, rank=0, device_id=dev)      # before any other GPU call of this process
+    torch.cuda.set_device(dev)
+    from vae_tagger_amd import synth
+    from vae_tagger_amd.modules import AttentionClassificationDecoder
+    from vae_tagger_amd.train import DecoderTrainer, GradientExchange
+    N, B, L, K = args.classes, args.batch, args.latent, args.merge
+    dec = AttentionClassificationDecoder(16, L, L, N, True, True, True, 8)
+    dec.load_state_dict(synth.synth_state_dict(synth.attention_decoder_manifest(N, 16, True, True, True), seed=1), strict=False)
+    dec = dec.to(dev).eval()
+    tr, plain = DecoderTrainer(dec), DecoderTrainer(dec)
+    ex = GradientExchange(tr, dist.group.WORLD, force_collective=True)
+    P = tr.grads_floats()
+    g = torch.Generator().manual_seed(0)
+    src = (1e-3 * torch.randn(K, P, generator=g)).to(dev)
+    dst, mine = torch.empty_like(src), torch.empty(P, dtype=torch.float32, device=dev)
+    w = [(r + 1) / (K * (K + 1) / 2) for r in range(K)]
+    lat = (0.1 + 0.8 * torch.randn(B, 16, L, L, generator=g)).to(dev)
+    y = (torch.rand(B, N, generator=g) < 0.01).float().to(dev)
+
+    def exchange_side(n):
+        for _ in range(n):
+            tr.export_gradients(mine)
+            tr.merge_gradients(src, P, w)
+            tr.clip(1.0)
+
+    def merge_only(n):
+        for _ in range(n):
+            tr.merge_gradients(src, P, w)
+
+    def torch_copy(n):
+        for _ in range(n):
+            dst.copy_(src)
+
+    def step_plain(n):
+        for _ in range(n):
+            plain.forward_backward(lat, y)
+            plain.clip(1.0)
+            plain.step(1e-3, 1e-6)
+
+    def step_exchange(n):
+        for _ in range(n):
+            tr.forward_backward(lat, y)
+            ex.exchange(B)
+            tr.clip(1.0)
+            tr.step(1e-3, 1e-6)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn(args.steps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / args.steps            # microseconds per iteration
+
+    fns = {"export_merge_clip": exchange_side, "merge": merge_only, "torch_copy": torch_copy, "step_plain": step_plain,
+           "step_forced_exchange": step_exchange}
+    for fn in fns.values():
+        fn(5)
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for k, fn in fns.items():
+            times[k].append(timed(fn))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"bench": "train_merge", "classes": N, "batch": B, "latent": [L, L], "ranks": K, "steps": args.steps, "rounds": args.rounds,
+           "grads_floats": P, "blocks": [b.grads_floats() for b in tr.blocks()], "gathered_bytes": K * P * 4,
+           "received_bytes_per_step_formula": "(K - 1) * 4 * (P_total + 4)", "received_bytes_per_step": (K - 1) * 4 * ex.row,
+           "us": med, "us_min_max": {k: [min(v), max(v)] for k, v in times.items()},
+           "merge_over_torch_copy": med["merge"] / med["torch_copy"], "export_merge_clip_over_torch_copy": med["export_merge_clip"] / med["torch_copy"],
+           "merge_GBps": (K + 1) * P * 4 / (med["merge"] * 1e-6) / 1e9, "torch_copy_GBps": 2 * K * P * 4 / (med["torch_copy"] * 1e-6) / 1e9,
+           "forced_exchange_step_over_plain_step": med["step_forced_exchange"] / med["step_plain"],
+           "forced_exchange_overhead_us": med["step_forced_exchange"] - med["step_plain"], "backend": dist.get_backend()}
+    print(json.dumps(out))
+    dist.destroy_process_group()
+    return out
+
+
 def cli_front_mode(args, tmp, common, trn):
     from vae_tagger_amd import train_decoder
     common = [a for a in common if a != "--no_attention"]
@@ -271,7 +364,10 @@ def main(argv=None):
     ap.add_argument("--plain", action="store_true")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--merge", type=int, default=0, help="time the sharded run's gradient export + merge of this many synthetic ranks (1..64) and exit")
     args = ap.parse_args(argv)
+    if args.merge:
+        return merge_mode(args)
     if args.cli:
         return cli_mode(args)
     if args.front:

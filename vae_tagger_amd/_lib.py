@@ -124,7 +124,16 @@ PROTOTYPES = {
     "vt_cross_read": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
     "vt_cross_write": (_i, [_vp, _vp, _sz, _i, _c.c_char_p, _vp, _sz, _vp]),
     "vt_train_clip3": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _f, _vp]),
-    "vt_encoder_flops": (_c.c_double, [_vp, _i, _i]),
+    "vt_head_grads_floats": (_sz, [_vp]),
+    "vt_head_grads_export": (_i, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    "vt_head_grads_merge": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _c.POINTER(_c.c_double), _vp]),
+    "vt_front_grads_floats": (_sz, [_vp]),
+    "vt_front_grads_export": (_i, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    "vt_front_grads_merge": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _c.POINTER(_c.c_double), _vp]),
+    "vt_cross_grads_floats": (_sz, [_vp]),
+    "vt_cross_grads_export": (_i, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    "vt_cross_grads_merge": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _c.POINTER(_c.c_double), _vp]),
+    "vt_encoder_flops":(_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),
     "vt_profile_num_configs": (_i, []),

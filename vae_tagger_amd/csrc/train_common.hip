@@ -1,5 +1,5 @@
 // What the trainers share (vt_train.h: TrainBlock): the kernels that work on any block -- the gradient norm and clip coefficient, the
-// gradient scale, AdamW -- and one host implementation of the state check, clip, step, the kind -> byte range dispatch of the four
+// gradient scale, AdamW, the in-order merge of K ranks' gradients -- and one host implementation of the state check, clip, step, the kind -> byte range dispatch of the four
 // parameter arrays and the scalars, and the read / write copies.  train_head.hip, train_front.hip and train_cross.hip call these with their own layout
 // and the name of the entry point they were reached through.  The conventions are theirs: fp32 storage, fp64 reductions in an order
 // fixed by the shapes, no atomics, nothing synchronises the host.
@@ -76,6 +76,45 @@ __global__ __launch_bounds__(256) VT_NO_PACKED_F32 void train_adamw_kernel(float
     P[i] = p; G[i] = g; M[i] = m; V[i] = v;
 }
 
+// The gradient exchange of a sharded run: grads[e] = (float) sum over r = 0 .. K-1, in that order, of w[r] * (double)src[r * stride + e],
+// in fp64 with the multiply and the add rounded separately (a rank whose weight is 0 is still read).  Workgroup b owns chunk b of the
+// block's float4s (vt_train_merge_chunk4) and rewrites squared-norm partial b from the fp32 values it stored, so clip and step follow
+// as after a backward; a workgroup whose chunk is empty writes 0.0.
+struct MergeWeights { double w[VT_MERGE_MAX_RANKS]; };
+__global__ __launch_bounds__(256) VT_NO_PACKED_F32 void train_merge_kernel(const float4* __restrict__ src, long long stride4, int K, MergeWeights w,
+                                                                           float4* __restrict__ grads, long long n4, long long chunk4,
+                                                                           double* __restrict__ normpart) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    const long long lo = (long long)blockIdx.x * chunk4;
+    const long long hi = lo + chunk4 < n4 ? lo + chunk4 : n4;
+    double sq = 0.0;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+        double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
+        for (int r = 0; r < K; ++r) {
+            const float4 v = src[(long long)r * stride4 + i];
+            const double wr = w.w[r];
+            double px = wr * (double)v.x, py = wr * (double)v.y, pz = wr * (double)v.z, pw = wr * (double)v.w;
+            // the products are pinned in registers: with -ffp-contract=fast on the command line the backend fuses a multiply into
+            // the add that follows whatever the pragma says, and w[r] x has more than 53 bits, so the fused sum has other bits
+            asm volatile("" : "+v"(px), "+v"(py), "+v"(pz), "+v"(pw));
+            ax = ax + px;
+            ay = ay + py;
+            az = az + pz;
+            aw = aw + pw;
+        }
+        float4 o;
+        o.x = (float)ax; o.y = (float)ay; o.z = (float)az; o.w = (float)aw;
+        grads[i] = o;
+        sq = sq + (double)o.x * (double)o.x;
+        sq = sq + (double)o.y * (double)o.y;
+        sq = sq + (double)o.z * (double)o.z;
+        sq = sq + (double)o.w * (double)o.w;
+    }
+    const double t = block_sum_256d(sq, red);
+    if (threadIdx.x == 0) normpart[blockIdx.x] = t;
+}
+
 }  // namespace
 
 int vt_train_check(vt_context* c, const char* who, const TrainBlock& b, const void* state, size_t state_bytes) {
@@ -116,6 +155,33 @@ int vt_train_step(vt_context* c, const char* who, const TrainBlock& b, void* sta
     hipLaunchKernelGGL(train_adamw_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (float4*)(st + b.params), (float4*)(st + b.grads),
                        (float4*)(st + b.m), (float4*)(st + b.v), n4, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2,
                        (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2), (float)eps);
+    HIPCK(c, hipGetLastError(), who);
+    return VT_OK;
+}
+
+int vt_train_grads_export(vt_context* c, const char* who, const TrainBlock& b, const void* state, void* dst, size_t dst_bytes, hipStream_t s) {
+    if (!dst || ((uintptr_t)dst & 15)) return c->fail(VT_ERR_INVALID, "%s: dst is null or not 16-B aligned", who);
+    if (dst_bytes < 4 * b.P) return c->fail(VT_ERR_WORKSPACE, "%s: dst holds %zu bytes, %zu needed", who, dst_bytes, 4 * b.P);
+    HIPCK(c, hipMemcpyAsync(dst, (const char*)state + b.grads, 4 * b.P, hipMemcpyDeviceToDevice, s), who);
+    return VT_OK;
+}
+
+int vt_train_grads_merge(vt_context* c, const char* who, const TrainBlock& b, void* state, const void* src, size_t stride_floats, int K,
+                         const double* weights, hipStream_t s) {
+    if (K < 1 || K > VT_MERGE_MAX_RANKS) return c->fail(VT_ERR_INVALID, "%s: K = %d ranks, 1 to %d expected", who, K, VT_MERGE_MAX_RANKS);
+    if (!src || ((uintptr_t)src & 15)) return c->fail(VT_ERR_INVALID, "%s: src is null or not 16-B aligned", who);
+    if (stride_floats % 4 || stride_floats < b.P)
+        return c->fail(VT_ERR_INVALID, "%s: stride of %zu floats, a multiple of 4 that is at least %zu expected", who, stride_floats, b.P);
+    if (!weights) return c->fail(VT_ERR_INVALID, "%s: weights is null", who);
+    MergeWeights w;
+    for (int r = 0; r < VT_MERGE_MAX_RANKS; ++r) {
+        w.w[r] = r < K ? weights[r] : 0.0;
+        if (!isfinite(w.w[r]) || w.w[r] < 0.0) return c->fail(VT_ERR_INVALID, "%s: weight %d = %g must be finite and non-negative", who, r, w.w[r]);
+    }
+    char* st = (char*)state;
+    const long long n4 = (long long)(b.P / 4);
+    hipLaunchKernelGGL(train_merge_kernel, dim3((unsigned)b.norm_parts), dim3(256), 0, s, (const float4*)src, (long long)(stride_floats / 4), K, w,
+                       (float4*)(st + b.grads), n4, vt_train_merge_chunk4(b.P, b.norm_parts), (double*)(st + b.normpart));
     HIPCK(c, hipGetLastError(), who);
     return VT_OK;
 }

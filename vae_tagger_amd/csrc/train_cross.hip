@@ -391,6 +391,28 @@ int vt_cross_step(vt_context* c, void* state, size_t state_bytes, double lr, dou
     return vt_train_step(c, "vt_cross_step", l, state, lr, beta1, beta2, eps, weight_decay, t, (hipStream_t)stream);
 }
 
+// the gradient exchange of a sharded run (vt_train.h)
+size_t vt_cross_grads_floats(const vt_context* c) {
+    return vt_cross_state_bytes(c) ? vt_cross_layout(c->dec).P : 0;
+}
+
+int vt_cross_grads_export(vt_context* c, const void* state, size_t state_bytes, void* dst, size_t dst_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    CrossLayout l;
+    VTCK(cross_check(c, "vt_cross_grads_export", state, state_bytes, &l));
+    return vt_train_grads_export(c, "vt_cross_grads_export", l, state, dst, dst_bytes, (hipStream_t)stream);
+}
+
+int vt_cross_grads_merge(vt_context* c, void* state, size_t state_bytes, const float* src, size_t stride_floats, int K, const double* weights,
+                         void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    CrossLayout l;
+    VTCK(cross_check(c, "vt_cross_grads_merge", state, state_bytes, &l));
+    return vt_train_grads_merge(c, "vt_cross_grads_merge", l, state, src, stride_floats, K, weights, (hipStream_t)stream);
+}
+
 int vt_cross_read(vt_context* c, const void* state, size_t state_bytes, int kind, const char* name, void* out, size_t out_bytes, void* stream) {
     if (!c) return VT_ERR_INVALID;
     DeviceGuard guard(c);

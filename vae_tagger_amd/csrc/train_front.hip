@@ -946,6 +946,28 @@ int vt_front_step(vt_context* c, void* state, size_t state_bytes, double lr, dou
     return front_fold(c, l, (char*)state, (hipStream_t)stream);
 }
 
+// the gradient exchange of a sharded run (vt_train.h)
+size_t vt_front_grads_floats(const vt_context* c) {
+    return vt_front_state_bytes(c) ? vt_front_layout(c->dec).P : 0;
+}
+
+int vt_front_grads_export(vt_context* c, const void* state, size_t state_bytes, void* dst, size_t dst_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    FrontLayout l;
+    VTCK(front_check(c, "vt_front_grads_export", state, state_bytes, &l));
+    return vt_train_grads_export(c, "vt_front_grads_export", l, state, dst, dst_bytes, (hipStream_t)stream);
+}
+
+int vt_front_grads_merge(vt_context* c, void* state, size_t state_bytes, const float* src, size_t stride_floats, int K, const double* weights,
+                         void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    FrontLayout l;
+    VTCK(front_check(c, "vt_front_grads_merge", state, state_bytes, &l));
+    return vt_train_grads_merge(c, "vt_front_grads_merge", l, state, src, stride_floats, K, weights, (hipStream_t)stream);
+}
+
 // the front's own kinds (the BatchNorm buffers); the parameter arrays of a named tensor and the scalars are the common layer's
 static int front_section(vt_context* c, const char* who, const FrontLayout& l, int kind, const char* name, size_t* off, size_t* bytes) {
     if (kind == VT_FRONT_BN_MEAN) { *off = l.bn; *bytes = 32; return VT_OK; }

@@ -519,6 +519,28 @@ int vt_head_step(vt_context* c, void* state, size_t state_bytes, double lr, doub
     return vt_train_step(c, "vt_head_step", l, state, lr, beta1, beta2, eps, weight_decay, t, (hipStream_t)stream);
 }
 
+// the gradient exchange of a sharded run (vt_train.h): the floats of the grads section, its copy out, the in-order merge of K ranks'
+size_t vt_head_grads_floats(const vt_context* c) {
+    return vt_head_state_bytes(c) ? vt_head_layout(vt_decoder_head_shape(c->dec)).P : 0;
+}
+
+int vt_head_grads_export(vt_context* c, const void* state, size_t state_bytes, void* dst, size_t dst_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    HeadLayout l;
+    VTCK(head_check(c, "vt_head_grads_export", state, state_bytes, &l));
+    return vt_train_grads_export(c, "vt_head_grads_export", l, state, dst, dst_bytes, (hipStream_t)stream);
+}
+
+int vt_head_grads_merge(vt_context* c, void* state, size_t state_bytes, const float* src, size_t stride_floats, int K, const double* weights,
+                        void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    HeadLayout l;
+    VTCK(head_check(c, "vt_head_grads_merge", state, state_bytes, &l));
+    return vt_train_grads_merge(c, "vt_head_grads_merge", l, state, src, stride_floats, K, weights, (hipStream_t)stream);
+}
+
 // the head's own kind (the loss ring); the parameter arrays of a named tensor and the scalars are the common layer's
 static int head_section(vt_context* c, const char* who, const HeadLayout& l, int kind, const char* name, size_t* off, size_t* bytes) {
     if (kind == VT_HEAD_LOSS_RING) { *off = l.ring; *bytes = sizeof(double) * VT_HEAD_RING; return VT_OK; }

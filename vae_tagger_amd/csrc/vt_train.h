@@ -31,6 +31,18 @@ struct TrainBlockRef { const TrainBlock* layout; void* state; };
 int vt_train_clip_blocks(vt_context* c, const char* who, const TrainBlockRef* blocks, int n, float max_norm, hipStream_t s);
 int vt_train_step(vt_context* c, const char* who, const TrainBlock& b, void* state, double lr, double beta1, double beta2, double eps,
                   double weight_decay, long long t, hipStream_t s);
+// The gradient exchange of a sharded run.  export: the block's `grads` section (P floats, padding included) -> dst, device to device.
+// merge: grads[e] = (float) sum over ranks r = 0 .. K-1, in that order, of weights[r] * (double)src[r * stride_floats + e] (fp64, multiply
+// and add rounded separately; `weights` is a HOST array of K finite, non-negative values; src is 16-B aligned device memory that does
+// not overlap the state, stride_floats a multiple of 4 and >= P), and ALL norm_parts squared-norm partials are rewritten from the merged
+// fp32 values, so vt_train_clip_blocks and vt_train_step follow unchanged.  The partition of P behind those partials is written here,
+// once: partial i is the fp64 sum of squares of float4s [i * chunk4, min((i + 1) * chunk4, P / 4)), chunk4 = ceil((P / 4) / norm_parts);
+// a partial whose range is empty is 0.0.
+constexpr int VT_MERGE_MAX_RANKS = 64;
+inline long long vt_train_merge_chunk4(size_t P, int norm_parts) { return (long long)((P / 4 + (size_t)norm_parts - 1) / (size_t)norm_parts); }
+int vt_train_grads_export(vt_context* c, const char* who, const TrainBlock& b, const void* state, void* dst, size_t dst_bytes, hipStream_t s);
+int vt_train_grads_merge(vt_context* c, const char* who, const TrainBlock& b, void* state, const void* src, size_t stride_floats, int K,
+                         const double* weights, hipStream_t s);
 // VT_HEAD_PARAM .. VT_HEAD_ADAM_V of the tensor at float offset `toff` with `numel` floats, or VT_HEAD_NORM -> byte range of the block
 int vt_train_section(vt_context* c, const char* who, const TrainBlock& b, int kind, size_t toff, size_t numel, size_t* off, size_t* bytes);
 int vt_train_read(vt_context* c, const char* who, const void* state, size_t off, size_t bytes, void* out, size_t out_bytes, hipStream_t s);

@@ -13,6 +13,9 @@ reference's train_decoder.py (train_decoder.py:173-216) does to `classifier.*`.
   DecoderTrainer front (+ cross-attention) + head: one forward_backward, ONE clip_grad_norm_ over all blocks (vt_train_clip /
                  vt_train_clip3), one step / commit
   LatentCache    the encoder's latents of every image in one flat device arena, so that later epochs skip the encoder
+  GradientExchange   sharded training's one cross-rank operation: export the gradients, ONE all-gather, and the merge of the ranks'
+                 rows in rank order on every rank (vt_*_grads_export / vt_*_grads_merge; merge_gradients_host states the arithmetic);
+                 owned / batch_count / agreed_steps are the static ownership and the epoch's step count
 
 With HeadTrainer alone the decoder's FRONT (everything before `classifier`) is frozen: for ClassificationDecoder it is the
 parameter-free 4x4 pool, so the head is the whole model; for AttentionClassificationDecoder it runs as in inference (BatchNorm on its
@@ -284,6 +287,38 @@ class _BlockTrainer:
         torch.cuda.current_stream(self.device).synchronize()
         off = self._ptr - self._buf.data_ptr()
         return self._buf[off:off + self._bytes].cpu()
+
+    # -- the gradient exchange of a sharded run (GradientExchange) --
+    def grads_floats(self):
+        """P: the floats of the block's gradient section, padding included."""
+        return int(getattr(self.ctx.lib, self.PREFIX + "grads_floats")(self.ctx.handle))
+
+    def export_gradients(self, out):
+        """out (a contiguous fp32 device tensor or view of at least P floats, 16-B aligned) <- the gradient section, in stream order."""
+        if out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError("export_gradients: a contiguous fp32 tensor on the trainer's device is expected")
+        self._call("grads_export", vp(out), out.numel() * 4)
+
+    def merge_gradients(self, src, stride, weights):
+        """gradients <- the in-order weighted sum of K = len(weights) ranks' sections, rank r's at src[r * stride:] (merge_gradients_host
+        states the arithmetic); every squared-norm partial is rewritten, so clip() and step() follow as after a backward.  `src` is an
+        fp32 device tensor that holds all K sections and is not changed."""
+        w = [float(x) for x in weights]
+        K, P = len(w), self.grads_floats()
+        if src.dtype != torch.float32 or src.device != self.device or not src.is_contiguous():
+            raise ValueError("merge_gradients: a contiguous fp32 tensor on the trainer's device is expected")
+        if 1 <= K <= 64 and int(stride) >= P and src.numel() < (K - 1) * int(stride) + P:      # (a K out of range is the library's to refuse)
+            raise ValueError(f"merge_gradients: src holds {src.numel()} floats, {(K - 1) * int(stride) + P} needed")
+        self._call("grads_merge", vp(src), int(stride), K, (ctypes.c_double * max(1, K))(*w))
+
+    def optimizer_state_sha256(self, h=None):
+        """SHA-256 over the parameters, Adam m and Adam v of every tensor, in the order of `shapes` (ranks of a sharded run compare it)."""
+        import hashlib
+        h = hashlib.sha256() if h is None else h
+        for kind in (_lib.HEAD_PARAM, _lib.HEAD_ADAM_M, _lib.HEAD_ADAM_V):
+            for name, shape in self.shapes.items():
+                h.update(self._read(kind, name, shape, torch.float32).numpy().tobytes())
+        return h
 
 
 class HeadTrainer(_BlockTrainer):
@@ -599,3 +634,124 @@ class DecoderTrainer:
         """The decoder's full state_dict with the head's, the front's and the cross-attention's tensors read from the device."""
         names = [*self.head.shapes, *self.front.shapes, *self.front.buffers, *(self.cross.shapes if self.cross is not None else ())]
         return export_state_dict(self.decoder, self._tensor, names)
+
+    # -- the gradient exchange of a sharded run: the blocks side by side in ONE fp32 buffer [P_front (+ P_cross) + P_head] --
+    def blocks(self):
+        return [b for b in (self.front, self.cross, self.head) if b is not None]
+
+    def grads_floats(self):
+        return sum(b.grads_floats() for b in self.blocks())
+
+    def export_gradients(self, out):
+        off = 0
+        for b in self.blocks():
+            P = b.grads_floats()
+            b.export_gradients(out[off:off + P])
+            off += P
+
+    def merge_gradients(self, src, stride, weights):
+        """Every block from its range of the K rows of `src` (row r starts at float r * stride; stride >= grads_floats())."""
+        if not src.is_contiguous():
+            raise ValueError("merge_gradients: a contiguous fp32 tensor on the trainer's device is expected")
+        flat, off = src.view(-1), 0
+        for b in self.blocks():
+            b.merge_gradients(flat[off:], stride, weights)
+            off += b.grads_floats()
+
+    def optimizer_state_sha256(self):
+        h = None
+        for b in self.blocks():
+            h = b.optimizer_state_sha256(h)
+        return h
+
+
+# ---- sharded training: static ownership and the gradient exchange -------------------------------------------------------------------
+RANK_SEED_STRIDE = 1000003                             # the trainer seed of rank r is seed + RANK_SEED_STRIDE * r: other dropout masks
+EXCHANGE_TAIL = 4                                      # floats behind a rank's gradients in the exchanged row: its image count (int32) + 3 spare
+
+
+def owned(items, rank, world):
+    """Rank `rank`'s share of a list under static ownership: items[rank::world]."""
+    return list(items)[int(rank)::int(world)]
+
+
+def batch_count(n_items, batch_size):
+    return (int(n_items) + int(batch_size) - 1) // int(batch_size)
+
+
+def agreed_steps(local_batch_counts):
+    """The optimizer steps of one epoch: the maximum over the ranks of their local batch counts (a rank that has run out of batches
+    joins the remaining exchanges with weight 0)."""
+    return max(int(c) for c in local_batch_counts)
+
+
+def merge_gradients_host(blocks, weights):
+    """What vt_*_grads_merge computes, in numpy: blocks [K][P] fp32 (or a list of K arrays), weights K floats ->
+    fp32 [P] with out[e] = (float) acc, acc = 0.0 (fp64); for r = 0 .. K-1 in that order: acc = acc + w[r] * (double)blocks[r][e] --
+    the product rounded to fp64, then the sum rounded to fp64, one final cast to fp32."""
+    rows = [np.asarray(b, dtype=np.float32).reshape(-1) for b in blocks]
+    w = [np.float64(x) for x in weights]
+    if len(rows) != len(w) or not rows:
+        raise ValueError("merge_gradients_host: one weight per block, at least one block")
+    acc = np.zeros(rows[0].shape, dtype=np.float64)
+    for r, row in enumerate(rows):
+        prod = w[r] * row.astype(np.float64)           # (numpy rounds each ufunc's result: nothing is fused)
+        acc = acc + prod
+    return acc.astype(np.float32)
+
+
+def exchange_weights(counts):
+    """w[r] = n_r / sum n: the merged gradient of per-rank batch-mean gradients is then the concatenated batch's mean gradient."""
+    total = sum(int(c) for c in counts)
+    if total <= 0:
+        raise ValueError("no rank brought an image to this step")
+    return [int(c) / total for c in counts]
+
+
+class GradientExchange:
+    """The one cross-rank operation of a training step: every rank exports its gradients (all blocks of `trainer`, HeadTrainer or
+    DecoderTrainer) and its image count into one row, ONE collective gathers the rows (all_gather_into_tensor on RCCL, all_gather into
+    chunks on gloo, as sharding.all_gather_logits chooses), and every rank merges them itself, on the device, in rank order.  Same
+    bytes in, same kernel: the ranks' states stay bit-identical and nothing is broadcast.  Reading the K counts is the step's one host
+    synchronisation.  Without a process group, or on a one-rank group without force_collective, exchange() does nothing."""
+
+    def __init__(self, trainer, group=None, force_collective=False):
+        import torch.distributed as dist
+        self.trainer, self.group, self.device = trainer, group, trainer.device
+        grouped = group is not None and dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size(group) if grouped else 1
+        self.active = grouped and (self.world > 1 or bool(force_collective))
+        self.backend = dist.get_backend(group) if grouped else None
+        if self.world > 64:
+            raise ValueError(f"{self.world} ranks: the gradient merge takes at most 64")
+        self.P = trainer.grads_floats()
+        self.row = self.P + EXCHANGE_TAIL
+        self.calls, self.last_counts = 0, None
+        if self.active:
+            self._mine = torch.zeros(self.row, dtype=torch.float32, device=self.device)
+            self._all = torch.zeros(self.world * self.row, dtype=torch.float32, device=self.device)
+
+    @property
+    def bytes_received_per_step(self):
+        return (self.world - 1) * 4 * self.row
+
+    def exchange(self, n_local):
+        """After forward_backward (or none: n_local = 0, the gradients are the zeros the last step left), before clip / step.
+        Returns the ranks' image counts."""
+        if not self.active:
+            return [int(n_local)]
+        import torch.distributed as dist
+        self.trainer.export_gradients(self._mine[:self.P])
+        self._mine[self.P:].view(torch.int32).copy_(torch.tensor([int(n_local), 0, 0, 0], dtype=torch.int32), non_blocking=True)
+        if self.backend == "gloo":
+            parts = [torch.empty(self.row, dtype=torch.float32) for _ in range(self.world)]
+            dist.all_gather(parts, self._mine.cpu(), group=self.group)
+            counts = [int(p[self.P:].view(torch.int32)[0]) for p in parts]
+            self._all.copy_(torch.cat(parts))
+        else:
+            dist.all_gather_into_tensor(self._all, self._mine, group=self.group)
+            counts = self._all.view(self.world, self.row)[:, self.P:].contiguous().view(torch.int32)[:, 0].cpu().tolist()
+        self.trainer.merge_gradients(self._all, self.row, exchange_weights(counts))
+        self.calls += 1
+        self.last_counts = counts
+        return counts

@@ -25,6 +25,24 @@ batches from the epoch's order grouped by latent shape (batch statistics need on
 Files, as the reference writes them: best_pytorch_model.bin (strictly lower validation loss), pytorch_model.bin (every --save_steps
 epochs), training_history.json, then the threshold search and the metrics on the validation set (optimal_thresholds.json,
 evaluation_results.csv, evaluation_results_overall.json); plus train_report.json (per epoch: seconds, images/s, encoder batches, steps).
+
+    torchrun --nproc-per-node 8 -m vae_tagger_amd.train_decoder ... --sharded
+
+trains data-parallel, one rank per GPU.  Ownership is static: rank r owns train_paths[r::world] and val_paths[r::world], encodes its
+share once into a cache sized for that share alone (so K ranks cache K times the data set one --latent_cache_gb allows), shuffles it
+with epoch_order(len(share), seed, epoch) and forms its batches locally (with --train_front grouped by latent shape).  The ranks agree
+once per epoch on the number of steps, the largest local batch count; a step is forward_backward -> the gradient exchange
+(train.GradientExchange: one all-gather, then every rank merges the rows in rank order at weights n_r / sum n, so the merged gradient
+is the concatenated batch's and every rank's parameters and Adam moments stay bit-identical without a broadcast) -> clip -> step; a
+rank that has run out of batches joins with zero gradients at weight 0.  The learning-rate schedule counts these global steps.
+Rank r's trainer seed is seed + 1000003 r (other dropout masks); BatchNorm runs on each rank's own batch statistics, and rank 0's
+running statistics are written on every rank before each validation (what DDP's broadcast_buffers amounts to).  Every rank scores
+its validation share; the loss blocks are gathered and merged in rank order on rank 0 (the checkpoint sweep's path), which computes
+val_loss and broadcasts it; train_loss is the mean over all ranks' step losses.  Rank 0 alone prints the progress lines and writes the
+files; the final evaluation is the sharded pass of `evaluate --sharded`; train_report.json gains "sharded" (world, backend, steps per
+epoch, per-rank images, cache bytes and a SHA-256 over each rank's parameters and Adam moments).  Refused, before any GPU or
+process-group work: --sharded with --gradient_accumulation_steps > 1 or --no_feature_cache, and a split that leaves a rank fewer than 2
+training images or no validation image.  Without --sharded nothing changes, under torchrun included.
 """
 import argparse
 import json
@@ -40,7 +58,8 @@ FRONT_MESSAGE = ("an attention decoder needs --freeze_front or --train_front: tr
                  "query_generator.* and cross_attention.* too)")
 
 
-def build_parser():
+def build_parser(distributed=False):
+    """The single-process flag set; distributed=True adds --sharded (`main` parses with it)."""
     p = argparse.ArgumentParser(description="训练分类解码器 (decoder on the GPU behind the frozen encoder; see --freeze_front / --train_front)")
     p.add_argument("--vae_checkpoint", type=str, required=True, help="预训练VAE模型文件路径 (.safetensors)")
     p.add_argument("--vae_config_path", type=str, default=None, help="VAE配置文件路径 (JSON格式)")
@@ -104,6 +123,10 @@ def build_parser():
     p.add_argument("--host_resize", action="store_true", help="PIL transforms on the CPU (the reference's input route)")
     p.add_argument("--fp16_operands", action="store_true", help="fp16 instead of bf16 MFMA operands for the encoder's convolutions")
     p.add_argument("--fp8", action="store_true", help="3x3 convs of the encoder on fp8 (e4m3) operands")
+    if distributed:
+        p.add_argument("--sharded", action="store_true",
+                       help="under torchrun: data-parallel training, one rank per GPU; rank r owns every world-th image from the r-th on, "
+                            "the ranks' gradients are all-gathered and merged in rank order on every rank; rank 0 writes the files")
     return p
 
 
@@ -144,7 +167,25 @@ def check_args(args):
         raise RuntimeError(f"--lr_scheduler_type {args.lr_scheduler_type}: one of {', '.join(SCHEDULES)} expected")
     if args.train_batch_size < 1 or args.num_epochs < 1 or args.save_steps < 1 or args.logging_steps < 1:
         raise RuntimeError("--train_batch_size, --num_epochs, --save_steps and --logging_steps must be at least 1")
+    if getattr(args, "sharded", False):
+        if args.gradient_accumulation_steps > 1:
+            raise RuntimeError("--sharded with --gradient_accumulation_steps > 1 is not implemented: the loop clips every micro-step, "
+                               "which has no clean meaning when the gradients are merged across ranks once per optimizer step")
+        if args.no_feature_cache:
+            raise RuntimeError("--sharded with --no_feature_cache is not implemented: a rank forms its batches, and the ranks agree on "
+                               "the steps of an epoch, from what each has cached of its own share")
     return args
+
+
+def check_shares(n_train, n_val, world):
+    """--sharded, before any GPU or process-group work: every rank must own at least 2 training images and 1 validation image
+    (rank r owns every world-th image from the r-th on, so the LAST rank owns the fewest)."""
+    world = int(world)
+    fewest_train, fewest_val = int(n_train) // world, int(n_val) // world
+    if fewest_train < 2 or fewest_val < 1:
+        raise RuntimeError(f"--sharded over {world} ranks: {n_train} training and {n_val} validation images leave a rank with "
+                           f"{fewest_train} training and {fewest_val} validation image(s); every rank needs at least 2 and 1 "
+                           "(run fewer ranks, or without --sharded)")
 
 
 def _load_models(args, device):
@@ -202,25 +243,54 @@ def train(args):
     """`args`: a namespace of build_parser() that has passed check_args (main does both)."""
     from . import _lib
     from .evaluate import TaggedImageList
-    from .evaluation import evaluate_and_search
+    from .evaluation import _merge_losses_across_ranks, evaluate_and_search
     from .losses import DeviceLossAccumulator, class_balanced_weights, class_distribution, loss_report, select_loss
     from .modules import AspectRatioBucketing, get_image_transform
     from .pipeline import EncodeTagPipeline
     from .prefetch import FeederLoader
     from .train import DecoderTrainer, FeatureCache, HeadTrainer, LatentCache, epoch_order, lr_schedule, split_indices
+    world, rank, group, dist = 1, 0, None, None
+    if getattr(args, "sharded", False):
+        # the shares are refused or accepted from the lists alone; then the process group, BEFORE any GPU call of this process
+        from .infer_full import _dist_setup
+        data = TaggedImageList(args.json_path, args.tags_csv_path)
+        train_idx, val_idx = split_indices(len(data.image_paths), args.seed)
+        check_shares(len(train_idx), len(val_idx), max(1, int(os.environ.get("WORLD_SIZE", "1"))))
+        world, rank, dev_index = _dist_setup()
+        if dev_index is not None:
+            import torch.distributed as dist
+            group = dist.group.WORLD
+    sharded, chief = group is not None, rank == 0      # (--sharded in a single process without a group is the plain run)
     ignored = ignored_arguments(args)
-    if ignored:
+    if ignored and chief:
         print("ignored arguments (no meaning here): " + ", ".join("--" + k for k in ignored))
     if not torch.cuda.is_available():
         raise RuntimeError("vae_tagger_amd needs an MI355X (no HIP device visible; there is no CPU fallback)")
+    if sharded:
+        torch.cuda.set_device(dev_index)
     device = torch.device("cuda", torch.cuda.current_device())
     vae_model, decoder, tag_names = _load_models(args, device)
+    if sharded:
+        # one set of initial parameters: rank 0's (a decoder trained from scratch is initialised from each process's own generator)
+        box = [{k: v.detach().cpu() for k, v in decoder.state_dict().items()} if chief else None]
+        dist.broadcast_object_list(box, src=0, group=group)
+        if not chief:
+            decoder.load_state_dict(box[0])
+            decoder.to(device).eval()
     data = TaggedImageList(args.json_path, args.tags_csv_path)
-    for p in data.missing:
-        print(f"跳过图像 {p}，错误原因: 文件不存在")
+    if chief:
+        for p in data.missing:
+            print(f"跳过图像 {p}，错误原因: 文件不存在")
     train_idx, val_idx = split_indices(len(data.image_paths), args.seed)
     train_paths, val_paths = [data.image_paths[i] for i in train_idx], [data.image_paths[i] for i in val_idx]
-    print(f"训练集大小: {len(train_paths)}, 验证集大小: {len(val_paths)}")
+    if chief:
+        print(f"训练集大小: {len(train_paths)}, 验证集大小: {len(val_paths)}")
+    all_train = train_paths
+    if sharded:
+        from .train import RANK_SEED_STRIDE, GradientExchange, agreed_steps, batch_count, owned
+        train_paths, val_paths = owned(train_paths, rank, world), owned(val_paths, rank, world)
+    n_owned = len(train_paths) + len(val_paths) if sharded else len(data.image_paths)      # what this process may cache
+    trainer_seed = args.seed + (RANK_SEED_STRIDE * rank if sharded else 0)                 # other dropout masks on every rank
     N = len(tag_names)
     selected = select_loss(args.use_class_balanced, args.use_focal_loss)
     weights = None
@@ -243,39 +313,47 @@ def train(args):
     full = bool(args.train_front)                      # the trainer's inputs are latents (full) or the frozen front's feature rows
     if full:
         trainer = DecoderTrainer(decoder, loss=selected, focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, class_weights=weights,
-                                 attention_dropout=args.attention_dropout, seed=args.seed)
+                                 attention_dropout=args.attention_dropout, seed=trainer_seed)
         side = (args.max_resolution if args.use_bucketing else args.resolution) // 8
         latent_numel = 16 * side * side              # the largest latent: a bucket's area never exceeds max_resolution^2
         budget = int(args.latent_cache_gb * (1 << 30))
-        fits = not args.no_feature_cache and LatentCache.fits(len(data.image_paths), latent_numel, N, budget)
-        cache = LatentCache(len(data.image_paths), latent_numel, N, device) if fits else None
+        fits = not args.no_feature_cache and LatentCache.fits(n_owned, latent_numel, N, budget)
+        cache = LatentCache(n_owned, latent_numel, N, device) if fits else None
     else:
         trainer = HeadTrainer(decoder, loss=selected, focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, class_weights=weights,
-                              seed=args.seed)
-        cache = None if args.no_feature_cache else FeatureCache(len(data.image_paths), trainer.F, N, device)
+                              seed=trainer_seed)
+        cache = None if args.no_feature_cache else FeatureCache(n_owned, trainer.F, N, device)
+    if sharded and cache is None:
+        raise RuntimeError(f"--sharded: the latents of this rank's {n_owned} images do not fit --latent_cache_gb {args.latent_cache_gb}; "
+                           "a sharded run trains from each rank's cache (raise the budget or run more ranks)")
     acc = DeviceLossAccumulator(N, device, args.focal_alpha, args.focal_gamma, weights, context=decoder._context())
     accum = max(1, args.gradient_accumulation_steps)
     bs = args.train_batch_size
-    total_steps = args.num_epochs * ((len(train_paths) + bs - 1) // bs)
+    # (--sharded: the largest share's batches; every rank computes the same figure from the lists)
+    total_steps = args.num_epochs * (batch_count(len(owned(all_train, 0, world)), bs) if sharded else (len(train_paths) + bs - 1) // bs)
     os.makedirs(args.output_dir, exist_ok=True)
     history = {"train_loss": [], "val_loss": [], "learning_rates": []}
     report = {"epochs": [], "feature_cache_bytes": cache.nbytes if cache is not None and not full else 0, "feature_dim": trainer.F,
               "train_images": len(train_paths), "val_images": len(val_paths)}
     if full:
         report["latent_cache"] = {"cached": cache is not None, "budget_bytes": budget,
-                                  "bytes_needed": LatentCache.bytes_needed(len(data.image_paths), latent_numel, N), "bytes_used": 0}
+                                  "bytes_needed": LatentCache.bytes_needed(n_owned, latent_numel, N), "bytes_used": 0}
     reader = _LossReader(trainer, _lib.HEAD_RING)
     micro, sched, best, current_lr = 0, 0, float("inf"), args.learning_rate * lr_schedule(args.lr_scheduler_type, 0, args.lr_warmup_steps, total_steps)
     val_batches = None                                 # the validation batches of the first pass, by name: every epoch scores the same ones
 
+    failures = []                                      # (path, error) of the files a pass could not read
+
     def encoded(paths, counter):
-        for batch in loader(paths):
+        source = loader(paths)
+        for batch in source:
             latent = vae_model.encode(batch["pixel_values"])
             feats = latent if full else trainer.features(latent)
             counter[0] += 1
             if cache is not None:
                 cache.put(batch["names"], feats, batch["labels"])
             yield batch["names"], feats, batch["labels"]
+        failures.extend((str(p), str(e)) for p, e in source.failed)
 
     def cached(batches):
         for names in batches:
@@ -283,7 +361,103 @@ def train(args):
             if names:
                 yield (names, *cache.gather(names))
 
+    # ---- --sharded: one epoch of the data-parallel loop (see the module docstring) ----
+    exchange = GradientExchange(trainer, group, force_collective=True) if sharded else None
+    agreed, local_steps = [], []                       # per epoch: the agreed step count; the steps this rank had a batch for
+
+    def gather_objects(obj):
+        out = [None] * world
+        dist.all_gather_object(out, obj, group=group)
+        return out
+
+    def sync_batch_norm_buffers():
+        """Rank 0's BatchNorm buffers on every rank (each rank's running statistics follow its own batches, as under DDP without
+        SyncBatchNorm; this has the net effect of DDP's broadcast_buffers)."""
+        if not full:
+            return
+        box = [{k: trainer.front.buffer(k) for k in trainer.front.buffers} if chief else None]
+        dist.broadcast_object_list(box, src=0, group=group)
+        if not chief:
+            for k, t in box[0].items():
+                trainer.front.write_buffer(k, t)
+
+    def sharded_epoch(epoch):
+        nonlocal micro, sched, best, current_lr, val_batches
+        t0, enc, first, images = time.perf_counter(), [0], micro, 0
+        order = [train_paths[i] for i in epoch_order(len(train_paths), args.seed, epoch)]
+        if epoch == 0:
+            for _ in encoded(order, enc):              # this rank's share through the encoder, once: into its cache
+                pass
+        if full:
+            batches = cache.batches(order, bs)
+        else:
+            have = [p for p in order if p in cache]
+            batches = [have[i:i + bs] for i in range(0, len(have), bs)]
+        steps = agreed_steps(gather_objects(len(batches)))      # the ranks agree on the epoch's steps, once
+        agreed.append(steps)
+        for step in range(steps):
+            reader.before_step(micro)
+            n_local = 0
+            if step < len(batches):                    # a rank that has run out joins the exchange with its zero gradients at weight 0
+                names, feats, labels = batches[step], *cache.gather(batches[step])
+                trainer.forward_backward(feats, labels, loss_scale=1.0, train=True, step=micro)
+                n_local = len(names)
+                local_steps.append(micro)
+            exchange.exchange(n_local)
+            if args.max_grad_norm > 0:
+                trainer.clip(args.max_grad_norm)
+            trainer.step(current_lr, args.weight_decay)
+            sched += 1
+            current_lr = args.learning_rate * lr_schedule(args.lr_scheduler_type, sched, args.lr_warmup_steps, total_steps)
+            micro += 1
+            images += n_local
+            if chief and n_local and step % args.logging_steps == 0:
+                every = reader.drain(micro)
+                vals = [every[m] for m in local_steps if m >= first]
+                print(f"Epoch: {epoch}, Step: {step}, Loss: {vals[-1]:.4f}, Avg Loss: {sum(vals) / len(vals):.4f}, LR: {current_lr:.2e}")
+        sync_batch_norm_buffers()                      # before the validation; nothing trains between it and the saves below
+        acc.reset()
+        if val_batches is None:
+            seen = []
+            for names, feats, labels in encoded(val_paths, enc):
+                acc.update(trainer.forward(feats), labels)
+                seen.append(list(names))
+            val_batches = seen
+        else:
+            for names, feats, labels in cached(val_batches):
+                acc.update(trainer.forward(feats), labels)
+        vae_model.vae.raise_on_status()
+        every = reader.drain(micro)
+        vals = [every[m] for m in local_steps if m >= first]
+        per_rank = gather_objects((vals, acc.steps))
+        if any(not v or not s for v, s in per_rank):
+            raise RuntimeError("a rank could read no image of its share of the training or the validation set")
+        merged = _merge_losses_across_ranks([acc], group)       # one all-gather; merged in rank order on rank 0
+        box = [loss_report(merged[0].read(tag_names), selected)["val_loss"] if chief else None]
+        dist.broadcast_object_list(box, src=0, group=group)
+        val_loss = box[0]
+        seconds = time.perf_counter() - t0
+        every_loss = [x for v, _ in per_rank for x in v]        # the mean over all ranks' step losses, in rank order
+        history["train_loss"].append(sum(every_loss) / len(every_loss))
+        history["val_loss"].append(val_loss)
+        history["learning_rates"].append(current_lr)
+        n_img = images + sum(len(b) for b in val_batches)       # (this rank's)
+        report["epochs"].append({"epoch": epoch, "seconds": seconds, "images_per_second": n_img / seconds, "images": n_img,
+                                 "encoder_batches": enc[0], "steps": steps, "optimizer_steps": sched})
+        if chief:
+            print(f"Epoch {epoch} completed - Train Loss: {history['train_loss'][-1]:.4f}, Val Loss: {val_loss:.4f}")
+        if val_loss < best:
+            best = val_loss
+            if chief:
+                print(f"New best validation loss: {best:.4f}")
+                torch.save(trainer.state_dict(), os.path.join(args.output_dir, "best_pytorch_model.bin"))
+        if chief and (epoch + 1) % args.save_steps == 0:
+            torch.save(trainer.state_dict(), os.path.join(args.output_dir, "pytorch_model.bin"))
+
     for epoch in range(args.num_epochs):
+        if sharded:
+            sharded_epoch(epoch)
+            continue
         t0, enc, first, images = time.perf_counter(), [0], micro, 0
         order = [train_paths[i] for i in epoch_order(len(train_paths), args.seed, epoch)]
         from_cache = cache is not None and epoch > 0
@@ -336,23 +510,38 @@ def train(args):
             torch.save(trainer.state_dict(), os.path.join(args.output_dir, "best_pytorch_model.bin"))
         if (epoch + 1) % args.save_steps == 0:
             torch.save(trainer.state_dict(), os.path.join(args.output_dir, "pytorch_model.bin"))
-    print("训练完成，开始最终评估...")
-    with open(os.path.join(args.output_dir, "training_history.json"), "w") as fh:
-        json.dump(history, fh, indent=2)
+    if chief:
+        print("训练完成，开始最终评估...")
     if full and cache is not None:
         report["latent_cache"]["bytes_used"] = cache.nbytes
-    with open(os.path.join(args.output_dir, "train_report.json"), "w") as fh:
-        json.dump(report, fh, indent=2)
+    if sharded:
+        # what every rank reports of itself, in rank order; state_sha256: the parameters, Adam m and v of every block after the last step
+        mine = {"train_images": len(train_paths), "val_images": len(val_paths), "cache_bytes": cache.nbytes,
+                "state_sha256": trainer.optimizer_state_sha256().hexdigest(), "failures": failures}
+        ranks = gather_objects(mine)
+        report["train_images"], report["val_images"] = len(all_train), sum(r["val_images"] for r in ranks)
+        report["sharded"] = {"world": world, "backend": exchange.backend, "steps_per_epoch": agreed,
+                             "exchange_bytes_received_per_step": exchange.bytes_received_per_step,
+                             **{k: [r[k] for r in ranks] for k in ("train_images", "val_images", "cache_bytes", "state_sha256")}}
+        if chief:
+            for p, e in sorted({p: e for r in ranks for p, e in r["failures"]}.items()):      # every file belongs to one rank: each once
+                print(f"跳过图像 {p}，错误原因: {e}")
+    if chief:
+        with open(os.path.join(args.output_dir, "training_history.json"), "w") as fh:
+            json.dump(history, fh, indent=2)
+        with open(os.path.join(args.output_dir, "train_report.json"), "w") as fh:
+            json.dump(report, fh, indent=2)
     trainer.commit()
     decoder.load_state_dict(trainer.state_dict(), strict=False)   # the module's own tensors follow the device tables
     decoder.to(device).eval()
-    optimal, metrics, _ = evaluate_and_search(vae_model, decoder, loader(val_paths), tag_names, device, args.output_dir)
-    print("训练和评估完成！")
+    optimal, metrics, _ = evaluate_and_search(vae_model, decoder, loader(val_paths), tag_names, device, args.output_dir, group=group)
+    if chief:
+        print("训练和评估完成！")
     return {"history": history, "report": report, "optimal_thresholds": optimal, "metrics": metrics, "best_val_loss": best}
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(distributed=True).parse_args(argv)
     try:
         check_args(args)
     except RuntimeError as e:
