@@ -541,6 +541,10 @@ int vt_cross_grads_merge(vt_context* ctx, void* state, size_t state_bytes, const
 
  * flag 21: 1 (default) = vt_eval_export / vt_eval_merge move the keys 16 B per lane on the 16-B aligned part of every destination run;
  *         0 = 8 B per lane throughout.  Same bytes out (tools/bench_eval.py --merge times both).
+ * flag 22: 0 (default) = Upsample2D (nearest 2x + 3x3 conv) runs folded, as four 2x2 phase convs of the low-resolution input
+ *         (conv3x3_up2.hip: 4 taps per output pixel instead of 9, no 4x-sized intermediate tensor); 1 = the literal route, a nearest-2x
+ *         pass into a 16-bit buffer followed by the stride-1 3x3 conv -- the A/B partner and on-device cross-check, and what a channel
+ *         count the folded kernel refuses takes either way.  The two differ by accumulation order and by the folded weights' one rounding.
  */
 int vt_set_flag(vt_context* ctx, int flag, int value);
 
@@ -562,6 +566,30 @@ int vt_profile_begin(vt_context* ctx);
 int vt_profile_end(vt_context* ctx, int max_cfg, long long* launches, double* total_ms, double* total_flops,
                    const char** kernel_names);
 
+/* ---- the VAE's image decoder: latents -> images ------------------------------------------------
+ * diffusers' Decoder for AutoencoderKL: conv_in (latent -> block_out[-1]), mid block (resnet, single-head attention, resnet), one up
+ * block per entry of block_out_channels taken in reverse (layers_per_block + 1 resnets each, an Upsample2D -- nearest 2x + 3x3 conv --
+ * after all but the last), conv_norm_out + SiLU, conv_out.  Weights are diffusers' `decoder.*` keys (49 545 475 parameters for the FLUX
+ * configuration), handed over with vt_set_weight between vt_image_decoder_configure and vt_image_decoder_finalize; the packed weights
+ * live in an allocation list of their own, so configuring / finalizing the encoder or the tag decoder leaves them alone and vice versa.
+ * GroupNorm eps is 1e-6.  out_channels <= 32 (conv_out rides the 32-cout tiles, zero-padded); conv_in runs over the latent channels
+ * zero-padded to a 32-channel chunk; block_out_channels as for the encoder.
+ * scaling / shift (with their has_ flags) are the configuration's scaling_factor / shift_factor, used by `unscale` below.
+ * Decode runs 16-bit operands everywhere -- bf16, or fp16 with flag 18 where a kernel has that form -- and ignores the fp8 flags
+ * (11, 14, 15, 16).  Flags 0-4, 6-10, 12, 13, 17, 18, 20 act as in the encoder; flag 22 selects the Upsample2D route. */
+int vt_image_decoder_configure(vt_context* ctx, int out_channels, int latent_channels, const int* block_out_channels, int n_blocks,
+                               int layers_per_block, int groups, float scaling, int has_scaling, float shift, int has_shift);
+int vt_image_decoder_finalize(vt_context* ctx);
+/* bytes of 256-B aligned scratch vt_decode_image needs for B latents of h x w; 0 for an unsupported shape (or before configure) */
+size_t vt_decode_image_workspace_bytes(const vt_context* ctx, int B, int h, int w);
+/* z: fp32 NCHW [B][latent][h][w] (device).  unscale = 1 applies (z - shift) / scaling first (IEEE fp32: DiffusersVAEWrapper.decode's
+ * arithmetic); 0 decodes z as it is (AutoencoderKL.decode).  image_out: fp32 NCHW [B][out_channels][h * 2^(n_blocks-1)][w * 2^(n_blocks-1)],
+ * image_bytes its size: VT_ERR_INVALID if that is too small for the result, VT_ERR_WORKSPACE if workspace_bytes is below
+ * vt_decode_image_workspace_bytes.  Asynchronous on `stream`; an overflow of the fp16 residual-stream storage raises bit 0 of the sticky
+ * status word (vt_status), as in vt_encode.  Bit-identical from run to run. */
+int vt_decode_image(vt_context* ctx, const float* z_nchw, int B, int h, int w, int unscale, float* image_out, size_t image_bytes,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- single operators (parity tests drive each kernel through the same ABI) ------------------
  * NHWC bf16 activations, weights in the reference's own layouts (fp32 host order is converted by
  * the caller to bf16 [Cout][kh][kw][Cin]); fp32 accumulate.
@@ -581,6 +609,20 @@ int vt_op_conv2d_gn(vt_context* ctx, const void* x_bf16_nhwc, const void* w_bf16
                     const float* residual_f32, float* out_f32, void* out_bf16, int B, int Hin, int Win, int Cin,
                     int Cout, int ksize, int stride, int pad_lo, int pad_hi, int groups, float eps, const float* gamma,
                     const float* beta, float* scale_shift_out, void* workspace, void* stream);
+/* Upsample2D of the VAE decoder as a single operator: out = conv3x3(nearest_2x(x)) + bias, stride 1, pad 1, Cin == Cout == C.
+ * x is the LOW-resolution tensor, NHWC 16-bit [B][h][w][C] (bf16; fp16 bits with flag 18); w fp32 OIHW [C][C][3][3] ON THE DEVICE, packed
+ * inside the call on the stream; out fp32 NHWC [B][2h][2w][C].  By default the folded kernel runs (conv3x3_up2.hip: four 2x2 phase convs
+ * of the low-resolution input with pre-summed weights -- each folded weight is the fp32 sum, ky-major then kx, of 1, 2 or 4 original taps,
+ * rounded to the operand type once; C % 64 == 0); with flag 22, or for a C the folded kernel refuses, the literal route: a nearest-2x pass
+ * into a 16-bit buffer, then the stride-1 3x3 conv (C % 8 == 0; fp16 operands only where the halo conv has that form).  Scratch comes
+ * from the context (grown on demand: the first call of a size may synchronise).  No atomics: bit-identical from run to run.
+ * _gn additionally returns the GroupNorm (scale, shift) [B][C][2] of the OUTPUT from the epilogue's (n, mean, M2) partials, finalised
+ * as vt_op_conv2d_gn does (C / groups in {4, 8, 16}; bias required). */
+int vt_op_upsample2x_conv3x3(vt_context* ctx, const void* x_bf16_nhwc, const float* w_f32_oihw, const float* bias, float* out_f32,
+                             int B, int h, int w, int C, void* stream);
+int vt_op_upsample2x_conv3x3_gn(vt_context* ctx, const void* x_bf16_nhwc, const float* w_f32_oihw, const float* bias, float* out_f32,
+                                int B, int h, int w, int C, int groups, float eps, const float* gamma, const float* beta,
+                                float* scale_shift_out, void* stream);
 /* the fp8 conv of flag 11 as a single operator: x fp32 NHWC and w fp32 OIHW (both on the device) are quantised exactly as the
  * encoder quantises them (x -> e4m3(8 x), w -> e4m3 with per-cout absmax scales); out fp32 NHWC.  Cin % 64 == 0, Cout % 128 == 0. */
 size_t vt_op_conv3x3_fp8_workspace_bytes(int B, int H, int W, int Cin, int Cout);

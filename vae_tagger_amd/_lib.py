@@ -133,6 +133,10 @@ PROTOTYPES = {
     "vt_cross_grads_floats": (_sz, [_vp]),
     "vt_cross_grads_export": (_i, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "vt_cross_grads_merge": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _c.POINTER(_c.c_double), _vp]),
+    "vt_image_decoder_configure": (_i, [_vp, _i, _i, _c.POINTER(_i), _i, _i, _i, _f, _i, _f, _i]),
+    "vt_image_decoder_finalize": (_i, [_vp]),
+    "vt_decode_image_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "vt_decode_image": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     "vt_encoder_flops":(_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),
@@ -143,6 +147,8 @@ PROTOTYPES = {
     "vt_op_norm_silu_conv3x3": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vt_op_conv2d_gn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "vt_op_conv2d_gn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "vt_op_upsample2x_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "vt_op_upsample2x_conv3x3_gn": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "vt_op_conv3x3_fp8_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "vt_op_conv3x3_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vt_op_gemm_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _ll, _ll, _f, _i, _vp]),

@@ -4,7 +4,7 @@ Stands in for `diffusers.models.AutoencoderKL` at exactly the surface the refere
 (diffusers_vae_loader.py:8-35, :44, :73-86; infer_full.py:27-28; train_full.py:213,220):
 constructor keywords, `.config.scaling_factor / .shift_factor`, `load_state_dict(sd, strict=False)`,
 `.to()`, `.eval()`, `.parameters()`, and `encode(x).latent_dist.{mode,sample,kl}()`.
-Only the ENCODER is implemented (the inference hot path); `decode` raises.
+`decode(z)` runs the image decoder (vae_decoder.py), which lives outside the registered submodules: state_dict() is the encoder's.
 """
 from types import SimpleNamespace
 
@@ -75,6 +75,9 @@ class AutoencoderKL(HipModule):
         cfg["scaling_factor"] = scaling_factor
         cfg["shift_factor"] = shift_factor
         self.config = SimpleNamespace(**cfg)
+        # the image decoder (decoder.* tensors): NOT a registered submodule -- state_dict() / load_state_dict() stay the encoder's -- and
+        # built on the first decode() / load_decoder_state_dict(), so constructing the encoder does not draw 50 M decoder parameters
+        object.__setattr__(self, "_image_decoder", None)
 
     # -- HIP plumbing ------------------------------------------------------------------------------
     def _upload(self, ctx):
@@ -146,8 +149,54 @@ class AutoencoderKL(HipModule):
         straight from the conv_out epilogue (no moments tensor, no elementwise pass)."""
         return self._run_encode(x, _lib.ENCODE_MODE_SCALED)
 
-    def decode(self, z, *a, **kw):
-        raise NotImplementedError("vae_tagger_amd implements the encoder (inference hot path) only")
+    # -- the image decoder ---------------------------------------------------------------------------
+    def image_decoder(self):
+        """The VAEImageDecoder of this model (created on first use with the seeded default initialisation), in this model's vt_context."""
+        if self._image_decoder is None:
+            from .vae_decoder import VAEImageDecoder
+            c = self.config
+            dec = VAEImageDecoder(tuple(c.block_out_channels), c.out_channels, c.latent_channels, c.layers_per_block, c.norm_num_groups,
+                                  c.scaling_factor, c.shift_factor)
+            p = next(self.parameters())
+            dec.to(device=p.device)
+            dec.share_context_of(self)
+            object.__setattr__(self, "_image_decoder", dec)
+        return self._image_decoder
+
+    def _apply(self, fn, *a, **kw):
+        out = super()._apply(fn, *a, **kw)
+        if self.__dict__.get("_image_decoder") is not None:
+            self._image_decoder._apply(fn, *a, **kw)          # .to() / .cuda() / .float() move the decoder half too
+        return out
+
+    def load_decoder_state_dict(self, state_dict, strict=False):
+        """Load the `decoder.*` tensors of a (full) checkpoint into the image decoder; other keys are ignored.  Tensors not provided keep
+        the seeded default initialisation.  Returns load_state_dict's (missing_keys, unexpected_keys) over the decoder's own keys."""
+        sd = {k: v for k, v in state_dict.items() if k.startswith("decoder.")}
+        if not strict:
+            # strict=False keeps what fits, as for the encoder half: a tensor of another shape is not this architecture's (torch would raise)
+            c = self.config
+            manifest = synth.image_decoder_manifest(tuple(c.block_out_channels), c.out_channels, c.latent_channels, c.layers_per_block)
+            sd = {k: v for k, v in sd.items() if k not in manifest or tuple(v.shape) == tuple(manifest[k])}
+            if self._image_decoder is None and not any(k in manifest for k in sd):
+                return torch.nn.modules.module._IncompatibleKeys(list(manifest), list(sd))     # nothing to load: do not build the decoder for it
+        return self.image_decoder().load_state_dict(sd, strict=strict)
+
+    @torch.no_grad()
+    def decode(self, z, return_dict=True, generator=None, _unscale=False):
+        if self.config.use_post_quant_conv:
+            raise NotImplementedError("use_post_quant_conv=True is not supported by decode(): post_quant_conv is not implemented "
+                                      "(the FLUX VAE config sets it False)")
+        from .vae_decoder import DecoderOutput
+        sample = self.image_decoder().decode(z, unscale=_unscale)
+        if self.check_finite:
+            self.raise_on_status()
+        return DecoderOutput(sample) if return_dict else (sample,)
+
+    @torch.no_grad()
+    def decode_unscaled(self, z):
+        """Fused fast path of DiffusersVAEWrapper.decode: (z - shift_factor) / scaling_factor applied while the latents are staged."""
+        return self.decode(z, _unscale=True).sample
 
     @classmethod
     def from_config(cls, config_dict):

@@ -58,6 +58,7 @@ void vt_destroy(vt_context* c) {
         for (auto& sl : c->rs_ring) { if (sl.host) (void)hipHostFree(sl.host); if (sl.ev) (void)hipEventDestroy(sl.ev); }
         c->free_allocs(c->enc_allocs);
         c->free_allocs(c->dec_allocs);
+        c->free_allocs(c->imgdec_allocs);
         if (c->zeros) (void)hipFree(c->zeros);
     }
     delete c;
@@ -191,7 +192,7 @@ int vt_decoder_finalize(vt_context* c) {
     }
 #undef G
     for (auto it = c->weights.begin(); it != c->weights.end();)
-        it = (it->first.compare(0, 8, "encoder.") != 0) ? c->weights.erase(it) : ++it;
+        it = (it->first.compare(0, 8, "encoder.") != 0 && it->first.compare(0, 8, "decoder.") != 0) ? c->weights.erase(it) : ++it;   // (decoder.*: the VAE's image decoder)
     c->dec_finalized = true;
     return VT_OK;
 }
@@ -481,6 +482,7 @@ int vt_set_flag(vt_context* c, int flag, int value) {
     if (flag == 19) { c->s2_planar = value != 0; return VT_OK; }
     if (flag == 21) { c->eval_merge_vec = value != 0; return VT_OK; }
     if (flag == 20) { c->conv_out_halo = value != 0; return VT_OK; }
+    if (flag == 22) { c->up2_literal = value != 0; return VT_OK; }
     if (flag == 13) { c->s2_halo = value != 0; return VT_OK; }
     if (flag == 14) { c->attn_fp8 = value != 0; return VT_OK; }
     if (flag == 15) { c->proj_fp8 = value != 0; return VT_OK; }

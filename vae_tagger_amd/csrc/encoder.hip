@@ -29,11 +29,11 @@ int launch_halo_fp8(vt_context* c, const Conv3x3Fp8Args& a, hipStream_t s, const
                     2.0 * a.batch * (double)a.H * a.W * a.Cout * (9.0 * a.Cin + (a.scX ? a.scCin : 0)), what, [&] { return vt_launch_conv3x3_halo_fp8(a, s); });
 }
 
-namespace {
+// (run_gn, conv_f16 and run_norm_conv are shared with the image decoder's schedule, image_decoder.hip: declared in vt_context.h)
 
 // y = act(GroupNorm(x)) as bf16 rows.  Uses epilogue-produced partials when present.
 int run_gn(vt_context* c, const void* x, int xdt /*0 bf16, 1 fp32, 2 fp16*/, int B, int HW, const NormW& n, int groups, int silu, bf16_t* y,
-           GnState& g, hipStream_t s, bool out_fp8 = false, bool out_f16 = false /* y holds fp16 bits: the consumer conv runs on fp16 operands */) {
+           GnState& g, hipStream_t s, bool out_fp8, bool out_f16 /* y holds fp16 bits: the consumer conv runs on fp16 operands */) {
     const float o8 = out_fp8 ? FP8_ACT_SCALE : 0.f;       // y then holds e4m3(8 y), one byte per element
     int parts = g.parts;
     if (parts == 0) HIPCK(c, vt_launch_gn_stats(x, xdt, B, HW, n.c, groups, g.partial, &parts, s), "gn_stats");
@@ -53,6 +53,8 @@ bool conv_f16(const vt_context* c, const ConvW& w, int stride, bool has_sc) {
     if (stride == 2) return c->s2_halo && w.wp2_16 != nullptr;
     return c->use_halo_conv && w.wp && w.wp16 && !c->fuse_gn_apply && vt_conv3x3_halo_f16_supported(w.cout, c->halo_occ2, has_sc ? 1 : 0);
 }   // (conv_out, the one conv on the 32-cout GEMM tile, is decided where it is launched)
+
+namespace {
 
 // One run_conv call with the residual-stream pointers resolved by type: what each kernel family below fills its arguments from.
 struct ConvCall {
@@ -175,14 +177,9 @@ int run_conv(vt_context* c, const ConvW& w, const bf16_t* x, int B, int Hin, int
     return conv_gemm(c, k);
 }
 
-namespace {
-
-bool norm_conv_fusable(const vt_context* c, const ConvW& w, int cin) {
+static bool norm_conv_fusable(const vt_context* c, const ConvW& w, int cin) {
     return c->fuse_gn_apply && c->use_halo_conv && w.wp && w.k == 3 && cin * 8 <= 8192;
 }
-
-// what run_norm_conv's caller may ask of the conv's 16-bit output, and the shortcut to fuse
-struct NormConvOpts { const ScFuse* sc = nullptr; bool o16_e4m3 = false, o16_f16 = false, o16_planar = false; };
 
 // conv3x3(silu(GroupNorm(x))) with x fp32 (x32) or bf16 (x16).  Statistics come from the producer's epilogue
 // when available (gn.parts > 0); the normalise+SiLU runs inside the conv's halo staging when the halo kernel
@@ -190,7 +187,7 @@ struct NormConvOpts { const ScFuse* sc = nullptr; bool o16_e4m3 = false, o16_f16
 // x: the tensor to normalise (xdt 0 = bf16 conv output, 1 = fp32 / 2 = fp16 residual stream); res / oh: residual in / out (rdt).
 int run_norm_conv(vt_context* c, const NormW& n, const ConvW& w, const void* x, int xdt, int B, int H, int W,
                   int groups, bf16_t* act, const void* res, void* oh, bf16_t* o16, GnState& gn, bool want_stats,
-                  hipStream_t s, int rdt, const NormConvOpts& nc = NormConvOpts()) {
+                  hipStream_t s, int rdt, const NormConvOpts& nc) {
     const ScFuse* sc = nc.sc;
     const bool f8 = c->fp8 && w.wp8 && w.k == 3 && (!sc || sc->wp8);      // fp8 operands: the GroupNorm-apply pass writes e4m3, the conv reads it
     if (nc.o16_e4m3 && !f8) return c->fail(VT_ERR_STATE, "internal: e4m3 output requested from a bf16 conv");
@@ -214,6 +211,8 @@ int run_norm_conv(vt_context* c, const NormW& n, const ConvW& w, const void* x, 
     o.xnorm_f32 = xdt == 1 ? (const float*)x : nullptr; o.ss = gn.ss;
     return run_conv(c, w, xdt == 0 ? (const bf16_t*)x : nullptr, B, H, W, 1, 1, H, W, res, oh, o16, s, o);
 }
+
+namespace {
 
 // ---- encoder plan ---------------------------------------------------------------------------------
 struct EncPlan {

@@ -1,4 +1,6 @@
 // The vt_op_* single-layer entry points: one kernel (or one conv of the encoder's schedule) on caller-owned buffers.
+#include <algorithm>
+
 #include "vt_context.h"
 
 using namespace vt;
@@ -108,6 +110,69 @@ int vt_op_conv2d_gn(vt_context* c, const void* x, const void* w, const float* bi
     if (gn.parts == 0) return c->fail(VT_ERR_INVALID, "vt_op_conv2d_gn: this shape has no stats epilogue");
     HIPCK(c, vt_launch_gn_finalize(gn.partial, gn.parts, B, Cout, groups, eps, gamma, beta, scale_shift, s), "gn_finalize");
     return VT_OK;
+}
+
+// Upsample2D (nearest 2x + conv3x3) of the low-resolution x: the folded kernel, or with vt_set_flag(ctx, 22, 1) / a shape it refuses the
+// literal route (upsample pass + the stride-1 conv).  Scratch comes from the context's operator buffer.
+static int op_upsample2x_conv3x3(vt_context* c, const void* x, const float* w, const float* bias, float* o32, int B, int h, int wd, int C,
+                                 int groups, float eps, const float* gamma, const float* beta, float* scale_shift, hipStream_t s) {
+    if (!x || !w || !o32) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3: null buffer");
+    if (B <= 0 || h <= 0 || wd <= 0 || C < 8 || (C % 8)) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3: bad shape");
+    if ((long long)B * h * wd * C >= (1LL << 29)) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3: tensor too large for the operator entry");
+    const bool f16 = c->f16_ops != 0;
+    const bool want_gn = scale_shift != nullptr;
+    const bool folded = !c->up2_literal && vt_conv3x3_up2_supported(C, C);
+    const int cpg = want_gn ? C / groups : 0;
+    const int parts_max = std::max({vt_conv3x3_up2_tiles(h, wd), vt_conv3x3_halo_tiles_max(2 * h, 2 * wd), vt_conv_gemm_ptiles(4 * h * wd, C)});
+    const size_t gn_bytes = want_gn ? align_up((size_t)B * parts_max * groups * 3 * 4) : 0;
+    const size_t w_bytes = align_up((size_t)C * C * 16 * 2), up_bytes = align_up((size_t)B * 4 * h * wd * C * 2);
+    VTCK(ensure_op_scratch(c, gn_bytes + w_bytes + (folded ? 0 : up_bytes)));
+    char* p = (char*)c->op_scratch;
+    GnState gn; gn.partial = (float*)p; p += gn_bytes;
+    bf16_t* wp = (bf16_t*)p; p += w_bytes;
+    if (folded) {
+        HIPCK(c, vt_launch_pack_up2(w, f16 ? nullptr : wp, f16 ? (f16_t*)wp : nullptr, C, C, s), "pack_up2");
+        ConvUp2Args a{};
+        a.X = (const bf16_t*)x; a.Wp = wp; a.bias = bias; a.out_f32 = o32; a.zeros = c->zeros; a.batch = B; a.H = h; a.W = wd; a.Cin = C; a.Cout = C; a.f16 = f16;
+        if (want_gn) { a.gn_partial = gn.partial; a.gn_cpg = cpg; gn.parts = vt_conv3x3_up2_tiles(h, wd); }
+        HIPCK(c, vt_launch_conv3x3_up2(a, s), "conv3x3_up2");
+    } else {
+        bf16_t* up = (bf16_t*)p;
+        const bool halo = c->use_halo_conv && vt_conv3x3_halo_supported(C, C);
+        if (f16 && !(halo && vt_conv3x3_halo_f16_supported(C, c->halo_occ2, 0)))
+            return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3: the literal route has no fp16-operand kernel for %d channels", C);
+        HIPCK(c, vt_launch_upsample2x_nhwc16(x, up, B, h, wd, C, s), "upsample2x");
+        HIPCK(c, vt_launch_pack_f32_oihw(w, wp, C, C, halo ? 1 : 0, f16, s), "pack_f32_oihw");
+        ConvW cw; cw.cin = C; cw.cout = C; cw.k = 3; cw.b = bias;
+        if (halo) { cw.wp = wp; cw.wp16 = wp; } else cw.w = wp;
+        ConvOpts o; o.x_f16 = f16; o.groups = want_gn ? groups : 32; o.gn = want_gn ? &gn : nullptr;
+        const int saved = c->fuse_gn_stats; c->fuse_gn_stats = 1;
+        const int r = run_conv(c, cw, up, B, 2 * h, 2 * wd, 1, 1, 2 * h, 2 * wd, nullptr, o32, nullptr, s, o);
+        c->fuse_gn_stats = saved;
+        if (r) return r;
+    }
+    if (want_gn) {
+        if (gn.parts == 0) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_gn: this shape has no stats epilogue");
+        HIPCK(c, vt_launch_gn_finalize(gn.partial, gn.parts, B, C, groups, eps, gamma, beta, scale_shift, s), "gn_finalize");
+    }
+    return VT_OK;
+}
+
+int vt_op_upsample2x_conv3x3(vt_context* c, const void* x, const float* w_oihw, const float* bias, float* o32, int B, int h, int w, int C,
+                             void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    return op_upsample2x_conv3x3(c, x, w_oihw, bias, o32, B, h, w, C, 0, 0.f, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vt_op_upsample2x_conv3x3_gn(vt_context* c, const void* x, const float* w_oihw, const float* bias, float* o32, int B, int h, int w, int C,
+                                int groups, float eps, const float* gamma, const float* beta, float* scale_shift, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!gamma || !beta || !scale_shift || !bias || groups < 1 || groups > 64 || C % groups) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_gn: bad argument");
+    const int cpg = C / groups;
+    if (cpg != 4 && cpg != 8 && cpg != 16) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_gn: channels per group must be 4, 8 or 16");
+    return op_upsample2x_conv3x3(c, x, w_oihw, bias, o32, B, h, w, C, groups, eps, gamma, beta, scale_shift, (hipStream_t)stream);
 }
 
 size_t vt_op_conv3x3_fp8_workspace_bytes(int B, int H, int W, int Cin, int Cout) {

@@ -61,6 +61,27 @@ struct EncoderW {
     ConvW conv_out;
 };
 
+// The VAE's image decoder (diffusers Decoder: conv_in, mid block, up blocks with Upsample2D, conv_norm_out, conv_out).
+struct UpBlockW {
+    std::vector<ResnetW> res; bool has_up = false;
+    ConvW up;                                                    // upsamplers.0.conv as an ordinary 3x3 conv: the literal route (vt_set_flag 22)
+    const bf16_t* up_wp = nullptr; const bf16_t* up_wp16 = nullptr;   // the folded packing (conv3x3_up2.hip), bf16 / fp16 bits; null where the kernel refuses the shape
+};
+struct ImageDecoderW {
+    bool configured = false, finalized = false;
+    int out_ch = 3, latent = 16, layers = 2, groups = 32;
+    std::vector<int> block_out;
+    float scaling = 1.f, shift = 0.f;
+    bool has_scaling = false, has_shift = false;
+    ConvW conv_in;                                               // over the latent channels zero-padded to a 32-channel chunk
+    int conv_in_cin() const { return (latent + 31) / 32 * 32; }
+    ResnetW mid0, mid1;
+    AttnW attn;
+    std::vector<UpBlockW> ups;
+    NormW norm_out;
+    ConvW conv_out;                                              // zero-padded to 32 couts (the 32-cout tiles write the first out_ch as fp32 NCHW)
+};
+
 constexpr float FP8_ACT_SCALE = 8.0f;      // activations are stored as e4m3(8 x): |silu(GroupNorm)| up to 56 before saturation
 constexpr float FP8_RES_SCALE = 1.0f;      // the un-normalised residual stream feeding a stride-2 conv is stored as e4m3(x): |x| up to 448
 
@@ -73,8 +94,10 @@ struct vt_context {
     int device = 0;
     std::string err;
     std::map<std::string, vt::HostTensor> weights;
-    std::vector<void*> enc_allocs, dec_allocs;     // packed weights, freed when the model is configured again
+    std::vector<void*> enc_allocs, dec_allocs, imgdec_allocs;     // packed weights (encoder, tag decoder, image decoder), each freed when ITS model is configured again
+    vt::ImageDecoderW imgdec;
     std::vector<void*>* cur_allocs = &enc_allocs;
+    bool pack_fp8 = true;           // weights.hip: pack the e4m3 forms of the 3x3 convs too (off while the image decoder, which has no fp8 mode, is finalized)
     void* zeros = nullptr;
     int* status = nullptr;          // device word: sticky VT_STATUS_* bits raised by kernels (vt_status reads / clears it)
     vt::EncoderW enc;
@@ -104,6 +127,7 @@ struct vt_context {
     int attn_proj_kernel = 1;       // vt_set_flag(ctx, 17, v): the bf16 q | k and v^T projections on attn_qk.hip's skeleton (mode 4) instead of the generic GEMM
     int fp8_tile = 0;               // vt_set_flag(ctx, 16, v): fp8 halo conv tile shape = v & 3 (0: 8 x 32 px, 4 waves, two workgroups per CU; 1: 16 x 32 px;
                                     // 2: 8 x 64 px, 8 waves, one per CU) on the layers with Cin <= 128, or on every layer with v & 4
+    int up2_literal = 0;            // vt_set_flag(ctx, 22, v): Upsample2D as a nearest-2x pass + the stride-1 3x3 conv instead of the folded kernel (conv3x3_up2.hip)
     int s2_halo = 1;                // vt_set_flag(ctx, 13, v): stride-2 convs on the phase-plane halo kernel instead of the generic GEMM
     // vt_resize_u8: pinned staging of the coefficient tables + the event of the last H2D copy that read it
     int* rs_host = nullptr; size_t rs_host_ints = 0; hipEvent_t rs_event = nullptr;
@@ -237,6 +261,16 @@ int launch_halo(vt_context* c, const Conv3x3Args& a, hipStream_t s, const char* 
 int launch_halo_fp8(vt_context* c, const Conv3x3Fp8Args& a, hipStream_t s, const char* what);
 int run_conv(vt_context* c, const ConvW& w, const bf16_t* x, int B, int Hin, int Win, int stride, int pad, int Hout, int Wout,
              const void* res, void* oh, bf16_t* o16, hipStream_t s, const ConvOpts& o = ConvOpts());
+// y = act(GroupNorm(x)) as 16-bit rows (xdt 0 bf16, 1 fp32, 2 fp16); uses epilogue-produced partials when g.parts > 0
+int run_gn(vt_context* c, const void* x, int xdt, int B, int HW, const NormW& n, int groups, int silu, bf16_t* y, GnState& g, hipStream_t s,
+           bool out_fp8 = false, bool out_f16 = false);
+// fp16-operand mode (vt_set_flag 18): does THIS conv multiply fp16 operands?
+bool conv_f16(const vt_context* c, const ConvW& w, int stride, bool has_sc);
+// what run_norm_conv's caller may ask of the conv's 16-bit output, and the shortcut to fuse
+struct NormConvOpts { const ScFuse* sc = nullptr; bool o16_e4m3 = false, o16_f16 = false, o16_planar = false; };
+// conv3x3(silu(GroupNorm(x))): x is the tensor to normalise (xdt), res / oh the residual in / out (rdt), o16 an optional 16-bit copy
+int run_norm_conv(vt_context* c, const NormW& n, const ConvW& w, const void* x, int xdt, int B, int H, int W, int groups, bf16_t* act,
+                  const void* res, void* oh, bf16_t* o16, GnState& gn, bool want_stats, hipStream_t s, int rdt, const NormConvOpts& nc = NormConvOpts());
 
 // ---- attention.hip --------------------------------------------------------------------------------
 struct AttnScratch {

@@ -62,8 +62,9 @@ constexpr int VT_PROF_PROJ_FP8 = 18;     // fp8 mode's q | k and v projections (
 constexpr int VT_PROF_HALO_FP8_C128 = 19; // the fp8 halo conv's launches with Cin <= 128 (18 K-steps per tile), same kernel name as slot 11: tools read them apart
 constexpr int VT_PROF_PROJ_BF16 = 20;    // bf16 q | k and v^T projections on attn_qk_kernel<4> (round 4)
 constexpr int VT_PROF_CONV_OUT = 21;     // conv_out on its 32-cout halo tile (conv_out_halo.hip, round 4)
-constexpr int VT_PROF_GN_APPLY = 22;     // HBM-bound GroupNorm(+SiLU) apply pass: 'flops' slot carries algorithmic BYTES (last slot)
-constexpr int VT_NUM_PROF_SLOTS = 23;
+constexpr int VT_PROF_UP2 = 22;          // folded Upsample2D conv of the image decoder (conv3x3_up2.hip): FLOPs counted at 4 taps per output pixel
+constexpr int VT_PROF_GN_APPLY = 23;     // HBM-bound GroupNorm(+SiLU) apply pass: 'flops' slot carries algorithmic BYTES (last slot)
+constexpr int VT_NUM_PROF_SLOTS = 24;
 
 // Q.K^T of the mid-block attention with the softmax numerators in the epilogue (attn_qk.hip; d = 512 only)
 struct AttnQkArgs {
@@ -207,6 +208,29 @@ bool vt_conv3x3_halo_f16_supported(int Cout, int occ2, int has_sc);
 int vt_conv3x3_halo_config(const Conv3x3Args& a);
 hipError_t vt_launch_conv3x3_halo(const Conv3x3Args& a, hipStream_t s);
 hipError_t vt_launch_repack_ohwi_to_halo(const bf16_t* w_ohwi, bf16_t* wp, int Cin, int Cout, hipStream_t s);
+
+// Upsample2D: nearest-neighbour 2x + 3x3 stride-1 pad-1 conv folded into four 2x2 phase convs of the low-resolution input (conv3x3_up2.hip)
+struct ConvUp2Args {
+    const bf16_t* X;        // NHWC 16-bit [batch][H][W][Cin], LOW resolution (bf16, or fp16 bits with f16)
+    const bf16_t* Wp;       // folded packing [Cin/32][phase * 4 + tap][Cout rows (vt_halo_row_of_cout)][32] (vt_launch_pack_up2), same type as X
+    const float* bias;      // [Cout] or null
+    float* out_f32; f16_t* out_f16;        // the residual stream [batch][2H][2W][Cout], fp32 or fp16 (at least one output of the three)
+    bf16_t* out_16; int out16_f16;         // optional 16-bit operand copy (bf16, or fp16 bits with out16_f16)
+    const void* zeros;
+    float* gn_partial; int gn_cpg;         // optional [batch][tiles][Cout/gn_cpg][3] (n, mean, M2) of the output; gn_cpg 4, 8 or 16
+    int batch, H, W, Cin, Cout;
+    int f16;
+    int tiles_x, ptiles, ctiles;           // filled by the launcher
+};
+bool vt_conv3x3_up2_supported(int Cin, int Cout);
+int vt_conv3x3_up2_tiles(int H, int W);                   // GroupNorm partials per image its epilogue writes (H, W: low resolution)
+hipError_t vt_launch_conv3x3_up2(const ConvUp2Args& a, hipStream_t s);
+// fp32 OIHW [Cout][Cin][3][3] (device) -> the folded packing; either copy may be null
+hipError_t vt_launch_pack_up2(const float* w_oihw, bf16_t* wp_bf16, f16_t* wp_f16, int Cin, int Cout, hipStream_t s);
+// fp32 OIHW 3x3 (device) -> 16-bit operands of the stride-1 kernels: layout 0 = [Cout][tap][Cin], 1 = conv3x3_halo.hip's packing; f16 = fp16 bits
+hipError_t vt_launch_pack_f32_oihw(const float* w_oihw, bf16_t* dst, int Cin, int Cout, int layout, int f16, hipStream_t s);
+// nearest-neighbour 2x of NHWC 16-bit rows [B][H][W][C] -> [B][2H][2W][C] (C % 8 == 0): the literal route's intermediate tensor
+hipError_t vt_launch_upsample2x_nhwc16(const void* x, void* y, int B, int H, int W, int C, hipStream_t s);
 
 // 3x3 stride-2 conv with Downsample2D's (0,1,0,1) padding, phase-plane halo kernel (conv3x3_s2_halo.hip): out = W . x + bias (+ res)
 struct Conv3x3S2Args {

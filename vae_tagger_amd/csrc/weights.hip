@@ -1,5 +1,7 @@
 // Weight packing (host code): number conversions, the operand layouts of every conv / attention kernel, vt_encoder_finalize.
 #include <math.h>
+
+#include <algorithm>
 #include <string.h>
 
 #include "vt_context.h"
@@ -127,7 +129,7 @@ static int get_conv(vt_context* c, const std::string& name, int cout, int cin, i
     }
     if (out->wp && !up(c, &out->wp16, permute_weights<uint16_t>(wv, cout, cin, 9, 32, step_halo, row64, to_f16))) return failed();
     if (out->wp2 && !up(c, &out->wp2_16, permute_weights<uint16_t>(wv, cout, cin, 9, 32, step_s2, row64, to_f16))) return failed();
-    if (k == 3 && vt_conv3x3_halo_fp8_supported(cin, cout)) {
+    if (k == 3 && c->pack_fp8 && vt_conv3x3_halo_fp8_supported(cin, cout)) {
         const ConvE4m3 p = pack_conv_e4m3(wv, cout, cin, stride2 && vt_conv3x3_s2_fp8_supported(cin, cout));
         if (!up(c, &out->wp8, p.wp8) || !up(c, &out->mult8, p.mult8) || !up(c, &out->w8g, p.w8g) || !up(c, &out->mult8g, p.mult8g)) return failed();
         if (!p.wp8s2.empty() && !up(c, &out->wp8s2, p.wp8s2)) return failed();
@@ -285,5 +287,104 @@ extern "C" int vt_encoder_finalize(vt_context* c) {
     for (auto it = c->weights.begin(); it != c->weights.end();)
         it = (it->first.compare(0, 8, "encoder.") == 0) ? c->weights.erase(it) : ++it;
     e.finalized = true;
+    return VT_OK;
+}
+
+// ---- the VAE's image decoder ----------------------------------------------------------------------
+// upsamplers.0.conv: the ordinary packings (the literal route) and, where conv3x3_up2.hip takes the shape, the folded one -- packed on the
+// device from the fp32 OIHW tensor into a bf16 and an fp16 copy
+static int get_upsample_conv(vt_context* c, const std::string& name, int ch, UpBlockW* u) {
+    VTCK(get_conv(c, name, ch, ch, 3, &u->up));
+    if (!vt_conv3x3_up2_supported(ch, ch)) return VT_OK;
+    const HostTensor* w = c->find(name + ".weight");
+    const size_t n = (size_t)ch * ch * 9, nf = (size_t)ch * ch * 16;
+    float* tmp = nullptr;
+    void *p16 = nullptr, *ph = nullptr;
+    if (hipMalloc(&p16, nf * 2) != hipSuccess) return c->fail(VT_ERR_HIP, "upload failed for %s", name.c_str());
+    c->cur_allocs->push_back(p16);
+    if (hipMalloc(&ph, nf * 2) != hipSuccess) return c->fail(VT_ERR_HIP, "upload failed for %s", name.c_str());
+    c->cur_allocs->push_back(ph);
+    if (hipMalloc((void**)&tmp, n * 4) != hipSuccess) return c->fail(VT_ERR_HIP, "upload failed for %s", name.c_str());
+    hipError_t e = hipMemcpy(tmp, w->v.data(), n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = vt_launch_pack_up2(tmp, (bf16_t*)p16, (f16_t*)ph, ch, ch, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(tmp);
+    if (e != hipSuccess) return c->hipfail(e, "pack_up2");
+    u->up_wp = (const bf16_t*)p16; u->up_wp16 = (const bf16_t*)ph;
+    return VT_OK;
+}
+
+static int finalize_image_decoder(vt_context* c, ImageDecoderW& d) {
+    const int nb = (int)d.block_out.size(), C = d.block_out.back();
+    {   // conv_in: the latent channels zero-padded to a 32-channel chunk, so that it runs on the halo conv (and on fp16 operands with flag 18)
+        const int Lp = (d.latent + 31) / 32 * 32;
+        const HostTensor* w = c->find("decoder.conv_in.weight");
+        const HostTensor* b = c->find("decoder.conv_in.bias");
+        if (!w || !b) return c->fail(VT_ERR_MISSING_WEIGHT, "missing weight decoder.conv_in.{weight,bias}");
+        if (w->numel() != (int64_t)C * d.latent * 9 || b->numel() != C) return c->fail(VT_ERR_INVALID, "shape mismatch for decoder.conv_in");
+        HostTensor wpad;
+        wpad.shape = {C, Lp, 3, 3}; wpad.v.assign((size_t)C * Lp * 9, 0.f);
+        for (int o = 0; o < C; ++o) std::copy(w->v.begin() + (size_t)o * d.latent * 9, w->v.begin() + (size_t)(o + 1) * d.latent * 9, wpad.v.begin() + (size_t)o * Lp * 9);
+        HostTensor bias = *b;
+        c->weights["decoder.conv_in.padded.weight"] = std::move(wpad);
+        c->weights["decoder.conv_in.padded.bias"] = std::move(bias);
+        VTCK(get_conv(c, "decoder.conv_in.padded", C, Lp, 3, &d.conv_in));
+    }
+    VTCK(get_resnet(c, "decoder.mid_block.resnets.0", C, C, &d.mid0));
+    VTCK(get_attention(c, "decoder.mid_block.attentions.0", C, &d.attn));
+    VTCK(get_resnet(c, "decoder.mid_block.resnets.1", C, C, &d.mid1));
+    int ci = C;
+    for (int i = 0; i < nb; ++i) {
+        UpBlockW u;
+        const int co = d.block_out[nb - 1 - i];
+        for (int j = 0; j < d.layers + 1; ++j) {
+            ResnetW rw;
+            char nm[128]; snprintf(nm, sizeof nm, "decoder.up_blocks.%d.resnets.%d", i, j);
+            VTCK(get_resnet(c, nm, ci, co, &rw));
+            u.res.push_back(rw);
+            ci = co;
+        }
+        if (i + 1 < nb) {
+            char nm[128]; snprintf(nm, sizeof nm, "decoder.up_blocks.%d.upsamplers.0.conv", i);
+            VTCK(get_upsample_conv(c, nm, co, &u));
+            u.has_up = true;
+        }
+        d.ups.push_back(u);
+    }
+    VTCK(get_norm(c, "decoder.conv_norm_out", ci, &d.norm_out));
+    // conv_out (ci -> out_ch <= 32) rides the encoder's 32-cout conv_out tiles: rows [out_ch, 32) of the weight and the bias are zero
+    const HostTensor* w = c->find("decoder.conv_out.weight");
+    const HostTensor* b = c->find("decoder.conv_out.bias");
+    if (!w || !b) return c->fail(VT_ERR_MISSING_WEIGHT, "missing weight decoder.conv_out.{weight,bias}");
+    if (w->numel() != (int64_t)d.out_ch * ci * 9 || b->numel() != d.out_ch) return c->fail(VT_ERR_INVALID, "shape mismatch for decoder.conv_out");
+    HostTensor wpad, bpad;
+    wpad.shape = {32, ci, 3, 3}; wpad.v.assign((size_t)32 * ci * 9, 0.f);
+    std::copy(w->v.begin(), w->v.end(), wpad.v.begin());
+    bpad.shape = {32}; bpad.v.assign(32, 0.f);
+    std::copy(b->v.begin(), b->v.end(), bpad.v.begin());
+    c->weights["decoder.conv_out.padded.weight"] = std::move(wpad);
+    c->weights["decoder.conv_out.padded.bias"] = std::move(bpad);
+    return get_conv(c, "decoder.conv_out.padded", 32, ci, 3, &d.conv_out);
+}
+
+extern "C" int vt_image_decoder_finalize(vt_context* c) {
+    if (!c) return VT_ERR_INVALID;
+    ImageDecoderW& d = c->imgdec;
+    if (!d.configured) return c->fail(VT_ERR_STATE, "vt_image_decoder_configure was not called");
+    DeviceGuard guard(c);
+    // as vt_encoder_finalize: until THIS call succeeds the decoder is "not finalized" and no pointer of an earlier packing survives
+    d.finalized = false;
+    d.conv_in = ConvW(); d.mid0 = ResnetW(); d.mid1 = ResnetW(); d.attn = AttnW(); d.ups.clear(); d.norm_out = NormW(); d.conv_out = ConvW();
+    c->free_allocs(c->imgdec_allocs);
+    std::vector<void*>* const saved = c->cur_allocs;
+    c->cur_allocs = &c->imgdec_allocs;
+    c->pack_fp8 = false;                                  // decode has no fp8 mode
+    const int r = finalize_image_decoder(c, d);
+    c->pack_fp8 = true;
+    c->cur_allocs = saved;
+    for (auto it = c->weights.begin(); it != c->weights.end();)
+        it = (it->first.compare(0, 8, "decoder.") == 0) ? c->weights.erase(it) : ++it;
+    if (r) return r;
+    d.finalized = true;
     return VT_OK;
 }

@@ -38,7 +38,10 @@ def load_diffusers_vae_from_config(config_dict, model_path=None):
             # checkpoint code and accepts tensor-only files
             state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
         missing_keys, unexpected_keys = vae.load_state_dict(state_dict, strict=False)
-        # the HIP object holds encoder tensors only: decoder.* / post_quant_conv.* are expected extras
+        # the object's own state dict holds encoder tensors only: decoder.* / post_quant_conv.* are reported as extras, as before;
+        # the decoder.* tensors then go to the image decoder
+        if any(k.startswith("decoder.") for k in state_dict):
+            vae.load_decoder_state_dict(state_dict, strict=False)
         if missing_keys:
             print(f"缺失的键: {missing_keys}")
         if unexpected_keys:
@@ -79,7 +82,15 @@ class DiffusersVAEWrapper(torch.nn.Module):
         self.vae = vae_model
 
     def forward(self, x):
-        raise NotImplementedError("reconstruction needs the VAE decoder, which is outside the inference hot path")
+        posterior = self.vae.encode(x).latent_dist
+        z = posterior.sample()
+        reconstruction = self.vae.decode(z).sample
+        self._raise_on_status()
+        return reconstruction, posterior
+
+    def _raise_on_status(self):
+        if self.check_finite and isinstance(self.vae, AutoencoderKL) and not self.vae.check_finite:
+            self.vae.raise_on_status()
 
     def encode(self, x):
         if isinstance(self.vae, AutoencoderKL):
@@ -97,7 +108,16 @@ class DiffusersVAEWrapper(torch.nn.Module):
         return latent
 
     def decode(self, z):
-        raise NotImplementedError("the VAE decoder is outside the inference hot path")
+        if isinstance(self.vae, AutoencoderKL):
+            # fused: (z - shift_factor) / scaling_factor in IEEE fp32 while the latents are staged for conv_in
+            image = self.vae.decode_unscaled(z)
+            self._raise_on_status()
+            return image
+        if getattr(self.vae.config, "shift_factor", None) is not None:
+            z = z - self.vae.config.shift_factor
+        if getattr(self.vae.config, "scaling_factor", None) is not None:
+            z = z / self.vae.config.scaling_factor
+        return self.vae.decode(z).sample
 
 
 def create_vae_from_config_file(config_path, model_path=None):

@@ -71,6 +71,56 @@ def encoder_manifest(block_out=FLUX_BLOCK_OUT, in_channels=FLUX_IN_CHANNELS,
     return m
 
 
+def image_decoder_manifest(block_out=FLUX_BLOCK_OUT, out_channels=FLUX_IN_CHANNELS,
+                           latent_channels=FLUX_LATENT_CHANNELS,
+                           layers_per_block=FLUX_LAYERS_PER_BLOCK):
+    """Ordered {key: shape} of every tensor of the VAE's image decoder in diffusers AutoencoderKL naming
+    (`decoder.*`: conv_in, mid block, up blocks over block_out reversed with layers_per_block + 1 resnets each, conv_norm_out, conv_out)."""
+    m = {}
+
+    def conv(name, co, ci, k):
+        m[name + ".weight"] = (co, ci, k, k)
+        m[name + ".bias"] = (co,)
+
+    def norm(name, c):
+        m[name + ".weight"] = (c,)
+        m[name + ".bias"] = (c,)
+
+    def lin(name, co, ci):
+        m[name + ".weight"] = (co, ci)
+        m[name + ".bias"] = (co,)
+
+    def resnet(name, ci, co):
+        norm(name + ".norm1", ci)
+        conv(name + ".conv1", co, ci, 3)
+        norm(name + ".norm2", co)
+        conv(name + ".conv2", co, co, 3)
+        if ci != co:
+            conv(name + ".conv_shortcut", co, ci, 1)
+
+    c = block_out[-1]
+    conv("decoder.conv_in", c, latent_channels, 3)
+    resnet("decoder.mid_block.resnets.0", c, c)
+    a = "decoder.mid_block.attentions.0"
+    norm(a + ".group_norm", c)
+    lin(a + ".to_q", c, c)
+    lin(a + ".to_k", c, c)
+    lin(a + ".to_v", c, c)
+    lin(a + ".to_out.0", c, c)
+    resnet("decoder.mid_block.resnets.1", c, c)
+    ci = c
+    rev = tuple(reversed(tuple(block_out)))
+    for i, co in enumerate(rev):
+        for j in range(layers_per_block + 1):
+            resnet(f"decoder.up_blocks.{i}.resnets.{j}", ci, co)
+            ci = co
+        if i != len(rev) - 1:
+            conv(f"decoder.up_blocks.{i}.upsamplers.0.conv", co, co, 3)
+    norm("decoder.conv_norm_out", ci)
+    conv("decoder.conv_out", out_channels, ci, 3)
+    return m
+
+
 def attention_decoder_manifest(num_classes, latent_channels=16, use_spatial_attention=True,
                                use_self_attention=True, use_cross_attention=False):
     """{key: shape} of reference AttentionClassificationDecoder (modules.py:358-422)."""
