@@ -590,6 +590,51 @@ size_t vt_decode_image_workspace_bytes(const vt_context* ctx, int B, int h, int 
 int vt_decode_image(vt_context* ctx, const float* z_nchw, int B, int h, int w, int unscale, float* image_out, size_t image_bytes,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- VAE validation loss <- the validation loops of train_vae.py:216-268 and train_full.py:290-338 with the losses of
+ * improved_losses.py (ImprovedTripletLoss :81-105, ContrastiveLoss :13-37, CombinedLoss' reconstruction and KL :277-287).  Forward only.
+ * Same contract as vt_loss_*: one caller-owned device block (256-B aligned), every size checked on the host before anything is
+ * launched -- an undersized buffer is VT_ERR_WORKSPACE, a null / misaligned pointer or an out-of-range argument VT_ERR_INVALID, and
+ * nothing is written --, no host synchronisation, no atomics, every sum in fp64 from the fp32 inputs in an order fixed by the shapes
+ * alone (partials per 4096 elements, added in index order by a second launch): bit-identical from run to run.
+ *
+ * vt_posterior_sample: moments fp32 NCHW [B][2C][hw] (mean | logvar, vt_encode mode 0); logvar is clamped to [-30, 20].
+ *   z_out (fp32 [B][C][hw], may be NULL) = mean + std eps with std = fp32(exp(0.5 logvar)) and one fp32 multiply and one fp32 add;
+ *   kl_out (fp64 [B], may be NULL) = 0.5 sum(mean^2 + var - 1 - logvar).  eps is a counter-based standard normal keyed on
+ *   (seed, draw) and (first_image + b, element index within the image): two 64-bit words of vt_head_mix64, u1 = ((x1 >> 11) + 1) 2^-53
+ *   in (0, 1], u2 = (x2 >> 11) 2^-53, eps = fp32(sqrt(-2 ln u1) cos(2 pi u2)) evaluated in fp64.  An image's noise depends on its
+ *   global index, not on the batching.
+ * vt_vae_loss_update: anchor / positive / negative (negative may be NULL: contrastive only) each give `z` fp32 [B][C][hw], or
+ *   `moments` to sample z in flight with (seed of reset, draw, first_image) -- the same bits vt_posterior_sample writes, never stored --,
+ *   or both (z is used, moments give the KL).  moments == NULL: that stream contributes no KL (kl_mean divides by the streams that do).
+ *   recon and target fp32 [B][3][H][W], both or neither; labels_a and labels_p [B][N] VT_F32 or VT_U8, both or neither (then N = 0).
+ *   Per image i (row of rows_out, fp64 [B][VT_VAE_LOSS_ROW], may be NULL):
+ *     0 mse | 1 kl_a | 2 kl_p | 3 kl_n | 4 kl_mean | 5 log1p(kl_mean / 10000) | 6 pos cosine distance | 7 neg cosine distance |
+ *     8 pos euclidean distance | 9 neg euclidean distance | 10 triplet (cosine) | 11 triplet (euclidean) | 12 contrastive (cosine) |
+ *     13 contrastive (euclidean) | 14 sum labels_a | 15 overlap | 16 union | 17 triplet weight | 18 label similarity
+ *   cosine distance = 1 - a.p / (max(|a|, 1e-12) max(|p|, 1e-12)); euclidean = sqrt(sum (a - p + 1e-6)^2);
+ *   triplet = max(pos - neg + margin_triplet, 0) (1 + 0.5 overlap / (sum labels_a + 1e-8)) (weight 1 without labels);
+ *   contrastive, with s = overlap / (union + 1e-8): s > jaccard_threshold ? s pos^2 : (1 - s) max(margin_contrastive - pos, 0)^2.
+ *   Block: params { fp64 margin_triplet, margin_contrastive, jaccard_threshold, uint64 seed } at 0 | totals at 256 { fp64 [7] sums over
+ *   the updates of the per-batch components (mse, kl_mean, log1p(kl_mean / 10000) of the BATCH's kl_mean, triplet cos, triplet euclid,
+ *   contrastive cos, contrastive euclid: each the mean over the batch), fp64 [7] sums over the images of the per-image values, added
+ *   one image after the other -- independent of the batching --, uint64 [7] updates, images, non-finite inputs, updates with recon,
+ *   images with recon, updates with a negative, images with a negative } | scratch of the last update from 512.
+ * vt_vae_loss_state_bytes: the block for updates of up to B images of C x hw latents and H x W images; 0 if out of range.
+ * vt_vae_loss_read copies the first VT_VAE_LOSS_HEAD_BYTES bytes (params and totals) in stream order into device or pinned host memory. */
+#define VT_VAE_LOSS_ROW 19
+#define VT_VAE_LOSS_HEAD_BYTES 512
+typedef struct { const float* moments; const float* z; int draw; } vt_vae_loss_input;
+int vt_posterior_sample(vt_context* ctx, const float* moments, int B, int C, int hw, unsigned long long seed, int draw,
+                        long long first_image, float* z_out, double* kl_out, void* stream);
+size_t vt_vae_loss_state_bytes(int B, int C, int hw, int H, int W);
+int vt_vae_loss_reset(vt_context* ctx, void* state, size_t state_bytes, double margin_triplet, double margin_contrastive,
+                      double jaccard_threshold, unsigned long long seed, void* stream);
+int vt_vae_loss_update(vt_context* ctx, void* state, size_t state_bytes, const vt_vae_loss_input* anchor, const vt_vae_loss_input* positive,
+                       const vt_vae_loss_input* negative /* or NULL */, const float* recon, const float* target, int H, int W,
+                       const void* labels_a, const void* labels_p, int labels_dtype /* VT_F32 | VT_U8 */, int N, int B, int C, int hw,
+                       long long first_image, double* rows_out /* [B][VT_VAE_LOSS_ROW] or NULL */, void* stream);
+int vt_vae_loss_read(vt_context* ctx, const void* state, size_t state_bytes, void* out, size_t out_bytes, void* stream);
+
 /* ---- single operators (parity tests drive each kernel through the same ABI) ------------------
  * NHWC bf16 activations, weights in the reference's own layouts (fp32 host order is converted by
  * the caller to bf16 [Cout][kh][kw][Cin]); fp32 accumulate.

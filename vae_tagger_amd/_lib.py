@@ -38,6 +38,14 @@ class LossSource(_c.Structure):
     _fields_ = [("state", _vp), ("state_bytes", _sz), ("alpha", _c.c_double), ("gamma", _c.c_double), ("class_weights", _vp)]
 
 
+class VAELossInput(_c.Structure):
+    """vt_vae_loss_input: one of anchor / positive / negative -- its moments, its latent, or both, and the draw of an in-flight sample."""
+    _fields_ = [("moments", _vp), ("z", _vp), ("draw", _i)]
+
+
+VAE_LOSS_ROW, VAE_LOSS_HEAD_BYTES = 19, 512              # VT_VAE_LOSS_ROW, VT_VAE_LOSS_HEAD_BYTES
+
+
 # name -> (restype, argtypes); every symbol include/vae_tagger_hip.h declares
 PROTOTYPES = {
     "vt_version": (_c.c_char_p, []),
@@ -137,6 +145,12 @@ PROTOTYPES = {
     "vt_image_decoder_finalize": (_i, [_vp]),
     "vt_decode_image_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "vt_decode_image": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "vt_posterior_sample": (_i, [_vp, _vp, _i, _i, _i, _c.c_ulonglong, _i, _ll, _vp, _vp, _vp]),
+    "vt_vae_loss_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "vt_vae_loss_reset": (_i, [_vp, _vp, _sz, _c.c_double, _c.c_double, _c.c_double, _c.c_ulonglong, _vp]),
+    "vt_vae_loss_update": (_i, [_vp, _vp, _sz, _c.POINTER(VAELossInput), _c.POINTER(VAELossInput), _c.POINTER(VAELossInput), _vp, _vp, _i, _i,
+                                _vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _vp]),
+    "vt_vae_loss_read": (_i, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "vt_encoder_flops":(_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),

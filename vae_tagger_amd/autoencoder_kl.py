@@ -19,8 +19,9 @@ import ctypes
 class DiagonalGaussianDistribution:
     """moments = [mean | logvar] along dim 1; logvar clamped to [-30, 20] as diffusers does."""
 
-    def __init__(self, parameters):
+    def __init__(self, parameters, context=None):
         self.parameters = parameters
+        self._ctx = context
         self.mean, self.logvar = torch.chunk(parameters, 2, dim=1)
         self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
         self.std = torch.exp(0.5 * self.logvar)
@@ -38,6 +39,33 @@ class DiagonalGaussianDistribution:
             return 0.5 * torch.sum(self.mean.pow(2) + self.var - 1.0 - self.logvar, dim=[1, 2, 3])
         return 0.5 * torch.sum((self.mean - other.mean).pow(2) / other.var + self.var / other.var
                                - 1.0 - self.logvar + other.logvar, dim=[1, 2, 3])
+
+    # -- the device forms (vt_posterior_sample): one launch each over the moments, no temporaries, no torch random stream --------------
+    def _posterior_call(self, seed, draw, first_image, want_z, want_kl):
+        m = self.parameters
+        if m.device.type != "cuda":
+            raise _lib.VTError("sample_device() / kl_device() run on a HIP device; sample() / kl() are the torch forms")
+        if self._ctx is None or self._ctx.device_index != m.device.index:
+            self._ctx = _lib.Context(m.device.index if m.device.index is not None else torch.cuda.current_device())
+        m = m.detach().to(torch.float32).contiguous()
+        B, C2 = m.shape[0], m.shape[1]
+        hw = 1
+        for s in m.shape[2:]:
+            hw *= int(s)
+        z = torch.empty((B, C2 // 2) + tuple(m.shape[2:]), dtype=torch.float32, device=m.device) if want_z else None
+        kl = torch.empty(B, dtype=torch.float64, device=m.device) if want_kl else None
+        self._ctx.call("vt_posterior_sample", vp(m), B, C2 // 2, hw, int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw), int(first_image), vp(z), vp(kl),
+                       stream_ptr(m.device))
+        return z, kl
+
+    def sample_device(self, seed, draw=0, first_image=0):
+        """mean + std * eps with a counter-based standard normal keyed on (seed, draw) and on (first_image + b, element): the noise of an
+        image depends on its global index, not on the batching, and no generator state is kept.  improved_losses.sample_elements mirrors it."""
+        return self._posterior_call(seed, draw, first_image, True, False)[0]
+
+    def kl_device(self):
+        """kl() against the standard normal, summed in fp64 on the device: a float64 tensor [B]."""
+        return self._posterior_call(0, 0, 0, False, True)[1]
 
 
 class AutoencoderKLOutput:
@@ -140,7 +168,7 @@ class AutoencoderKL(HipModule):
     @torch.no_grad()
     def encode(self, x, return_dict=True):
         moments = self._run_encode(x, _lib.ENCODE_MOMENTS)
-        out = AutoencoderKLOutput(DiagonalGaussianDistribution(moments))
+        out = AutoencoderKLOutput(DiagonalGaussianDistribution(moments, self._ctx))
         return out if return_dict else (out.latent_dist,)
 
     @torch.no_grad()

@@ -1,0 +1,480 @@
+// VAE validation loss on the device: posterior.sample() / .kl() and the per-batch loss of the reference's VAE validation loops
+// (train_vae.py:216-268, train_full.py:290-338; improved_losses.py:13-37, :81-105, :277-287), accumulated in one caller-owned block.
+// Forward only.  Every sum is fp64 from the fp32 inputs.  No atomics: a workgroup owns 4096 consecutive elements of one image (thread t
+// takes the four float4 at 4t, 4t + 1024, ...), its 256 threads are combined by a wave tree and the four waves in wave order; a second
+// launch adds an image's partials in index order (lane l takes l, l + 64, ...; wave tree) and forms the per-image row; a third, one-wave
+// launch adds the rows one image after the other.  The order of every sum is a function of the shapes alone.
+// The latent pass reads the three moments tensors once and writes partials only: z = mean + std eps is formed in registers by the same
+// device function vt_posterior_sample stores it with, so the in-flight state is the given-z state bit for bit.
+#include <math.h>
+
+#include "vt_context.h"
+#include "vt_vae_loss.h"
+
+using namespace vt;
+
+namespace {
+
+constexpr int VL_T = 256;                   // threads of a partial's workgroup
+constexpr int VL_STEP = 4 * VL_T;           // elements one sweep of the workgroup covers
+constexpr int VL_SWEEPS = VT_VAE_CHUNK / VL_STEP;
+constexpr int VL_KL_T = 1024;               // vt_posterior_sample's kl_out: one workgroup per image
+
+struct VaeStream { const float* moments; const float* z; int draw; int present; };
+struct VaeLatentArg { VaeStream s[3]; };
+
+__device__ __forceinline__ bool vl_bad(float x) { return !(fabsf(x) <= 3.0e38f); }
+
+// the element's standard normal: Box-Muller in fp64 on two words of the image key, rounded to fp32 once
+__device__ __forceinline__ float vae_eps(uint64_t image_key, uint64_t e) {
+#pragma clang fp contract(off)
+    const uint64_t x1 = vt_head_mix64(image_key ^ (2 * e)), x2 = vt_head_mix64(image_key ^ (2 * e + 1));
+    const double u1 = (double)((x1 >> 11) + 1) * 0x1p-53, u2 = (double)(x2 >> 11) * 0x1p-53;
+    return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+}
+
+// z = mean + fp32(exp(0.5 logvar)) eps in explicit fp32 steps, and the element's KL term mean^2 + var - 1 - logvar (var = std^2, fp64).
+// A NaN logvar stays NaN through the clamp, as torch.clamp keeps it.
+__device__ __forceinline__ float vae_z(float mean, float logvar, float eps, double& kl_term) {
+#pragma clang fp contract(off)
+    const float lc = logvar < -30.0f ? -30.0f : (logvar > 20.0f ? 20.0f : logvar);
+    const double sd = exp(0.5 * (double)lc);
+    kl_term = (double)mean * (double)mean + sd * sd - 1.0 - (double)lc;
+    return __fadd_rn(mean, __fmul_rn((float)sd, eps));
+}
+
+// four consecutive floats from e0 (a multiple of 4): one 16-byte load, or guarded scalar loads with the same element-to-thread mapping
+template <bool VEC>
+__device__ __forceinline__ void vl_load4(const float* __restrict__ p, long long e0, long long n, float out[4]) {
+    if (VEC) {
+        const float4 v = *(const float4*)(p + e0);
+        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[k] = e0 + k < n ? p[e0 + k] : 0.0f;
+    }
+}
+
+// the workgroup's NV running sums -> partial[0 .. NV-1] and the non-finite count -> partial[NV] (as uint64): wave tree, then waves in order
+template <int NV>
+__device__ __forceinline__ void vl_block_fold(double (&acc)[NV], unsigned bad, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    __shared__ double s_red[VL_T / 64][NV];
+    __shared__ unsigned s_bad[VL_T / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        for (int d = 32; d > 0; d >>= 1) acc[i] += __shfl_down(acc[i], d);
+    for (int d = 32; d > 0; d >>= 1) bad += __shfl_down(bad, d);
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) s_red[wave][i] = acc[i];
+        s_bad[wave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        double v = s_red[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < VL_T / 64; ++w) v += s_red[w][threadIdx.x];
+        partial[threadIdx.x] = v;
+    } else if (threadIdx.x == NV) {
+        unsigned long long b = 0;
+#pragma unroll
+        for (int w = 0; w < VL_T / 64; ++w) b += s_bad[w];
+        ((unsigned long long*)partial)[NV] = b;
+    }
+}
+
+// grid (chunks of D, B).  partial: aa pp nn ap an dap dan kl_a kl_p kl_n | non-finite
+template <bool VEC>
+__global__ __launch_bounds__(VL_T) void vae_latent_kernel(VaeLatentArg a, const double* __restrict__ params, long long D, long long first_image,
+                                                          long long chunks, double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    const long long b = blockIdx.y, chunk = blockIdx.x;
+    const unsigned long long seed = ((const unsigned long long*)params)[3];
+    uint64_t key[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) key[s] = vt_vae_image_key(vt_vae_stream_key(seed, (uint64_t)(int64_t)a.s[s].draw), (uint64_t)(first_image + b));
+    const bool has_n = a.s[2].present != 0;
+    double acc[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) acc[i] = 0.0;
+    unsigned bad = 0;
+    for (int j = 0; j < VL_SWEEPS; ++j) {
+        const long long e0 = chunk * VT_VAE_CHUNK + (long long)j * VL_STEP + 4 * (long long)threadIdx.x;
+        if (e0 >= D) break;
+        float z[3][4];
+        double kt[3][4];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { z[s][k] = 0.0f; kt[s][k] = 0.0; }
+            if (!a.s[s].present) continue;
+            float mean[4], lv[4];
+            if (a.s[s].moments) {
+                const float* m = a.s[s].moments + 2 * b * D;
+                vl_load4<VEC>(m, e0, D, mean);
+                vl_load4<VEC>(m + D, e0, D, lv);
+            }
+            if (a.s[s].z) vl_load4<VEC>(a.s[s].z + b * D, e0, D, z[s]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (e0 + k >= D) continue;
+                if (a.s[s].moments) {
+                    const float eps = a.s[s].z ? 0.0f : vae_eps(key[s], (uint64_t)(e0 + k));
+                    const float zs = vae_z(mean[k], lv[k], eps, kt[s][k]);
+                    if (!a.s[s].z) z[s][k] = zs;
+                    bad += (vl_bad(mean[k]) ? 1u : 0u) + (vl_bad(lv[k]) ? 1u : 0u);
+                }
+                bad += vl_bad(z[s][k]) ? 1u : 0u;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (e0 + k >= D) continue;
+            const double va = (double)z[0][k], vp = (double)z[1][k], vn = (double)z[2][k];
+            const double dp = va - vp + 1e-6;
+            acc[0] += va * va; acc[1] += vp * vp; acc[3] += va * vp; acc[5] += dp * dp;
+            if (has_n) {
+                const double dn = va - vn + 1e-6;
+                acc[2] += vn * vn; acc[4] += va * vn; acc[6] += dn * dn;
+            }
+            acc[7] += kt[0][k]; acc[8] += kt[1][k]; acc[9] += kt[2][k];
+        }
+    }
+    vl_block_fold<10>(acc, bad, partials + VT_VAE_LAT_PART * (b * chunks + chunk));
+}
+
+// grid (chunks of E, B).  partial: sum (recon - target)^2 | non-finite
+template <bool VEC>
+__global__ __launch_bounds__(VL_T) void vae_image_kernel(const float* __restrict__ recon, const float* __restrict__ target, long long E, long long chunks,
+                                                         double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    const long long b = blockIdx.y, chunk = blockIdx.x;
+    double acc[1] = {0.0};
+    unsigned bad = 0;
+    for (int j = 0; j < VL_SWEEPS; ++j) {
+        const long long e0 = chunk * VT_VAE_CHUNK + (long long)j * VL_STEP + 4 * (long long)threadIdx.x;
+        if (e0 >= E) break;
+        float r[4], t[4];
+        vl_load4<VEC>(recon + b * E, e0, E, r);
+        vl_load4<VEC>(target + b * E, e0, E, t);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (e0 + k >= E) continue;
+            const double d = (double)r[k] - (double)t[k];
+            acc[0] += d * d;
+            bad += (vl_bad(r[k]) ? 1u : 0u) + (vl_bad(t[k]) ? 1u : 0u);
+        }
+    }
+    vl_block_fold<1>(acc, bad, partials + VT_VAE_IMG_PART * (b * chunks + chunk));
+}
+
+__device__ __forceinline__ double vl_label(const float* p, long long i) { return (double)p[i]; }
+__device__ __forceinline__ double vl_label(const unsigned char* p, long long i) { return p[i] ? 1.0 : 0.0; }
+// F.relu / torch.clamp(min=0): a NaN stays a NaN
+__device__ __forceinline__ double vl_relu(double x) { return x <= 0.0 ? 0.0 : x; }
+__device__ __forceinline__ double vl_wave_sum(double v) {
+#pragma clang fp contract(off)
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+    return v;
+}
+__device__ __forceinline__ double vl_contrastive(double dist, double sim, double thr, double margin) {
+#pragma clang fp contract(off)
+    const double similar = sim > thr ? 1.0 : 0.0;
+    const double gap = vl_relu(margin - dist);
+    return (similar * (dist * dist) + (1.0 - similar) * (gap * gap)) * (sim > thr ? sim : 1.0 - sim);
+}
+
+struct VaeRowArg { int has_kl[3]; int has_n, has_recon, has_labels; };
+
+// grid B, one wave: an image's partials in index order and its labels -> the image's row
+template <typename L>
+__global__ __launch_bounds__(64) void vae_row_kernel(VaeRowArg f, const double* __restrict__ params, const double* __restrict__ lat, long long lat_chunks,
+                                                     const double* __restrict__ img, long long img_chunks, long long E, const L* __restrict__ labels_a,
+                                                     const L* __restrict__ labels_p, int N, double* __restrict__ rows, double* __restrict__ rows_out,
+                                                     unsigned long long* __restrict__ bad_out) {
+#pragma clang fp contract(off)
+    const int l = threadIdx.x;
+    const long long b = blockIdx.x;
+    double v[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) v[i] = 0.0;
+    unsigned long long bad = 0;
+    for (long long i = l; i < lat_chunks; i += 64) {
+        const double* p = lat + VT_VAE_LAT_PART * (b * lat_chunks + i);
+#pragma unroll
+        for (int k = 0; k < 10; ++k) v[k] += p[k];
+        bad += ((const unsigned long long*)p)[10];
+    }
+    double se = 0.0;
+    if (f.has_recon)
+        for (long long i = l; i < img_chunks; i += 64) {
+            const double* p = img + VT_VAE_IMG_PART * (b * img_chunks + i);
+            se += p[0];
+            bad += ((const unsigned long long*)p)[1];
+        }
+    double sa = 0.0, ov = 0.0, un = 0.0;
+    if (f.has_labels)
+        for (int j = l; j < N; j += 64) {
+            const double ya = vl_label(labels_a, b * N + j), yp = vl_label(labels_p, b * N + j);
+            sa += ya; ov += ya * yp; un += ya + yp - ya * yp;
+        }
+#pragma unroll
+    for (int k = 0; k < 10; ++k) v[k] = vl_wave_sum(v[k]);
+    se = vl_wave_sum(se); sa = vl_wave_sum(sa); ov = vl_wave_sum(ov); un = vl_wave_sum(un);
+    for (int d = 32; d > 0; d >>= 1) bad += __shfl_down(bad, d);
+    if (l != 0) return;
+    const double mt = params[0], mc = params[1], thr = params[2];
+    double r[VT_VAE_LOSS_ROW];
+    r[0] = f.has_recon ? se / (double)E : 0.0;
+    r[1] = f.has_kl[0] ? 0.5 * v[7] : 0.0;
+    r[2] = f.has_kl[1] ? 0.5 * v[8] : 0.0;
+    r[3] = f.has_kl[2] ? 0.5 * v[9] : 0.0;
+    const int nk = f.has_kl[0] + f.has_kl[1] + f.has_kl[2];
+    r[4] = nk ? (r[1] + r[2] + r[3]) / (double)nk : 0.0;
+    r[5] = log1p(r[4] / 10000.0);
+    const double na = fmax(sqrt(v[0]), 1e-12), np = fmax(sqrt(v[1]), 1e-12), nn = fmax(sqrt(v[2]), 1e-12);
+    r[6] = 1.0 - v[3] / (na * np);
+    r[7] = f.has_n ? 1.0 - v[4] / (na * nn) : 0.0;
+    r[8] = sqrt(v[5]);
+    r[9] = f.has_n ? sqrt(v[6]) : 0.0;
+    const double w = f.has_labels ? 1.0 + 0.5 * (ov / (sa + 1e-8)) : 1.0;
+    const double sim = ov / (un + 1e-8);
+    r[10] = f.has_n ? vl_relu(r[6] - r[7] + mt) * w : 0.0;
+    r[11] = f.has_n ? vl_relu(r[8] - r[9] + mt) * w : 0.0;
+    r[12] = vl_contrastive(r[6], sim, thr, mc);
+    r[13] = vl_contrastive(r[8], sim, thr, mc);
+    r[14] = sa; r[15] = ov; r[16] = un; r[17] = w; r[18] = sim;
+#pragma unroll
+    for (int k = 0; k < VT_VAE_LOSS_ROW; ++k) {
+        rows[VT_VAE_LOSS_ROW * b + k] = r[k];
+        if (rows_out) rows_out[VT_VAE_LOSS_ROW * b + k] = r[k];
+    }
+    bad_out[b] = bad;
+}
+
+// one wave: lane k < 7 owns component k and walks the rows one image after the other; lane 7 the counters
+__global__ __launch_bounds__(64) void vae_batch_kernel(VaeRowArg f, const double* __restrict__ rows, const unsigned long long* __restrict__ bad, int B,
+                                                       double* __restrict__ totals) {
+#pragma clang fp contract(off)
+    const int k = threadIdx.x;
+    unsigned long long* counters = (unsigned long long*)(totals + 2 * VT_VAE_LOSS_K);
+    if (k < VT_VAE_LOSS_K) {
+        const int column = k == 0 ? 0 : k < 3 ? 3 + k : 7 + k;                    // row entries 0, 4, 5, 10, 11, 12, 13
+        const bool on = k == 0 ? f.has_recon != 0 : (k == 3 || k == 4) ? f.has_n != 0 : true;
+        if (!on) return;
+        double batch = 0.0, kl = 0.0, images = totals[VT_VAE_LOSS_K + k];
+        for (int b = 0; b < B; ++b) {
+            const double x = rows[VT_VAE_LOSS_ROW * b + column];
+            batch += x; images += x;
+            if (k == 2) kl += rows[VT_VAE_LOSS_ROW * b + 4];
+        }
+        totals[k] += k == 2 ? log1p(kl / (double)B / 10000.0) : batch / (double)B;
+        totals[VT_VAE_LOSS_K + k] = images;
+    } else if (k == VT_VAE_LOSS_K) {
+        unsigned long long nb = 0;
+        for (int b = 0; b < B; ++b) nb += bad[b];
+        counters[0] += 1ull; counters[1] += (unsigned long long)B; counters[2] += nb;
+        if (f.has_recon) { counters[3] += 1ull; counters[4] += (unsigned long long)B; }
+        if (f.has_n) { counters[5] += 1ull; counters[6] += (unsigned long long)B; }
+    }
+}
+
+__global__ __launch_bounds__(64) void vae_init_kernel(double* __restrict__ params, double mt, double mc, double thr, unsigned long long seed) {
+    if (threadIdx.x == 0) { params[0] = mt; params[1] = mc; params[2] = thr; ((unsigned long long*)params)[3] = seed; }
+}
+
+// grid (chunks of D, B): z_out = mean + std eps, the element-to-thread mapping of the latent pass
+template <bool VEC>
+__global__ __launch_bounds__(VL_T) void vae_sample_kernel(const float* __restrict__ moments, long long D, unsigned long long seed, int draw,
+                                                          long long first_image, float* __restrict__ z_out) {
+#pragma clang fp contract(off)
+    const long long b = blockIdx.y;
+    const uint64_t key = vt_vae_image_key(vt_vae_stream_key(seed, (uint64_t)(int64_t)draw), (uint64_t)(first_image + b));
+    const float* m = moments + 2 * b * D;
+    for (int j = 0; j < VL_SWEEPS; ++j) {
+        const long long e0 = (long long)blockIdx.x * VT_VAE_CHUNK + (long long)j * VL_STEP + 4 * (long long)threadIdx.x;
+        if (e0 >= D) break;
+        float mean[4], lv[4], z[4];
+        vl_load4<VEC>(m, e0, D, mean);
+        vl_load4<VEC>(m + D, e0, D, lv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            double unused;
+            z[k] = e0 + k < D ? vae_z(mean[k], lv[k], vae_eps(key, (uint64_t)(e0 + k)), unused) : 0.0f;
+        }
+        if (VEC) {
+            *(float4*)(z_out + b * D + e0) = make_float4(z[0], z[1], z[2], z[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (e0 + k < D) z_out[b * D + e0 + k] = z[k];
+        }
+    }
+}
+
+// grid B, 1024 threads: kl_out[b] = 0.5 sum of the image's KL terms (thread t takes t, t + 1024, ...; wave tree; waves in order)
+__global__ __launch_bounds__(VL_KL_T) void vae_kl_kernel(const float* __restrict__ moments, long long D, double* __restrict__ kl_out) {
+#pragma clang fp contract(off)
+    __shared__ double s_red[VL_KL_T / 64];
+    const long long b = blockIdx.x;
+    const float* m = moments + 2 * b * D;
+    double acc = 0.0;
+    for (long long e = threadIdx.x; e < D; e += VL_KL_T) {
+        double t;
+        (void)vae_z(m[e], m[D + e], 0.0f, t);
+        acc += t;
+    }
+    acc = vl_wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double v = s_red[0];
+        for (int w = 1; w < VL_KL_T / 64; ++w) v += s_red[w];
+        kl_out[b] = 0.5 * v;
+    }
+}
+
+bool vl_misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+bool vl_shape_ok(int B, int C, int hw) {
+    return B >= 1 && B <= VT_EVAL_MAX_B && C >= 1 && hw >= 1 && (long long)C * hw <= VT_VAE_MAX_D;
+}
+bool vl_image_ok(int H, int W) { return H >= 1 && W >= 1 && 3ll * H * W <= VT_VAE_MAX_D; }
+int vl_check_state(vt_context* c, const char* who, const void* state, size_t state_bytes, size_t need) {
+    if (!state || vl_misaligned(state, ALIGN)) return c->fail(VT_ERR_INVALID, "%s: state is null or not 256-B aligned", who);
+    if (state_bytes < need) return c->fail(VT_ERR_WORKSPACE, "%s: state holds %zu bytes, %zu needed", who, state_bytes, need);
+    return VT_OK;
+}
+
+#define VLCK(c, what) HIPCK(c, hipGetLastError(), what)
+
+}  // namespace
+
+extern "C" {
+
+int vt_posterior_sample(vt_context* c, const float* moments, int B, int C, int hw, unsigned long long seed, int draw, long long first_image,
+                        float* z_out, double* kl_out, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!vl_shape_ok(B, C, hw)) return c->fail(VT_ERR_INVALID, "vt_posterior_sample: B = %d (1..%d), C = %d or hw = %d out of range", B, VT_EVAL_MAX_B, C, hw);
+    if (!moments || vl_misaligned(moments, 4) || vl_misaligned(z_out, 4) || vl_misaligned(kl_out, 8))
+        return c->fail(VT_ERR_INVALID, "vt_posterior_sample: moments is null, or a pointer is misaligned");
+    if (draw < 0 || first_image < 0) return c->fail(VT_ERR_INVALID, "vt_posterior_sample: draw and first_image are >= 0");
+    const long long D = (long long)C * hw;
+    hipStream_t s = (hipStream_t)stream;
+    if (z_out) {
+        const dim3 grid((unsigned)vt_vae_chunks(D), (unsigned)B);
+        if (D % 4 == 0 && !vl_misaligned(moments, 16) && !vl_misaligned(z_out, 16))
+            hipLaunchKernelGGL(vae_sample_kernel<true>, grid, dim3(VL_T), 0, s, moments, D, seed, draw, first_image, z_out);
+        else
+            hipLaunchKernelGGL(vae_sample_kernel<false>, grid, dim3(VL_T), 0, s, moments, D, seed, draw, first_image, z_out);
+        VLCK(c, "posterior_sample");
+    }
+    if (kl_out) {
+        hipLaunchKernelGGL(vae_kl_kernel, dim3((unsigned)B), dim3(VL_KL_T), 0, s, moments, D, kl_out); VLCK(c, "posterior_sample kl");
+    }
+    return VT_OK;
+}
+
+size_t vt_vae_loss_state_bytes(int B, int C, int hw, int H, int W) {
+    if (!vl_shape_ok(B, C, hw) || H < 0 || W < 0 || ((H == 0) != (W == 0)) || (H > 0 && !vl_image_ok(H, W))) return 0;
+    return vt_vae_loss_layout(B, (long long)C * hw, 3ll * H * W).total;
+}
+
+int vt_vae_loss_reset(vt_context* c, void* state, size_t state_bytes, double margin_triplet, double margin_contrastive, double jaccard_threshold,
+                      unsigned long long seed, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = vl_check_state(c, "vt_vae_loss_reset", state, state_bytes, VT_VAE_LOSS_HEAD)) return r;
+    if (!isfinite(margin_triplet) || !isfinite(margin_contrastive) || !isfinite(jaccard_threshold))
+        return c->fail(VT_ERR_INVALID, "vt_vae_loss_reset: the margins and the threshold must be finite");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCK(c, hipMemsetAsync(state, 0, VT_VAE_LOSS_HEAD, s), "vae_loss_reset clear");
+    hipLaunchKernelGGL(vae_init_kernel, dim3(1), dim3(64), 0, s, (double*)state, margin_triplet, margin_contrastive, jaccard_threshold, seed);
+    VLCK(c, "vae_loss_reset init");
+    return VT_OK;
+}
+
+int vt_vae_loss_update(vt_context* c, void* state, size_t state_bytes, const vt_vae_loss_input* anchor, const vt_vae_loss_input* positive,
+                       const vt_vae_loss_input* negative, const float* recon, const float* target, int H, int W, const void* labels_a,
+                       const void* labels_p, int labels_dtype, int N, int B, int C, int hw, long long first_image, double* rows_out, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!vl_shape_ok(B, C, hw)) return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: B = %d (1..%d), C = %d or hw = %d out of range", B, VT_EVAL_MAX_B, C, hw);
+    if (!anchor || !positive) return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: anchor and positive are required");
+    if (first_image < 0) return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: first_image < 0");
+    const long long D = (long long)C * hw;
+    const vt_vae_loss_input* in[3] = {anchor, positive, negative};
+    VaeLatentArg la;
+    VaeRowArg f;
+    bool vec = D % 4 == 0;
+    for (int s = 0; s < 3; ++s) {
+        VaeStream& v = la.s[s];
+        v.moments = nullptr; v.z = nullptr; v.draw = 0; v.present = in[s] != nullptr;
+        f.has_kl[s] = 0;
+        if (!in[s]) continue;
+        if (!in[s]->moments && !in[s]->z) return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: input %d has neither moments nor z", s);
+        if (vl_misaligned(in[s]->moments, 4) || vl_misaligned(in[s]->z, 4)) return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: input %d is misaligned", s);
+        if (in[s]->draw < 0) return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: input %d has a negative draw", s);
+        v.moments = in[s]->moments; v.z = in[s]->z; v.draw = in[s]->draw;
+        f.has_kl[s] = v.moments != nullptr;
+        vec = vec && !vl_misaligned(v.moments, 16) && !vl_misaligned(v.z, 16);
+    }
+    if ((recon == nullptr) != (target == nullptr)) return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: recon and target come together or not at all");
+    if (recon && (!vl_image_ok(H, W) || vl_misaligned(recon, 4) || vl_misaligned(target, 4)))
+        return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: H = %d, W = %d out of range, or recon / target misaligned", H, W);
+    if ((labels_a == nullptr) != (labels_p == nullptr)) return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: labels_a and labels_p come together or not at all");
+    if (labels_a && ((labels_dtype != VT_F32 && labels_dtype != VT_U8) || N < 1 || N > (1 << 24) ||
+                     (labels_dtype == VT_F32 && (vl_misaligned(labels_a, 4) || vl_misaligned(labels_p, 4)))))
+        return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: labels neither VT_F32 nor VT_U8, misaligned, or N = %d outside [1, 2^24]", N);
+    if (vl_misaligned(rows_out, 8)) return c->fail(VT_ERR_INVALID, "vt_vae_loss_update: rows_out is misaligned");
+    const long long E = recon ? 3ll * H * W : 0;
+    const VaeLossLayout l = vt_vae_loss_layout(B, D, E);
+    if (int r = vl_check_state(c, "vt_vae_loss_update", state, state_bytes, l.total)) return r;
+    f.has_n = negative != nullptr; f.has_recon = recon != nullptr; f.has_labels = labels_a != nullptr;
+
+    hipStream_t s = (hipStream_t)stream;
+    char* st = (char*)state;
+    const double* params = (const double*)(st + l.params);
+    double* totals = (double*)(st + l.totals);
+    double* rows = (double*)(st + l.rows);
+    double* lat = (double*)(st + l.lat);
+    double* img = (double*)(st + l.img);
+    unsigned long long* bad = (unsigned long long*)(rows + (size_t)VT_VAE_LOSS_ROW * B);      // the images' non-finite counts follow the rows
+    const dim3 lgrid((unsigned)l.lat_chunks, (unsigned)B);
+    if (vec) hipLaunchKernelGGL(vae_latent_kernel<true>, lgrid, dim3(VL_T), 0, s, la, params, D, first_image, l.lat_chunks, lat);
+    else hipLaunchKernelGGL(vae_latent_kernel<false>, lgrid, dim3(VL_T), 0, s, la, params, D, first_image, l.lat_chunks, lat);
+    VLCK(c, "vae_loss_update latent");
+    if (recon) {
+        const dim3 igrid((unsigned)l.img_chunks, (unsigned)B);
+        if (E % 4 == 0 && !vl_misaligned(recon, 16) && !vl_misaligned(target, 16))
+            hipLaunchKernelGGL(vae_image_kernel<true>, igrid, dim3(VL_T), 0, s, recon, target, E, l.img_chunks, img);
+        else
+            hipLaunchKernelGGL(vae_image_kernel<false>, igrid, dim3(VL_T), 0, s, recon, target, E, l.img_chunks, img);
+        VLCK(c, "vae_loss_update image");
+    }
+    if (labels_a && labels_dtype == VT_U8)
+        hipLaunchKernelGGL(vae_row_kernel<unsigned char>, dim3((unsigned)B), dim3(64), 0, s, f, params, lat, l.lat_chunks, img, l.img_chunks, E,
+                           (const unsigned char*)labels_a, (const unsigned char*)labels_p, N, rows, rows_out, bad);
+    else
+        hipLaunchKernelGGL(vae_row_kernel<float>, dim3((unsigned)B), dim3(64), 0, s, f, params, lat, l.lat_chunks, img, l.img_chunks, E,
+                           (const float*)labels_a, (const float*)labels_p, N, rows, rows_out, bad);
+    VLCK(c, "vae_loss_update rows");
+    hipLaunchKernelGGL(vae_batch_kernel, dim3(1), dim3(64), 0, s, f, rows, bad, B, totals); VLCK(c, "vae_loss_update batch");
+    return VT_OK;
+}
+
+int vt_vae_loss_read(vt_context* c, const void* state, size_t state_bytes, void* out, size_t out_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (int r = vl_check_state(c, "vt_vae_loss_read", state, state_bytes, VT_VAE_LOSS_HEAD)) return r;
+    if (!out || vl_misaligned(out, 8)) return c->fail(VT_ERR_INVALID, "vt_vae_loss_read: out is null or misaligned");
+    if (out_bytes < (size_t)VT_VAE_LOSS_HEAD) return c->fail(VT_ERR_WORKSPACE, "vt_vae_loss_read: out holds %zu bytes, %d needed", out_bytes, VT_VAE_LOSS_HEAD);
+    const uintptr_t a = (uintptr_t)state, b = (uintptr_t)out;
+    if (a < b + VT_VAE_LOSS_HEAD && b < a + VT_VAE_LOSS_HEAD) return c->fail(VT_ERR_INVALID, "vt_vae_loss_read: out overlaps the state");
+    HIPCK(c, hipMemcpyAsync(out, state, VT_VAE_LOSS_HEAD, hipMemcpyDefault, (hipStream_t)stream), "vae_loss_read");
+    return VT_OK;
+}
+
+}  // extern "C"

@@ -88,6 +88,15 @@ class DiffusersVAEWrapper(torch.nn.Module):
         self._raise_on_status()
         return reconstruction, posterior
 
+    def forward_device(self, x, seed, first_image=0):
+        """forward() with the posterior sampled on the device (sample_device, draw 0): image first_image + b gets the same noise whatever
+        the batching, and torch's random stream is not touched."""
+        posterior = self.vae.encode(x).latent_dist
+        z = posterior.sample_device(seed, 0, first_image)
+        reconstruction = self.vae.decode(z).sample
+        self._raise_on_status()
+        return reconstruction, posterior
+
     def _raise_on_status(self):
         if self.check_finite and isinstance(self.vae, AutoencoderKL) and not self.vae.check_finite:
             self.vae.raise_on_status()
