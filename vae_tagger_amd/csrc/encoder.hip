@@ -1,8 +1,9 @@
-// The encoder's launch schedule (host code): which conv kernel runs for which shape and flag set, GroupNorm bookkeeping,
-// the workspace plan, vt_encode.  No host synchronisation, caller-owned buffers.
+// The conv / GroupNorm launch helpers of both VAE schedules (host code): which conv kernel runs for which shape and flag set, GroupNorm
+// bookkeeping (run_conv, run_gn, run_norm_conv) -- and the encoder's schedule over the shared run layer (vt_vae_run.h): its plan, conv_in,
+// the down stages, vt_encode, vt_encode_tag.  No host synchronisation, caller-owned buffers.
 #include <algorithm>
 
-#include "vt_context.h"
+#include "vt_vae_run.h"
 
 namespace vt {
 
@@ -29,7 +30,7 @@ int launch_halo_fp8(vt_context* c, const Conv3x3Fp8Args& a, hipStream_t s, const
                     2.0 * a.batch * (double)a.H * a.W * a.Cout * (9.0 * a.Cin + (a.scX ? a.scCin : 0)), what, [&] { return vt_launch_conv3x3_halo_fp8(a, s); });
 }
 
-// (run_gn, conv_f16 and run_norm_conv are shared with the image decoder's schedule, image_decoder.hip: declared in vt_context.h)
+// (run_gn, conv_f16 and run_norm_conv serve the shared run layer, vae_run.hip, and the image decoder's schedule: declared in vt_context.h)
 
 // y = act(GroupNorm(x)) as bf16 rows.  Uses epilogue-produced partials when present.
 int run_gn(vt_context* c, const void* x, int xdt /*0 bf16, 1 fp32, 2 fp16*/, int B, int HW, const NormW& n, int groups, int silu, bf16_t* y,
@@ -215,25 +216,17 @@ int run_norm_conv(vt_context* c, const NormW& n, const ConvW& w, const void* x, 
 namespace {
 
 // ---- encoder plan ---------------------------------------------------------------------------------
-struct EncPlan {
-    size_t max_elems = 0;      // per image, largest activation tensor (elements)
-    int max_c = 0;
-    int max_chunks = 0;
+struct EncPlan : VaePlan {
     int hl = 0, wl = 0;        // latent spatial size
-    size_t total = 0;
 };
-constexpr size_t SLACK = 4096;
 
 EncPlan plan_encoder(const EncoderW& e, int B, int H, int W) {
     EncPlan p;
     int h = H, w = W;
+    // the producers of GroupNorm partials that only the encoder has: both conv_in kernels, the fp8 halo conv, the stride-2 kernels
     auto note = [&](int hh, int ww, int ch) {
-        p.max_elems = std::max(p.max_elems, (size_t)hh * ww * ch);
-        p.max_c = std::max(p.max_c, ch);
-        // GroupNorm partials: the most triples per (image, group) that any producer of this tensor writes
-        p.max_chunks = std::max({p.max_chunks, vt_gn_max_chunks(hh * ww, ch), vt_conv_gemm_ptiles(hh * ww, ch), vt_conv3x3_halo_tiles_max(hh, ww),
-                                 vt_conv_in_parts(hh, ww), vt_conv_in_mfma_parts(hh, ww), vt_conv3x3_halo_fp8_tiles(hh, ww),
-                                 vt_conv3x3_s2_tiles(hh, ww), vt_conv3x3_s2_fp8_tiles(hh, ww)});
+        p.note(hh, ww, ch, std::max({vt_conv_in_parts(hh, ww), vt_conv_in_mfma_parts(hh, ww), vt_conv3x3_halo_fp8_tiles(hh, ww),
+                                     vt_conv3x3_s2_tiles(hh, ww), vt_conv3x3_s2_fp8_tiles(hh, ww)}));
     };
     note(h, w, e.block_out[0]);
     for (size_t i = 0; i < e.block_out.size(); ++i) {
@@ -241,42 +234,16 @@ EncPlan plan_encoder(const EncoderW& e, int B, int H, int W) {
         if (i + 1 < e.block_out.size()) { h /= 2; w /= 2; note(h, w, e.block_out[i]); }
     }
     p.hl = h; p.wl = w;
-    const int S = h * w, C = e.block_out.back();
-    p.max_chunks = std::max(p.max_chunks, vt_attn_linear_parts(S));     // to_out's GroupNorm partials: one per 32-token slab (attn_qk.hip, mode 5)
-    p.total = 3 * align_up(p.max_elems * B * 4 + SLACK) + 3 * align_up(p.max_elems * B * 2 + SLACK) +
-              align_up((size_t)B * p.max_chunks * e.groups * 3 * 4) + align_up((size_t)B * p.max_c * 2 * 4) +
-              attn_scratch_bytes(B, S, C) + ALIGN;
+    p.finish(B, e.groups, h * w, e.block_out.back());
     return p;
 }
 
-// what the stage's stride-2 conv wants of the block output that feeds it (the 16-bit copy `hb`)
-struct BlockOut {
-    bool only16 = false;      // the only consumer is the downsample conv (16-bit operand, no norm): skip the residual-stream copy of h and the stats
-    bool e4m3 = false;        // the downsample conv runs on fp8 operands, so the copy is written as e4m3 instead of bf16
-    bool f16 = false, planar = false;
-};
+// One vt_encode call: the shared run plus what only the encoder has, conv_in and the down stages.
+struct EncRun : VaeRun {
+    const EncoderW& e;
 
-// One vt_encode call: the carved workspace and the position in the rotating buffers.
-struct EncRun {
-    vt_context* c; const EncoderW& e; int B; hipStream_t s;
-    int rdt;                                       // residual-stream buffers: fp16 by default (res_fp16), fp32 otherwise; sized for fp32 either way
-    void* f32[3]; bf16_t* b16[3];
-    GnState gn; AttnScratch as;
-    int cur = 0;                                   // f32[cur] holds the fp32 residual stream h
-    bf16_t *act, *tmid, *hb;                       // GN(+SiLU) output = conv operand / conv1 output, bf16 copy of h after a downsample / bf16 copy of h feeding a downsample conv
-    int h, w;
-    const bf16_t* h16 = nullptr;                   // 16-bit copy of the current h, when one exists ...
-    bool h16_is_f16 = false;                       // ... holding fp16 bits (fp16-operand mode, for a fused shortcut) instead of bf16
-
-    EncRun(vt_context* c_, const EncPlan& p, int B_, int H, int W, void* ws, hipStream_t s_)
-        : c(c_), e(c_->enc), B(B_), s(s_), rdt(c_->res_fp16 ? 2 : 1), h(H), w(W) {
-        char* q = (char*)ws;
-        for (int i = 0; i < 3; ++i) { f32[i] = (void*)q; q += align_up(p.max_elems * B * 4 + SLACK); }
-        for (int i = 0; i < 3; ++i) { b16[i] = (bf16_t*)q; q += align_up(p.max_elems * B * 2 + SLACK); }
-        gn.partial = (float*)q; q += align_up((size_t)B * p.max_chunks * e.groups * 3 * 4);
-        gn.ss = (float*)q; q += align_up((size_t)B * p.max_c * 2 * 4);
-        as = carve_attn(q, B, p.hl * p.wl, e.block_out.back());
-        act = b16[0]; tmid = b16[1]; hb = b16[2];
+    EncRun(vt_context* c_, const EncPlan& p, int B_, int H, int W, void* ws, hipStream_t s_) : VaeRun(c_, c_->enc.groups, B_, H, W, s_), e(c_->enc) {
+        carve(p, ws);
     }
 
     int conv_in(const float* x) {
@@ -296,42 +263,6 @@ struct EncRun {
         return VT_OK;
     }
 
-    bool fuse_sc(const ResnetW& rw) const {
-        return c->fuse_shortcut && rw.sc_wp && c->use_halo_conv && rw.c2.wp && !c->fuse_gn_apply && (!(c->fp8 && rw.c2.wp8) || rw.sc_wp8);
-    }
-
-    // one ResnetBlock2D: h <- conv2(silu(gn(conv1(silu(gn(h)))))) + shortcut(h)
-    int resnet(const ResnetW& rw, const bf16_t* h16_for_shortcut, const BlockOut& out = BlockOut()) {
-        const int nxt = (cur + 1) % 3, scb = (cur + 2) % 3;
-        const void* res = f32[cur];
-        const ScFuse scf{h16_for_shortcut, rw.sc_wp, rw.b_c2sc, rw.cin, rw.sc_wp8, rw.sc_wp16, h16_is_f16};
-        NormConvOpts c2;
-        if (rw.has_sc) {
-            if (fuse_sc(rw)) {
-                // conv_shortcut rides in conv2's launch (extra K-steps on the bf16 copy of the block input, which the
-                // downsample conv left in f32[scb]): no shortcut tensor is written or read back
-                c2.sc = &scf; res = nullptr;
-            } else {
-                ConvOpts o; o.rdt = rdt;
-                VTCK(run_conv(c, rw.sc, h16_for_shortcut, B, h, w, 1, 0, h, w, nullptr, f32[scb], nullptr, s, o));
-                res = f32[scb];
-            }
-        }
-        // conv1's output is only ever read by norm2: with the fp16 storage mode it is kept as fp16 too (11 significand
-        // bits instead of bf16's 8 at the same 2 B: one of the three 8-bit roundings per resnet block disappears)
-        const bool c1h = rdt == 2;
-        const int c1dt = c1h ? 2 : 0;
-        VTCK(run_norm_conv(c, rw.n1, rw.c1, f32[cur], rdt, B, h, w, e.groups, act, nullptr, c1h ? (void*)tmid : nullptr,
-                           c1h ? nullptr : tmid, gn, true, s, rdt));
-        if (out.only16) {
-            c2.o16_e4m3 = out.e4m3; c2.o16_f16 = out.f16; c2.o16_planar = out.planar;
-            return run_norm_conv(c, rw.n2, rw.c2, tmid, c1dt, B, h, w, e.groups, act, res, nullptr, hb, gn, false, s, rdt, c2);
-        }
-        VTCK(run_norm_conv(c, rw.n2, rw.c2, tmid, c1dt, B, h, w, e.groups, act, res, f32[nxt], nullptr, gn, true, s, rdt, c2));
-        cur = nxt;
-        return VT_OK;
-    }
-
     // the resnet blocks of one stage and, unless it is the last, its Downsample2D
     int stage(size_t i) {
         const StageW& st = e.stages[i];
@@ -339,7 +270,6 @@ struct EncRun {
         for (size_t j = 0; j < st.res.size(); ++j) {
             const ResnetW& rw = st.res[j];
             const bool last = j + 1 == st.res.size();
-            if (rw.has_sc && !h16) return c->fail(VT_ERR_STATE, "internal: shortcut conv without a bf16 input");
             BlockOut out;
             out.only16 = last && st.has_down;
             // fp8 mode: the last block of a stage hands its output to the stride-2 conv as e4m3 when both run on fp8 operands
@@ -349,9 +279,9 @@ struct EncRun {
             // the copy is chunk-planar when the stride-2 conv that reads it runs on a phase-plane kernel (and the producer is a halo kernel that can write it so)
             out.planar = out.only16 && c->s2_planar && c->s2_halo && !c->fuse_gn_apply &&
                          (out.e4m3 ? st.down.wp8s2 != nullptr : (st.down.wp2 != nullptr && c->use_halo_conv && rw.c2.wp && !(c->fp8 && rw.c2.wp8)));
-            VTCK(resnet(rw, h16, out));
+            VTCK(resnet(rw, out));
             if (last) hbo = out;
-            h16 = out.only16 ? hb : nullptr; h16_is_f16 = false;
+            if (out.only16) h16 = hb;
         }
         if (!st.has_down) return VT_OK;
         // Downsample2D(padding=0): F.pad(x,(0,1,0,1)) then conv3x3 stride 2 -> out = floor(in/2)
@@ -366,46 +296,11 @@ struct EncRun {
         // (only the phase-plane kernel can write them; on the generic GEMM the copy stays bf16 and that conv2 keeps bf16 operands)
         const bool copy16 = copy && fuse_sc(*next) && conv_f16(c, next->c2, 1, true) && c->s2_halo && st.down.wp2 && !hbo.e4m3;
         ConvOpts o;
-        o.gn = &gn; o.groups = e.groups; o.rdt = rdt; o.x_fp8 = hbo.e4m3; o.x_f16 = hbo.f16; o.o16_f16 = copy16; o.planar = hbo.planar;
+        o.gn = &gn; o.groups = groups; o.rdt = rdt; o.x_fp8 = hbo.e4m3; o.x_f16 = hbo.f16; o.o16_f16 = copy16; o.planar = hbo.planar;
         VTCK(run_conv(c, st.down, hb, B, h, w, 2, 0, ho, wo, nullptr, f32[nxt], copy, s, o));
         h16 = copy; h16_is_f16 = copy16;
         cur = nxt; h = ho; w = wo;
         return VT_OK;
-    }
-
-    int mid_attention() {
-        const int S = h * w, nxt = (cur + 1) % 3;
-        const bool tok8 = attn_proj_is_fp8(c, e.attn, S, e.attn.c);       // the tokens leave the GroupNorm pass as e4m3(8 x): the projections' operand
-        VTCK(run_gn(c, f32[cur], rdt, B, S, e.attn.gn, e.groups, 0, act, gn, s, tok8));
-        VTCK(run_attention(c, e.attn, act, f32[cur], f32[nxt], B, S, as, s, &gn, e.groups, rdt, tok8));
-        cur = nxt;
-        return VT_OK;
-    }
-
-    // conv_norm_out + conv_out -> moments (mode 0) / mode() = mean = the first `latent` channels (mode 1) / * scaling + shift (mode 2)
-    int conv_out(int mode, float* latent) {
-        const ConvW& cw = e.conv_out;
-        const bool out16 = cw.cout <= 32 && cw.w16 && c->f16_ops && !c->fp8;      // fp16-operand mode: conv_out multiplies fp16 too (both of its kernels have the form)
-        VTCK(run_gn(c, f32[cur], rdt, B, h * w, e.norm_out, e.groups, 1, act, gn, s, false, out16));
-        const int keep = mode == 0 ? 2 * e.latent : e.latent;
-        const float post_scale = (mode == 2 && e.has_scaling) ? e.scaling : 1.f, post_shift = (mode == 2 && e.has_shift) ? e.shift : 0.f;
-        if (c->conv_out_halo && cw.wpo && cw.k == 3 && keep <= cw.cout) {
-            // on its 32-cout halo tile
-            ConvOutArgs o{};
-            o.X = act; o.Wp = out16 ? cw.wpo16 : cw.wpo; o.f16 = out16; o.bias = cw.b; o.out = latent; o.zeros = c->zeros;
-            o.batch = B; o.H = h; o.W = w; o.Cin = cw.cin; o.Cout = cw.cout; o.keep = keep;
-            o.post_scale = post_scale; o.post_shift = post_shift;
-            return profiled(c, s, VT_PROF_CONV_OUT, 2.0 * B * (double)h * w * cw.cout * 9.0 * cw.cin, "conv_out_halo", [&] { return vt_launch_conv_out_halo(o, s); });
-        }
-        ConvGemmArgs a{};
-        a.X = act; a.W = out16 ? cw.w16 : cw.w; a.f16 = out16; a.bias = cw.b; a.out_f32 = latent; a.zeros = c->zeros;
-        a.Hin = a.Hout = h; a.Win = a.Wout = w; a.Cin = cw.cin; a.Cout = cw.cout; a.Wrows = cw.cout;
-        a.ksize = 3; a.stride = 1; a.pad = 1; a.ldx = cw.cin; a.ldw = 9 * cw.cin; a.ldo = cw.cout;
-        a.cout_keep = keep;
-        a.x_bs = (long long)h * w * cw.cin; a.o_bs = (long long)a.cout_keep * h * w; a.batch = B; a.alpha = 1.f;
-        a.bias_mode = 1; a.out_mode = 1;
-        a.post_scale = post_scale; a.post_shift = post_shift;
-        return launch_gemm(c, a, s, "conv_out");
     }
 };
 
@@ -427,11 +322,7 @@ int vt_encoder_configure(vt_context* c, int in_ch, int latent, const int* block_
     e = EncoderW();
     e.in_ch = in_ch; e.latent = latent; e.layers = layers; e.groups = groups;
     e.block_out.assign(block_out, block_out + n_blocks);
-    for (int ch : e.block_out) {
-        if (ch % groups || ch % 64 || ch > 2048) return c->fail(VT_ERR_INVALID, "block_out_channels entries must be multiples of 64 and of norm_num_groups (got %d)", ch);
-        const int cpg = ch / groups;
-        if (cpg < 2 || (cpg & (cpg - 1)) || (256 % (ch / 8))) return c->fail(VT_ERR_INVALID, "unsupported channels/groups combination %d/%d", ch, groups);
-    }
+    VTCK(check_block_out(c, block_out, n_blocks, groups));
     if (2 * latent > 32 || (2 * latent) % 4) return c->fail(VT_ERR_INVALID, "latent_channels must be <= 16 and even");
     e.scaling = scaling; e.has_scaling = has_scaling != 0; e.shift = shift; e.has_shift = has_shift != 0;
     e.configured = true;
@@ -478,10 +369,12 @@ int vt_encode(vt_context* c, const float* x, int B, int H, int W, int mode, floa
     EncRun run(c, p, B, H, W, ws, (hipStream_t)stream);
     VTCK(run.conv_in(x));
     for (size_t i = 0; i < e.stages.size(); ++i) VTCK(run.stage(i));
-    VTCK(run.resnet(e.mid0, nullptr));
-    VTCK(run.mid_attention());
-    VTCK(run.resnet(e.mid1, nullptr));
-    return run.conv_out(mode, latent);
+    VTCK(run.resnet(e.mid0));
+    VTCK(run.mid_attention(e.attn));
+    VTCK(run.resnet(e.mid1));
+    // conv_norm_out + conv_out -> moments (mode 0) / mode() = mean = the first `latent` channels (mode 1) / * scaling + shift (mode 2)
+    return run.conv_out(e.conv_out, e.norm_out, mode == 0 ? 2 * e.latent : e.latent, (mode == 2 && e.has_scaling) ? e.scaling : 1.f,
+                        (mode == 2 && e.has_shift) ? e.shift : 0.f, latent);
 }
 
 size_t vt_encode_tag_workspace_bytes(const vt_context* c, int B, int H, int W) {

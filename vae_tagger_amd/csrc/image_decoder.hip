@@ -1,12 +1,13 @@
 // The VAE image decoder's launch schedule (host code) and its ABI: latents [B][latent][h][w] -> image [B][out_ch][8h][8w] for the FLUX
 // configuration.  Layer order of the diffusers Decoder: conv_in, mid block (resnet, attention, resnet), the up blocks (layers_per_block + 1
 // resnets each, an Upsample2D after all but the last), conv_norm_out + SiLU, conv_out.  Every layer but the Upsample2D conv runs on the
-// kernels the encoder uses, through the same helpers (run_gn / run_norm_conv / run_conv / run_attention); Upsample2D runs folded
-// (conv3x3_up2.hip) or, with vt_set_flag 22 or for a shape that kernel refuses, as a nearest-2x pass + the stride-1 conv.  No fp8 mode:
-// the fp8 flags are ignored here.  No host synchronisation, caller-owned buffers.
+// kernels the encoder uses, and the mid block, every resnet and conv_out through the run layer both schedules share (VaeRun, vt_vae_run.h);
+// what is the decoder's own: the latent staging + conv_in and the up blocks.  Upsample2D runs folded (conv3x3_up2.hip) or, with
+// vt_set_flag 22 or for a shape that kernel refuses, as a nearest-2x pass + the stride-1 conv.  No fp8 mode: vt_decode_image switches the
+// context's fp8 flag off for its own launches (the shared steps have fp8 branches).  No host synchronisation, caller-owned buffers.
 #include <algorithm>
 
-#include "vt_context.h"
+#include "vt_vae_run.h"
 
 namespace vt {
 namespace {
@@ -29,22 +30,13 @@ void latent_to_nhwc_kernel(const float* __restrict__ z, bf16_t* __restrict__ y, 
     if (f16) ((f16_t*)y)[idx] = (f16_t)v; else y[idx] = (bf16_t)v;
 }
 
-struct DecPlan {
-    size_t max_elems = 0;      // per image, largest activation tensor (elements)
-    int max_c = 0, max_chunks = 0;
-    size_t total = 0;
-};
-constexpr size_t SLACK = 4096;
+// the staged latents (conv_in's operand), carved between the (scale, shift) table and the attention scratch
+size_t z16_bytes(const ImageDecoderW& d, int B, int h, int w) { return align_up((size_t)B * h * w * d.conv_in_cin() * 2 + SLACK); }
 
-DecPlan plan_decoder(const ImageDecoderW& d, int B, int h, int w) {
-    DecPlan p;
-    auto note = [&](int hh, int ww, int ch) {
-        p.max_elems = std::max(p.max_elems, (size_t)hh * ww * ch);
-        p.max_c = std::max(p.max_c, ch);
-        // GroupNorm partials: the most triples per (image, group) that any producer of this tensor writes
-        p.max_chunks = std::max({p.max_chunks, vt_gn_max_chunks(hh * ww, ch), vt_conv_gemm_ptiles(hh * ww, ch), vt_conv3x3_halo_tiles_max(hh, ww),
-                                 vt_conv3x3_up2_tiles((hh + 1) / 2, (ww + 1) / 2)});
-    };
+VaePlan plan_decoder(const ImageDecoderW& d, int B, int h, int w) {
+    VaePlan p;
+    // the producer of GroupNorm partials that only the decoder has: the folded Upsample2D conv, over the low-resolution tile grid
+    auto note = [&](int hh, int ww, int ch) { p.note(hh, ww, ch, vt_conv3x3_up2_tiles((hh + 1) / 2, (ww + 1) / 2)); };
     const int nb = (int)d.block_out.size();
     int hh = h, ww = w;
     note(hh, ww, d.block_out.back());
@@ -53,11 +45,7 @@ DecPlan plan_decoder(const ImageDecoderW& d, int B, int h, int w) {
         note(hh, ww, co);
         if (i + 1 < nb) { hh *= 2; ww *= 2; note(hh, ww, co); }
     }
-    const int S = h * w, C = d.block_out.back();
-    p.max_chunks = std::max(p.max_chunks, vt_attn_linear_parts(S));
-    p.total = 3 * align_up(p.max_elems * B * 4 + SLACK) + 3 * align_up(p.max_elems * B * 2 + SLACK) +
-              align_up((size_t)B * p.max_chunks * d.groups * 3 * 4) + align_up((size_t)B * p.max_c * 2 * 4) +
-              align_up((size_t)B * h * w * d.conv_in_cin() * 2 + SLACK) + attn_scratch_bytes(B, S, C) + ALIGN;
+    p.finish(B, d.groups, h * w, d.block_out.back(), z16_bytes(d, B, h, w));
     return p;
 }
 
@@ -71,32 +59,21 @@ bool shape_ok(const ImageDecoderW& d, int B, int h, int w) {
     return H * W * cmax < (1LL << 31) && H < (1 << 20) && W < (1 << 20);
 }
 
-// the last resnet of a block that ends in an Upsample2D hands its output to that conv only, as a 16-bit operand
-struct BlockOut { bool only16 = false, f16 = false; };
+// The shared resnet / attention / conv_out steps take their fp8 branches from c->fp8: off for the lifetime of one vt_decode_image call,
+// and back to what the caller (the encoder's mode) had set on every return path.
+struct NoFp8 {
+    vt_context* c; int saved;
+    explicit NoFp8(vt_context* c_) : c(c_), saved(c_->fp8) { c->fp8 = 0; }
+    ~NoFp8() { c->fp8 = saved; }
+};
 
-// One vt_decode_image call: the carved workspace and the position in the rotating buffers (the encoder's EncRun, run the other way).
-struct DecRun {
-    vt_context* c; const ImageDecoderW& d; int B; hipStream_t s;
-    int rdt;                                       // residual-stream buffers: fp16 by default (res_fp16), fp32 otherwise; sized for fp32 either way
-    void* f32[3]; bf16_t* b16[3];
-    GnState gn; AttnScratch as;
-    bf16_t* z16;
-    int cur = 0;
-    bf16_t *act, *tmid, *hb;                       // GN(+SiLU) output = conv operand (and the literal route's upsampled tensor) / conv1 output / 16-bit block output feeding an Upsample2D
-    int h, w;
-    const bf16_t* h16 = nullptr;                   // 16-bit copy of the current h (an Upsample2D wrote it for the next block's conv_shortcut) ...
-    bool h16_is_f16 = false;                       // ... holding fp16 bits
+// One vt_decode_image call: the shared run plus what only the decoder has, the staged latents, conv_in and the up blocks.
+struct DecRun : VaeRun {
+    const ImageDecoderW& d;
+    bf16_t* z16;                                   // the latents as conv_in's operand
 
-    DecRun(vt_context* c_, const DecPlan& p, int B_, int h_, int w_, void* ws, hipStream_t s_)
-        : c(c_), d(c_->imgdec), B(B_), s(s_), rdt(c_->res_fp16 ? 2 : 1), h(h_), w(w_) {
-        char* q = (char*)ws;
-        for (int i = 0; i < 3; ++i) { f32[i] = (void*)q; q += align_up(p.max_elems * B * 4 + SLACK); }
-        for (int i = 0; i < 3; ++i) { b16[i] = (bf16_t*)q; q += align_up(p.max_elems * B * 2 + SLACK); }
-        gn.partial = (float*)q; q += align_up((size_t)B * p.max_chunks * d.groups * 3 * 4);
-        gn.ss = (float*)q; q += align_up((size_t)B * p.max_c * 2 * 4);
-        z16 = (bf16_t*)q; q += align_up((size_t)B * h * w * d.conv_in_cin() * 2 + SLACK);
-        as = carve_attn(q, B, h * w, d.block_out.back());
-        act = b16[0]; tmid = b16[1]; hb = b16[2];
+    DecRun(vt_context* c_, const VaePlan& p, int B_, int h_, int w_, void* ws, hipStream_t s_) : VaeRun(c_, c_->imgdec.groups, B_, h_, w_, s_), d(c_->imgdec) {
+        z16 = (bf16_t*)carve(p, ws, z16_bytes(d, B, h, w));
     }
 
     int conv_in(const float* z, int unscale) {
@@ -106,38 +83,8 @@ struct DecRun {
         hipLaunchKernelGGL(latent_to_nhwc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z, z16, d.latent, Lp, h * w, n,
                            d.has_shift ? d.shift : 0.f, d.has_scaling ? d.scaling : 1.f, unscale, (int)xf16);
         HIPCK(c, hipGetLastError(), "latent_to_nhwc");
-        ConvOpts o; o.gn = &gn; o.groups = d.groups; o.rdt = rdt; o.x_f16 = xf16;
+        ConvOpts o; o.gn = &gn; o.groups = groups; o.rdt = rdt; o.x_f16 = xf16;
         return run_conv(c, d.conv_in, z16, B, h, w, 1, 1, h, w, nullptr, f32[cur], nullptr, s, o);       // the halo conv where it takes the shape, else the generic GEMM
-    }
-
-    bool fuse_sc(const ResnetW& rw) const { return c->fuse_shortcut && rw.sc_wp && c->use_halo_conv && rw.c2.wp && !c->fuse_gn_apply; }
-
-    // one ResnetBlock2D: h <- conv2(silu(gn(conv1(silu(gn(h)))))) + shortcut(h)
-    int resnet(const ResnetW& rw, const BlockOut& out = BlockOut()) {
-        const int nxt = (cur + 1) % 3, scb = (cur + 2) % 3;
-        const void* res = f32[cur];
-        if (rw.has_sc && !h16) return c->fail(VT_ERR_STATE, "internal: shortcut conv without a 16-bit input");
-        const ScFuse scf{h16, rw.sc_wp, rw.b_c2sc, rw.cin, nullptr, rw.sc_wp16, h16_is_f16};
-        NormConvOpts c2;
-        if (rw.has_sc) {
-            if (fuse_sc(rw)) { c2.sc = &scf; res = nullptr; }          // conv_shortcut rides in conv2's launch, reading the copy the Upsample2D left in f32[scb]
-            else {
-                ConvOpts o; o.rdt = rdt;
-                VTCK(run_conv(c, rw.sc, h16, B, h, w, 1, 0, h, w, nullptr, f32[scb], nullptr, s, o));
-                res = f32[scb];
-            }
-        }
-        const bool c1h = rdt == 2;                                      // conv1's output, read only by norm2, is kept as fp16 with the fp16 storage mode
-        const int c1dt = c1h ? 2 : 0;
-        VTCK(run_norm_conv(c, rw.n1, rw.c1, f32[cur], rdt, B, h, w, d.groups, act, nullptr, c1h ? (void*)tmid : nullptr, c1h ? nullptr : tmid, gn, true, s, rdt));
-        h16 = nullptr; h16_is_f16 = false;
-        if (out.only16) {
-            c2.o16_f16 = out.f16;
-            return run_norm_conv(c, rw.n2, rw.c2, tmid, c1dt, B, h, w, d.groups, act, res, nullptr, hb, gn, false, s, rdt, c2);
-        }
-        VTCK(run_norm_conv(c, rw.n2, rw.c2, tmid, c1dt, B, h, w, d.groups, act, res, f32[nxt], nullptr, gn, true, s, rdt, c2));
-        cur = nxt;
-        return VT_OK;
     }
 
     bool up_folded(const UpBlockW& u) const { return !c->up2_literal && u.up_wp != nullptr; }
@@ -166,7 +113,7 @@ struct DecRun {
         bf16_t* copy = !next ? nullptr : (fuse_sc(*next) ? (bf16_t*)f32[(nxt + 2) % 3] : tmid);
         const bool folded = up_folded(u);
         const bool copy16 = copy && fuse_sc(*next) && conv_f16(c, next->c2, 1, true) && (folded || (c->use_halo_conv && u.up.wp));
-        const int cpg = ch / d.groups;
+        const int cpg = ch / groups;
         const bool fuse = c->fuse_gn_stats && (cpg == 4 || cpg == 8 || cpg == 16);
         if (folded) {
             ConvUp2Args a{};
@@ -180,42 +127,12 @@ struct DecRun {
         } else {
             HIPCK(c, vt_launch_upsample2x_nhwc16(hb, act, B, h, w, ch, s), "upsample2x");
             ConvOpts o;
-            o.gn = &gn; o.groups = d.groups; o.rdt = rdt; o.x_f16 = xf16; o.o16_f16 = copy16;
+            o.gn = &gn; o.groups = groups; o.rdt = rdt; o.x_f16 = xf16; o.o16_f16 = copy16;
             VTCK(run_conv(c, u.up, act, B, 2 * h, 2 * w, 1, 1, 2 * h, 2 * w, nullptr, f32[nxt], copy, s, o));
         }
         h16 = copy; h16_is_f16 = copy16;
         cur = nxt; h *= 2; w *= 2;
         return VT_OK;
-    }
-
-    int mid_attention() {
-        const int S = h * w, nxt = (cur + 1) % 3;
-        VTCK(run_gn(c, f32[cur], rdt, B, S, d.attn.gn, d.groups, 0, act, gn, s));
-        VTCK(run_attention(c, d.attn, act, f32[cur], f32[nxt], B, S, as, s, &gn, d.groups, rdt, false));
-        cur = nxt;
-        return VT_OK;
-    }
-
-    // conv_norm_out + SiLU + conv_out -> fp32 NCHW image (the first out_ch of the zero-padded 32 couts)
-    int conv_out(float* image) {
-        const ConvW& cw = d.conv_out;
-        const bool out16 = cw.w16 && c->f16_ops;
-        VTCK(run_gn(c, f32[cur], rdt, B, h * w, d.norm_out, d.groups, 1, act, gn, s, false, out16));
-        if (c->conv_out_halo && cw.wpo) {
-            ConvOutArgs o{};
-            o.X = act; o.Wp = out16 ? cw.wpo16 : cw.wpo; o.f16 = out16; o.bias = cw.b; o.out = image; o.zeros = c->zeros;
-            o.batch = B; o.H = h; o.W = w; o.Cin = cw.cin; o.Cout = cw.cout; o.keep = d.out_ch;
-            o.post_scale = 1.f; o.post_shift = 0.f;
-            return profiled(c, s, VT_PROF_CONV_OUT, 2.0 * B * (double)h * w * cw.cout * 9.0 * cw.cin, "conv_out_halo", [&] { return vt_launch_conv_out_halo(o, s); });
-        }
-        ConvGemmArgs a{};
-        a.X = act; a.W = out16 ? cw.w16 : cw.w; a.f16 = out16; a.bias = cw.b; a.out_f32 = image; a.zeros = c->zeros;
-        a.Hin = a.Hout = h; a.Win = a.Wout = w; a.Cin = cw.cin; a.Cout = cw.cout; a.Wrows = cw.cout;
-        a.ksize = 3; a.stride = 1; a.pad = 1; a.ldx = cw.cin; a.ldw = 9 * cw.cin; a.ldo = cw.cout;
-        a.cout_keep = d.out_ch;
-        a.x_bs = (long long)h * w * cw.cin; a.o_bs = (long long)a.cout_keep * h * w; a.batch = B; a.alpha = 1.f;
-        a.bias_mode = 1; a.out_mode = 1; a.post_scale = 1.f; a.post_shift = 0.f;
-        return launch_gemm(c, a, s, "conv_out");
     }
 };
 
@@ -237,11 +154,7 @@ int vt_image_decoder_configure(vt_context* c, int out_ch, int latent, const int*
     d = ImageDecoderW();
     d.out_ch = out_ch; d.latent = latent; d.layers = layers; d.groups = groups;
     d.block_out.assign(block_out, block_out + n_blocks);
-    for (int ch : d.block_out) {
-        if (ch % groups || ch % 64 || ch > 2048) return c->fail(VT_ERR_INVALID, "block_out_channels entries must be multiples of 64 and of norm_num_groups (got %d)", ch);
-        const int cpg = ch / groups;
-        if (cpg < 2 || (cpg & (cpg - 1)) || (256 % (ch / 8))) return c->fail(VT_ERR_INVALID, "unsupported channels/groups combination %d/%d", ch, groups);
-    }
+    VTCK(check_block_out(c, block_out, n_blocks, groups));
     if (has_scaling && scaling == 0.f) return c->fail(VT_ERR_INVALID, "scaling_factor must not be 0");
     d.scaling = scaling; d.has_scaling = has_scaling != 0; d.shift = shift; d.has_shift = has_shift != 0;
     d.configured = true;
@@ -264,20 +177,18 @@ int vt_decode_image(vt_context* c, const float* z, int B, int h, int w, int unsc
     const int up = 1 << ((int)d.block_out.size() - 1);
     const size_t need_img = (size_t)B * d.out_ch * ((size_t)h * up) * ((size_t)w * up) * 4;
     if (image_bytes < need_img) return c->fail(VT_ERR_INVALID, "vt_decode_image: image buffer %zu < required %zu", image_bytes, need_img);
-    const DecPlan p = plan_decoder(d, B, h, w);
+    const VaePlan p = plan_decoder(d, B, h, w);
     if (ws_bytes < p.total) return c->fail(VT_ERR_WORKSPACE, "vt_decode_image: workspace %zu < required %zu", ws_bytes, p.total);
     if (((uintptr_t)ws) % ALIGN) return c->fail(VT_ERR_INVALID, "vt_decode_image: workspace must be 256-B aligned");
-    const int saved_fp8 = c->fp8;
-    c->fp8 = 0;                                                          // decode has no fp8 form: 16-bit operands everywhere
+    const NoFp8 no_fp8(c);                                               // decode has no fp8 form: 16-bit operands everywhere
     DecRun run(c, p, B, h, w, ws, (hipStream_t)stream);
-    int r = run.conv_in(z, unscale);
-    if (!r) r = run.resnet(d.mid0);
-    if (!r) r = run.mid_attention();
-    if (!r) r = run.resnet(d.mid1);
-    for (size_t i = 0; i < d.ups.size() && !r; ++i) r = run.up_block(i);
-    if (!r) r = run.conv_out(image);
-    c->fp8 = saved_fp8;
-    return r;
+    VTCK(run.conv_in(z, unscale));
+    VTCK(run.resnet(d.mid0));
+    VTCK(run.mid_attention(d.attn));
+    VTCK(run.resnet(d.mid1));
+    for (size_t i = 0; i < d.ups.size(); ++i) VTCK(run.up_block(i));
+    // conv_norm_out + SiLU + conv_out -> fp32 NCHW image (the first out_ch of the zero-padded 32 couts)
+    return run.conv_out(d.conv_out, d.norm_out, d.out_ch, 1.f, 0.f, image);
 }
 
 }  // extern "C"

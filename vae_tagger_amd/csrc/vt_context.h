@@ -1,5 +1,7 @@
 // Internal to the host side of the library: the context behind the C ABI, the packed-weight tables, and the few functions that
-// cross the host units (weights.hip, encoder.hip, attention.hip, ops.hip, capi.hip).  Nothing here is part of the public header.
+// cross the host units (weights.hip, encoder.hip, vae_run.hip, image_decoder.hip, attention.hip, ops.hip, capi.hip): the conv / GroupNorm
+// launch helpers of encoder.hip and attention.hip's entry.  The run layer both VAE schedules are built on (VaeRun: workspace plan and
+// carve, resnet / mid-attention / conv_out steps) has a header of its own, vt_vae_run.h.  Nothing here is part of the public header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>

@@ -1,4 +1,5 @@
-// Weight packing (host code): number conversions, the operand layouts of every conv / attention kernel, vt_encoder_finalize.
+// Weight packing (host code): number conversions, the operand layouts of every conv / attention kernel, vt_encoder_finalize and
+// vt_image_decoder_finalize over the same per-layer packers (pack_conv, get_resnet, get_mid_block).
 #include <math.h>
 
 #include <algorithm>
@@ -105,17 +106,13 @@ ConvE4m3 pack_conv_e4m3(const float* w_oihw, int cout, int cin, bool s2_layout) 
 template <class T, class V>
 static bool up(vt_context* c, const T** dst, const std::vector<V>& v) { return (*dst = (const T*)c->upload(v.data(), v.size() * sizeof(V))) != nullptr; }
 
+// Every packing of one conv from its fp32 OIHW weight `wv` and bias `bv` (cout floats); `name` is for messages only.
 // `mult8_host`: receives the fp8 halo kernel's per-cout multipliers (empty when the conv has no fp8 form)
-static int get_conv(vt_context* c, const std::string& name, int cout, int cin, int k, ConvW* out, bool stride2 = false, std::vector<float>* mult8_host = nullptr) {
-    const HostTensor* w = c->find(name + ".weight");
-    const HostTensor* b = c->find(name + ".bias");
-    if (!w || !b) return c->fail(VT_ERR_MISSING_WEIGHT, "missing weight %s.{weight,bias}", name.c_str());
-    if (w->shape.size() != 4 || w->shape[0] != cout || w->shape[1] != cin || w->shape[2] != k || w->shape[3] != k || b->numel() != cout)
-        return c->fail(VT_ERR_INVALID, "shape mismatch for %s", name.c_str());
-    const float* wv = w->v.data();
+static int pack_conv(vt_context* c, const std::string& name, const float* wv, const float* bv, int cout, int cin, int k, ConvW* out, bool stride2 = false,
+                     std::vector<float>* mult8_host = nullptr) {
     const auto failed = [&] { return c->fail(VT_ERR_HIP, "upload failed for %s", name.c_str()); };
     out->cin = cin; out->cout = cout; out->k = k;
-    if (!up(c, &out->w, pack_ohwi<uint16_t>(wv, cout, cin, k * k, to_bf16)) || !up(c, &out->b, b->v)) return failed();
+    if (!up(c, &out->w, pack_ohwi<uint16_t>(wv, cout, cin, k * k, to_bf16)) || !(out->b = (const float*)c->upload(bv, (size_t)cout * 4))) return failed();
     // halo kernel: Wp[cin/32][step][cout][32] (step = kx*3 + ky) so each K-step's weight tile is one contiguous block
     if (k == 3 && vt_conv3x3_halo_supported(cin, cout) && !up(c, &out->wp, permute_weights<uint16_t>(wv, cout, cin, 9, 32, step_halo, row64, to_bf16))) return failed();
     // stride-2 kernel: Wp2[cin/32][step][cout row][32], steps in plane order (vt_s2_step_of_tap)
@@ -136,6 +133,15 @@ static int get_conv(vt_context* c, const std::string& name, int cout, int cin, i
         if (mult8_host) *mult8_host = p.mult8;
     }
     return VT_OK;
+}
+// ... of the conv whose tensors the caller set as `name`.weight / .bias
+static int get_conv(vt_context* c, const std::string& name, int cout, int cin, int k, ConvW* out, bool stride2 = false, std::vector<float>* mult8_host = nullptr) {
+    const HostTensor* w = c->find(name + ".weight");
+    const HostTensor* b = c->find(name + ".bias");
+    if (!w || !b) return c->fail(VT_ERR_MISSING_WEIGHT, "missing weight %s.{weight,bias}", name.c_str());
+    if (w->shape.size() != 4 || w->shape[0] != cout || w->shape[1] != cin || w->shape[2] != k || w->shape[3] != k || b->numel() != cout)
+        return c->fail(VT_ERR_INVALID, "shape mismatch for %s", name.c_str());
+    return pack_conv(c, name, w->v.data(), b->v.data(), cout, cin, k, out, stride2, mult8_host);
 }
 static int get_norm(vt_context* c, const std::string& name, int ch, NormW* out) {
     const HostTensor* g = c->find(name + ".weight");
@@ -243,6 +249,22 @@ static int get_attention(vt_context* c, const std::string& a, int C, AttnW* at) 
     return ok ? VT_OK : c->fail(VT_ERR_HIP, "upload failed for attention");
 }
 
+// `prefix`.mid_block: resnet, attention, resnet.  The packing order decides only the order of the model's allocation list, and each model
+// keeps the one it had: the encoder packs the attention after both resnets, the image decoder between them.
+static int get_mid_block(vt_context* c, const std::string& prefix, int C, bool attn_last, ResnetW* mid0, AttnW* attn, ResnetW* mid1) {
+    VTCK(get_resnet(c, prefix + ".mid_block.resnets.0", C, C, mid0));
+    if (!attn_last) VTCK(get_attention(c, prefix + ".mid_block.attentions.0", C, attn));
+    VTCK(get_resnet(c, prefix + ".mid_block.resnets.1", C, C, mid1));
+    if (attn_last) VTCK(get_attention(c, prefix + ".mid_block.attentions.0", C, attn));
+    return VT_OK;
+}
+
+// the host copies of a finalized model's tensors are no longer needed: erase every key that starts with `prefix`
+static void erase_host_tensors(vt_context* c, const std::string& prefix) {
+    for (auto it = c->weights.begin(); it != c->weights.end();)
+        it = (it->first.compare(0, prefix.size(), prefix) == 0) ? c->weights.erase(it) : ++it;
+}
+
 }  // namespace vt
 
 using namespace vt;
@@ -279,13 +301,10 @@ extern "C" int vt_encoder_finalize(vt_context* c) {
         e.stages.push_back(st);
     }
     const int C = e.block_out.back();
-    VTCK(get_resnet(c, "encoder.mid_block.resnets.0", C, C, &e.mid0));
-    VTCK(get_resnet(c, "encoder.mid_block.resnets.1", C, C, &e.mid1));
-    VTCK(get_attention(c, "encoder.mid_block.attentions.0", C, &e.attn));
+    VTCK(get_mid_block(c, "encoder", C, true, &e.mid0, &e.attn, &e.mid1));
     VTCK(get_norm(c, "encoder.conv_norm_out", C, &e.norm_out));
     VTCK(get_conv(c, "encoder.conv_out", 2 * e.latent, C, 3, &e.conv_out));
-    for (auto it = c->weights.begin(); it != c->weights.end();)
-        it = (it->first.compare(0, 8, "encoder.") == 0) ? c->weights.erase(it) : ++it;
+    erase_host_tensors(c, "encoder.");
     e.finalized = true;
     return VT_OK;
 }
@@ -322,17 +341,11 @@ static int finalize_image_decoder(vt_context* c, ImageDecoderW& d) {
         const HostTensor* b = c->find("decoder.conv_in.bias");
         if (!w || !b) return c->fail(VT_ERR_MISSING_WEIGHT, "missing weight decoder.conv_in.{weight,bias}");
         if (w->numel() != (int64_t)C * d.latent * 9 || b->numel() != C) return c->fail(VT_ERR_INVALID, "shape mismatch for decoder.conv_in");
-        HostTensor wpad;
-        wpad.shape = {C, Lp, 3, 3}; wpad.v.assign((size_t)C * Lp * 9, 0.f);
-        for (int o = 0; o < C; ++o) std::copy(w->v.begin() + (size_t)o * d.latent * 9, w->v.begin() + (size_t)(o + 1) * d.latent * 9, wpad.v.begin() + (size_t)o * Lp * 9);
-        HostTensor bias = *b;
-        c->weights["decoder.conv_in.padded.weight"] = std::move(wpad);
-        c->weights["decoder.conv_in.padded.bias"] = std::move(bias);
-        VTCK(get_conv(c, "decoder.conv_in.padded", C, Lp, 3, &d.conv_in));
+        std::vector<float> wpad((size_t)C * Lp * 9, 0.f);
+        for (int o = 0; o < C; ++o) std::copy(w->v.begin() + (size_t)o * d.latent * 9, w->v.begin() + (size_t)(o + 1) * d.latent * 9, wpad.begin() + (size_t)o * Lp * 9);
+        VTCK(pack_conv(c, "decoder.conv_in", wpad.data(), b->v.data(), C, Lp, 3, &d.conv_in));
     }
-    VTCK(get_resnet(c, "decoder.mid_block.resnets.0", C, C, &d.mid0));
-    VTCK(get_attention(c, "decoder.mid_block.attentions.0", C, &d.attn));
-    VTCK(get_resnet(c, "decoder.mid_block.resnets.1", C, C, &d.mid1));
+    VTCK(get_mid_block(c, "decoder", C, false, &d.mid0, &d.attn, &d.mid1));
     int ci = C;
     for (int i = 0; i < nb; ++i) {
         UpBlockW u;
@@ -357,14 +370,10 @@ static int finalize_image_decoder(vt_context* c, ImageDecoderW& d) {
     const HostTensor* b = c->find("decoder.conv_out.bias");
     if (!w || !b) return c->fail(VT_ERR_MISSING_WEIGHT, "missing weight decoder.conv_out.{weight,bias}");
     if (w->numel() != (int64_t)d.out_ch * ci * 9 || b->numel() != d.out_ch) return c->fail(VT_ERR_INVALID, "shape mismatch for decoder.conv_out");
-    HostTensor wpad, bpad;
-    wpad.shape = {32, ci, 3, 3}; wpad.v.assign((size_t)32 * ci * 9, 0.f);
-    std::copy(w->v.begin(), w->v.end(), wpad.v.begin());
-    bpad.shape = {32}; bpad.v.assign(32, 0.f);
-    std::copy(b->v.begin(), b->v.end(), bpad.v.begin());
-    c->weights["decoder.conv_out.padded.weight"] = std::move(wpad);
-    c->weights["decoder.conv_out.padded.bias"] = std::move(bpad);
-    return get_conv(c, "decoder.conv_out.padded", 32, ci, 3, &d.conv_out);
+    std::vector<float> wpad((size_t)32 * ci * 9, 0.f), bpad(32, 0.f);
+    std::copy(w->v.begin(), w->v.end(), wpad.begin());
+    std::copy(b->v.begin(), b->v.end(), bpad.begin());
+    return pack_conv(c, "decoder.conv_out", wpad.data(), bpad.data(), 32, ci, 3, &d.conv_out);
 }
 
 extern "C" int vt_image_decoder_finalize(vt_context* c) {
@@ -382,8 +391,7 @@ extern "C" int vt_image_decoder_finalize(vt_context* c) {
     const int r = finalize_image_decoder(c, d);
     c->pack_fp8 = true;
     c->cur_allocs = saved;
-    for (auto it = c->weights.begin(); it != c->weights.end();)
-        it = (it->first.compare(0, 8, "decoder.") == 0) ? c->weights.erase(it) : ++it;
+    erase_host_tensors(c, "decoder.");
     if (r) return r;
     d.finalized = true;
     return VT_OK;
