@@ -684,6 +684,45 @@ int vt_op_groupnorm(vt_context* ctx, const void* x, int x_dtype, int B, int HW, 
                     const float* gamma, const float* beta, int silu, void* y_bf16, void* workspace, void* stream);
 int vt_op_softmax_rows(vt_context* ctx, const float* scores, void* probs_bf16, int rows, int n, int lds, int ldp,
                        void* stream);
+/* ---- backward of one ResnetBlock2D's layers (the block both VAE models consist of).  All gradients fp32, all MFMA operands bf16 with fp32
+ * accumulation whatever flag 18 says; no atomics, every result bit-identical from run to run; one stream, no host synchronisation (the data
+ * gradient takes its scratch from the context: the first call of a size may synchronise).  vae_tagger_amd/vae_backward.py composes them.
+ *
+ * vt_op_cast_bias_grad: one pass over dy (fp32 [rows][C], rows = B*H*W): dy16 = bf16(dy), round to nearest even, and dbias[c] = sum over rows
+ * (either output may be NULL).  Sums: fp64 per lane, per row chunk, then a fixed-order fp64 finish.  C % 4 == 0, C <= 1024; workspace only
+ * with dbias. */
+size_t vt_op_cast_bias_grad_workspace_bytes(long long rows, int C);
+int vt_op_cast_bias_grad(vt_context* ctx, const float* dy_f32, void* dy16_out, float* dbias_out, long long rows, int C, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* Data gradient of a stride-1 conv, 3x3 pad 1 or 1x1: dx[b][y][x][ci] = sum dy16[b][y+1-ky][x+1-kx][co] * bf16(W[co][ci][ky][kx]) (+ dx_add),
+ * fp32 NHWC.  W is the conv's fp32 OIHW parameter ON THE DEVICE; it is packed (rotated by 180 degrees, transposed in (co, ci), rounded to bf16)
+ * on the stream and the forward stride-1 conv vt_op_conv2d runs is launched on it.  dy16 bf16 NHWC [B][H][W][Cout]; dx_add optional fp32
+ * [B][H][W][Cin] (the conv's residual input).  Cin % 8 == 0, Cout % 8 == 0. */
+int vt_op_conv_backward_data(vt_context* ctx, const void* dy16_nhwc, const float* w_f32_oihw, const float* dx_add, float* dx_f32, int B, int H,
+                             int W, int Cin, int Cout, int ksize, void* stream);
+/* Weight gradient of the same convs: dw[co][ci][ky][kx] = sum_{b,y,x} dy16[b][y][x][co] * a16[b][y+ky-1][x+kx-1][ci] (taps outside the image
+ * count as 0), fp32 OIHW.  a16 is the conv's forward operand, bf16 NHWC [B][H][W][Cin].  The pixels are cut into `splits` slices (0: chosen from
+ * the shape so that workgroups ~ twice the CU count, two being resident per CU; more than the number of pixel steps: clamped); each slice writes a partial dw to the
+ * workspace, a second launch adds them in slice order.  Cin % 64 == 0, Cout % 64 == 0, ksize 1 or 3, any B, H, W >= 1.  The workspace must
+ * be sized with the same `splits`. */
+size_t vt_op_conv_backward_weight_workspace_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int splits);
+int vt_op_conv_backward_weight(vt_context* ctx, const void* dy16_nhwc, const void* a16_nhwc, float* dw_f32_oihw, int B, int H, int W, int Cin,
+                               int Cout, int ksize, int splits, void* workspace, size_t workspace_bytes, void* stream);
+/* error while flag 18 (fp16 operands) is on: functions that mix these operators with the forward ones ask here first */
+int vt_op_backward_operands_check(vt_context* ctx);
+/* (mean, rstd) fp32 [B][groups][2] of an fp32 tensor [B][HW][C], from fp64 sums of x and x^2 taken in a fixed order (the forward's (scale, shift)
+ * table cannot stand in: it loses xh wherever gamma = 0).  Same shapes as vt_op_groupnorm_silu_backward. */
+size_t vt_op_groupnorm_stats_workspace_bytes(int B, int HW, int C);
+int vt_op_groupnorm_stats(vt_context* ctx, const float* x_f32, int B, int HW, int C, int groups, float eps, float* stats_out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* Backward of a = silu(GroupNorm(x)): with xh = (x - mean) rstd, u = gamma xh + beta, s = sigmoid(u), du = da s (1 + u (1 - s)):
+ * dbeta[c] = sum du, dgamma[c] = sum du xh, dx = rstd (gamma du - mean_g(gamma du) - xh mean_g(gamma du xh)) (+ dx_add), means over the (C/groups) HW
+ * elements of one image's group.  x, da, dx_add, dx fp32 [B][HW][C]; stats from vt_op_groupnorm_stats; dx16 (optional) = bf16(dx); dgamma, dbeta
+ * optional.  Two passes over x and da; the sums are fp64 throughout, in a fixed order.  C / groups in {4, 8, 16}, C a power of two <= 1024. */
+size_t vt_op_groupnorm_silu_backward_workspace_bytes(int B, int HW, int C);
+int vt_op_groupnorm_silu_backward(vt_context* ctx, const float* x_f32, const float* stats, const float* gamma, const float* beta, const float* da_f32,
+                                  const float* dx_add, float* dx_f32, void* dx16_out, float* dgamma_out, float* dbeta_out, int B, int HW, int C,
+                                  int groups, void* workspace, size_t workspace_bytes, void* stream);
 size_t vt_op_attention_workspace_bytes(int B, int S, int C);
 int vt_op_attention(vt_context* ctx, const void* x_bf16 /* [B][S][C] normed tokens */, const float* residual_f32,
                     float* out_f32, int B, int S, int C, void* workspace, void* stream);

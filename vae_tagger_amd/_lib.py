@@ -170,6 +170,16 @@ PROTOTYPES = {
     "vt_op_groupnorm_workspace_bytes": (_sz, [_i, _i, _i]),
     "vt_op_groupnorm": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp]),
     "vt_op_softmax_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "vt_op_cast_bias_grad_workspace_bytes": (_sz, [_ll, _i]),
+    "vt_op_cast_bias_grad": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _vp, _sz, _vp]),
+    "vt_op_conv_backward_data": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "vt_op_conv_backward_weight_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "vt_op_conv_backward_weight": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "vt_op_backward_operands_check": (_i, [_vp]),
+    "vt_op_groupnorm_stats_workspace_bytes": (_sz, [_i, _i, _i]),
+    "vt_op_groupnorm_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    "vt_op_groupnorm_silu_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "vt_op_groupnorm_silu_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "vt_op_attention_workspace_bytes": (_sz, [_i, _i, _i]),
     "vt_op_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
 }

@@ -280,6 +280,134 @@ int vt_op_groupnorm(vt_context* c, const void* x, int x_dtype, int B, int HW, in
     return VT_OK;
 }
 
+// ---- backward of the resnet block's layers: bf16 operands whatever flag 18 says, fp32 results, no atomics ----
+
+size_t vt_op_cast_bias_grad_workspace_bytes(long long rows, int C) {
+    const int chunks = vt_cast_bias_chunks(rows, C);
+    return chunks > 0 ? align_up((size_t)chunks * C * sizeof(double)) : 0;
+}
+
+int vt_op_cast_bias_grad(vt_context* c, const float* dy, void* dy16, float* dbias, long long rows, int C, void* ws, size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!dy || (!dy16 && !dbias)) return c->fail(VT_ERR_INVALID, "vt_op_cast_bias_grad: null buffer");
+    if (rows <= 0 || !vt_cast_bias_supported(C) || vt_cast_bias_chunks(rows, C) <= 0)
+        return c->fail(VT_ERR_INVALID, "vt_op_cast_bias_grad: needs rows > 0 and C a multiple of 4, at most 1024 (got rows %lld, C %d)", rows, C);
+    if (dbias && (!ws || ((uintptr_t)ws % 16) || ws_bytes < vt_op_cast_bias_grad_workspace_bytes(rows, C)))
+        return c->fail(VT_ERR_INVALID, "vt_op_cast_bias_grad: workspace must be 16-byte aligned and hold vt_op_cast_bias_grad_workspace_bytes = %zu bytes (got %zu)",
+                       vt_op_cast_bias_grad_workspace_bytes(rows, C), ws_bytes);
+    HIPCK(c, vt_launch_cast_bias_grad(dy, (bf16_t*)dy16, dbias, rows, C, (double*)ws, (hipStream_t)stream), "vt_op_cast_bias_grad");
+    return VT_OK;
+}
+
+int vt_op_conv_backward_data(vt_context* c, const void* dy16, const float* w_oihw, const float* dx_add, float* dx, int B, int H, int W, int Cin, int Cout,
+                             int ksize, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!dy16 || !w_oihw || !dx) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_data: null buffer");
+    if (ksize != 1 && ksize != 3) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_data: ksize must be 1 or 3 (stride 1, pad ksize / 2), got %d", ksize);
+    if (B <= 0 || H <= 0 || W <= 0 || Cin < 8 || (Cin % 8) || Cout < 8 || (Cout % 8))
+        return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_data: Cin and Cout must be multiples of 8 and B, H, W >= 1 (got %d -> %d, %d x %d x %d)", Cin, Cout, B, H, W);
+    hipStream_t s = (hipStream_t)stream;
+    // dx = conv(dy16, W'), W'[ci][ky'][kx'][co] = bf16(W[co][ci][2 - ky'][2 - kx']): the forward conv with Cout input and Cin output channels
+    const int taps = ksize * ksize;
+    const size_t w_bytes = align_up((size_t)Cin * taps * Cout * 2);
+    const bool halo = c->use_halo_conv && ksize == 3 && vt_conv3x3_halo_supported(Cout, Cin);
+    VTCK(ensure_op_scratch(c, w_bytes * (halo ? 2 : 1)));
+    bf16_t* wt = (bf16_t*)c->op_scratch;
+    HIPCK(c, vt_launch_pack_dgrad_weights(w_oihw, wt, Cin, Cout, ksize, s), "pack_dgrad_weights");
+    if (halo) {
+        bf16_t* wp = (bf16_t*)((char*)c->op_scratch + w_bytes);
+        HIPCK(c, vt_launch_repack_ohwi_to_halo(wt, wp, Cout, Cin, s), "repack");
+        Conv3x3Args h{};
+        h.X = (const bf16_t*)dy16; h.Wp = wp; h.res = dx_add; h.out_f32 = dx; h.zeros = c->zeros; h.batch = B; h.H = H; h.W = W; h.Cin = Cout; h.Cout = Cin;
+        return launch_halo(c, h, s, "vt_op_conv_backward_data(halo)");
+    }
+    ConvGemmArgs a{};
+    a.X = (const bf16_t*)dy16; a.W = wt; a.res = dx_add; a.out_f32 = dx; a.zeros = c->zeros;
+    a.Hin = H; a.Win = W; a.Hout = H; a.Wout = W; a.Cin = Cout; a.Cout = Cin; a.Wrows = Cin; a.ksize = ksize; a.stride = 1; a.pad = ksize / 2;
+    a.ldx = Cout; a.ldw = taps * Cout; a.ldo = Cin; a.ldr = Cin;
+    a.x_bs = (long long)H * W * Cout; a.o_bs = (long long)H * W * Cin; a.r_bs = a.o_bs; a.batch = B; a.alpha = 1.f; a.bias_mode = 0;
+    return launch_gemm(c, a, s, "vt_op_conv_backward_data");
+}
+
+static int wgrad_splits(int B, int H, int W, int Cin, int Cout, int splits) {
+    const int steps = vt_conv_wgrad_steps(B, H, W);
+    if (splits <= 0) return vt_conv_wgrad_auto_splits(B, H, W, Cin, Cout);
+    return splits > steps ? steps : splits;             // more slices than pixel steps: clamped, every slice holds at least one step
+}
+
+size_t vt_op_conv_backward_weight_workspace_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int splits) {
+    if (!vt_conv_wgrad_supported(Cin, Cout, ksize) || vt_conv_wgrad_steps(B, H, W) <= 0) return 0;
+    return align_up((size_t)wgrad_splits(B, H, W, Cin, Cout, splits) * Cout * Cin * ksize * ksize * sizeof(float));
+}
+
+int vt_op_conv_backward_weight(vt_context* c, const void* dy16, const void* a16, float* dw, int B, int H, int W, int Cin, int Cout, int ksize, int splits,
+                               void* ws, size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!dy16 || !a16 || !dw) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: null buffer");
+    if (!vt_conv_wgrad_supported(Cin, Cout, ksize))
+        return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: Cin and Cout must be multiples of 64 and ksize 1 or 3 (got %d -> %d, ksize %d)", Cin, Cout, ksize);
+    if (B <= 0 || H <= 0 || W <= 0 || vt_conv_wgrad_steps(B, H, W) <= 0) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: B, H, W must be >= 1");
+    if (splits < 0) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: splits must be >= 0 (0 = chosen from the shape)");
+    const size_t need = vt_op_conv_backward_weight_workspace_bytes(B, H, W, Cin, Cout, ksize, splits);
+    if (!ws || ((uintptr_t)ws % 16) || ((uintptr_t)dw % 16) || ws_bytes < need)
+        return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: workspace must be 16-byte aligned and hold vt_op_conv_backward_weight_workspace_bytes = %zu "
+                       "bytes (got %zu)", need, ws_bytes);
+    ConvWgradArgs a{};
+    a.dy = (const bf16_t*)dy16; a.a = (const bf16_t*)a16; a.dw = dw; a.ws = (float*)ws; a.batch = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksize = ksize;
+    a.splits = wgrad_splits(B, H, W, Cin, Cout, splits);
+    HIPCK(c, vt_launch_conv_wgrad(a, (hipStream_t)stream), "vt_op_conv_backward_weight");
+    return VT_OK;
+}
+
+// The block functions (vae_backward.py) mix these operators with the forward ones, which follow flag 18: they ask here first.
+int vt_op_backward_operands_check(vt_context* c) {
+    if (!c) return VT_ERR_INVALID;
+    if (c->f16_ops) return c->fail(VT_ERR_INVALID, "the resnet block's backward runs on bf16 operands: fp16-operand mode (vt_set_flag 18) must be off");
+    return VT_OK;
+}
+
+size_t vt_op_groupnorm_stats_workspace_bytes(int B, int HW, int C) {
+    const size_t n = vt_gn_stats64_ws_bytes(B, HW, C);
+    return n ? align_up(n) : 0;
+}
+
+int vt_op_groupnorm_stats(vt_context* c, const float* x, int B, int HW, int C, int groups, float eps, float* stats, void* ws, size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!x || !stats) return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: null buffer");
+    if (B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups))
+        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: channels per group must be 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
+    const size_t need = vt_op_groupnorm_stats_workspace_bytes(B, HW, C);
+    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
+        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
+    HIPCK(c, vt_launch_gn_stats64(x, B, HW, C, groups, eps, stats, ws, (hipStream_t)stream), "vt_op_groupnorm_stats");
+    return VT_OK;
+}
+
+size_t vt_op_groupnorm_silu_backward_workspace_bytes(int B, int HW, int C) {
+    const size_t n = vt_gn_silu_bwd_ws_bytes(B, HW, C);
+    return n ? align_up(n) : 0;
+}
+
+int vt_op_groupnorm_silu_backward(vt_context* c, const float* x, const float* stats, const float* gamma, const float* beta, const float* da,
+                                  const float* dx_add, float* dx, void* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws,
+                                  size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!x || !stats || !gamma || !beta || !da || !dx) return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: null buffer");
+    if (B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups))
+        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: channels per group must be 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
+    const size_t need = vt_op_groupnorm_silu_backward_workspace_bytes(B, HW, C);
+    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
+        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
+    HIPCK(c, vt_launch_gn_silu_backward(x, stats, gamma, beta, da, dx_add, dx, (bf16_t*)dx16, dgamma, dbeta, B, HW, C, groups, ws, (hipStream_t)stream),
+          "vt_op_groupnorm_silu_backward");
+    return VT_OK;
+}
+
 int vt_op_softmax_rows(vt_context* c, const float* scores, void* probs, int rows, int n, int lds, int ldp, void* stream) {
     if (!c) return VT_ERR_INVALID;
     DeviceGuard guard(c);

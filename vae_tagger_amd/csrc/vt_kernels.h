@@ -357,5 +357,39 @@ hipError_t vt_launch_attn_row_reduce(const float* part, int slots, long long row
 hipError_t vt_launch_softmax_rows(const void* scores, int scores_f16, bf16_t* probs, long long rows, int n, int lds,
                                   int ldp, hipStream_t s);
 
+// ---- backward of the VAE's resnet block (conv_wgrad.hip, backward_kernels.hip).  bf16 MFMA operands, fp32 results, no atomics.
+// Weight gradient of a 3x3 pad-1 / 1x1 stride-1 conv: dw[co][ci][ky][kx] = sum_p dy16[p][co] * a16[p + (ky - 1, kx - 1)][ci], fp32 OIHW.  The pixel
+// tiles (vt_conv_wgrad_steps of them) are cut into `splits` contiguous slices; every slice writes a partial dw to `ws`, a second launch adds them in
+// slice order.  Cin % 64 == 0, Cout % 64 == 0, ksize 1 or 3, 1 <= splits <= steps.
+struct ConvWgradArgs {
+    const bf16_t* dy;       // NHWC bf16 [batch][H][W][Cout]
+    const bf16_t* a;        // NHWC bf16 [batch][H][W][Cin]: the conv's forward operand
+    float* dw;              // fp32 [Cout][Cin][ksize][ksize]
+    float* ws;              // >= splits * Cout * Cin * ksize^2 floats
+    int batch, H, W, Cin, Cout, ksize, splits;
+    int tiles_x, tiles_y, steps;     // filled by the launcher
+};
+int vt_conv_wgrad_steps(int B, int H, int W);
+int vt_conv_wgrad_auto_splits(int B, int H, int W, int Cin, int Cout);      // workgroups = splits * (Cin / 64) * (Cout / 64) <= 512: two per CU
+bool vt_conv_wgrad_supported(int Cin, int Cout, int ksize);
+hipError_t vt_launch_conv_wgrad(const ConvWgradArgs& a, hipStream_t s);
+// fp32 OIHW (device) -> bf16 [Cin][tap'][Cout] with tap' = taps - 1 - tap: the weights of the forward conv that IS the data gradient
+// (rotated by 180 degrees, transposed in (co, ci)); ksize 1 or 3
+hipError_t vt_launch_pack_dgrad_weights(const float* w_oihw, bf16_t* dst, int Cin, int Cout, int ksize, hipStream_t s);
+// dy16 = bf16(dy) (optional) and dbias[c] = sum over rows (optional): fp64 partials per row chunk in `part`, then a fixed-order fp64 finish.
+// C % 4 == 0, C <= 1024.  part: vt_cast_bias_chunks(rows, C) * C doubles.
+int vt_cast_bias_chunks(long long rows, int C);
+bool vt_cast_bias_supported(int C);
+hipError_t vt_launch_cast_bias_grad(const float* dy, bf16_t* dy16, float* dbias, long long rows, int C, double* part, hipStream_t s);
+// (mean, rstd) [B][groups][2] of fp32 rows [B][HW][C]: fp64 sums of x and x^2 per pixel chunk, then a fixed-order fp64 finish; same shapes as
+// vt_gn_silu_bwd_supported; ws: vt_gn_stats64_ws_bytes(B, HW, C) bytes, 16-B aligned
+size_t vt_gn_stats64_ws_bytes(int B, int HW, int C);
+hipError_t vt_launch_gn_stats64(const float* x, int B, int HW, int C, int groups, float eps, float* stats, void* ws, hipStream_t s);
+// GroupNorm + SiLU backward on fp32 rows [B][HW][C] (see vt_op_groupnorm_silu_backward); ws: vt_gn_silu_bwd_ws_bytes(B, HW, C) bytes, 16-B aligned
+size_t vt_gn_silu_bwd_ws_bytes(int B, int HW, int C);
+bool vt_gn_silu_bwd_supported(int C, int groups);
+hipError_t vt_launch_gn_silu_backward(const float* x, const float* stats, const float* gamma, const float* beta, const float* da, const float* dx_add,
+                                      float* dx, bf16_t* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws, hipStream_t s);
+
 // decoder (all fp32)
 struct DecoderWeights;   // defined in vt_decoder.h

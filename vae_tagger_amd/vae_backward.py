@@ -1,0 +1,227 @@
+"""Backward of one ResnetBlock2D -- the block both VAE models consist of -- on the device: thin wrappers over the vt_op_* backward operators
+(include/vae_tagger_hip.h).  Tensors are torch tensors of one HIP device, activations NHWC ([B, H, W, C]), parameters in
+diffusers' own layouts (conv weights fp32 OIHW).  All gradients are fp32; every MFMA operand is bf16.  Every launch goes to torch's current stream
+of the tensors' device and nothing here synchronises with the host.  There is no eager fallback: a shape an operator refuses raises VTError.
+
+This is NOT train_vae: there is no optimiser, no loss and no backward of the other layer kinds (stride-2 convs, Upsample2D, attention, conv_in,
+conv_out) here.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+GROUPS, EPS = 32, 1e-6          # ResnetBlock2D's GroupNorm in the FLUX VAE
+
+_contexts = {}
+
+
+def context(device=None):
+    """The vt_context this module's functions use on `device` (default: the current one); flags set on it (vt_set_flag) apply to them."""
+    idx = torch.device(device).index if device is not None else None
+    if idx is None:
+        idx = torch.cuda.current_device()
+    if idx not in _contexts:
+        _contexts[idx] = _lib.Context(idx)
+    return _contexts[idx]
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _stream(t):
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _f32(t, what):
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous fp32 tensor on the device")
+    return t
+
+
+def _bf16(t, what):
+    if t.dtype != torch.bfloat16 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous bf16 tensor on the device")
+    return t
+
+
+def _workspace(nbytes, device):
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)      # (torch's allocations are 512-byte aligned)
+
+
+def cast_bias_grad(dy, *, want_dy16=True, want_bias=True):
+    """dy fp32 [..., C] -> (bf16 copy or None, column sums over all leading dimensions or None), one pass."""
+    dy = _f32(dy, "dy")
+    ctx = context(dy.device)
+    C = dy.shape[-1]
+    rows = dy.numel() // C
+    dy16 = torch.empty(dy.shape, dtype=torch.bfloat16, device=dy.device) if want_dy16 else None
+    db = torch.empty(C, dtype=torch.float32, device=dy.device) if want_bias else None
+    n = ctx.lib.vt_op_cast_bias_grad_workspace_bytes(rows, C) if want_bias else 0
+    ws = _workspace(n, dy.device)
+    ctx.call("vt_op_cast_bias_grad", _vp(dy), _vp(dy16), _vp(db), rows, C, _vp(ws), ws.numel(), _stream(dy))
+    return dy16, db
+
+
+def conv_backward_data(dy16, weight, *, dx_add=None):
+    """dy16 bf16 [B, H, W, Cout], weight fp32 OIHW (3x3 pad 1 or 1x1, stride 1) -> dx fp32 [B, H, W, Cin] (+ dx_add)."""
+    dy16 = _bf16(dy16, "dy16")
+    weight = _f32(weight, "weight")
+    B, H, W, Cout = dy16.shape
+    Cin, k = weight.shape[1], weight.shape[2]
+    if weight.shape[0] != Cout or weight.shape[3] != k:
+        raise ValueError("weight does not match dy16")
+    if dx_add is not None and tuple(_f32(dx_add, "dx_add").shape) != (B, H, W, Cin):
+        raise ValueError("dx_add must have dx's shape")
+    dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dy16.device)
+    context(dy16.device).call("vt_op_conv_backward_data", _vp(dy16), _vp(weight), _vp(dx_add), _vp(dx), B, H, W, Cin, Cout, k, _stream(dy16))
+    return dx
+
+
+def conv_backward_weight(dy16, a16, ksize, *, splits=0):
+    """dy16 bf16 [B, H, W, Cout], a16 bf16 [B, H, W, Cin] (the conv's forward operand) -> dW fp32 [Cout, Cin, k, k]."""
+    dy16, a16 = _bf16(dy16, "dy16"), _bf16(a16, "a16")
+    B, H, W, Cout = dy16.shape
+    Cin = a16.shape[-1]
+    if tuple(a16.shape[:3]) != (B, H, W):
+        raise ValueError("a16 does not match dy16")
+    ctx = context(dy16.device)
+    dw = torch.empty(Cout, Cin, ksize, ksize, dtype=torch.float32, device=dy16.device)
+    ws = _workspace(ctx.lib.vt_op_conv_backward_weight_workspace_bytes(B, H, W, Cin, Cout, ksize, int(splits)), dy16.device)
+    ctx.call("vt_op_conv_backward_weight", _vp(dy16), _vp(a16), _vp(dw), B, H, W, Cin, Cout, ksize, int(splits), _vp(ws), ws.numel(), _stream(dy16))
+    return dw
+
+
+def conv_backward(dy, a16, weight, *, need_input=True, need_weight=True, need_bias=True, dx_add=None, splits=0):
+    """Backward of y = conv(a16, bf16(weight)) + bias, stride 1, 3x3 pad 1 or 1x1.  dy: the fp32 gradient [B, H, W, Cout], or its bf16 copy when
+    no bias gradient is asked for (a producer that already wrote the copy saves the cast pass).  -> (dx or None, dW or None, dbias or None)."""
+    if dy.dtype == torch.bfloat16:
+        if need_bias:
+            raise ValueError("the bias gradient needs the fp32 dy")
+        dy16, db = dy, None
+    else:
+        dy16, db = cast_bias_grad(dy, want_bias=need_bias)
+    dw = conv_backward_weight(dy16, a16, weight.shape[2], splits=splits) if need_weight else None
+    dx = conv_backward_data(dy16, weight, dx_add=dx_add) if need_input else None
+    return dx, dw, db
+
+
+def groupnorm_stats(x, groups=GROUPS, eps=EPS):
+    """x fp32 [B, ..., C] -> (mean, rstd) fp32 [B, groups, 2]"""
+    x = _f32(x, "x")
+    ctx = context(x.device)
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    stats = torch.empty(B, groups, 2, dtype=torch.float32, device=x.device)
+    ws = _workspace(ctx.lib.vt_op_groupnorm_stats_workspace_bytes(B, HW, C), x.device)
+    ctx.call("vt_op_groupnorm_stats", _vp(x), B, HW, C, groups, float(eps), _vp(stats), _vp(ws), ws.numel(), _stream(x))
+    return stats
+
+
+def groupnorm_silu_backward(x, stats, gamma, beta, da, *, dx_add=None, want_dx16=False):
+    """Backward of a = silu(GroupNorm(x)).  -> (dx fp32, dx16 bf16 or None, dgamma, dbeta); dx_add (fp32, x's shape) is added into dx."""
+    x, da = _f32(x, "x"), _f32(da, "da")
+    if da.shape != x.shape or (dx_add is not None and _f32(dx_add, "dx_add").shape != x.shape):
+        raise ValueError("da and dx_add must have x's shape")
+    ctx = context(x.device)
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    groups = stats.shape[1]
+    dx = torch.empty_like(x)
+    dx16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_dx16 else None
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    ws = _workspace(ctx.lib.vt_op_groupnorm_silu_backward_workspace_bytes(B, HW, C), x.device)
+    ctx.call("vt_op_groupnorm_silu_backward", _vp(x), _vp(_f32(stats, "stats")), _vp(_f32(gamma, "gamma")), _vp(_f32(beta, "beta")), _vp(da), _vp(dx_add),
+             _vp(dx), _vp(dx16), _vp(dg), _vp(db), B, HW, C, groups, _vp(ws), ws.numel(), _stream(x))
+    return dx, dx16, dg, db
+
+
+# ---- the block ------------------------------------------------------------------------------------------------------------------------------------
+
+def _norm_silu(ctx, x, gamma, beta):
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    ws = _workspace(ctx.lib.vt_op_groupnorm_workspace_bytes(B, HW, C), x.device)
+    ctx.call("vt_op_groupnorm", _vp(x), _lib.VT_F32, B, HW, C, GROUPS, EPS, _vp(gamma), _vp(beta), 1, _vp(y), _vp(ws), _stream(x))
+    return y
+
+
+def _conv(ctx, a16, weight, bias, residual=None):
+    B, H, W, Cin = a16.shape
+    Cout, k = weight.shape[0], weight.shape[2]
+    w16 = weight.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)             # the forward operator's weight operand: bf16 OHWI
+    y = torch.empty(B, H, W, Cout, dtype=torch.float32, device=a16.device)
+    ctx.call("vt_op_conv2d", _vp(a16), _vp(w16), _vp(bias), _vp(residual), _vp(y), None, B, H, W, Cin, Cout, k, 1, k // 2, k // 2, _stream(a16))
+    return y
+
+
+def _check_params(params, x):
+    names = ["norm1.weight", "norm1.bias", "conv1.weight", "conv1.bias", "norm2.weight", "norm2.bias", "conv2.weight", "conv2.bias"]
+    cin, cout = params["conv1.weight"].shape[1], params["conv1.weight"].shape[0]
+    if cin != cout:
+        names += ["conv_shortcut.weight", "conv_shortcut.bias"]
+    missing = [n for n in names if n not in params]
+    if missing or set(params) - set(names):
+        raise ValueError(f"params must hold exactly {names}")
+    for n in names:
+        _f32(params[n], n)
+    if x.shape[-1] != cin:
+        raise ValueError(f"x has {x.shape[-1]} channels, the block takes {cin}")
+    return cin != cout
+
+
+def resnet_block_forward_train(params, x):
+    """ResnetBlock2D forward on the existing operators, keeping what the backward needs.  x fp32 NHWC.  -> (y fp32 NHWC, saved)"""
+    x = _f32(x, "x")
+    ctx = context(x.device)
+    ctx.call("vt_op_backward_operands_check")
+    has_sc = _check_params(params, x)
+    stats1 = groupnorm_stats(x)
+    a1 = _norm_silu(ctx, x, params["norm1.weight"], params["norm1.bias"])
+    h1 = _conv(ctx, a1, params["conv1.weight"], params["conv1.bias"])
+    stats2 = groupnorm_stats(h1)
+    a2 = _norm_silu(ctx, h1, params["norm2.weight"], params["norm2.bias"])
+    saved = {"x": x, "h1": h1, "a1": a1, "a2": a2, "stats1": stats1, "stats2": stats2}
+    if has_sc:
+        saved["x16"] = x.to(torch.bfloat16)
+        res = _conv(ctx, saved["x16"], params["conv_shortcut.weight"], params["conv_shortcut.bias"])
+    else:
+        res = x
+    y = _conv(ctx, a2, params["conv2.weight"], params["conv2.bias"], residual=res)
+    return y, saved
+
+
+def resnet_block_backward(params, saved, dy, *, splits=0):
+    """dy fp32 NHWC, the gradient of resnet_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params)"""
+    dy = _f32(dy, "dy")
+    ctx = context(dy.device)
+    ctx.call("vt_op_backward_operands_check")
+    has_sc = "x16" in saved
+    g = {}
+    # 1. cast + db2 (the shortcut conv sees the same dy: dbsc = db2)
+    dy16, db2 = cast_bias_grad(dy)
+    g["conv2.bias"] = db2
+    # 2. conv2
+    g["conv2.weight"] = conv_backward_weight(dy16, saved["a2"], 3, splits=splits)
+    da2 = conv_backward_data(dy16, params["conv2.weight"])
+    # 3. norm2 + SiLU: dh1 and its bf16 copy
+    dh1, dh1_16, g["norm2.weight"], g["norm2.bias"] = groupnorm_silu_backward(saved["h1"], saved["stats2"], params["norm2.weight"], params["norm2.bias"], da2,
+                                                                              want_dx16=True)
+    # 4. conv1
+    g["conv1.weight"] = conv_backward_weight(dh1_16, saved["a1"], 3, splits=splits)
+    _, g["conv1.bias"] = cast_bias_grad(dh1, want_dy16=False)
+    da1 = conv_backward_data(dh1_16, params["conv1.weight"])
+    # 5. shortcut
+    if has_sc:
+        dxs = conv_backward_data(dy16, params["conv_shortcut.weight"])
+        g["conv_shortcut.weight"] = conv_backward_weight(dy16, saved["x16"], 1, splits=splits)
+        g["conv_shortcut.bias"] = db2.clone()
+    else:
+        dxs = dy
+    # 6. norm1 + SiLU, the shortcut's gradient added in the same pass
+    dx, _, g["norm1.weight"], g["norm1.bias"] = groupnorm_silu_backward(saved["x"], saved["stats1"], params["norm1.weight"], params["norm1.bias"], da1, dx_add=dxs)
+    return dx, {k: g[k] for k in params}
