@@ -723,6 +723,48 @@ size_t vt_op_groupnorm_silu_backward_workspace_bytes(int B, int HW, int C);
 int vt_op_groupnorm_silu_backward(vt_context* ctx, const float* x_f32, const float* stats, const float* gamma, const float* beta, const float* da_f32,
                                   const float* dx_add, float* dx_f32, void* dx16_out, float* dgamma_out, float* dbeta_out, int B, int HW, int C,
                                   int groups, void* workspace, size_t workspace_bytes, void* stream);
+/* The same passes for a GroupNorm WITHOUT activation (the attention block's): du = dh.  Everything else as vt_op_groupnorm_silu_backward. */
+size_t vt_op_groupnorm_backward_workspace_bytes(int B, int HW, int C);
+int vt_op_groupnorm_backward(vt_context* ctx, const float* x_f32, const float* stats, const float* gamma, const float* beta, const float* dh_f32,
+                             const float* dx_add, float* dx_f32, void* dx16_out, float* dgamma_out, float* dbeta_out, int B, int HW, int C, int groups,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Mid-block attention for training.  C = 512 only; any S >= 1.  One stream, no host synchronisation, no atomics.
+ *
+ * vt_op_attention_forward_train: y = to_out(softmax(q k^T / sqrt(C)) v) + x with h = GroupNorm32(x) (eps 1e-6, no SiLU), on CALLER-OWNED fp32
+ * parameters on the device in diffusers' layouts (group_norm.{weight,bias} [C]; to_q / to_k / to_v / to_out.0 .weight [C][C], .bias [C]).  The
+ * weights are packed to bf16 on the stream and the launches are those of vt_op_groupnorm + vt_op_attention at default flags (y is bit-identical
+ * to them on a context whose encoder holds the same weights); refused unless flags 7, 9, 11, 12, 17 and 18 are at their defaults.  What the
+ * backward needs is left in caller buffers: h16 bf16 [B][S][C]; qk16 bf16 [B][S][2C] (q | k per token); vT16 bf16 [B][C][pitch],
+ * pitch = vt_op_attention_vt_pitch(S), keys contiguous; o16 bf16 and o fp32 [B][S][C] (o = the bf16 values to_out consumed); shift fp32 [B][S]
+ * (the softmax exponent shift c_i of every row); sums fp32 [4][B][S] (the four key-segment sums of exp(s - c_i) per row, added as
+ * ((s0 + s1) + s2) + s3); stats fp32 [B][32][2] = (mean, rstd) as vt_op_groupnorm_stats writes them.  x is fp32 [B][S][C]; tokens are the
+ * NHWC pixels. */
+int vt_op_attention_vt_pitch(int S);
+size_t vt_op_attention_forward_train_workspace_bytes(int B, int S, int C);
+int vt_op_attention_forward_train(vt_context* ctx, const float* x_f32, const float* gn_weight, const float* gn_bias, const float* wq, const float* bq,
+                                  const float* wk, const float* bk, const float* wv, const float* bv, const float* wo, const float* bo, float* y_f32,
+                                  void* h16_out, void* qk16_out, void* vT16_out, void* o16_out, float* o_f32_out, float* shift_out, float* sums_out,
+                                  float* stats_out, int B, int S, int C, void* workspace, size_t workspace_bytes, void* stream);
+/* vt_op_attention_core_backward: given do (the gradient of o, fp32 [B][S][C]) and what the forward left, with p = softmax(alpha q k^T),
+ * alpha = 1 / sqrt(C), D_i = sum_c do[i][c] o[i][c]:  ds = p * (do v^T - D),  dq = alpha ds k,  dk = alpha ds^T q,  dv = p^T do  -- fp32 [B][S][C],
+ * plus their bf16 copies where dq16 / dk16 / dv16 are not NULL.  All MFMA operands are bf16 with fp32 accumulation whatever flags 11, 14, 15
+ * and 18 say.  Seven S x S x C products on the forward's two kernel skeletons (the minimum is five; the two extra recompute p once per
+ * direction so that no S x S matrix is ever read transposed).  Images are processed `group` at a time (0: as many as the forward; larger values
+ * are clamped to that) with two fragment-ordered S x S bf16 buffers per group image in the workspace; `nsplit` workgroups share a row
+ * block's sweep (0: chosen from the shape; clamped to the number of 64-row tiles).  Neither changes a bit of the result, nor does the batch an
+ * image runs in; results are bit-identical from run to run.  The workspace size is a function of the shape alone; 256-byte aligned. */
+size_t vt_op_attention_core_backward_workspace_bytes(int B, int S, int C);
+int vt_op_attention_core_backward(vt_context* ctx, const void* qk16, const void* vT16, const float* o_f32, const float* do_f32, const float* shift,
+                                  const float* sums, float* dq_f32, float* dk_f32, float* dv_f32, void* dq16_out, void* dk16_out, void* dv16_out, int B,
+                                  int S, int C, int group, int nsplit, void* workspace, size_t workspace_bytes, void* stream);
+/* Measurement aid (tools/bench_attention_backward.py): the same call running only the launches whose bit is set in `stages`, on whatever the
+ * workspace holds from an earlier full run -- bit 0 the layout passes, 1 the softmax numerators, 2 ds, 3 dq, 4 p^T, 5 dv, 6 ds^T, 7 dk; bit 8, not
+ * part of the backward, launches the forward's P.V on the first fragment buffer.  stages = 0xff is vt_op_attention_core_backward. */
+int vt_op_attention_core_backward_stages(vt_context* ctx, const void* qk16, const void* vT16, const float* o_f32, const float* do_f32, const float* shift,
+                                         const float* sums, float* dq_f32, float* dk_f32, float* dv_f32, void* dq16_out, void* dk16_out, void* dv16_out,
+                                         int B, int S, int C, int group, int nsplit, void* workspace, size_t workspace_bytes, void* stream, unsigned stages);
+
 size_t vt_op_attention_workspace_bytes(int B, int S, int C);
 int vt_op_attention(vt_context* ctx, const void* x_bf16 /* [B][S][C] normed tokens */, const float* residual_f32,
                     float* out_f32, int B, int S, int C, void* workspace, void* stream);

@@ -180,6 +180,14 @@ PROTOTYPES = {
     "vt_op_groupnorm_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
     "vt_op_groupnorm_silu_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "vt_op_groupnorm_silu_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "vt_op_groupnorm_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "vt_op_groupnorm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "vt_op_attention_vt_pitch": (_i, [_i]),
+    "vt_op_attention_forward_train_workspace_bytes": (_sz, [_i, _i, _i]),
+    "vt_op_attention_forward_train": (_i, [_vp] * 21 + [_i, _i, _i, _vp, _sz, _vp]),
+    "vt_op_attention_core_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "vt_op_attention_core_backward": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "vt_op_attention_core_backward_stages": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _vp, _sz, _vp, ctypes.c_uint]),
     "vt_op_attention_workspace_bytes": (_sz, [_i, _i, _i]),
     "vt_op_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
 }

@@ -43,6 +43,9 @@ size_t attn_p_elems(int S) {
 
 }  // namespace
 
+size_t attn_pitch_of(int S) { return attn_pitch(S); }
+int attn_group_of(int B, int S) { return attn_group(B, S); }
+
 size_t attn_scratch_bytes(int B, int S, int C) {
     const size_t ld = attn_pitch(S), G = (size_t)attn_group(B, S);
     return align_up((size_t)B * S * 2 * C * 2) + align_up((size_t)B * C * ld * 2) + align_up(G * S * ld * 2) +
@@ -278,6 +281,9 @@ int attn_group_scores_pv(const AttnRun& r, int b0, int nb) {
     }
     VTCK(profiled(c, s, VT_PROF_ATTN_QK, 2.0 * nb * (double)S * S * C, "attn exp scores", [&] { return vt_launch_attn_qk(k, s); }));
     if (!frag_pv) return attn_pv_gemm(r, a, b0, rinv);
+    if (sc.save_sums)      // the training forward keeps the segment sums of every image: [4][B][S], this group's columns
+        HIPCK(c, hipMemcpy2DAsync(sc.save_sums + (long long)b0 * S, (size_t)r.B * S * 4, sc.part, (size_t)nb * S * 4, (size_t)nb * S * 4, 4, hipMemcpyDeviceToDevice, s),
+              "attn segment sums");
     AttnPvArgs v{};
     v.Pt = sc.probs; v.pt_bs = vt_attn_pt_elems(S); v.vt = sc.vt + (long long)b0 * C * lp; v.ldv = lp; v.vt_bs = (long long)C * lp;
     v.rsum = sc.part; v.split_stride = (long long)nb * S; v.row_bs = S; v.o = sc.o + (long long)b0 * S * C; v.ldo = C; v.o_bs = (long long)S * C;
@@ -317,6 +323,8 @@ int attn_out_proj(const AttnRun& r, const void* res, void* out, GnState* gn, int
 }
 
 }  // namespace
+
+int attn_sweep_nsplit(int qblocks, int ktiles, int min_tiles) { return sweep_nsplit(qblocks, ktiles, min_tiles); }
 
 // diffusers Attention for the VAE mid block: 1 head, dim_head = C, scale 1/sqrt(C).
 // x16: group-normed tokens [B][S][C] bf16.  out = to_out(softmax(q k^T / sqrt(C)) v) + residual.

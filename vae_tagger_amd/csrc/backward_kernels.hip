@@ -147,10 +147,13 @@ __device__ __forceinline__ GnLane gn_lane(const float* stats, const float* gamma
     l.mean = st[0]; l.rstd = st[1];
     return l;
 }
+// (SILU = false: the plain GroupNorm of the attention block, du = da)
+template <bool SILU>
 __device__ __forceinline__ void gn_du(const GnLane& l, const f32x4& x, const f32x4& da, float (&xh)[4], float (&du)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         xh[i] = (x[i] - l.mean) * l.rstd;
+        if constexpr (!SILU) { du[i] = da[i]; continue; }
         const float u = fmaf(l.g[i], xh[i], l.bt[i]);
         const float s = sigmoid_acc(u);
         du[i] = da[i] * s * (1.0f + u * (1.0f - s));
@@ -158,6 +161,7 @@ __device__ __forceinline__ void gn_du(const GnLane& l, const f32x4& x, const f32
 }
 
 // pass 1: part[b][chunk][c][2] = (sum du, sum du * xh) over the chunk's pixels
+template <bool SILU>
 __global__ __launch_bounds__(BK_THREADS) void gn_bwd_partials_kernel(const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                                                                      const float* __restrict__ beta, const float* __restrict__ da, double* __restrict__ part,
                                                                      int HW, int C, int groups, int chunk_pix, int nchunks) {
@@ -173,7 +177,7 @@ __global__ __launch_bounds__(BK_THREADS) void gn_bwd_partials_kernel(const float
     for (int p = p0 + tp; p < p1; p += L.ppp) {
         const f32x4 xv = *(const f32x4*)(x + base + (long long)p * C), dv = *(const f32x4*)(da + base + (long long)p * C);
         float xh[4], du[4];
-        gn_du(l, xv, dv, xh, du);
+        gn_du<SILU>(l, xv, dv, xh, du);
 #pragma unroll
         for (int i = 0; i < 4; ++i) { s1[i] += (double)du[i]; s2[i] += (double)du[i] * (double)xh[i]; }
     }
@@ -238,6 +242,7 @@ __global__ void gn_bwd_params_kernel(const double* __restrict__ S, float* __rest
 }
 
 // pass 2: dx = rstd * (gamma du - m1 - xh m2) (+ dx_add), and its bf16 copy
+template <bool SILU>
 __global__ __launch_bounds__(BK_THREADS) void gn_bwd_dx_kernel(const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, const float* __restrict__ da, const float* __restrict__ gm,
                                                                const float* __restrict__ dx_add, float* __restrict__ dx, bf16_t* __restrict__ dx16, int HW, int C,
@@ -255,7 +260,7 @@ __global__ __launch_bounds__(BK_THREADS) void gn_bwd_dx_kernel(const float* __re
         const long long o = base + (long long)p * C;
         const f32x4 xv = *(const f32x4*)(x + o), dv = *(const f32x4*)(da + o);
         float xh[4], du[4];
-        gn_du(l, xv, dv, xh, du);
+        gn_du<SILU>(l, xv, dv, xh, du);
         f32x4 r;
 #pragma unroll
         for (int i = 0; i < 4; ++i) r[i] = l.rstd * (l.g[i] * du[i] - m1 - xh[i] * m2);
@@ -331,8 +336,9 @@ size_t vt_gn_silu_bwd_ws_bytes(int B, int HW, int C) {
     return up16((size_t)B * gn_bwd_chunks(HW, C) * C * 2 * sizeof(double)) + up16((size_t)B * C * 2 * sizeof(double)) + up16((size_t)B * 64 * 2 * sizeof(float));
 }
 
-hipError_t vt_launch_gn_silu_backward(const float* x, const float* stats, const float* gamma, const float* beta, const float* da, const float* dx_add,
-                                      float* dx, bf16_t* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws, hipStream_t s) {
+template <bool SILU>
+static hipError_t launch_gn_backward(const float* x, const float* stats, const float* gamma, const float* beta, const float* da, const float* dx_add,
+                                     float* dx, bf16_t* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws, hipStream_t s) {
     if (!x || !stats || !gamma || !beta || !da || !dx || !ws || B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups)) return hipErrorInvalidValue;
     const Lanes L = lanes_of(C);
     const int nchunks = gn_bwd_chunks(HW, C);
@@ -340,11 +346,21 @@ hipError_t vt_launch_gn_silu_backward(const float* x, const float* stats, const 
     double* part = (double*)p; p += up16((size_t)B * nchunks * C * 2 * sizeof(double));
     double* S = (double*)p; p += up16((size_t)B * C * 2 * sizeof(double));
     float* gm = (float*)p;
-    hipLaunchKernelGGL(gn_bwd_partials_kernel, dim3(nchunks, B), dim3(L.threads), (size_t)L.threads * 8 * sizeof(double), s, x, stats, gamma, beta, da, part, HW, C,
+    hipLaunchKernelGGL(gn_bwd_partials_kernel<SILU>, dim3(nchunks, B), dim3(L.threads), (size_t)L.threads * 8 * sizeof(double), s, x, stats, gamma, beta, da, part, HW, C,
                        groups, L.ppp * BK_PASSES, nchunks);
     hipLaunchKernelGGL(gn_bwd_finish_kernel, dim3(C / BK_FIN_ROWS, B), dim3(BK_THREADS), 0, s, part, gamma, S, gm, HW, C, groups, nchunks);
     if (dgamma || dbeta) hipLaunchKernelGGL(gn_bwd_params_kernel, dim3((C + 255) / 256), dim3(256), 0, s, S, dgamma, dbeta, B, C);
     const int ppb = L.ppp * 4;
-    hipLaunchKernelGGL(gn_bwd_dx_kernel, dim3((HW + ppb - 1) / ppb, B), dim3(L.threads), 0, s, x, stats, gamma, beta, da, gm, dx_add, dx, dx16, HW, C, groups, ppb);
+    hipLaunchKernelGGL(gn_bwd_dx_kernel<SILU>, dim3((HW + ppb - 1) / ppb, B), dim3(L.threads), 0, s, x, stats, gamma, beta, da, gm, dx_add, dx, dx16, HW, C, groups, ppb);
     return hipGetLastError();
+}
+
+hipError_t vt_launch_gn_silu_backward(const float* x, const float* stats, const float* gamma, const float* beta, const float* da, const float* dx_add,
+                                      float* dx, bf16_t* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws, hipStream_t s) {
+    return launch_gn_backward<true>(x, stats, gamma, beta, da, dx_add, dx, dx16, dgamma, dbeta, B, HW, C, groups, ws, s);
+}
+
+hipError_t vt_launch_gn_backward(const float* x, const float* stats, const float* gamma, const float* beta, const float* da, const float* dx_add,
+                                 float* dx, bf16_t* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws, hipStream_t s) {
+    return launch_gn_backward<false>(x, stats, gamma, beta, da, dx_add, dx, dx16, dgamma, dbeta, B, HW, C, groups, ws, s);
 }

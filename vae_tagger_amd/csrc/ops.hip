@@ -408,6 +408,23 @@ int vt_op_groupnorm_silu_backward(vt_context* c, const float* x, const float* st
     return VT_OK;
 }
 
+size_t vt_op_groupnorm_backward_workspace_bytes(int B, int HW, int C) { return vt_op_groupnorm_silu_backward_workspace_bytes(B, HW, C); }
+
+int vt_op_groupnorm_backward(vt_context* c, const float* x, const float* stats, const float* gamma, const float* beta, const float* dh, const float* dx_add,
+                             float* dx, void* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws, size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!x || !stats || !gamma || !beta || !dh || !dx) return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: null buffer");
+    if (B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups))
+        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: channels per group must be 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
+    const size_t need = vt_op_groupnorm_backward_workspace_bytes(B, HW, C);
+    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
+        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
+    HIPCK(c, vt_launch_gn_backward(x, stats, gamma, beta, dh, dx_add, dx, (bf16_t*)dx16, dgamma, dbeta, B, HW, C, groups, ws, (hipStream_t)stream),
+          "vt_op_groupnorm_backward");
+    return VT_OK;
+}
+
 int vt_op_softmax_rows(vt_context* c, const float* scores, void* probs, int rows, int n, int lds, int ldp, void* stream) {
     if (!c) return VT_ERR_INVALID;
     DeviceGuard guard(c);

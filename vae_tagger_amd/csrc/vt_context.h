@@ -281,7 +281,11 @@ struct AttnScratch {
     unsigned char* x8; float* ident;            // op-level entry only: e4m3(8 x) tokens made from the caller's bf16 ones, and the identity (scale, shift) that pass takes
     float* qn; float* kn; float* sd; float* shift; float* rinv; float* part; int* flags;
     int group;
+    float* save_sums = nullptr;                 // training forward: [4][B][S] copy of every image's segment sums (the partials scratch holds one group's)
 };
+size_t attn_pitch_of(int S);                    // row pitch (elements) of v^T and of the row-major S x S matrices
+int attn_group_of(int B, int S);                // images whose probabilities are materialised at a time
+int attn_sweep_nsplit(int qblocks, int ktiles, int min_tiles);      // workgroups per query block of a segment-sum sweep
 size_t attn_scratch_bytes(int B, int S, int C);
 AttnScratch carve_attn(char* p, int B, int S, int C);
 bool attn_proj_is_fp8(const vt_context* c, const AttnW& w, int S, int C);

@@ -116,6 +116,44 @@ __host__ __device__ inline long long vt_attn_pt_slab_stride(int S) { return (lon
 long long vt_attn_pt_elems(int S);
 hipError_t vt_launch_attn_pv(const AttnPvArgs& a, hipStream_t s);
 
+// ---- backward of the attention core on the same two skeletons (attn_bwd.hip; d = 512 only)
+// attn_qk's skeleton with the gradient epilogues; every mode writes bf16 pieces in the fragment order of AttnPvArgs::Pt:
+//   mode 0: rows = do16, streamed = v16:  Pout = bf16(alpha * Pin * rowscale[row] * (rows.str - rowd[row]))       (Pin = softmax numerators -> ds)
+//   mode 1: rows = k16,  streamed = q16:  Pout = bf16(exp2(alpha * log2(e) * rows.str - colv[streamed row]))      (-> p^T; colv = c log2(e) + log2(sum))
+//   mode 2: rows = v16,  streamed = do16: Pout = bf16(alpha * Pin * (rows.str - colv[streamed row]))              (Pin = p^T, colv = D -> ds^T)
+// Padding rows and streamed rows >= S are stored as 0.  nsplit (any value from 1 to the number of 64-row tiles) spreads a row block's tiles over
+// that many workgroups; it cannot change a bit of the result.
+struct AttnBwdQkArgs {
+    const bf16_t* rows; int ldr; long long r_bs;        // resident operand [S][ldr] bf16
+    const bf16_t* str; int lds; long long s_bs;         // streamed operand [S][lds] bf16
+    int S, C, batch, mode;
+    const bf16_t* Pin; bf16_t* Pout; long long p_bs;    // fragment-ordered, >= vt_attn_pt_elems(S) elements per image
+    const float* rowscale; const float* rowd;           // mode 0: per resident row, [batch][vec_bs]
+    const float* colv;                                  // modes 1, 2: per streamed row, [batch][vec_bs]; rows [S, vec_bs) hold 0
+    long long vec_bs;                                   // multiple of 8, >= S rounded up to 64
+    float alpha; int nsplit; const void* zeros;
+};
+// attn_pv's skeleton with the gradient epilogue: out[q][c] = sum_k Pt[q][k] * xt[c][k] as fp32 (and its bf16 copy when out16 is given)
+struct AttnBwdPvArgs {
+    const bf16_t* Pt; long long pt_bs;
+    const bf16_t* xt; int ldx; long long xt_bs;         // [C][ldx] bf16, columns [S, round8(S)) zero
+    float* out; bf16_t* out16; int ldo; long long o_bs; // [S][ldo]
+    int S, C, batch;
+    const void* zeros;
+};
+bool vt_attn_bwd_supported(int S, int C);
+hipError_t vt_launch_attn_bwd_qk(const AttnBwdQkArgs& a, hipStream_t s);
+hipError_t vt_launch_attn_bwd_pv(const AttnBwdPvArgs& a, hipStream_t s);
+// per token: do16 = bf16(do), dvec = sum_c do * o, rinv = 1 / (((s0 + s1) + s2) + s3) of the forward's segment sums [4][split_stride] (image stride S),
+// coff = shift * log2(e) + log2(sum); the three vectors are [batch][vec_bs] with rows [S, vec_bs) written as 0.  C = 512.
+hipError_t vt_launch_attn_bwd_rows(const float* dout, const float* o, const float* shift, const float* sums, long long split_stride, bf16_t* do16, float* dvec,
+                                   float* rinv, float* coff, int batch, int S, int vec_bs, hipStream_t s);
+// dst[c][r] = src[r][c], bf16, R rows x Cc columns; dst columns [R, Rpad) are written as 0
+hipError_t vt_launch_transpose16(const bf16_t* src, bf16_t* dst, int R, int Cc, int Rpad, int lds, int ldd, long long s_bs, long long d_bs, int batch, hipStream_t s);
+
+// fp32 copy of n bf16 values (n a multiple of 8)
+hipError_t vt_launch_bf16_to_f32(const bf16_t* src, float* dst, long long n, hipStream_t s);
+
 // ---- the same two contractions on fp8 (e4m3) operands (attn_fp8.hip; vt_set_flag 11 + 14)
 struct AttnQk8Args {
     const unsigned char* qk8; int ldq; long long qk_bs;   // [S][ldq] e4m3 bytes: q8 (C bytes) | k8 (C bytes) per row, batch stride qk_bs
@@ -390,6 +428,9 @@ size_t vt_gn_silu_bwd_ws_bytes(int B, int HW, int C);
 bool vt_gn_silu_bwd_supported(int C, int groups);
 hipError_t vt_launch_gn_silu_backward(const float* x, const float* stats, const float* gamma, const float* beta, const float* da, const float* dx_add,
                                       float* dx, bf16_t* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws, hipStream_t s);
+// the same passes for a GroupNorm without activation (the attention block's): du = da
+hipError_t vt_launch_gn_backward(const float* x, const float* stats, const float* gamma, const float* beta, const float* da, const float* dx_add,
+                                 float* dx, bf16_t* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws, hipStream_t s);
 
 // decoder (all fp32)
 struct DecoderWeights;   // defined in vt_decoder.h

@@ -1,10 +1,10 @@
-"""Backward of one ResnetBlock2D -- the block both VAE models consist of -- on the device: thin wrappers over the vt_op_* backward operators
-(include/vae_tagger_hip.h).  Tensors are torch tensors of one HIP device, activations NHWC ([B, H, W, C]), parameters in
+"""Backward of the VAE's mid block -- ResnetBlock2D (the block both VAE models consist of), the mid attention block, and their composition -- on
+the device: thin wrappers over the vt_op_* backward operators (include/vae_tagger_hip.h, DESIGN.md sections 4.19 and 4.20).  Tensors are torch tensors of one HIP device, activations NHWC ([B, H, W, C]), parameters in
 diffusers' own layouts (conv weights fp32 OIHW).  All gradients are fp32; every MFMA operand is bf16.  Every launch goes to torch's current stream
 of the tensors' device and nothing here synchronises with the host.  There is no eager fallback: a shape an operator refuses raises VTError.
 
-This is NOT train_vae: there is no optimiser, no loss and no backward of the other layer kinds (stride-2 convs, Upsample2D, attention, conv_in,
-conv_out) here.
+This is NOT train_vae: there is no optimiser, no loss and no backward of the other layer kinds (stride-2 convs, Upsample2D, conv_in, conv_out)
+here.
 """
 import ctypes
 
@@ -225,3 +225,151 @@ def resnet_block_backward(params, saved, dy, *, splits=0):
     # 6. norm1 + SiLU, the shortcut's gradient added in the same pass
     dx, _, g["norm1.weight"], g["norm1.bias"] = groupnorm_silu_backward(saved["x"], saved["stats1"], params["norm1.weight"], params["norm1.bias"], da1, dx_add=dxs)
     return dx, {k: g[k] for k in params}
+
+
+# ---- the attention block -------------------------------------------------------------------------------------------------------------------------
+
+ATTN_C = 512                      # the attention kernels' only channel count (the FLUX VAE's mid block)
+ATTN_PARAMS = ["group_norm.weight", "group_norm.bias", "to_q.weight", "to_q.bias", "to_k.weight", "to_k.bias", "to_v.weight", "to_v.bias",
+               "to_out.0.weight", "to_out.0.bias"]
+ATTN_SAVED = ["x", "h16", "qk16", "vT16", "o16", "o", "shift", "sums", "stats"]
+
+
+def groupnorm_backward(x, stats, gamma, beta, dh, *, dx_add=None, want_dx16=False):
+    """Backward of h = GroupNorm(x) (no activation).  -> (dx fp32, dx16 bf16 or None, dgamma, dbeta); dx_add (fp32, x's shape) is added into dx."""
+    x, dh = _f32(x, "x"), _f32(dh, "dh")
+    if dh.shape != x.shape or (dx_add is not None and _f32(dx_add, "dx_add").shape != x.shape):
+        raise ValueError("dh and dx_add must have x's shape")
+    ctx = context(x.device)
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    groups = stats.shape[1]
+    dx = torch.empty_like(x)
+    dx16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_dx16 else None
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    ws = _workspace(ctx.lib.vt_op_groupnorm_backward_workspace_bytes(B, HW, C), x.device)
+    ctx.call("vt_op_groupnorm_backward", _vp(x), _vp(_f32(stats, "stats")), _vp(_f32(gamma, "gamma")), _vp(_f32(beta, "beta")), _vp(dh), _vp(dx_add),
+             _vp(dx), _vp(dx16), _vp(dg), _vp(db), B, HW, C, groups, _vp(ws), ws.numel(), _stream(x))
+    return dx, dx16, dg, db
+
+
+def attention_core_backward(qk16, vT16, o, do, shift, sums, *, want_bf16=True, group=0, nsplit=0):
+    """dq, dk, dv of o = softmax(q k^T / sqrt(C)) v from what attention_block_forward_train saved.  qk16 bf16 [B, S, 2C], vT16 bf16 [B, C, pitch],
+    o and do fp32 [B, S, C], shift fp32 [B, S], sums fp32 [4, B, S].  -> (dq, dk, dv fp32 [B, S, C], (dq16, dk16, dv16) or None).  `group` (images per
+    launch) and `nsplit` (workgroups per row block of a sweep) are scheduling knobs: 0 = chosen from the shape; no value changes a bit."""
+    qk16, vT16, o, do = _bf16(qk16, "qk16"), _bf16(vT16, "vT16"), _f32(o, "o"), _f32(do, "do")
+    B, S, C = o.shape
+    ctx = context(o.device)
+    if C == ATTN_C:
+        if tuple(qk16.shape) != (B, S, 2 * C) or tuple(vT16.shape) != (B, C, ctx.lib.vt_op_attention_vt_pitch(S)) or do.shape != o.shape:
+            raise ValueError("qk16 / vT16 / do do not match o")
+        if tuple(_f32(shift, "shift").shape) != (B, S) or tuple(_f32(sums, "sums").shape) != (4, B, S):
+            raise ValueError("shift must be [B, S] and sums [4, B, S]")
+    outs = [torch.empty(B, S, C, dtype=torch.float32, device=o.device) for _ in range(3)]
+    outs16 = [torch.empty(B, S, C, dtype=torch.bfloat16, device=o.device) for _ in range(3)] if want_bf16 else [None] * 3
+    ws = _workspace(ctx.lib.vt_op_attention_core_backward_workspace_bytes(B, S, C), o.device)
+    ctx.call("vt_op_attention_core_backward", _vp(qk16), _vp(vT16), _vp(o), _vp(do), _vp(shift), _vp(sums), *[_vp(t) for t in outs], *[_vp(t) for t in outs16],
+             B, S, C, int(group), int(nsplit), _vp(ws), ws.numel(), _stream(o))
+    return outs[0], outs[1], outs[2], (tuple(outs16) if want_bf16 else None)
+
+
+def _check_attn_params(params, x):
+    if sorted(params) != sorted(ATTN_PARAMS):
+        raise ValueError(f"params must hold exactly {ATTN_PARAMS}")
+    C = x.shape[-1]
+    for n in ATTN_PARAMS:
+        want = (C, C) if n.endswith("weight") and not n.startswith("group_norm") else (C,)
+        if tuple(_f32(params[n], n).shape) != want:
+            raise ValueError(f"{n}: expected shape {want}")
+
+
+def attention_block_forward_train(params, x):
+    """The mid-block attention (GroupNorm, to_q / to_k / to_v, softmax(q k^T / sqrt(C)) v, to_out, + x) on caller-owned fp32 parameters, keeping what
+    the backward needs.  x fp32 NHWC [B, H, W, 512].  -> (y fp32 NHWC, saved)"""
+    x = _f32(x, "x")
+    if x.dim() != 4:
+        raise ValueError("x must be NHWC")
+    ctx = context(x.device)
+    ctx.call("vt_op_backward_operands_check")
+    _check_attn_params(params, x)
+    B, H, W, C = x.shape
+    S, dev = H * W, x.device
+    pitch = ctx.lib.vt_op_attention_vt_pitch(S) if C == ATTN_C else S
+    bf, f32 = torch.bfloat16, torch.float32
+    y = torch.empty_like(x)
+    saved = {"x": x, "h16": torch.empty(B, H, W, C, dtype=bf, device=dev), "qk16": torch.empty(B, S, 2 * C, dtype=bf, device=dev),
+             "vT16": torch.empty(B, C, pitch, dtype=bf, device=dev), "o16": torch.empty(B, H, W, C, dtype=bf, device=dev),
+             "o": torch.empty(B, S, C, dtype=f32, device=dev), "shift": torch.empty(B, S, dtype=f32, device=dev),
+             "sums": torch.empty(4, B, S, dtype=f32, device=dev), "stats": torch.empty(B, GROUPS, 2, dtype=f32, device=dev)}
+    ws = _workspace(ctx.lib.vt_op_attention_forward_train_workspace_bytes(B, S, C), dev)
+    ctx.call("vt_op_attention_forward_train", _vp(x), *[_vp(params[n]) for n in ATTN_PARAMS], _vp(y), *[_vp(saved[n]) for n in ATTN_SAVED[1:]], B, S, C,
+             _vp(ws), ws.numel(), _stream(x))
+    return y, saved
+
+
+def attention_block_backward(params, saved, dy, *, splits=0, group=0, nsplit=0):
+    """dy fp32 NHWC, the gradient of attention_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params)"""
+    dy = _f32(dy, "dy")
+    ctx = context(dy.device)
+    ctx.call("vt_op_backward_operands_check")
+    B, H, W, C = dy.shape
+    S = H * W
+    w4 = lambda n: params[n].view(C, C, 1, 1)
+    g = {}
+    # 1. to_out: dbo, dWo = dy^T o, do = dy Wo (the residual passes dy on to dx in step 4)
+    dy16, g["to_out.0.bias"] = cast_bias_grad(dy)
+    g["to_out.0.weight"] = conv_backward_weight(dy16, saved["o16"], 1, splits=splits).view(C, C)
+    do = conv_backward_data(dy16, w4("to_out.0.weight"))
+    # 2. the core
+    dq, dk, dv, (dq16, dk16, dv16) = attention_core_backward(saved["qk16"], saved["vT16"], saved["o"], do.view(B, S, C), saved["shift"], saved["sums"],
+                                                              group=group, nsplit=nsplit)
+    # 3. the three linears: weight gradients from the bf16 copies, bias sums from the fp32 gradients, dh chained through dx_add
+    dh = None
+    for name, d32, d16 in (("to_q", dq, dq16), ("to_k", dk, dk16), ("to_v", dv, dv16)):
+        d16 = d16.view(B, H, W, C)
+        g[name + ".weight"] = conv_backward_weight(d16, saved["h16"], 1, splits=splits).view(C, C)
+        _, g[name + ".bias"] = cast_bias_grad(d32, want_dy16=False)
+        dh = conv_backward_data(d16, w4(name + ".weight"), dx_add=dh)
+    # 4. the norm, the residual's dy added in the same pass
+    dx, _, g["group_norm.weight"], g["group_norm.bias"] = groupnorm_backward(saved["x"], saved["stats"], params["group_norm.weight"], params["group_norm.bias"], dh,
+                                                                              dx_add=dy)
+    return dx, {k: g[k] for k in params}
+
+
+# ---- the mid block: resnets.0, attentions.0, resnets.1 ---------------------------------------------------------------------------------------------
+
+MID_PARTS = (("resnets.0.", "resnet"), ("attentions.0.", "attention"), ("resnets.1.", "resnet"))
+
+
+def _split_mid(params):
+    parts = {p: {} for p, _ in MID_PARTS}
+    for k, v in params.items():
+        for p, _ in MID_PARTS:
+            if k.startswith(p):
+                parts[p][k[len(p):]] = v
+                break
+        else:
+            raise ValueError(f"{k}: not a parameter of resnets.0, attentions.0 or resnets.1")
+    return parts
+
+
+def mid_block_forward_train(params, x):
+    """UNetMidBlock2D of the VAE: resnets.0 -> attentions.0 -> resnets.1, parameters under diffusers' names.  -> (y fp32 NHWC, saved)"""
+    parts = _split_mid(params)
+    saved = {}
+    for p, kind in MID_PARTS:
+        fwd = resnet_block_forward_train if kind == "resnet" else attention_block_forward_train
+        x, saved[p] = fwd(parts[p], x)
+    return x, saved
+
+
+def mid_block_backward(params, saved, dy, *, splits=0):
+    """dy fp32 NHWC, the gradient of mid_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params)"""
+    parts = _split_mid(params)
+    g = {}
+    for p, kind in reversed(MID_PARTS):
+        bwd = resnet_block_backward if kind == "resnet" else attention_block_backward
+        dy, gp = bwd(parts[p], saved[p], dy, splits=splits)
+        g.update({p + k: v for k, v in gp.items()})
+    return dy, {k: g[k] for k in params}
