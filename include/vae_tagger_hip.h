@@ -674,6 +674,30 @@ size_t vt_op_conv3x3_fp8_workspace_bytes(int B, int H, int W, int Cin, int Cout)
 int vt_op_conv3x3_fp8(vt_context* ctx, const float* x_f32_nhwc, const float* w_f32_oihw, const float* bias, const float* residual_f32,
                       float* out_f32, int B, int H, int W, int Cin, int Cout, int stride /* 1: pad 1; 2: pad (0,1,0,1), x -> e4m3(x) */,
                       void* workspace, void* stream);
+/* One 3x3 conv of a ResnetBlock2D / Downsample2D in the forms the VAE schedules launch by default, through their own dispatcher
+ * (run_conv: flags 0, 3, 13 and 18 pick the kernel exactly as in vt_encode) and their own weight packers.  stride 1 (pad 1) or 2 (pad
+ * (0,1,0,1), out H / 2 x W / 2).  Cin % 32 == 0, Cout % 128 == 0 (what both halo kernels take).
+ *   x16       16-bit NHWC [B][H][W][Cin]; with x_planar (stride 2 only) chunk-planar, [Cin/32][H][W][32] per image.  bf16, or fp16 bits
+ *             when flag 18 is on -- then the conv must have an fp16-operand kernel under the current flags, else VT_ERR_INVALID.
+ *   w, bias   fp32 OIHW [Cout][Cin][3][3] and [Cout] ON THE DEVICE; bias is the launch's final bias (conv2's + the shortcut's).  Copied to
+ *             the host, packed by the finalizers' routines, uploaded and freed inside the call: synchronises.
+ *   sc_x16, sc_w   optional fused conv_shortcut (stride 1, no residual): 16-bit NHWC [B][H][W][sc_cin] of x16's type and fp32 [Cout][sc_cin]
+ *             (device), sc_cin % 32 == 0; runs as sc_cin / 32 extra K-steps at the centre tap.
+ *   residual, out   the residual stream in and out, [B][Ho][Wo][Cout], each optional, VT_F32 or VT_F16 (res_dtype, out_dtype: one type
+ *             for both when both are given -- the stream has one).
+ *   out16     optional 16-bit operand copy of the output: bf16, or fp16 bits with out16_f16; NHWC, or with out16_planar (stride 1)
+ *             chunk-planar [Cout/32][H][W][32] per image, element (b, y, x, c) at (((b * (Cout/32) + c/32) * H + y) * W + x) * 32 + c % 32.
+ *   scale_shift_out   optional [B][Cout][2]: GroupNorm (scale, shift) of the output from the epilogue's (n, mean, M2) partials, finalised
+ *             as vt_op_conv2d_gn does (Cout / groups in {4, 8, 16}; gamma, beta [Cout]); workspace (256-B aligned, >=
+ *             vt_op_conv3x3_block_workspace_bytes) holds the partials and is needed only then.
+ * Every combination is checked on the host first: what the dispatcher or a launcher refuses (a shortcut or a planar copy off the halo
+ * kernel, planar input at stride 1, an fp16 residual with an fp32 output, fp16 operands where no kernel has them, ...) returns an error
+ * code with a message and writes nothing. */
+size_t vt_op_conv3x3_block_workspace_bytes(int B, int H, int W, int Cout, int stride);
+int vt_op_conv3x3_block(vt_context* ctx, const void* x16, int x_planar, const float* w_f32_oihw, const float* bias, const void* sc_x16,
+                        const float* sc_w_f32, int sc_cin, const void* residual, int res_dtype, void* out, int out_dtype, void* out16,
+                        int out16_f16, int out16_planar, int B, int H, int W, int Cin, int Cout, int stride, int groups, float eps,
+                        const float* gamma, const float* beta, float* scale_shift_out, void* workspace, size_t workspace_bytes, void* stream);
 int vt_op_gemm_nt(vt_context* ctx, const void* a_bf16, const void* b_bf16, const float* bias, float* out_f32,
                   void* out_bf16, int batch, int M, int N, int K, int lda, int ldb, int ldo, long long a_bs,
                   long long b_bs, long long o_bs, float alpha, int bias_per_row, void* stream);

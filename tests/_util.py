@@ -39,6 +39,32 @@ def checksum(x):
     return torch.tensor([x.double().sum().item(), x.double().abs().sum().item()], dtype=torch.float64)
 
 
+class Guarded:
+    """`nbytes` of device memory, 256-B aligned, between two guard bands; every byte starts as 0xFF (a NaN in fp32, fp16 and bf16 alike), so a
+    store outside the buffer breaks a band and an element that was never stored still reads as that NaN."""
+    GUARD = 4096
+
+    def __init__(self, nbytes, dev):
+        self.n = int(nbytes)
+        self.t = torch.full((self.n + 2 * self.GUARD + 256,), 0xFF, dtype=torch.uint8, device=dev)
+        base = self.t.data_ptr()
+        self.off = (base + self.GUARD + 255) // 256 * 256 - base
+        self.ptr = ctypes.c_void_p(base + self.off)
+
+    def body(self, dtype=torch.uint8):
+        return self.t[self.off:self.off + self.n].view(dtype)
+
+    def guards_intact(self):
+        return bool((self.t[:self.off] == 0xFF).all()) and bool((self.t[self.off + self.n:] == 0xFF).all())
+
+    def untouched(self):
+        return bool((self.t == 0xFF).all())
+
+    def all_written(self, dtype):
+        """no element of the body still holds the fill (16-bit 0xFFFF / 32-bit 0xFFFFFFFF: never a finite result)"""
+        return not bool((self.body(dtype) == -1).any())
+
+
 class Ops:
     """Single-operator entry points of the C ABI on cuda:0."""
 
@@ -106,6 +132,70 @@ class Ops:
                       pad_hi, groups, float(eps), vp(g), vp(bt), vp(ss), vp(ws), self.stream)
         torch.cuda.synchronize()
         return nchw(o32.cpu()), ss.cpu()
+
+    def conv3x3_block(self, x, w, bias, stride=1, sc_x=None, sc_w=None, residual=None, out="f32", copy=None, copy_planar=False, x_planar=False,
+                      f16_operands=False, gn=None, shape=None):
+        """vt_op_conv3x3_block.  All tensors NHWC.  x / sc_x: CPU float tensors holding values of the operand type (bf16, or fp16 with
+        f16_operands: what flag 18 makes the op read) -- or x a CUDA int16 tensor of raw operand bits in the layout the call reads, with
+        shape = (B, H, W, Cin).  w OIHW and sc_w [Cout][scCin] fp32.  residual: a float32 or float16 CPU tensor (its dtype is the stream's).
+        out: "f32" | "f16" | None; copy: None | "bf16" | "f16" (+ copy_planar); gn: (gamma, beta, groups, eps) | None.
+        Every output and the workspace sit between guard bands and start as NaN: after a successful call the bands must be intact and every
+        output element written; after a refused one (VTError, raised with the library's message) nothing at all may have changed.
+        -> dict: out, copy (its written layout: NHWC or [B][C/32][H][W][32]), copy_dev (the same on the device, int16), ss [B][Cout][2]"""
+        from _conv_block_ref import planar_pack
+        L = self.L
+        op16 = torch.float16 if f16_operands else torch.bfloat16
+        if x.is_cuda:
+            B, H, W, Cin = shape
+            xd = x
+        else:
+            B, H, W, Cin = x.shape
+            xd = (planar_pack(x.to(op16)) if x_planar else x.to(op16).contiguous()).to(self.dev)
+        Cout = w.shape[0]
+        Ho, Wo = (H, W) if stride == 1 else (H // 2, W // 2)
+        wd = w.to(self.dev, torch.float32).contiguous()
+        bd = bias.to(self.dev, torch.float32).contiguous()
+        sxd = sc_x.to(op16).contiguous().to(self.dev) if sc_x is not None else None
+        swd = sc_w.to(self.dev, torch.float32).contiguous() if sc_w is not None else None
+        sc_cin = sc_w.shape[1] if sc_w is not None else (sc_x.shape[3] if sc_x is not None else 0)
+        rd = residual.contiguous().to(self.dev) if residual is not None else None
+        res_dt = L.VT_F16 if (residual is not None and residual.dtype == torch.float16) else L.VT_F32
+        n_out = B * Ho * Wo * Cout
+        out_t = {"f32": torch.float32, "f16": torch.float16, None: None}[out]
+        gout = Guarded(n_out * (4 if out == "f32" else 2), self.dev) if out else None
+        gcopy = Guarded(n_out * 2, self.dev) if copy else None
+        gss = gws = None
+        gamma = beta = None
+        groups, eps, ws_bytes = 32, 1e-6, 0
+        if gn is not None:
+            gamma, beta, groups, eps = gn
+            gamma, beta = gamma.to(self.dev, torch.float32).contiguous(), beta.to(self.dev, torch.float32).contiguous()
+            ws_bytes = self.ctx.lib.vt_op_conv3x3_block_workspace_bytes(B, H, W, Cout, stride)
+            assert ws_bytes > 0
+            gws, gss = Guarded(ws_bytes, self.dev), Guarded(B * Cout * 2 * 4, self.dev)
+        bufs = [g for g in (gout, gcopy, gss, gws) if g is not None]
+        rc = self.ctx.lib.vt_op_conv3x3_block(
+            self.ctx.handle, vp(xd), int(x_planar), vp(wd), vp(bd), vp(sxd), vp(swd), int(sc_cin), vp(rd), res_dt,
+            gout.ptr if gout else None, L.VT_F16 if out == "f16" else L.VT_F32, gcopy.ptr if gcopy else None, int(copy == "f16"), int(copy_planar),
+            B, H, W, Cin, Cout, stride, int(groups), float(eps), vp(gamma), vp(beta), gss.ptr if gss else None, gws.ptr if gws else None, ws_bytes, self.stream)
+        torch.cuda.synchronize()
+        if rc != 0:
+            assert all(g.untouched() for g in bufs), "a refused call wrote to its buffers"
+            self.ctx.check(rc, "vt_op_conv3x3_block")
+        assert all(g.guards_intact() for g in bufs), "a store outside the buffers it was given"
+        r = {}
+        if gout:
+            assert gout.all_written(torch.int32 if out == "f32" else torch.int16), "output elements left unwritten"
+            r["out"] = gout.body(out_t).view(B, Ho, Wo, Cout).cpu()
+        if gcopy:
+            assert gcopy.all_written(torch.int16), "operand-copy elements left unwritten"
+            r["copy_dev"] = gcopy.body(torch.int16)
+            c = gcopy.body(torch.float16 if copy == "f16" else torch.bfloat16)
+            r["copy"] = (c.view(B, Cout // 32, Ho, Wo, 32) if copy_planar else c.view(B, Ho, Wo, Cout)).cpu()
+        if gss:
+            assert gss.all_written(torch.int32), "(scale, shift) entries hold the NaN fill: left unwritten, or computed from partials of the poisoned workspace that no launch wrote"
+            r["ss"] = gss.body(torch.float32).view(B, Cout, 2).cpu()
+        return r
 
     def conv3x3_fp8(self, x_nchw, w_oihw, bias=None, residual_nchw=None, stride=1):
         """x, w fp32 -> fp32 NCHW result of the fp8 (e4m3) halo conv; operands are quantised inside the call exactly as the

@@ -222,6 +222,96 @@ int vt_op_conv3x3_fp8(vt_context* c, const float* x_nhwc, const float* w_oihw, c
     return launch_halo_fp8(c, h, s, "vt_op_conv3x3_fp8");
 }
 
+size_t vt_op_conv3x3_block_workspace_bytes(int B, int H, int W, int Cout, int stride) {
+    if (stride != 1 && stride != 2) return 0;
+    return vt_op_conv2d_gn_workspace_bytes(B, stride == 2 ? H / 2 : H, stride == 2 ? W / 2 : W, Cout);
+}
+
+// One conv of a resnet block / Downsample2D in the forms the schedules launch: fused shortcut, fp16 residual stream, 16-bit operand copy
+// (bf16 / fp16 bits, NHWC / chunk-planar), GroupNorm partials -- through run_conv and the finalizers' packers (header: the contract).
+int vt_op_conv3x3_block(vt_context* c, const void* x, int x_planar, const float* w_oihw, const float* bias, const void* sc_x, const float* sc_w,
+                        int sc_cin, const void* res, int res_dtype, void* out, int out_dtype, void* o16, int out16_f16, int out16_planar, int B,
+                        int H, int W, int Cin, int Cout, int stride, int groups, float eps, const float* gamma, const float* beta,
+                        float* scale_shift, void* ws, size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    // ---- everything that can be refused is refused here or inside run_conv, before the first launch
+    if (!x || !w_oihw || !bias || (!out && !o16)) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: null buffer (x, w, bias and one of out / out16 are required)");
+    if (stride != 1 && stride != 2) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: stride must be 1 (pad 1) or 2 (pad (0,1,0,1)), got %d", stride);
+    if (B <= 0 || H < stride || W < stride) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: bad shape %d x %d x %d", B, H, W);
+    if (!vt_conv3x3_halo_supported(Cin, Cout) || !vt_conv3x3_s2_supported(Cin, Cout))
+        return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: the halo kernels take Cin %% 32 == 0 and Cout %% 128 == 0 (got %d -> %d)", Cin, Cout);
+    if ((long long)B * H * W * std::max(Cin, Cout) >= (1LL << 31)) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: tensor too large for the operator entry");
+    if ((res && res_dtype != VT_F32 && res_dtype != VT_F16) || (out && out_dtype != VT_F32 && out_dtype != VT_F16))
+        return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: residual / out must be VT_F32 or VT_F16");
+    if (res && out && res_dtype != out_dtype)
+        return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: the residual stream has one type: an %s residual with an %s output is not a form the kernels have",
+                       res_dtype == VT_F16 ? "fp16" : "fp32", out_dtype == VT_F16 ? "fp16" : "fp32");
+    const int rdt = (out ? out_dtype : (res ? res_dtype : VT_F32)) == VT_F16 ? 2 : 1;
+    const bool has_sc = sc_x || sc_w;
+    if (has_sc) {
+        if (!sc_x || !sc_w || sc_cin <= 0 || (sc_cin % 32)) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: the fused shortcut needs sc_x, sc_w and sc_cin %% 32 == 0");
+        if (stride != 1) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: the stride-2 kernel has no fused shortcut");
+        if (res) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: a fused shortcut replaces the residual (ConvOpts::sc): give one of them");
+        if ((long long)B * H * W * sc_cin >= (1LL << 31)) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: tensor too large for the operator entry");
+    }
+    if (x_planar && stride == 1) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: the stride-1 kernels read NHWC input only (chunk-planar x is the stride-2 kernel's)");
+    if (out16_planar && stride == 2) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: the stride-2 kernel writes no chunk-planar copy");
+    if ((out16_f16 || out16_planar) && !o16) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: out16_f16 / out16_planar without out16");
+    const bool want_gn = scale_shift != nullptr;
+    const int Ho = stride == 2 ? H / 2 : H, Wo = stride == 2 ? W / 2 : W;
+    if (want_gn) {
+        if (!gamma || !beta || groups < 1 || groups > 64 || Cout % groups) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: bad GroupNorm argument");
+        const int cpg = Cout / groups;
+        if (cpg != 4 && cpg != 8 && cpg != 16) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: channels per group must be 4, 8 or 16");
+        const size_t need = vt_op_conv3x3_block_workspace_bytes(B, H, W, Cout, stride);
+        if (!ws || ((uintptr_t)ws % ALIGN) || ws_bytes < need)
+            return c->fail(VT_ERR_WORKSPACE, "vt_op_conv3x3_block: workspace must be 256-B aligned and hold vt_op_conv3x3_block_workspace_bytes = %zu bytes (got %zu)", need, ws_bytes);
+        // the generic GEMM (flag 0 / 13 off, or a stride-2 conv with an fp16 residual) has a stats epilogue on whole 128- / 256-cout tiles only
+        const bool gemm = stride == 1 ? !c->use_halo_conv : !(c->s2_halo && !(res && rdt == 2));
+        if (gemm && Cout > 128 && (Cout % 256)) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: the generic GEMM has no stats epilogue for %d couts", Cout);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // ---- pack: the weights come to the host and go through pack_conv / pack_fused_shortcut, as in vt_encoder_finalize (synchronises)
+    std::vector<float> hw((size_t)Cout * Cin * 9), hb(Cout), hsw(has_sc ? (size_t)Cout * sc_cin : 0);
+    HIPCK(c, hipStreamSynchronize(s), "vt_op_conv3x3_block sync");
+    HIPCK(c, hipMemcpy(hw.data(), w_oihw, hw.size() * 4, hipMemcpyDeviceToHost), "vt_op_conv3x3_block copy");
+    HIPCK(c, hipMemcpy(hb.data(), bias, hb.size() * 4, hipMemcpyDeviceToHost), "vt_op_conv3x3_block copy");
+    if (has_sc) HIPCK(c, hipMemcpy(hsw.data(), sc_w, hsw.size() * 4, hipMemcpyDeviceToHost), "vt_op_conv3x3_block copy");
+    // the packed tensors live in a list of this call (not in a model's), without the e4m3 forms, and are freed when it returns
+    struct Uploads {
+        vt_context* c; std::vector<void*> list; std::vector<void*>* saved; bool fp8;
+        explicit Uploads(vt_context* c_) : c(c_), saved(c_->cur_allocs), fp8(c_->pack_fp8) { c->cur_allocs = &list; c->pack_fp8 = false; }
+        ~Uploads() { c->cur_allocs = saved; c->pack_fp8 = fp8; (void)hipDeviceSynchronize(); c->free_allocs(list); }
+    } uploads(c);
+    ConvW cw;
+    VTCK(pack_conv(c, "vt_op_conv3x3_block", hw.data(), hb.data(), Cout, Cin, 3, &cw, stride == 2));
+    ScFuse scf{};
+    if (has_sc) {
+        VTCK(pack_fused_shortcut(c, "vt_op_conv3x3_block shortcut", hsw.data(), hb.data(), Cout, sc_cin, &scf.wp, &scf.bias, &scf.wp16));
+        scf.x = (const bf16_t*)sc_x; scf.cin = sc_cin;
+    }
+    // fp16-operand mode: x (and sc_x) carry fp16 bits exactly when the schedules would have written them so for this conv
+    const bool f16 = c->f16_ops != 0;
+    if (f16 && !conv_f16(c, cw, stride, has_sc))
+        return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: fp16-operand mode (flag 18) is on, but under the current flags this conv has no fp16-operand kernel");
+    scf.x_f16 = f16;
+    GnState gn; gn.partial = (float*)ws;
+    ConvOpts o;
+    o.x_f16 = f16; o.o16_f16 = out16_f16 != 0; o.planar = stride == 1 ? out16_planar != 0 : x_planar != 0; o.rdt = rdt;
+    o.sc = has_sc ? &scf : nullptr; o.gn = want_gn ? &gn : nullptr; o.groups = want_gn ? groups : 32;
+    const int saved = c->fuse_gn_stats; c->fuse_gn_stats = 1;
+    const int r = run_conv(c, cw, (const bf16_t*)x, B, H, W, stride, stride == 1 ? 1 : 0, Ho, Wo, res, out, (bf16_t*)o16, s, o);
+    c->fuse_gn_stats = saved;
+    if (r) return r;
+    if (want_gn) {
+        if (gn.parts == 0) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: this shape has no stats epilogue");
+        HIPCK(c, vt_launch_gn_finalize(gn.partial, gn.parts, B, Cout, groups, eps, gamma, beta, scale_shift, s), "gn_finalize");
+    }
+    HIPCK(c, hipStreamSynchronize(s), "vt_op_conv3x3_block sync");
+    return VT_OK;
+}
+
 int vt_op_gemm_nt(vt_context* c, const void* A, const void* Bm, const float* bias, float* o32, void* o16, int batch, int M,
                   int N, int K, int lda, int ldb, int ldo, long long a_bs, long long b_bs, long long o_bs, float alpha,
                   int bias_per_row, void* stream) {

@@ -226,6 +226,15 @@ struct ConvE4m3 {
     std::vector<uint8_t> wp8s2;                               // conv3x3_s2_halo_fp8.hip's packing (scales: mult8g); only when asked for
 };
 ConvE4m3 pack_conv_e4m3(const float* w_oihw, int cout, int cin, bool s2_layout);
+// The per-layer packers vt_encoder_finalize / vt_image_decoder_finalize and vt_op_conv3x3_block share; every upload goes to c->cur_allocs.
+// pack_conv: every packing of one conv from its fp32 OIHW weight `wv` and bias `bv` (cout floats, host); `name` is for messages only;
+// `mult8_host` receives the fp8 halo kernel's per-cout multipliers (empty when the conv has no fp8 form).
+int pack_conv(vt_context* c, const std::string& name, const float* wv, const float* bv, int cout, int cin, int k, ConvW* out, bool stride2 = false,
+              std::vector<float>* mult8_host = nullptr);
+// pack_fused_shortcut: a 1x1 conv_shortcut for conv2's launch (Conv3x3Args::scW): [cin/32][cout rows, interleaved][32] as bf16 (*wp) and
+// fp16 bits (*wp16), and the launch's bias `bias_sum` = conv2's + the shortcut's (cout floats, host) as *bias.  cin % 32 == 0.
+int pack_fused_shortcut(vt_context* c, const std::string& name, const float* w_oi, const float* bias_sum, int cout, int cin, const bf16_t** wp,
+                        const float** bias, const bf16_t** wp16);
 
 // ---- capi.hip (Pillow's resample tables, shared with resize_batch.hip) ----------------------------
 int rs_ksize(int in_size, int out_size, int kind);

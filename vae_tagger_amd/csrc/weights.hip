@@ -108,8 +108,8 @@ static bool up(vt_context* c, const T** dst, const std::vector<V>& v) { return (
 
 // Every packing of one conv from its fp32 OIHW weight `wv` and bias `bv` (cout floats); `name` is for messages only.
 // `mult8_host`: receives the fp8 halo kernel's per-cout multipliers (empty when the conv has no fp8 form)
-static int pack_conv(vt_context* c, const std::string& name, const float* wv, const float* bv, int cout, int cin, int k, ConvW* out, bool stride2 = false,
-                     std::vector<float>* mult8_host = nullptr) {
+int pack_conv(vt_context* c, const std::string& name, const float* wv, const float* bv, int cout, int cin, int k, ConvW* out, bool stride2,
+              std::vector<float>* mult8_host) {
     const auto failed = [&] { return c->fail(VT_ERR_HIP, "upload failed for %s", name.c_str()); };
     out->cin = cin; out->cout = cout; out->k = k;
     if (!up(c, &out->w, pack_ohwi<uint16_t>(wv, cout, cin, k * k, to_bf16)) || !(out->b = (const float*)c->upload(bv, (size_t)cout * 4))) return failed();
@@ -132,6 +132,14 @@ static int pack_conv(vt_context* c, const std::string& name, const float* wv, co
         if (!p.wp8s2.empty() && !up(c, &out->wp8s2, p.wp8s2)) return failed();
         if (mult8_host) *mult8_host = p.mult8;
     }
+    return VT_OK;
+}
+// conv_shortcut for conv2's launch (declared in vt_context.h): the packing both the finalizers and vt_op_conv3x3_block read
+int pack_fused_shortcut(vt_context* c, const std::string& name, const float* w_oi, const float* bias_sum, int cout, int cin, const bf16_t** wp,
+                        const float** bias, const bf16_t** wp16) {
+    if (!up(c, wp, permute_weights<uint16_t>(w_oi, cout, cin, 1, 32, same, row64, to_bf16)) || !(*bias = (const float*)c->upload(bias_sum, (size_t)cout * 4)) ||
+        !up(c, wp16, permute_weights<uint16_t>(w_oi, cout, cin, 1, 32, same, row64, to_f16)))
+        return c->fail(VT_ERR_HIP, "upload failed for %s", name.c_str());
     return VT_OK;
 }
 // ... of the conv whose tensors the caller set as `name`.weight / .bias
@@ -169,9 +177,7 @@ static int get_resnet(vt_context* c, const std::string& p, int cin, int cout, Re
         const HostTensor* b2 = c->find(p + ".conv2.bias");
         std::vector<float> bb(cout);
         for (int o = 0; o < cout; ++o) bb[o] = b2->v[o] + bs->v[o];
-        if (!up(c, &r->sc_wp, permute_weights<uint16_t>(w, cout, cin, 1, 32, same, row64, to_bf16)) || !up(c, &r->b_c2sc, bb) ||
-            !up(c, &r->sc_wp16, permute_weights<uint16_t>(w, cout, cin, 1, 32, same, row64, to_f16)))
-            return c->fail(VT_ERR_HIP, "upload failed for %s.conv_shortcut", p.c_str());
+        VTCK(pack_fused_shortcut(c, p + ".conv_shortcut", w, bb.data(), cout, cin, &r->sc_wp, &r->b_c2sc, &r->sc_wp16));
         // fp8 conv2: its epilogue multiplies the accumulator by mult[cout] = scale / 8, so the shortcut rows carry 1 / mult
         if (r->c2.wp8 && !up(c, &r->sc_wp8, permute_weights<uint16_t>(w, cout, cin, 1, 32, same, row32, [&](float f, int o) { return f2bf(f / mult2[o]); })))
             return c->fail(VT_ERR_HIP, "upload failed for %s.conv_shortcut", p.c_str());
