@@ -545,6 +545,9 @@ int vt_cross_grads_merge(vt_context* ctx, void* state, size_t state_bytes, const
  *         (conv3x3_up2.hip: 4 taps per output pixel instead of 9, no 4x-sized intermediate tensor); 1 = the literal route, a nearest-2x
  *         pass into a 16-bit buffer followed by the stride-1 3x3 conv -- the A/B partner and on-device cross-check, and what a channel
  *         count the folded kernel refuses takes either way.  The two differ by accumulation order and by the folded weights' one rounding.
+ *         The data gradient vt_op_upsample2x_conv3x3_backward_data follows the same flag: the route of the backward is the route of the forward.
+ * flag 23: 0 (default) = vt_op_conv_s2_backward_data runs the scatter kernel (conv3x3_s2_dgrad.hip: 9 products per 2x2 quad of dx); 1 = the
+ *         literal route, dy scattered to the odd positions of a zeroed tensor + the stride-1 data gradient (36 products) -- the A/B partner.
  */
 int vt_set_flag(vt_context* ctx, int flag, int value);
 
@@ -732,6 +735,35 @@ int vt_op_conv_backward_data(vt_context* ctx, const void* dy16_nhwc, const float
 size_t vt_op_conv_backward_weight_workspace_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int splits);
 int vt_op_conv_backward_weight(vt_context* ctx, const void* dy16_nhwc, const void* a16_nhwc, float* dw_f32_oihw, int B, int H, int W, int Cin,
                                int Cout, int ksize, int splits, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- backward of the two resampling layers.  Precision and discipline as above: bf16 MFMA operands with fp32 accumulation
+ * whatever flag 18 says, fp32 gradients, one stream, no atomics, bit-identical from run to run and across any `splits`.
+ *
+ * Downsample2D, y = conv3x3(pad(x, (0,1,0,1)), W), stride 2, Ho = H / 2, Wo = W / 2 (odd H, W are legal; H, W >= 2).
+ * Data gradient: dx[b][2i+a][2j+a'][ci] by the parity of the output pixel -- row phase a = 0 takes ky 0 from dy row i and ky 2 from dy row i - 1,
+ * phase a = 1 takes ky 1 from dy row i, columns alike, dy outside [0, Ho) x [0, Wo) = 0 -- on bf16(W), 9 (phase, tap) products per 2x2 quad
+ * (conv3x3_s2_dgrad.hip; Cin % 64 == 0, Cout % 64 == 0).  With vt_set_flag(ctx, 23, 1), or channel counts that kernel refuses (multiples of 8), the
+ * literal route: dy16 scattered to the odd positions of a zeroed H x W tensor, then vt_op_conv_backward_data's launch.  dy16 bf16 NHWC
+ * [B][Ho][Wo][Cout], W fp32 OIHW on the device, dx_add optional fp32 [B][H][W][Cin], dx fp32 [B][H][W][Cin]; scratch from the context. */
+int vt_op_conv_s2_backward_data(vt_context* ctx, const void* dy16_nhwc, const float* w_f32_oihw, const float* dx_add, float* dx_f32, int B, int H, int W,
+                                int Cin, int Cout, void* stream);
+/* Weight gradient: dw[co][ci][ky][kx] = sum_{b,i,j} dy16[b][i][j][co] * a16[b][2i+ky][2j+kx][ci], a16 (bf16 NHWC [B][H][W][Cin], the layer's input)
+ * outside the image = 0.  `splits`, the workspace and the channel rule as vt_op_conv_backward_weight. */
+size_t vt_op_conv_s2_backward_weight_workspace_bytes(int B, int H, int W, int Cin, int Cout, int splits);
+int vt_op_conv_s2_backward_weight(vt_context* ctx, const void* dy16_nhwc, const void* a16_nhwc, float* dw_f32_oihw, int B, int H, int W, int Cin, int Cout,
+                                  int splits, void* workspace, size_t workspace_bytes, void* stream);
+/* Upsample2D, y = conv3x3(nearest2x(x), W) as vt_op_upsample2x_conv3x3 computes it; h, w >= 1 are the LOW resolution.
+ * Data gradient: the route follows the forward's.  Default: the exact adjoint of the folded forward -- dx[i][j] = sum over the 16 (phase, tap)
+ * pairs of Wf^T[phase][tap] . dy16[2 (i + 1 - ry - a) + a][2 (j + 1 - rx - a') + a'], Wf the forward's folded matrices (fp32 sum ky-major then kx,
+ * rounded to bf16 once), a 4x4 stride-2 gather (conv3x3_up2_dgrad.hip; C % 64 == 0).  With flag 22 (literal forward), or a C that kernel
+ * refuses (multiples of 8): vt_op_conv_backward_data's launch on bf16(W) at 2h x 2w, then the 2x2 sum ((00 + 01) + 10) + 11.  dy16 bf16
+ * [B][2h][2w][C], dx_add optional and dx fp32 [B][h][w][C]; scratch from the context. */
+int vt_op_upsample2x_conv3x3_backward_data(vt_context* ctx, const void* dy16_nhwc, const float* w_f32_oihw, const float* dx_add, float* dx_f32, int B, int h,
+                                           int w, int C, void* stream);
+/* Weight gradient: dw[co][ci][ky][kx] = sum_P dy16[P][co] * x16[(P + (ky-1, kx-1)) >> 1][ci] over the high-resolution pixels P, the bounds tested
+ * before the shift; x16 bf16 NHWC [B][h][w][C] (no upsampled tensor is written).  `splits` and the workspace as vt_op_conv_backward_weight. */
+size_t vt_op_upsample2x_conv3x3_backward_weight_workspace_bytes(int B, int h, int w, int C, int splits);
+int vt_op_upsample2x_conv3x3_backward_weight(vt_context* ctx, const void* dy16_nhwc, const void* x16_nhwc, float* dw_f32_oihw, int B, int h, int w, int C,
+                                             int splits, void* workspace, size_t workspace_bytes, void* stream);
 /* error while flag 18 (fp16 operands) is on: functions that mix these operators with the forward ones ask here first */
 int vt_op_backward_operands_check(vt_context* ctx);
 /* (mean, rstd) fp32 [B][groups][2] of an fp32 tensor [B][HW][C], from fp64 sums of x and x^2 taken in a fixed order (the forward's (scale, shift)
@@ -742,7 +774,7 @@ int vt_op_groupnorm_stats(vt_context* ctx, const float* x_f32, int B, int HW, in
 /* Backward of a = silu(GroupNorm(x)): with xh = (x - mean) rstd, u = gamma xh + beta, s = sigmoid(u), du = da s (1 + u (1 - s)):
  * dbeta[c] = sum du, dgamma[c] = sum du xh, dx = rstd (gamma du - mean_g(gamma du) - xh mean_g(gamma du xh)) (+ dx_add), means over the (C/groups) HW
  * elements of one image's group.  x, da, dx_add, dx fp32 [B][HW][C]; stats from vt_op_groupnorm_stats; dx16 (optional) = bf16(dx); dgamma, dbeta
- * optional.  Two passes over x and da; the sums are fp64 throughout, in a fixed order.  C / groups in {4, 8, 16}, C a power of two <= 1024. */
+ * optional.  Two passes over x and da; the sums are fp64 throughout, in a fixed order.  C / groups in {2, 4, 8, 16}, C a power of two <= 1024. */
 size_t vt_op_groupnorm_silu_backward_workspace_bytes(int B, int HW, int C);
 int vt_op_groupnorm_silu_backward(vt_context* ctx, const float* x_f32, const float* stats, const float* gamma, const float* beta, const float* da_f32,
                                   const float* dx_add, float* dx_f32, void* dx16_out, float* dgamma_out, float* dbeta_out, int B, int HW, int C,

@@ -6,7 +6,13 @@ own weight gradient on bf16 tensors, (c) a torch device copy, as the rate the HB
 Per block (C -> C of each layer shape, 128 -> 256 and 512 -> 256 at 512^2): the whole resnet_block_backward beside torch autograd's backward of the
 same block under bf16 autocast.  Everything is warmed first and timed in interleaved rounds; the figures are medians over the rounds.
 
-Usage: python tools/bench_conv_backward.py [--rounds 5] [--iters 5] [--scale 1024] [--skip-torch] [--out FILE]
+--resample times the two resampling layers instead, batch 1, at the FLUX VAE's resample layers -- Downsample2D at 128 ch
+1024^2 -> 512^2, 256 ch 512^2 -> 256^2, 512 ch 256^2 -> 128^2; Upsample2D at 512 ch 128^2 -> 256^2, 512 ch 256^2 -> 512^2, 256 ch 512^2 -> 1024^2:
+each data gradient on both of its routes (the new kernel and the literal route, flag 23 / flag 22) in the same interleaved rounds, the weight gradient
+beside the stride-1 weight gradient at the same output size, the forward layer, torch's conv2d_input / conv2d_weight on bf16 tensors and a torch copy
+of the operand bytes.
+
+Usage: python tools/bench_conv_backward.py [--resample] [--rounds 5] [--iters 5] [--scale 1024] [--skip-torch] [--out FILE]
 Prints text lines and, last, one JSON line (also written to --out)."""
 import argparse
 import ctypes
@@ -118,6 +124,79 @@ def bench_layer(C, side, rounds, iters, with_torch):
     return rec
 
 
+RESAMPLE = [("down", 128, 1024), ("down", 256, 512), ("down", 512, 256), ("up", 512, 128), ("up", 512, 256), ("up", 256, 512)]      # kind, channels, input side
+
+
+def bench_resample(kind, C, side, rounds, iters, with_torch):
+    """side: the layer's INPUT side; the gradient dy has side // 2 (down) or 2 * side (up)"""
+    ctx = vb.context(DEV)
+    down = kind == "down"
+    oside = side // 2 if down else 2 * side
+    n_out = oside * oside
+    dy16 = rnd(1, oside, oside, C, scale=n_out ** -0.5, dtype=torch.bfloat16, seed=31)
+    x16 = rnd(1, side, side, C, dtype=torch.bfloat16, seed=32)
+    s1_a16 = rnd(1, oside, oside, C, dtype=torch.bfloat16, seed=33)        # the stride-1 weight gradient at the same output size
+    w = rnd(C, C, 3, 3, scale=(9 * C) ** -0.5, seed=34)
+    bias = torch.zeros(C, device=DEV)
+    flag = 23 if down else 22
+
+    def routed(v, fn):
+        def call():
+            ctx.call("vt_set_flag", flag, v)
+            try:
+                return fn()
+            finally:
+                ctx.call("vt_set_flag", flag, 0)
+        return call
+
+    if down:
+        dgrad = lambda: vb.downsample_backward_data(dy16, w, side, side)  # noqa: E731
+        calls = {"wgrad": lambda: vb.downsample_backward_weight(dy16, x16), "forward": lambda: vb.downsample_forward(w, bias, x16)}
+    else:
+        dgrad = lambda: vb.upsample_backward_data(dy16, w)  # noqa: E731
+        calls = {"wgrad": lambda: vb.upsample_backward_weight(dy16, x16), "forward": lambda: vb.upsample_forward(w, bias, x16)}
+    calls["dgrad_kernel"], calls["dgrad_literal"] = routed(0, dgrad), routed(1, dgrad)
+    calls["wgrad_stride1_same_output"] = lambda: vb.conv_backward_weight(dy16, s1_a16, 3)
+    operand_bytes = (dy16.numel() + x16.numel()) * 2 + side * side * C * 4      # dy16 and the layer's input read, dx fp32 written
+    copy_src = torch.empty(operand_bytes // 2, dtype=torch.uint8, device=DEV)
+    copy_dst = torch.empty_like(copy_src)
+    calls["torch_copy_operand_bytes"] = lambda: copy_dst.copy_(copy_src)
+    note = None
+    if with_torch:
+        try:
+            tdy = dy16.permute(0, 3, 1, 2)
+            tw = w.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+            if down:
+                tx = F.pad(x16.permute(0, 3, 1, 2), (0, 1, 0, 1)).contiguous(memory_format=torch.channels_last)
+                stride = [2, 2]
+            else:
+                tx = F.interpolate(x16.permute(0, 3, 1, 2), scale_factor=2, mode="nearest").contiguous(memory_format=torch.channels_last)
+                stride = [1, 1]
+            pad = [0, 0] if down else [1, 1]
+            calls["torch_conv2d_input_bf16"] = lambda: torch.ops.aten.convolution_backward(tdy, tx, tw, None, stride, pad, [1, 1], False, [0, 0], 1, [True, False, False])
+            calls["torch_conv2d_weight_bf16"] = lambda: torch.ops.aten.convolution_backward(tdy, tx, tw, None, stride, pad, [1, 1], False, [0, 0], 1, [False, True, False])
+            calls["torch_conv2d_input_bf16"](); calls["torch_conv2d_weight_bf16"]()
+            torch.cuda.synchronize()
+        except Exception as e:  # noqa: BLE001
+            calls.pop("torch_conv2d_input_bf16", None); calls.pop("torch_conv2d_weight_bf16", None)
+            note = f"torch gradients not measured: {type(e).__name__}: {e}"
+    ms = interleaved(calls, rounds, iters)
+    flops = 2.0 * n_out * C * C * 9                         # the layer's own multiply-adds: 9 taps per output pixel
+    rec = {"kind": kind, "channels": C, "in_side": side, "out_side": oside, "ms": {k: round(v, 4) for k, v in ms.items()},
+           "dgrad_kernel_over_literal": round(ms["dgrad_kernel"] / ms["dgrad_literal"], 3),
+           "wgrad_over_stride1_same_output": round(ms["wgrad"] / ms["wgrad_stride1_same_output"], 3),
+           "wgrad_tflops": round(flops / ms["wgrad"] / 1e9, 1), "wgrad_stride1_tflops": round(flops / ms["wgrad_stride1_same_output"] / 1e9, 1),
+           "copy_gbs": round(2 * copy_src.numel() / ms["torch_copy_operand_bytes"] / 1e6, 1)}
+    if "torch_conv2d_weight_bf16" in ms:
+        rec["wgrad_over_torch"] = round(ms["wgrad"] / ms["torch_conv2d_weight_bf16"], 3)
+        rec["dgrad_kernel_over_torch"] = round(ms["dgrad_kernel"] / ms["torch_conv2d_input_bf16"], 3)
+    if note:
+        rec["note"] = note
+    print(f"{kind} {C} ch {side}^2 -> {oside}^2: " + "  ".join(f"{k} {v:.3f} ms" for k, v in ms.items()), flush=True)
+    print(f"    kernel / literal {rec['dgrad_kernel_over_literal']}  wgrad / stride-1 wgrad {rec['wgrad_over_stride1_same_output']}", flush=True)
+    return rec
+
+
 def torch_block(p, x):
     h = F.conv2d(F.silu(F.group_norm(x, 32, p["norm1.weight"], p["norm1.bias"], 1e-6)), p["conv1.weight"], p["conv1.bias"], padding=1)
     h = F.conv2d(F.silu(F.group_norm(h, 32, p["norm2.weight"], p["norm2.bias"], 1e-6)), p["conv2.weight"], p["conv2.bias"], padding=1)
@@ -164,6 +243,7 @@ def main():
     ap.add_argument("--scale", type=int, default=1024, help="image side the layer sides are scaled to (1024: the real ones)")
     ap.add_argument("--skip-torch", action="store_true")
     ap.add_argument("--skip-blocks", action="store_true")
+    ap.add_argument("--resample", action="store_true", help="time the two resampling layers' backward instead (both routes of each data gradient)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -171,10 +251,15 @@ def main():
     sc = lambda s: max(8, s * a.scale // 1024)  # noqa: E731
     res = {"tool": "bench_conv_backward", "batch": 1, "rounds": a.rounds, "iters": a.iters, "scale": a.scale, "device": torch.cuda.get_device_name(0),
            "layers": [], "blocks": []}
-    for C, side in LAYERS:
+    if a.resample:
+        res["resample"] = []
+        for kind, C, side in RESAMPLE:
+            res["resample"].append(bench_resample(kind, C, sc(side), a.rounds, a.iters, not a.skip_torch))
+            torch.cuda.empty_cache()
+    for C, side in ([] if a.resample else LAYERS):
         res["layers"].append(bench_layer(C, sc(side), a.rounds, a.iters, not a.skip_torch))
         torch.cuda.empty_cache()
-    if not a.skip_blocks:
+    if not a.skip_blocks and not a.resample:
         for cin, cout, side in BLOCKS:
             res["blocks"].append(bench_block(cin, cout, sc(side), a.rounds, a.iters, not a.skip_torch))
     line = json.dumps(res)

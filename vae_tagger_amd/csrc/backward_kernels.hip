@@ -137,14 +137,18 @@ __global__ __launch_bounds__(64) void gn_stats64_finish_kernel(const double* __r
 
 // ---- GroupNorm + SiLU backward ----------------------------------------------------------------------------------------------------------------
 // xh = (x - mean) * rstd, u = gamma * xh + beta, s = sigmoid(u), du = da * s * (1 + u * (1 - s))
-struct GnLane { float g[4], bt[4], mean, rstd; };
+struct GnLane { float g[4], bt[4], mean[4], rstd[4]; };
 __device__ __forceinline__ GnLane gn_lane(const float* stats, const float* gamma, const float* beta, int b, int c, int groups, int cpg) {
     GnLane l;
     const f32x4 gg = *(const f32x4*)(gamma + c), bb = *(const f32x4*)(beta + c);
 #pragma unroll
     for (int i = 0; i < 4; ++i) { l.g[i] = gg[i]; l.bt[i] = bb[i]; }
-    const float* st = stats + ((long long)b * groups + c / cpg) * 2;       // (4 aligned channels lie in one group: cpg is 4, 8 or 16)
-    l.mean = st[0]; l.rstd = st[1];
+    // 4 aligned channels lie in one group (cpg 4, 8 or 16) or in two, two channels each (cpg 2)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float* st = stats + ((long long)b * groups + (c + 2 * h) / cpg) * 2;
+        l.mean[2 * h] = l.mean[2 * h + 1] = st[0]; l.rstd[2 * h] = l.rstd[2 * h + 1] = st[1];
+    }
     return l;
 }
 // (SILU = false: the plain GroupNorm of the attention block, du = da)
@@ -152,7 +156,7 @@ template <bool SILU>
 __device__ __forceinline__ void gn_du(const GnLane& l, const f32x4& x, const f32x4& da, float (&xh)[4], float (&du)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        xh[i] = (x[i] - l.mean) * l.rstd;
+        xh[i] = (x[i] - l.mean[i]) * l.rstd[i];
         if constexpr (!SILU) { du[i] = da[i]; continue; }
         const float u = fmaf(l.g[i], xh[i], l.bt[i]);
         const float s = sigmoid_acc(u);
@@ -252,8 +256,12 @@ __global__ __launch_bounds__(BK_THREADS) void gn_bwd_dx_kernel(const float* __re
     const int tc = threadIdx.x % L.tpp, tp = threadIdx.x / L.tpp;
     const int cpg = C / groups;
     const GnLane l = gn_lane(stats, gamma, beta, b, tc * 4, groups, cpg);
-    const float* m = gm + ((long long)b * groups + (tc * 4) / cpg) * 2;
-    const float m1 = m[0], m2 = m[1];
+    float m1[4], m2[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float* m = gm + ((long long)b * groups + (tc * 4 + 2 * h) / cpg) * 2;
+        m1[2 * h] = m1[2 * h + 1] = m[0]; m2[2 * h] = m2[2 * h + 1] = m[1];
+    }
     const int p0 = blockIdx.x * pix_per_block, p1 = min(HW, p0 + pix_per_block);
     const long long base = (long long)b * HW * C + tc * 4;
     for (int p = p0 + tp; p < p1; p += L.ppp) {
@@ -263,7 +271,7 @@ __global__ __launch_bounds__(BK_THREADS) void gn_bwd_dx_kernel(const float* __re
         gn_du<SILU>(l, xv, dv, xh, du);
         f32x4 r;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = l.rstd * (l.g[i] * du[i] - m1 - xh[i] * m2);
+        for (int i = 0; i < 4; ++i) r[i] = l.rstd[i] * (l.g[i] * du[i] - m1[i] - xh[i] * m2[i]);
         if (dx_add) r += *(const f32x4*)(dx_add + o);
         *(f32x4*)(dx + o) = r;
         if (dx16) {
@@ -273,6 +281,41 @@ __global__ __launch_bounds__(BK_THREADS) void gn_bwd_dx_kernel(const float* __re
             *(bf16x4*)(dx16 + o) = h;
         }
     }
+}
+
+// ---- the resampling layers' literal routes ---------------------------------------------------------------------------------
+// Downsample2D: y[i][j] is the stride-1 pad-1 conv's output at (2i + 1, 2j + 1), so its data gradient is the stride-1 one of dy scattered there
+__global__ __launch_bounds__(256) void scatter_odd_kernel(const uint4* __restrict__ dy, uint4* __restrict__ out, int H, int W, int C8, long long n) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // over out [B][H][W][C8]
+    if (idx >= n) return;
+    const int c = (int)(idx % C8);
+    long long p = idx / C8;
+    const int X = (int)(p % W); p /= W;
+    const int Y = (int)(p % H);
+    const long long b = p / H;
+    const int Ho = H / 2, Wo = W / 2;
+    uint4 v = uint4{0u, 0u, 0u, 0u};
+    if ((Y & 1) && (X & 1)) v = dy[((b * Ho + (Y >> 1)) * Wo + (X >> 1)) * C8 + c];     // (Y odd and < H: Y >> 1 < Ho)
+    out[idx] = v;
+}
+
+// Upsample2D: the four high-resolution gradients of a low-resolution pixel, added in a fixed order
+__global__ __launch_bounds__(256) void sum2x2_kernel(const f32x4* __restrict__ t, const f32x4* __restrict__ dx_add, f32x4* __restrict__ dx, int h, int w, int C4,
+                                                     long long n) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // over dx [B][h][w][C4]
+    if (idx >= n) return;
+    const int c = (int)(idx % C4);
+    long long p = idx / C4;
+    const int j = (int)(p % w); p /= w;
+    const int i = (int)(p % h);
+    const long long b = p / h;
+    const long long r0 = ((b * 2 * h + 2 * i) * 2 * w + 2 * j) * C4 + c, r1 = r0 + (long long)2 * w * C4;
+    f32x4 s = t[r0];
+    s += t[r0 + C4];
+    s += t[r1];
+    s += t[r1 + C4];
+    if (dx_add) s += dx_add[idx];
+    dx[idx] = s;
 }
 
 int gn_bwd_chunks(int HW, int C) { const int cp = lanes_of(C).ppp * BK_PASSES; return (HW + cp - 1) / cp; }
@@ -310,10 +353,26 @@ hipError_t vt_launch_pack_dgrad_weights(const float* w_oihw, bf16_t* dst, int Ci
     return hipGetLastError();
 }
 
+hipError_t vt_launch_scatter_odd_nhwc16(const void* dy16, void* out16, int B, int H, int W, int C, hipStream_t s) {
+    if (!dy16 || !out16 || B <= 0 || H < 2 || W < 2 || C <= 0 || (C % 8)) return hipErrorInvalidValue;
+    const long long n = (long long)B * H * W * (C / 8);
+    if ((n + 255) / 256 > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scatter_odd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint4*)dy16, (uint4*)out16, H, W, C / 8, n);
+    return hipGetLastError();
+}
+
+hipError_t vt_launch_sum2x2_f32(const float* t, const float* dx_add, float* dx, int B, int h, int w, int C, hipStream_t s) {
+    if (!t || !dx || B <= 0 || h <= 0 || w <= 0 || C <= 0 || (C % 4)) return hipErrorInvalidValue;
+    const long long n = (long long)B * h * w * (C / 4);
+    if ((n + 255) / 256 > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sum2x2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const f32x4*)t, (const f32x4*)dx_add, (f32x4*)dx, h, w, C / 4, n);
+    return hipGetLastError();
+}
+
 bool vt_gn_silu_bwd_supported(int C, int groups) {
     if (C <= 0 || groups <= 0 || C % groups || C > 1024) return false;
     const int cpg = C / groups;
-    if (cpg != 4 && cpg != 8 && cpg != 16) return false;
+    if (cpg != 2 && cpg != 4 && cpg != 8 && cpg != 16) return false;
     return (C % BK_FIN_ROWS) == 0 && (BK_THREADS % (C / 4)) == 0;
 }
 

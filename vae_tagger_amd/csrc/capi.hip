@@ -483,6 +483,7 @@ int vt_set_flag(vt_context* c, int flag, int value) {
     if (flag == 21) { c->eval_merge_vec = value != 0; return VT_OK; }
     if (flag == 20) { c->conv_out_halo = value != 0; return VT_OK; }
     if (flag == 22) { c->up2_literal = value != 0; return VT_OK; }
+    if (flag == 23) { c->s2_dgrad_literal = value != 0; return VT_OK; }
     if (flag == 13) { c->s2_halo = value != 0; return VT_OK; }
     if (flag == 14) { c->attn_fp8 = value != 0; return VT_OK; }
     if (flag == 15) { c->proj_fp8 = value != 0; return VT_OK; }

@@ -390,6 +390,31 @@ int vt_op_cast_bias_grad(vt_context* c, const float* dy, void* dy16, float* dbia
     return VT_OK;
 }
 
+// dx = conv(dy16, W'), W'[ci][ky'][kx'][co] = bf16(W[co][ci][2 - ky'][2 - kx']): the forward conv with Cout input and Cin output channels.  The packed
+// weights go to the operator scratch behind `keep` bytes the caller has its own use for (the literal routes of the resampling layers).
+static int conv_dgrad_launch(vt_context* c, const void* dy16, const float* w_oihw, const float* dx_add, float* dx, int B, int H, int W, int Cin, int Cout,
+                             int ksize, size_t keep, hipStream_t s, const char* what) {
+    const int taps = ksize * ksize;
+    const size_t w_bytes = align_up((size_t)Cin * taps * Cout * 2);
+    const bool halo = c->use_halo_conv && ksize == 3 && vt_conv3x3_halo_supported(Cout, Cin);
+    VTCK(ensure_op_scratch(c, keep + w_bytes * (halo ? 2 : 1)));
+    bf16_t* wt = (bf16_t*)((char*)c->op_scratch + keep);
+    HIPCK(c, vt_launch_pack_dgrad_weights(w_oihw, wt, Cin, Cout, ksize, s), "pack_dgrad_weights");
+    if (halo) {
+        bf16_t* wp = (bf16_t*)((char*)wt + w_bytes);
+        HIPCK(c, vt_launch_repack_ohwi_to_halo(wt, wp, Cout, Cin, s), "repack");
+        Conv3x3Args h{};
+        h.X = (const bf16_t*)dy16; h.Wp = wp; h.res = dx_add; h.out_f32 = dx; h.zeros = c->zeros; h.batch = B; h.H = H; h.W = W; h.Cin = Cout; h.Cout = Cin;
+        return launch_halo(c, h, s, what);
+    }
+    ConvGemmArgs a{};
+    a.X = (const bf16_t*)dy16; a.W = wt; a.res = dx_add; a.out_f32 = dx; a.zeros = c->zeros;
+    a.Hin = H; a.Win = W; a.Hout = H; a.Wout = W; a.Cin = Cout; a.Cout = Cin; a.Wrows = Cin; a.ksize = ksize; a.stride = 1; a.pad = ksize / 2;
+    a.ldx = Cout; a.ldw = taps * Cout; a.ldo = Cin; a.ldr = Cin;
+    a.x_bs = (long long)H * W * Cout; a.o_bs = (long long)H * W * Cin; a.r_bs = a.o_bs; a.batch = B; a.alpha = 1.f; a.bias_mode = 0;
+    return launch_gemm(c, a, s, what);
+}
+
 int vt_op_conv_backward_data(vt_context* c, const void* dy16, const float* w_oihw, const float* dx_add, float* dx, int B, int H, int W, int Cin, int Cout,
                              int ksize, void* stream) {
     if (!c) return VT_ERR_INVALID;
@@ -398,27 +423,7 @@ int vt_op_conv_backward_data(vt_context* c, const void* dy16, const float* w_oih
     if (ksize != 1 && ksize != 3) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_data: ksize must be 1 or 3 (stride 1, pad ksize / 2), got %d", ksize);
     if (B <= 0 || H <= 0 || W <= 0 || Cin < 8 || (Cin % 8) || Cout < 8 || (Cout % 8))
         return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_data: Cin and Cout must be multiples of 8 and B, H, W >= 1 (got %d -> %d, %d x %d x %d)", Cin, Cout, B, H, W);
-    hipStream_t s = (hipStream_t)stream;
-    // dx = conv(dy16, W'), W'[ci][ky'][kx'][co] = bf16(W[co][ci][2 - ky'][2 - kx']): the forward conv with Cout input and Cin output channels
-    const int taps = ksize * ksize;
-    const size_t w_bytes = align_up((size_t)Cin * taps * Cout * 2);
-    const bool halo = c->use_halo_conv && ksize == 3 && vt_conv3x3_halo_supported(Cout, Cin);
-    VTCK(ensure_op_scratch(c, w_bytes * (halo ? 2 : 1)));
-    bf16_t* wt = (bf16_t*)c->op_scratch;
-    HIPCK(c, vt_launch_pack_dgrad_weights(w_oihw, wt, Cin, Cout, ksize, s), "pack_dgrad_weights");
-    if (halo) {
-        bf16_t* wp = (bf16_t*)((char*)c->op_scratch + w_bytes);
-        HIPCK(c, vt_launch_repack_ohwi_to_halo(wt, wp, Cout, Cin, s), "repack");
-        Conv3x3Args h{};
-        h.X = (const bf16_t*)dy16; h.Wp = wp; h.res = dx_add; h.out_f32 = dx; h.zeros = c->zeros; h.batch = B; h.H = H; h.W = W; h.Cin = Cout; h.Cout = Cin;
-        return launch_halo(c, h, s, "vt_op_conv_backward_data(halo)");
-    }
-    ConvGemmArgs a{};
-    a.X = (const bf16_t*)dy16; a.W = wt; a.res = dx_add; a.out_f32 = dx; a.zeros = c->zeros;
-    a.Hin = H; a.Win = W; a.Hout = H; a.Wout = W; a.Cin = Cout; a.Cout = Cin; a.Wrows = Cin; a.ksize = ksize; a.stride = 1; a.pad = ksize / 2;
-    a.ldx = Cout; a.ldw = taps * Cout; a.ldo = Cin; a.ldr = Cin;
-    a.x_bs = (long long)H * W * Cout; a.o_bs = (long long)H * W * Cin; a.r_bs = a.o_bs; a.batch = B; a.alpha = 1.f; a.bias_mode = 0;
-    return launch_gemm(c, a, s, "vt_op_conv_backward_data");
+    return conv_dgrad_launch(c, dy16, w_oihw, dx_add, dx, B, H, W, Cin, Cout, ksize, 0, (hipStream_t)stream, "vt_op_conv_backward_data");
 }
 
 static int wgrad_splits(int B, int H, int W, int Cin, int Cout, int splits) {
@@ -452,6 +457,117 @@ int vt_op_conv_backward_weight(vt_context* c, const void* dy16, const void* a16,
     return VT_OK;
 }
 
+// ---- backward of the two resampling layers: Downsample2D's stride-2 conv and Upsample2D ----
+
+// Downsample2D: y = conv3x3(pad(x, (0,1,0,1)), W), stride 2.  dy16 [B][H/2][W/2][Cout] -> dx [B][H][W][Cin].  The scatter kernel, or with
+// vt_set_flag(ctx, 23, 1) / channel counts it refuses the literal route: dy16 scattered to the odd positions of a zeroed H x W tensor, then
+// vt_op_conv_backward_data's launch.
+int vt_op_conv_s2_backward_data(vt_context* c, const void* dy16, const float* w_oihw, const float* dx_add, float* dx, int B, int H, int W, int Cin, int Cout,
+                                void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!dy16 || !w_oihw || !dx) return c->fail(VT_ERR_INVALID, "vt_op_conv_s2_backward_data: null buffer");
+    if (B <= 0 || H < 2 || W < 2 || Cin < 8 || (Cin % 8) || Cout < 8 || (Cout % 8))
+        return c->fail(VT_ERR_INVALID, "vt_op_conv_s2_backward_data: Cin and Cout must be multiples of 8, B >= 1 and H, W >= 2 (got %d -> %d, %d x %d x %d)", Cin, Cout,
+                       B, H, W);
+    if ((long long)H * W * std::max(Cin, Cout) >= (1LL << 31)) return c->fail(VT_ERR_INVALID, "vt_op_conv_s2_backward_data: image too large (32-bit per-image offsets)");
+    hipStream_t s = (hipStream_t)stream;
+    if (!c->s2_dgrad_literal && vt_conv3x3_s2_dgrad_supported(Cin, Cout) && (Cout % 64) == 0) {
+        VTCK(ensure_op_scratch(c, align_up((size_t)Cout * 9 * Cin * 2)));
+        HIPCK(c, vt_launch_pack_s2_dgrad(w_oihw, (bf16_t*)c->op_scratch, Cin, Cout, s), "pack_s2_dgrad");
+        ConvS2DgradArgs a{};
+        a.dy = (const bf16_t*)dy16; a.Wp = (const bf16_t*)c->op_scratch; a.dx_add = dx_add; a.dx = dx; a.zeros = c->zeros;
+        a.batch = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+        HIPCK(c, vt_launch_conv3x3_s2_dgrad(a, s), "conv3x3_s2_dgrad");
+        return VT_OK;
+    }
+    const size_t keep = align_up((size_t)B * H * W * Cout * 2);
+    VTCK(ensure_op_scratch(c, keep + 2 * align_up((size_t)Cin * 9 * Cout * 2)));      // (sized once: the launch below must not move the buffer)
+    HIPCK(c, vt_launch_scatter_odd_nhwc16(dy16, c->op_scratch, B, H, W, Cout, s), "scatter_odd");
+    return conv_dgrad_launch(c, c->op_scratch, w_oihw, dx_add, dx, B, H, W, Cin, Cout, 3, keep, s, "vt_op_conv_s2_backward_data(literal)");
+}
+
+static int rs_wgrad_splits(int mode, int B, int Hdy, int Wdy, int Cin, int Cout, int splits) {
+    const int steps = vt_conv_wgrad_rs_steps(mode, B, Hdy, Wdy);
+    if (splits <= 0) return vt_conv_wgrad_rs_auto_splits(mode, B, Hdy, Wdy, Cin, Cout);
+    return splits > steps ? steps : splits;
+}
+
+static size_t rs_wgrad_ws_bytes(int mode, int B, int Hdy, int Wdy, int Cin, int Cout, int splits) {
+    if (splits < 0 || !vt_conv_wgrad_supported(Cin, Cout, 3) || vt_conv_wgrad_rs_steps(mode, B, Hdy, Wdy) <= 0) return 0;
+    return align_up((size_t)rs_wgrad_splits(mode, B, Hdy, Wdy, Cin, Cout, splits) * Cout * Cin * 9 * sizeof(float));
+}
+
+static int rs_wgrad(vt_context* c, const char* name, int mode, const void* dy16, const void* a16, float* dw, int B, int Hdy, int Wdy, int aH, int aW, int Cin, int Cout,
+                    int splits, void* ws, size_t ws_bytes, void* stream) {
+    if (!dy16 || !a16 || !dw) return c->fail(VT_ERR_INVALID, "%s: null buffer", name);
+    if (!vt_conv_wgrad_supported(Cin, Cout, 3)) return c->fail(VT_ERR_INVALID, "%s: channel counts must be multiples of 64 (got %d -> %d)", name, Cin, Cout);
+    if (B <= 0 || aH < (mode == 1 ? 2 : 1) || aW < (mode == 1 ? 2 : 1) || vt_conv_wgrad_rs_steps(mode, B, Hdy, Wdy) <= 0)
+        return c->fail(VT_ERR_INVALID, "%s: B must be >= 1 and the layer's input at least %s (got %d x %d x %d)", name, mode == 1 ? "2 x 2" : "1 x 1", B, aH, aW);
+    if (splits < 0) return c->fail(VT_ERR_INVALID, "%s: splits must be >= 0 (0 = chosen from the shape)", name);
+    const size_t need = rs_wgrad_ws_bytes(mode, B, Hdy, Wdy, Cin, Cout, splits);
+    if (!ws || ((uintptr_t)ws % 16) || ((uintptr_t)dw % 16) || ws_bytes < need)
+        return c->fail(VT_ERR_INVALID, "%s: workspace must be 16-byte aligned and hold %s_workspace_bytes = %zu bytes (got %zu)", name, name, need, ws_bytes);
+    ConvWgradArgs a{};
+    a.dy = (const bf16_t*)dy16; a.a = (const bf16_t*)a16; a.dw = dw; a.ws = (float*)ws; a.batch = B; a.H = Hdy; a.W = Wdy; a.aH = aH; a.aW = aW; a.Cin = Cin; a.Cout = Cout;
+    a.ksize = 3; a.splits = rs_wgrad_splits(mode, B, Hdy, Wdy, Cin, Cout, splits);
+    HIPCK(c, vt_launch_conv_wgrad_rs(a, mode, (hipStream_t)stream), name);
+    return VT_OK;
+}
+
+size_t vt_op_conv_s2_backward_weight_workspace_bytes(int B, int H, int W, int Cin, int Cout, int splits) {
+    if (H < 2 || W < 2) return 0;
+    return rs_wgrad_ws_bytes(1, B, H / 2, W / 2, Cin, Cout, splits);
+}
+
+int vt_op_conv_s2_backward_weight(vt_context* c, const void* dy16, const void* a16, float* dw, int B, int H, int W, int Cin, int Cout, int splits, void* ws,
+                                  size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    return rs_wgrad(c, "vt_op_conv_s2_backward_weight", 1, dy16, a16, dw, B, H / 2, W / 2, H, W, Cin, Cout, splits, ws, ws_bytes, stream);
+}
+
+// Upsample2D: y = conv3x3(nearest2x(x), W).  dy16 [B][2h][2w][C] -> dx [B][h][w][C].  The route follows the forward's: the gather kernel on the
+// transposed folded matrices, or with vt_set_flag(ctx, 22, 1) / a C it refuses the literal one on bf16(W): vt_op_conv_backward_data's launch at
+// 2h x 2w into scratch, then the 2x2 sum.
+int vt_op_upsample2x_conv3x3_backward_data(vt_context* c, const void* dy16, const float* w_oihw, const float* dx_add, float* dx, int B, int h, int wd, int C,
+                                           void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (!dy16 || !w_oihw || !dx) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_backward_data: null buffer");
+    if (B <= 0 || h <= 0 || wd <= 0 || C < 8 || (C % 8))
+        return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_backward_data: C must be a multiple of 8 and B, h, w >= 1 (got %d, %d x %d x %d)", C, B, h, wd);
+    if ((long long)B * h * wd * C >= (1LL << 29)) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_backward_data: tensor too large for the operator entry");
+    hipStream_t s = (hipStream_t)stream;
+    if (!c->up2_literal && vt_conv3x3_up2_dgrad_supported(C)) {
+        VTCK(ensure_op_scratch(c, align_up((size_t)C * 16 * C * 2)));
+        HIPCK(c, vt_launch_pack_up2_dgrad(w_oihw, (bf16_t*)c->op_scratch, C, s), "pack_up2_dgrad");
+        ConvUp2DgradArgs a{};
+        a.dy = (const bf16_t*)dy16; a.Wp = (const bf16_t*)c->op_scratch; a.dx_add = dx_add; a.dx = dx; a.zeros = c->zeros; a.batch = B; a.H = h; a.W = wd; a.C = C;
+        HIPCK(c, vt_launch_conv3x3_up2_dgrad(a, s), "conv3x3_up2_dgrad");
+        return VT_OK;
+    }
+    const size_t keep = align_up((size_t)B * 4 * h * wd * C * sizeof(float));
+    VTCK(ensure_op_scratch(c, keep + 2 * align_up((size_t)C * 9 * C * 2)));
+    float* t = (float*)c->op_scratch;
+    VTCK(conv_dgrad_launch(c, dy16, w_oihw, nullptr, t, B, 2 * h, 2 * wd, C, C, 3, keep, s, "vt_op_upsample2x_conv3x3_backward_data(literal)"));
+    HIPCK(c, vt_launch_sum2x2_f32(t, dx_add, dx, B, h, wd, C, s), "sum2x2");
+    return VT_OK;
+}
+
+size_t vt_op_upsample2x_conv3x3_backward_weight_workspace_bytes(int B, int h, int w, int C, int splits) {
+    if (h < 1 || w < 1 || h >= (1 << 29) || w >= (1 << 29)) return 0;
+    return rs_wgrad_ws_bytes(2, B, 2 * h, 2 * w, C, C, splits);
+}
+
+int vt_op_upsample2x_conv3x3_backward_weight(vt_context* c, const void* dy16, const void* x16, float* dw, int B, int h, int w, int C, int splits, void* ws,
+                                             size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    if (h >= (1 << 29) || w >= (1 << 29)) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_backward_weight: shape too large");
+    return rs_wgrad(c, "vt_op_upsample2x_conv3x3_backward_weight", 2, dy16, x16, dw, B, 2 * h, 2 * w, h, w, C, C, splits, ws, ws_bytes, stream);
+}
+
 // The block functions (vae_backward.py) mix these operators with the forward ones, which follow flag 18: they ask here first.
 int vt_op_backward_operands_check(vt_context* c) {
     if (!c) return VT_ERR_INVALID;
@@ -469,7 +585,7 @@ int vt_op_groupnorm_stats(vt_context* c, const float* x, int B, int HW, int C, i
     DeviceGuard guard(c);
     if (!x || !stats) return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: null buffer");
     if (B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups))
-        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: channels per group must be 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
+        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: channels per group must be 2, 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
     const size_t need = vt_op_groupnorm_stats_workspace_bytes(B, HW, C);
     if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
         return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
@@ -489,7 +605,7 @@ int vt_op_groupnorm_silu_backward(vt_context* c, const float* x, const float* st
     DeviceGuard guard(c);
     if (!x || !stats || !gamma || !beta || !da || !dx) return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: null buffer");
     if (B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups))
-        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: channels per group must be 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
+        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: channels per group must be 2, 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
     const size_t need = vt_op_groupnorm_silu_backward_workspace_bytes(B, HW, C);
     if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
         return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
@@ -506,7 +622,7 @@ int vt_op_groupnorm_backward(vt_context* c, const float* x, const float* stats, 
     DeviceGuard guard(c);
     if (!x || !stats || !gamma || !beta || !dh || !dx) return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: null buffer");
     if (B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups))
-        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: channels per group must be 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
+        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: channels per group must be 2, 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
     const size_t need = vt_op_groupnorm_backward_workspace_bytes(B, HW, C);
     if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
         return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);

@@ -130,6 +130,7 @@ struct vt_context {
     int fp8_tile = 0;               // vt_set_flag(ctx, 16, v): fp8 halo conv tile shape = v & 3 (0: 8 x 32 px, 4 waves, two workgroups per CU; 1: 16 x 32 px;
                                     // 2: 8 x 64 px, 8 waves, one per CU) on the layers with Cin <= 128, or on every layer with v & 4
     int up2_literal = 0;            // vt_set_flag(ctx, 22, v): Upsample2D as a nearest-2x pass + the stride-1 3x3 conv instead of the folded kernel (conv3x3_up2.hip)
+    int s2_dgrad_literal = 0;       // vt_set_flag(ctx, 23, v): vt_op_conv_s2_backward_data as a scatter pass + the stride-1 data gradient instead of conv3x3_s2_dgrad.hip
     int s2_halo = 1;                // vt_set_flag(ctx, 13, v): stride-2 convs on the phase-plane halo kernel instead of the generic GEMM
     // vt_resize_u8: pinned staging of the coefficient tables + the event of the last H2D copy that read it
     int* rs_host = nullptr; size_t rs_host_ints = 0; hipEvent_t rs_event = nullptr;

@@ -406,7 +406,50 @@ struct ConvWgradArgs {
     float* ws;              // >= splits * Cout * Cin * ksize^2 floats
     int batch, H, W, Cin, Cout, ksize, splits;
     int tiles_x, tiles_y, steps;     // filled by the launcher
+    int aH, aW;                      // vt_launch_conv_wgrad_rs only: the activation's own size (H, W are dy's)
 };
+// The resampling layers' weight gradients on the same kernel body.  mode 1 = Downsample2D (3x3 stride 2, pad (0,1)): dy is
+// [batch][aH / 2][aW / 2][Cout], dw = sum dy[i][j] a[2i + ky][2j + kx]; mode 2 = Upsample2D: dy is [batch][2 aH][2 aW][Cout],
+// dw = sum_P dy[P] a[(P + (ky - 1, kx - 1)) >> 1] with the bounds tested before the shift.  H, W = dy's size; Cin % 64 == 0, Cout % 64 == 0.
+int vt_conv_wgrad_rs_steps(int mode, int B, int Hdy, int Wdy);
+int vt_conv_wgrad_rs_auto_splits(int mode, int B, int Hdy, int Wdy, int Cin, int Cout);
+hipError_t vt_launch_conv_wgrad_rs(const ConvWgradArgs& a, int mode, hipStream_t s);
+
+// Data gradient of Downsample2D's conv in scatter form (conv3x3_s2_dgrad.hip): dx[b][2i + a][2j + b'] from the low-resolution dy16, 9 (phase, tap)
+// products per 2x2 output quad.  Cin % 64 == 0, Cout % 32 == 0, H, W >= 2.
+struct ConvS2DgradArgs {
+    const bf16_t* dy;       // NHWC bf16 [batch][H / 2][W / 2][Cout]
+    const bf16_t* Wp;       // [Cout/32][ky * 3 + kx][Cin rows (vt_halo_row_of_cout)][32] bf16 (vt_launch_pack_s2_dgrad)
+    const float* dx_add;    // optional fp32 [batch][H][W][Cin]
+    float* dx;              // fp32 [batch][H][W][Cin]
+    const void* zeros;
+    int batch, H, W, Cin, Cout;
+    int Ho, Wo, tiles_x, ptiles, ctiles;     // filled by the launcher
+};
+bool vt_conv3x3_s2_dgrad_supported(int Cin, int Cout);
+hipError_t vt_launch_pack_s2_dgrad(const float* w_oihw, bf16_t* wp, int Cin, int Cout, hipStream_t s);
+hipError_t vt_launch_conv3x3_s2_dgrad(const ConvS2DgradArgs& a, hipStream_t s);
+
+// Data gradient of Upsample2D in gather form (conv3x3_up2_dgrad.hip): dx[b][i][j] from the four parity planes of the high-resolution dy16 on the
+// transposes of the forward's 16 folded matrices (same fp32 sums, rounded to bf16 once).  C % 64 == 0.
+struct ConvUp2DgradArgs {
+    const bf16_t* dy;       // NHWC bf16 [batch][2H][2W][C]
+    const bf16_t* Wp;       // [C/32 (cout chunks)][phase * 4 + tap][C rows (cin, vt_halo_row_of_cout)][32] bf16 (vt_launch_pack_up2_dgrad)
+    const float* dx_add;    // optional fp32 [batch][H][W][C]
+    float* dx;              // fp32 [batch][H][W][C]
+    const void* zeros;
+    int batch, H, W, C;     // H, W: LOW resolution
+    int tiles_x, ptiles, ctiles;             // filled by the launcher
+};
+bool vt_conv3x3_up2_dgrad_supported(int C);
+hipError_t vt_launch_pack_up2_dgrad(const float* w_oihw, bf16_t* wp, int C, hipStream_t s);
+hipError_t vt_launch_conv3x3_up2_dgrad(const ConvUp2DgradArgs& a, hipStream_t s);
+
+// the literal routes' passes (backward_kernels.hip): dy16 scattered to the odd positions of a zeroed [B][H][W][C] bf16 tensor; and the 2x2 sum
+// dx[i][j] = ((t[2i][2j] + t[2i][2j+1]) + t[2i+1][2j]) + t[2i+1][2j+1] (+ dx_add) of an fp32 [B][2h][2w][C] tensor.  C % 8 == 0.
+hipError_t vt_launch_scatter_odd_nhwc16(const void* dy16, void* out16, int B, int H, int W, int C, hipStream_t s);
+hipError_t vt_launch_sum2x2_f32(const float* t, const float* dx_add, float* dx, int B, int h, int w, int C, hipStream_t s);
+
 int vt_conv_wgrad_steps(int B, int H, int W);
 int vt_conv_wgrad_auto_splits(int B, int H, int W, int Cin, int Cout);      // workgroups = splits * (Cin / 64) * (Cout / 64) <= 512: two per CU
 bool vt_conv_wgrad_supported(int Cin, int Cout, int ksize);

@@ -1,10 +1,11 @@
-"""Backward of the VAE's mid block -- ResnetBlock2D (the block both VAE models consist of), the mid attention block, and their composition -- on
-the device: thin wrappers over the vt_op_* backward operators (include/vae_tagger_hip.h, DESIGN.md sections 4.19 and 4.20).  Tensors are torch tensors of one HIP device, activations NHWC ([B, H, W, C]), parameters in
-diffusers' own layouts (conv weights fp32 OIHW).  All gradients are fp32; every MFMA operand is bf16.  Every launch goes to torch's current stream
-of the tensors' device and nothing here synchronises with the host.  There is no eager fallback: a shape an operator refuses raises VTError.
+"""Backward of the VAE's blocks -- ResnetBlock2D (the block both VAE models consist of), the mid attention block, the two resampling layers
+(Downsample2D's stride-2 conv and Upsample2D), and their compositions: the mid block, a down block and an up block -- on the device: thin wrappers
+over the vt_op_* backward operators (include/vae_tagger_hip.h, DESIGN.md sections 4.19, 4.20 and 4.22).  Tensors are torch tensors of one HIP device,
+activations NHWC ([B, H, W, C]), parameters in diffusers' own layouts (conv weights fp32 OIHW).  All gradients are fp32; every MFMA operand is bf16.
+Every launch goes to torch's current stream of the tensors' device and nothing here synchronises with the host.  There is no eager fallback: a shape
+an operator refuses raises VTError.
 
-This is NOT train_vae: there is no optimiser, no loss and no backward of the other layer kinds (stride-2 convs, Upsample2D, conv_in, conv_out)
-here.
+This is NOT train_vae: there is no optimiser, no loss, no CLI, no backward of conv_in and conv_out and no whole-model backward here.
 """
 import ctypes
 
@@ -225,6 +226,185 @@ def resnet_block_backward(params, saved, dy, *, splits=0):
     # 6. norm1 + SiLU, the shortcut's gradient added in the same pass
     dx, _, g["norm1.weight"], g["norm1.bias"] = groupnorm_silu_backward(saved["x"], saved["stats1"], params["norm1.weight"], params["norm1.bias"], da1, dx_add=dxs)
     return dx, {k: g[k] for k in params}
+
+
+# ---- the resampling layers: Downsample2D's stride-2 conv and Upsample2D -----------------------------------------------------
+
+def downsample_backward_data(dy16, weight, H, W, *, dx_add=None):
+    """dy16 bf16 [B, H // 2, W // 2, Cout], weight fp32 [Cout, Cin, 3, 3] of y = conv(pad(x, (0,1,0,1)), W), stride 2 -> dx fp32 [B, H, W, Cin] (+ dx_add)."""
+    dy16, weight = _bf16(dy16, "dy16"), _f32(weight, "weight")
+    B, Ho, Wo, Cout = dy16.shape
+    Cin = weight.shape[1]
+    if tuple(weight.shape) != (Cout, Cin, 3, 3) or (Ho, Wo) != (H // 2, W // 2):
+        raise ValueError("weight or (H, W) does not match dy16")
+    if dx_add is not None and tuple(_f32(dx_add, "dx_add").shape) != (B, H, W, Cin):
+        raise ValueError("dx_add must have dx's shape")
+    dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dy16.device)
+    context(dy16.device).call("vt_op_conv_s2_backward_data", _vp(dy16), _vp(weight), _vp(dx_add), _vp(dx), B, H, W, Cin, Cout, _stream(dy16))
+    return dx
+
+
+def downsample_backward_weight(dy16, a16, *, splits=0):
+    """dy16 bf16 [B, H // 2, W // 2, Cout], a16 bf16 [B, H, W, Cin] (the layer's input) -> dW fp32 [Cout, Cin, 3, 3]."""
+    dy16, a16 = _bf16(dy16, "dy16"), _bf16(a16, "a16")
+    B, H, W, Cin = a16.shape
+    Cout = dy16.shape[-1]
+    if tuple(dy16.shape[:3]) != (B, H // 2, W // 2):
+        raise ValueError("a16 does not match dy16")
+    ctx = context(dy16.device)
+    dw = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=dy16.device)
+    ws = _workspace(ctx.lib.vt_op_conv_s2_backward_weight_workspace_bytes(B, H, W, Cin, Cout, int(splits)), dy16.device)
+    ctx.call("vt_op_conv_s2_backward_weight", _vp(dy16), _vp(a16), _vp(dw), B, H, W, Cin, Cout, int(splits), _vp(ws), ws.numel(), _stream(dy16))
+    return dw
+
+
+def upsample_backward_data(dy16, weight, *, dx_add=None):
+    """dy16 bf16 [B, 2h, 2w, C], weight fp32 [C, C, 3, 3] of y = conv3x3(nearest2x(x), W) -> dx fp32 [B, h, w, C] (+ dx_add); the route (folded or
+    literal, flag 22) is the forward operator's."""
+    dy16, weight = _bf16(dy16, "dy16"), _f32(weight, "weight")
+    B, H2, W2, C = dy16.shape
+    if tuple(weight.shape) != (C, C, 3, 3) or H2 % 2 or W2 % 2:
+        raise ValueError("weight does not match dy16, or dy16 has an odd size")
+    h, w = H2 // 2, W2 // 2
+    if dx_add is not None and tuple(_f32(dx_add, "dx_add").shape) != (B, h, w, C):
+        raise ValueError("dx_add must have dx's shape")
+    dx = torch.empty(B, h, w, C, dtype=torch.float32, device=dy16.device)
+    context(dy16.device).call("vt_op_upsample2x_conv3x3_backward_data", _vp(dy16), _vp(weight), _vp(dx_add), _vp(dx), B, h, w, C, _stream(dy16))
+    return dx
+
+
+def upsample_backward_weight(dy16, x16, *, splits=0):
+    """dy16 bf16 [B, 2h, 2w, C], x16 bf16 [B, h, w, C] (the layer's low-resolution input) -> dW fp32 [C, C, 3, 3]."""
+    dy16, x16 = _bf16(dy16, "dy16"), _bf16(x16, "x16")
+    B, h, w, C = x16.shape
+    if tuple(dy16.shape) != (B, 2 * h, 2 * w, C):
+        raise ValueError("x16 does not match dy16")
+    ctx = context(dy16.device)
+    dw = torch.empty(C, C, 3, 3, dtype=torch.float32, device=dy16.device)
+    ws = _workspace(ctx.lib.vt_op_upsample2x_conv3x3_backward_weight_workspace_bytes(B, h, w, C, int(splits)), dy16.device)
+    ctx.call("vt_op_upsample2x_conv3x3_backward_weight", _vp(dy16), _vp(x16), _vp(dw), B, h, w, C, int(splits), _vp(ws), ws.numel(), _stream(dy16))
+    return dw
+
+
+def _resample_backward(data_fn, weight_fn, dy, need_input, need_weight, need_bias, splits):
+    if dy.dtype == torch.bfloat16:
+        if need_bias:
+            raise ValueError("the bias gradient needs the fp32 dy")
+        dy16, db = dy, None
+    else:
+        dy16, db = cast_bias_grad(dy, want_bias=need_bias)
+    dw = weight_fn(dy16, splits) if need_weight else None
+    dx = data_fn(dy16) if need_input else None
+    return dx, dw, db
+
+
+def downsample_backward(dy, a16, weight, *, need_input=True, need_weight=True, need_bias=True, dx_add=None, splits=0):
+    """Backward of Downsample2D: y = conv(pad(a16, (0,1,0,1)), bf16(weight)) + bias, 3x3 stride 2.  dy: the fp32 gradient [B, H // 2, W // 2, Cout] (or
+    its bf16 copy when no bias gradient is asked for); a16 bf16 [B, H, W, Cin].  -> (dx or None, dW or None, dbias or None)"""
+    H, W = a16.shape[1], a16.shape[2]
+    return _resample_backward(lambda d: downsample_backward_data(d, weight, H, W, dx_add=dx_add), lambda d, sp: downsample_backward_weight(d, a16, splits=sp),
+                              dy, need_input, need_weight, need_bias, splits)
+
+
+def upsample_backward(dy, x16, weight, *, need_input=True, need_weight=True, need_bias=True, dx_add=None, splits=0):
+    """Backward of Upsample2D: y = conv3x3(nearest2x(x16), weight) + bias as vt_op_upsample2x_conv3x3 computes it.  dy: the fp32 gradient
+    [B, 2h, 2w, C] (or its bf16 copy when no bias gradient is asked for); x16 bf16 [B, h, w, C].  -> (dx or None, dW or None, dbias or None)"""
+    return _resample_backward(lambda d: upsample_backward_data(d, weight, dx_add=dx_add), lambda d, sp: upsample_backward_weight(d, x16, splits=sp),
+                              dy, need_input, need_weight, need_bias, splits)
+
+
+def downsample_forward(weight, bias, a16):
+    """Downsample2D on the forward operator: a16 bf16 [B, H, W, Cin] -> y fp32 [B, H // 2, W // 2, Cout]"""
+    a16, weight = _bf16(a16, "a16"), _f32(weight, "weight")
+    B, H, W, Cin = a16.shape
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, Cin, 3, 3) or H < 2 or W < 2:
+        raise ValueError("weight does not match a16, or a16 is smaller than 2 x 2")
+    w16 = weight.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
+    y = torch.empty(B, H // 2, W // 2, Cout, dtype=torch.float32, device=a16.device)
+    context(a16.device).call("vt_op_conv2d", _vp(a16), _vp(w16), _vp(bias), None, _vp(y), None, B, H, W, Cin, Cout, 3, 2, 0, 1, _stream(a16))
+    return y
+
+
+def upsample_forward(weight, bias, x16):
+    """Upsample2D on the forward operator: x16 bf16 [B, h, w, C] -> y fp32 [B, 2h, 2w, C]"""
+    x16, weight = _bf16(x16, "x16"), _f32(weight, "weight")
+    B, h, w, C = x16.shape
+    if tuple(weight.shape) != (C, C, 3, 3):
+        raise ValueError("weight does not match x16")
+    y = torch.empty(B, 2 * h, 2 * w, C, dtype=torch.float32, device=x16.device)
+    context(x16.device).call("vt_op_upsample2x_conv3x3", _vp(x16), _vp(weight), _vp(bias), _vp(y), B, h, w, C, _stream(x16))
+    return y
+
+
+# ---- a down block / an up block: resnets.0 .. resnets.N-1, then the optional resampling layer ---------------------------------------------------------
+
+DOWN_RESAMPLE, UP_RESAMPLE = "downsamplers.0.conv.", "upsamplers.0.conv."
+
+
+def _split_block(params, resample):
+    """-> ({"resnets.i.": its parameters} in order, the resampling layer's parameters or None)"""
+    parts, rs = {}, {}
+    for k, v in params.items():
+        if k.startswith(resample):
+            rs[k[len(resample):]] = v
+            continue
+        bits = k.split(".")
+        if len(bits) < 3 or bits[0] != "resnets" or not bits[1].isdigit():
+            raise ValueError(f"{k}: not a parameter of resnets.<i> or {resample[:-1]}")
+        parts.setdefault(f"resnets.{int(bits[1])}.", {})[".".join(bits[2:])] = v
+    n = len(parts)
+    if n == 0 or sorted(parts) != sorted(f"resnets.{i}." for i in range(n)):
+        raise ValueError("params must hold resnets.0 .. resnets.N-1")
+    if rs and sorted(rs) != ["bias", "weight"]:
+        raise ValueError(f"{resample}: expected weight and bias")
+    return {f"resnets.{i}.": parts[f"resnets.{i}."] for i in range(n)}, (rs or None)
+
+
+def _block_forward_train(params, x, resample, forward):
+    ctx = context(x.device)
+    ctx.call("vt_op_backward_operands_check")
+    parts, rs = _split_block(params, resample)
+    saved = {}
+    for p, q in parts.items():
+        x, saved[p] = resnet_block_forward_train(q, x)
+    if rs is not None:
+        x16 = x.to(torch.bfloat16)
+        saved[resample] = {"x16": x16}
+        x = forward(_f32(rs["weight"], "weight"), _f32(rs["bias"], "bias"), x16)
+    return x, saved
+
+
+def _block_backward(params, saved, dy, resample, backward, splits):
+    context(dy.device).call("vt_op_backward_operands_check")
+    parts, rs = _split_block(params, resample)
+    g = {}
+    if rs is not None:
+        dy, g[resample + "weight"], g[resample + "bias"] = backward(_f32(dy, "dy"), saved[resample]["x16"], rs["weight"], splits=splits)
+    for p in reversed(list(parts)):
+        dy, gp = resnet_block_backward(parts[p], saved[p], dy, splits=splits)
+        g.update({p + k: v for k, v in gp.items()})
+    return dy, {k: g[k] for k in params}
+
+
+def down_block_forward_train(params, x):
+    """DownEncoderBlock2D of the VAE: resnets.0 .. resnets.N-1, then downsamplers.0.conv where params holds it.  x fp32 NHWC.  -> (y fp32 NHWC, saved)"""
+    return _block_forward_train(params, _f32(x, "x"), DOWN_RESAMPLE, downsample_forward)
+
+
+def down_block_backward(params, saved, dy, *, splits=0):
+    """dy fp32 NHWC, the gradient of down_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params)"""
+    return _block_backward(params, saved, dy, DOWN_RESAMPLE, downsample_backward, splits)
+
+
+def up_block_forward_train(params, x):
+    """UpDecoderBlock2D of the VAE: resnets.0 .. resnets.N-1, then upsamplers.0.conv where params holds it.  x fp32 NHWC.  -> (y fp32 NHWC, saved)"""
+    return _block_forward_train(params, _f32(x, "x"), UP_RESAMPLE, upsample_forward)
+
+
+def up_block_backward(params, saved, dy, *, splits=0):
+    """dy fp32 NHWC, the gradient of up_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params)"""
+    return _block_backward(params, saved, dy, UP_RESAMPLE, upsample_backward, splits)
 
 
 # ---- the attention block -------------------------------------------------------------------------------------------------------------------------
