@@ -764,6 +764,33 @@ int vt_op_upsample2x_conv3x3_backward_data(vt_context* ctx, const void* dy16_nhw
 size_t vt_op_upsample2x_conv3x3_backward_weight_workspace_bytes(int B, int h, int w, int C, int splits);
 int vt_op_upsample2x_conv3x3_backward_weight(vt_context* ctx, const void* dy16_nhwc, const void* x16_nhwc, float* dw_f32_oihw, int B, int h, int w, int C,
                                              int splits, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- the two full-resolution end convs of the VAE, 3 channels on one side: encoder.conv_in 3 -> C, decoder.conv_out C -> 3.
+ *
+ * vt_op_conv_thin_backward_weight: their weight gradient, a [27 -> 32 rows] x Cw matrix with the pixel index as K.  `thin` is the 3-channel side,
+ * fp32 NCHW [B][3][H][W] (conv_in's image; conv_out's loss gradient); it enters the MFMA split, hi = bf16(v), lo = bf16(v - hi), two MFMAs per
+ * K-step into the same fp32 accumulators, so its side of every product is fp32-grade.  `wide` is bf16 NHWC [B][H][W][Cw].
+ *   thin_is_input = 1 (conv_in; wide = dy16):  dw[c][t][ky][kx] = sum_{b,y,x} wide[b][y][x][c] * thin[b][t][y+ky-1][x+kx-1], fp32 OIHW [Cw][3][3][3]
+ *   thin_is_input = 0 (conv_out; wide = a16, the conv's forward operand; thin = dy):
+ *                                               dw[t][c][ky][kx] = sum_{b,y,x} thin[b][t][y][x] * wide[b][y+ky-1][x+kx-1][c], fp32 OIHW [3][Cw][3][3]
+ * Taps outside the image count as 0.  thin_sums_out (optional) [3] = sum_{b,y,x} thin[b][t][y][x] (conv_out's bias gradient): fp64 partials per
+ * workgroup, finished in a fixed order.  The pixels are cut into `splits` slices (0: chosen from the shape so that the workgroups fill three slots on
+ * each of the 256 CUs; more than the number of pixel tiles: clamped); each slice writes an fp32 partial to the workspace, a second launch adds them
+ * in slice order.  No atomics, bit-identical from run to run; on exact data independent of `splits`.  Cw % 64 == 0, Cw <= 512, any B, H, W >= 1.  The
+ * workspace (16-byte aligned) must be sized with the same `splits`.  One stream, no host synchronisation; refused while flag 18 is on; a refused
+ * call writes nothing. */
+size_t vt_op_conv_thin_backward_weight_workspace_bytes(int B, int H, int W, int Cw, int splits);
+int vt_op_conv_thin_backward_weight(vt_context* ctx, const float* thin_nchw, const void* wide16_nhwc, int thin_is_input, float* dw_out,
+                                    float* thin_sums_out, int B, int H, int W, int Cw, int splits, void* workspace, size_t workspace_bytes, void* stream);
+/* vt_op_conv_thin_forward: vt_op_conv_in with the weights packed ON THE STREAM (no host copy, no synchronisation), then the same kernels: the
+ * matrix-core one when C == 128 and flag 5 is on, else the fp32 VALU one (C % 8 == 0, C <= 256).  x fp32 NCHW [B][3][H][W]; out_f32 and / or out_bf16 NHWC
+ * [B][H][W][C]; bias [C] or NULL (= 0).
+ *   transpose_rotate = 0: w is fp32 [C][3][3][3] -- conv_in's forward, bit-identical to vt_op_conv_in on the same weights.
+ *   transpose_rotate = 1: w is conv_out's own parameter [3][C][3][3]; the conv runs on W'[c][t][ky][kx] = w[t][c][2-ky][2-kx] with a zero bias
+ *     (`bias` is ignored) -- the DATA GRADIENT of conv_out: d image in, dx fp32 NHWC out, at conv_in's fp32-grade products.
+ * The workspace (16-byte aligned, vt_op_conv_thin_forward_workspace_bytes(C)) holds the packed weights and the zero bias.  Refused while flag 18 is on. */
+size_t vt_op_conv_thin_forward_workspace_bytes(int C);
+int vt_op_conv_thin_forward(vt_context* ctx, const float* x_nchw, const float* w, const float* bias, int transpose_rotate, float* out_f32,
+                            void* out_bf16, int B, int H, int W, int C, void* workspace, size_t workspace_bytes, void* stream);
 /* error while flag 18 (fp16 operands) is on: functions that mix these operators with the forward ones ask here first */
 int vt_op_backward_operands_check(vt_context* ctx);
 /* (mean, rstd) fp32 [B][groups][2] of an fp32 tensor [B][HW][C], from fp64 sums of x and x^2 taken in a fixed order (the forward's (scale, shift)

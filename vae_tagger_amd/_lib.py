@@ -184,6 +184,10 @@ PROTOTYPES = {
     "vt_op_upsample2x_conv3x3_backward_data": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "vt_op_upsample2x_conv3x3_backward_weight_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "vt_op_upsample2x_conv3x3_backward_weight": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "vt_op_conv_thin_backward_weight_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "vt_op_conv_thin_backward_weight": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "vt_op_conv_thin_forward_workspace_bytes": (_sz, [_i]),
+    "vt_op_conv_thin_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "vt_op_backward_operands_check": (_i, [_vp]),
     "vt_op_groupnorm_stats_workspace_bytes": (_sz, [_i, _i, _i]),
     "vt_op_groupnorm_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),

@@ -568,6 +568,70 @@ int vt_op_upsample2x_conv3x3_backward_weight(vt_context* c, const void* dy16, co
     return rs_wgrad(c, "vt_op_upsample2x_conv3x3_backward_weight", 2, dy16, x16, dw, B, 2 * h, 2 * w, h, w, C, C, splits, ws, ws_bytes, stream);
 }
 
+// ---- the full-resolution end convs, 3 channels on one side ----
+
+static int thin_wgrad_splits(int B, int H, int W, int Cw, int splits) {
+    const int steps = vt_conv_thin_wgrad_steps(B, H, W);
+    if (splits <= 0) return vt_conv_thin_wgrad_auto_splits(B, H, W, Cw);
+    return splits > steps ? steps : splits;
+}
+
+size_t vt_op_conv_thin_backward_weight_workspace_bytes(int B, int H, int W, int Cw, int splits) {
+    if (splits < 0 || !vt_conv_thin_wgrad_supported(Cw) || vt_conv_thin_wgrad_steps(B, H, W) <= 0) return 0;
+    return align_up(vt_conv_thin_wgrad_ws_bytes(Cw, thin_wgrad_splits(B, H, W, Cw, splits)));
+}
+
+int vt_op_conv_thin_backward_weight(vt_context* c, const float* thin, const void* wide16, int thin_is_input, float* dw, float* thin_sums, int B, int H, int W,
+                                    int Cw, int splits, void* ws, size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    VTCK(vt_op_backward_operands_check(c));
+    if (!thin || !wide16 || !dw) return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: null buffer");
+    if (!vt_conv_thin_wgrad_supported(Cw))
+        return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: Cw must be a multiple of 64, at most 512 (got %d)", Cw);
+    if (B <= 0 || H <= 0 || W <= 0 || vt_conv_thin_wgrad_steps(B, H, W) <= 0) return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: B, H, W must be >= 1");
+    if (splits < 0) return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: splits must be >= 0 (0 = chosen from the shape)");
+    const size_t need = vt_op_conv_thin_backward_weight_workspace_bytes(B, H, W, Cw, splits);
+    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
+        return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: workspace must be 16-byte aligned and hold "
+                       "vt_op_conv_thin_backward_weight_workspace_bytes = %zu bytes (got %zu)", need, ws_bytes);
+    ConvThinWgradArgs a{};
+    a.thin = thin; a.wide = (const bf16_t*)wide16; a.dw = dw; a.thin_sums = thin_sums; a.ws = ws; a.batch = B; a.H = H; a.W = W; a.Cw = Cw;
+    a.thin_is_input = thin_is_input; a.splits = thin_wgrad_splits(B, H, W, Cw, splits);
+    HIPCK(c, vt_launch_conv_thin_wgrad(a, (hipStream_t)stream), "vt_op_conv_thin_backward_weight");
+    return VT_OK;
+}
+
+// packed weights (the larger of the two layouts), then C zeros for the bias
+static size_t thin_forward_pack_bytes(int C) { return align_up(std::max((size_t)27 * C * sizeof(float), (size_t)2 * 128 * 32 * 2)); }
+
+size_t vt_op_conv_thin_forward_workspace_bytes(int C) {
+    if (C < 8 || (C % 8)) return 0;
+    return thin_forward_pack_bytes(C) + align_up((size_t)C * sizeof(float));
+}
+
+int vt_op_conv_thin_forward(vt_context* c, const float* x, const float* w, const float* bias, int transpose_rotate, float* o32, void* o16, int B, int H, int W,
+                            int C, void* ws, size_t ws_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    VTCK(vt_op_backward_operands_check(c));
+    if (!x || !w || (!o32 && !o16)) return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_forward: null buffer");
+    if (B <= 0 || H <= 0 || W <= 0 || C < 8 || (C % 8) || C > 256)
+        return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_forward: C must be a multiple of 8, at most 256, and B, H, W >= 1 (got %d, %d x %d x %d)", C, B, H, W);
+    const size_t need = vt_op_conv_thin_forward_workspace_bytes(C);
+    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
+        return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_forward: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const bool mfma = C == 128 && c->conv_in_mfma;
+    float* zero_bias = (float*)((char*)ws + thin_forward_pack_bytes(C));
+    if (transpose_rotate) bias = nullptr;
+    HIPCK(c, vt_launch_pack_conv_thin(w, bias, transpose_rotate != 0, mfma, ws, zero_bias, C, s), "pack_conv_thin");
+    const float* b = bias ? bias : zero_bias;
+    if (mfma) HIPCK(c, vt_launch_conv_in_mfma(x, (const bf16_t*)ws, b, o32, (bf16_t*)o16, nullptr, nullptr, nullptr, B, H, W, s), "vt_op_conv_thin_forward");
+    else HIPCK(c, vt_launch_conv_in(x, (const float*)ws, b, o32, (bf16_t*)o16, nullptr, nullptr, 0, nullptr, B, H, W, C, s), "vt_op_conv_thin_forward");
+    return VT_OK;
+}
+
 // The block functions (vae_backward.py) mix these operators with the forward ones, which follow flag 18: they ask here first.
 int vt_op_backward_operands_check(vt_context* c) {
     if (!c) return VT_ERR_INVALID;

@@ -454,6 +454,30 @@ int vt_conv_wgrad_steps(int B, int H, int W);
 int vt_conv_wgrad_auto_splits(int B, int H, int W, int Cin, int Cout);      // workgroups = splits * (Cin / 64) * (Cout / 64) <= 512: two per CU
 bool vt_conv_wgrad_supported(int Cin, int Cout, int ksize);
 hipError_t vt_launch_conv_wgrad(const ConvWgradArgs& a, hipStream_t s);
+// Weight gradient of a 3x3 pad-1 conv with 3 channels on one side (conv_thin_wgrad.hip): a [27 -> 32 rows] x Cw matrix with
+// the pixel index as K.  thin: fp32 NCHW [batch][3][H][W], split hi + lo on its way into the MFMA; wide: bf16 NHWC [batch][H][W][Cw].
+//   thin_is_input = 1 (conv_in):  dw[c][t][ky][kx] = sum wide[b][y][x][c] * thin[b][t][y + ky - 1][x + kx - 1], fp32 [Cw][3][3][3]
+//   thin_is_input = 0 (conv_out): dw[t][c][ky][kx] = sum wide[b][y][x][c] * thin[b][t][y + 1 - ky][x + 1 - kx], fp32 [3][Cw][3][3]
+// thin_sums (optional) [3] = sum of thin over (b, y, x), fp64 partials.  Cw % 64 == 0, Cw <= 512, 1 <= splits <= steps.
+struct ConvThinWgradArgs {
+    const float* thin;
+    const bf16_t* wide;
+    float* dw;
+    float* thin_sums;       // or null
+    void* ws;               // vt_conv_thin_wgrad_ws_bytes(Cw, splits)
+    int batch, H, W, Cw, thin_is_input, splits;
+    int tiles_x, tiles_y, steps;     // filled by the launcher
+};
+int vt_conv_thin_wgrad_steps(int B, int H, int W);
+int vt_conv_thin_wgrad_auto_splits(int B, int H, int W, int Cw);          // workgroups = splits * (Cw / 64) <= three per CU
+bool vt_conv_thin_wgrad_supported(int Cw);
+size_t vt_conv_thin_wgrad_ws_bytes(int Cw, int splits);
+hipError_t vt_launch_conv_thin_wgrad(const ConvThinWgradArgs& a, hipStream_t s);
+// conv_in's weight layouts written on the stream from fp32 weights on the device (what pack_conv_in / pack_conv_in_mfma write on the host).
+// rotate = 0: w is [C][3][3][3]; rotate = 1: w is conv_out's [3][C][3][3] and the packed conv is W'[c][t][ky][kx] = w[t][c][2 - ky][2 - kx].
+// mfma (C == 128): dst = [2][128][32] bf16 with the bias pieces (bias may be null = 0); else dst = [27][C] fp32.  zero_bias (optional): C zeros.
+hipError_t vt_launch_pack_conv_thin(const float* w, const float* bias, int rotate, int mfma, void* dst, float* zero_bias, int C, hipStream_t s);
+
 // fp32 OIHW (device) -> bf16 [Cin][tap'][Cout] with tap' = taps - 1 - tap: the weights of the forward conv that IS the data gradient
 // (rotated by 180 degrees, transposed in (co, ci)); ksize 1 or 3
 hipError_t vt_launch_pack_dgrad_weights(const float* w_oihw, bf16_t* dst, int Cin, int Cout, int ksize, hipStream_t s);

@@ -1,11 +1,17 @@
 """Backward of the VAE's blocks -- ResnetBlock2D (the block both VAE models consist of), the mid attention block, the two resampling layers
-(Downsample2D's stride-2 conv and Upsample2D), and their compositions: the mid block, a down block and an up block -- on the device: thin wrappers
-over the vt_op_* backward operators (include/vae_tagger_hip.h, DESIGN.md sections 4.19, 4.20 and 4.22).  Tensors are torch tensors of one HIP device,
+(Downsample2D's stride-2 conv and Upsample2D), the four end convs, and their compositions: the mid block, a down block, an up block and the two whole
+models (encoder_forward_train / encoder_backward: d moments -> the gradients of every encoder tensor; decoder_forward_train / decoder_backward: d image ->
+the gradients of every decoder tensor and d z) -- on the device: thin wrappers over the vt_op_* backward operators (include/vae_tagger_hip.h, DESIGN.md
+sections 4.19, 4.20, 4.22 and 4.23).  Tensors are torch tensors of one HIP device,
 activations NHWC ([B, H, W, C]), parameters in diffusers' own layouts (conv weights fp32 OIHW).  All gradients are fp32; every MFMA operand is bf16.
 Every launch goes to torch's current stream of the tensors' device and nothing here synchronises with the host.  There is no eager fallback: a shape
 an operator refuses raises VTError.
 
-This is NOT train_vae: there is no optimiser, no loss, no CLI, no backward of conv_in and conv_out and no whole-model backward here.
+The whole-model functions work in NCHW at their ends (the image, the moments, the latents) and in NHWC inside; encoder_saved_bytes / decoder_saved_bytes
+say what a batch keeps between forward and backward before anything is allocated.
+
+This is NOT train_vae: there is no optimiser, no loss gradient (MSE / KL / triplet), no backward of posterior.sample, no joining of encoder and decoder
+and no CLI here; the image's own gradient is not computed.
 """
 import ctypes
 
@@ -196,8 +202,9 @@ def resnet_block_forward_train(params, x):
     return y, saved
 
 
-def resnet_block_backward(params, saved, dy, *, splits=0):
-    """dy fp32 NHWC, the gradient of resnet_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params)"""
+def resnet_block_backward(params, saved, dy, *, splits=0, want_dx16=False):
+    """dy fp32 NHWC, the gradient of resnet_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params); with want_dx16 norm1's pass also
+    writes bf16(dx) and the result is (dx, grads, dx16)."""
     dy = _f32(dy, "dy")
     ctx = context(dy.device)
     ctx.call("vt_op_backward_operands_check")
@@ -224,8 +231,10 @@ def resnet_block_backward(params, saved, dy, *, splits=0):
     else:
         dxs = dy
     # 6. norm1 + SiLU, the shortcut's gradient added in the same pass
-    dx, _, g["norm1.weight"], g["norm1.bias"] = groupnorm_silu_backward(saved["x"], saved["stats1"], params["norm1.weight"], params["norm1.bias"], da1, dx_add=dxs)
-    return dx, {k: g[k] for k in params}
+    dx, dx16, g["norm1.weight"], g["norm1.bias"] = groupnorm_silu_backward(saved["x"], saved["stats1"], params["norm1.weight"], params["norm1.bias"], da1, dx_add=dxs,
+                                                                              want_dx16=want_dx16)
+    g = {k: g[k] for k in params}
+    return (dx, g, dx16) if want_dx16 else (dx, g)
 
 
 # ---- the resampling layers: Downsample2D's stride-2 conv and Upsample2D -----------------------------------------------------
@@ -375,16 +384,21 @@ def _block_forward_train(params, x, resample, forward):
     return x, saved
 
 
-def _block_backward(params, saved, dy, resample, backward, splits):
+def _block_backward(params, saved, dy, resample, backward, splits, want_dx16=False):
     context(dy.device).call("vt_op_backward_operands_check")
     parts, rs = _split_block(params, resample)
     g = {}
     if rs is not None:
         dy, g[resample + "weight"], g[resample + "bias"] = backward(_f32(dy, "dy"), saved[resample]["x16"], rs["weight"], splits=splits)
+    dx16 = None
     for p in reversed(list(parts)):
-        dy, gp = resnet_block_backward(parts[p], saved[p], dy, splits=splits)
+        if want_dx16 and p == "resnets.0.":
+            dy, gp, dx16 = resnet_block_backward(parts[p], saved[p], dy, splits=splits, want_dx16=True)
+        else:
+            dy, gp = resnet_block_backward(parts[p], saved[p], dy, splits=splits)
         g.update({p + k: v for k, v in gp.items()})
-    return dy, {k: g[k] for k in params}
+    g = {k: g[k] for k in params}
+    return (dy, g, dx16) if want_dx16 else (dy, g)
 
 
 def down_block_forward_train(params, x):
@@ -392,9 +406,10 @@ def down_block_forward_train(params, x):
     return _block_forward_train(params, _f32(x, "x"), DOWN_RESAMPLE, downsample_forward)
 
 
-def down_block_backward(params, saved, dy, *, splits=0):
-    """dy fp32 NHWC, the gradient of down_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params)"""
-    return _block_backward(params, saved, dy, DOWN_RESAMPLE, downsample_backward, splits)
+def down_block_backward(params, saved, dy, *, splits=0, want_dx16=False):
+    """dy fp32 NHWC, the gradient of down_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params); with want_dx16 also bf16(dx), as
+    resnet_block_backward writes it."""
+    return _block_backward(params, saved, dy, DOWN_RESAMPLE, downsample_backward, splits, want_dx16)
 
 
 def up_block_forward_train(params, x):
@@ -553,3 +568,299 @@ def mid_block_backward(params, saved, dy, *, splits=0):
         dy, gp = bwd(parts[p], saved[p], dy, splits=splits)
         g.update({p + k: v for k, v in gp.items()})
     return dy, {k: g[k] for k in params}
+
+
+# ---- the end convs ---------------------------------------------------------------------------------------------------------
+# Full resolution, 3 channels on one side (encoder.conv_in, decoder.conv_out): vt_op_conv_thin_backward_weight / vt_op_conv_thin_forward.
+# Latent resolution (encoder.conv_out 512 -> 32, decoder.conv_in 16 -> 512): the existing operators, the short side zero-padded to 64 channels here.
+
+WGRAD_C = 64                      # vt_op_conv_backward_weight's channel tile: the short side of a latent-resolution end is padded to it
+
+
+def _nchw3(t, what):
+    if _f32(t, what).dim() != 4 or t.shape[1] != 3:
+        raise ValueError(f"{what}: expected fp32 NCHW [B, 3, H, W]")
+    return t
+
+
+def conv_thin_backward_weight(thin_nchw, wide16, thin_is_input, *, want_sums=False, splits=0):
+    """The thin-side weight gradient.  thin fp32 NCHW [B, 3, H, W], wide16 bf16 NHWC [B, H, W, Cw].  -> (dW fp32 [Cw, 3, 3, 3] (thin_is_input) or
+    [3, Cw, 3, 3], the thin side's channel sums [3] or None)"""
+    thin, wide16 = _nchw3(thin_nchw, "thin"), _bf16(wide16, "wide16")
+    B, _, H, W = thin.shape
+    Cw = wide16.shape[-1]
+    if tuple(wide16.shape[:3]) != (B, H, W):
+        raise ValueError("wide16 does not match thin")
+    ctx = context(thin.device)
+    dw = torch.empty((Cw, 3, 3, 3) if thin_is_input else (3, Cw, 3, 3), dtype=torch.float32, device=thin.device)
+    sums = torch.empty(3, dtype=torch.float32, device=thin.device) if want_sums else None
+    ws = _workspace(ctx.lib.vt_op_conv_thin_backward_weight_workspace_bytes(B, H, W, Cw, int(splits)), thin.device)
+    ctx.call("vt_op_conv_thin_backward_weight", _vp(thin), _vp(wide16), int(bool(thin_is_input)), _vp(dw), _vp(sums), B, H, W, Cw, int(splits), _vp(ws), ws.numel(),
+             _stream(thin))
+    return dw, sums
+
+
+def conv_thin_forward(x_nchw, weight, bias=None, *, transpose_rotate=False, want_f32=True, want_bf16=False):
+    """The 3 -> C conv on conv_in's kernels, weights packed on the stream.  x fp32 NCHW [B, 3, H, W]; weight fp32 [C, 3, 3, 3], or with transpose_rotate
+    conv_out's [3, C, 3, 3] (then this is conv_out's data gradient, and bias is ignored).  -> (fp32 NHWC [B, H, W, C] or None, its bf16 form or None)"""
+    x, weight = _nchw3(x_nchw, "x"), _f32(weight, "weight")
+    B, _, H, W = x.shape
+    C = weight.shape[1] if transpose_rotate else weight.shape[0]
+    if tuple(weight.shape) != ((3, C, 3, 3) if transpose_rotate else (C, 3, 3, 3)):
+        raise ValueError("weight must be [C, 3, 3, 3], or [3, C, 3, 3] with transpose_rotate")
+    if bias is not None and tuple(_f32(bias, "bias").shape) != (C,):
+        raise ValueError("bias must be [C]")
+    ctx = context(x.device)
+    o32 = torch.empty(B, H, W, C, dtype=torch.float32, device=x.device) if want_f32 else None
+    o16 = torch.empty(B, H, W, C, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
+    ws = _workspace(ctx.lib.vt_op_conv_thin_forward_workspace_bytes(C), x.device)
+    ctx.call("vt_op_conv_thin_forward", _vp(x), _vp(weight), _vp(bias), int(bool(transpose_rotate)), _vp(o32), _vp(o16), B, H, W, C, _vp(ws), ws.numel(), _stream(x))
+    return o32, o16
+
+
+def conv_in_backward(dy, x_nchw, *, need_weight=True, need_bias=True, splits=0, dy16=None):
+    """Backward of encoder.conv_in, y = conv(x, W) + b with x the fp32 NCHW image.  dy: the fp32 gradient NHWC [B, H, W, C], or its bf16 copy when no bias
+    gradient is asked for; dy16 (optional): the bf16 copy a producer already wrote beside the fp32 dy.  -> (dW [C, 3, 3, 3], db); the image's own gradient
+    is not offered."""
+    if dy.dtype == torch.bfloat16:
+        if need_bias:
+            raise ValueError("the bias gradient needs the fp32 dy")
+        dy16, db = dy, None
+    else:
+        want16 = need_weight and dy16 is None
+        c16, db = cast_bias_grad(dy, want_dy16=want16, want_bias=need_bias) if (want16 or need_bias) else (None, None)
+        dy16 = c16 if dy16 is None else dy16
+    dw = conv_thin_backward_weight(x_nchw, dy16, True, splits=splits)[0] if need_weight else None
+    return dw, db
+
+
+def conv_out_backward(d_image_nchw, a16, weight, *, need_input=True, need_weight=True, need_bias=True, splits=0):
+    """Backward of decoder.conv_out, image = conv(a16, W) + b with W [3, C, 3, 3].  d_image fp32 NCHW [B, 3, H, W]; a16 bf16 NHWC [B, H, W, C], the conv's
+    forward operand.  -> (dx fp32 NHWC [B, H, W, C] or None, dW or None, db [3] or None)"""
+    dx = conv_thin_forward(d_image_nchw, weight, transpose_rotate=True)[0] if need_input else None
+    dw, db = None, None
+    if need_weight or need_bias:
+        dw, db = conv_thin_backward_weight(d_image_nchw, a16, False, want_sums=need_bias, splits=splits)
+    return dx, (dw if need_weight else None), db
+
+
+def _pad_channels(t16, C):
+    return t16 if t16.shape[-1] == C else torch.nn.functional.pad(t16, (0, C - t16.shape[-1]))
+
+
+def latent_conv_out_backward(dy, a16, weight, *, splits=0):
+    """Backward of encoder.conv_out (C -> 2L at latent resolution, 2L < 64): dy fp32 NHWC [B, h, w, 2L].  The weight gradient runs on dy16 zero-padded
+    to 64 channels and is sliced.  -> (dx fp32 NHWC, dW, db)"""
+    dy16, db = cast_bias_grad(dy)
+    n = dy16.shape[-1]
+    dw = conv_backward_weight(_pad_channels(dy16, -(-n // WGRAD_C) * WGRAD_C), a16, 3, splits=splits)[:n].contiguous()
+    return conv_backward_data(dy16, weight), dw, db
+
+
+def latent_conv_in_backward(dy, z16, weight, *, splits=0):
+    """Backward of decoder.conv_in (L -> C at latent resolution, L < 64): dy fp32 NHWC [B, h, w, C]; z16 the staged latents, bf16 NHWC zero-padded to
+    64 channels.  -> (dz fp32 NHWC [B, h, w, L], dW, db)"""
+    dy16, db = cast_bias_grad(dy)
+    L = weight.shape[1]
+    dw = conv_backward_weight(dy16, z16, 3, splits=splits)[:, :L].contiguous()
+    return conv_backward_data(dy16, weight), dw, db
+
+
+# ---- the whole models ---------------------------------------------------------------------------------------------------------------------------------
+
+ENDS = ("conv_in.", "conv_norm_out.", "conv_out.")
+
+
+def _split_model(params, prefix, blocks):
+    """params under `prefix` ("encoder." / "decoder.") -> ({"conv_in.": {weight, bias}, ...}, [block i's parameters], the mid block's)"""
+    ends, blk, mid = {e: {} for e in ENDS}, {}, {}
+    for k, v in params.items():
+        r = k[len(prefix):] if k.startswith(prefix) else None
+        bits = r.split(".", 2) if r else []
+        if r and r.startswith("mid_block."):
+            mid[r[len("mid_block."):]] = v
+        elif len(bits) == 3 and bits[0] == blocks and bits[1].isdigit():
+            blk.setdefault(int(bits[1]), {})[bits[2]] = v
+        elif r and any(r in (e + "weight", e + "bias") for e in ENDS):
+            ends[bits[0] + "."][bits[1]] = v
+        else:
+            raise ValueError(f"{k}: not a parameter of {prefix}conv_in, {blocks}.<i>, mid_block, conv_norm_out or conv_out")
+    if not blk or sorted(blk) != list(range(len(blk))):
+        raise ValueError(f"params must hold {prefix}{blocks}.0 .. {blocks}.N-1")
+    for e in ENDS:
+        if sorted(ends[e]) != ["bias", "weight"]:
+            raise ValueError(f"{prefix}{e[:-1]}: expected weight and bias")
+    return ends, [blk[i] for i in range(len(blk))], mid
+
+
+def _shape(v):
+    return tuple(v.shape) if hasattr(v, "shape") else tuple(v)
+
+
+def model_structure(params, prefix):
+    """The block structure read from the key names (values: tensors or shapes): {"blocks": [{"resnets": [(cin, cout), ...], "resample": bool}, ...],
+    "mid": C, "conv_in": (cout, cin), "conv_out": (cout, cin)}"""
+    blocks = "down_blocks" if prefix == "encoder." else "up_blocks"
+    ends, blks, mid = _split_model(params, prefix, blocks)
+    _split_mid(mid)
+    out = []
+    for q in blks:
+        parts, rs = _split_block(q, DOWN_RESAMPLE if prefix == "encoder." else UP_RESAMPLE)
+        out.append({"resnets": [(_shape(r["conv1.weight"])[1], _shape(r["conv1.weight"])[0]) for r in parts.values()], "resample": rs is not None})
+    return {"blocks": out, "mid": _shape(mid["resnets.0.conv1.weight"])[0], "conv_in": _shape(ends["conv_in."]["weight"])[:2],
+            "conv_out": _shape(ends["conv_out."]["weight"])[:2]}
+
+
+def _norm_out_forward(ctx, ends, x):
+    n = ends["conv_norm_out."]
+    return {"x": x, "stats": groupnorm_stats(x), "a16": _norm_silu(ctx, x, _f32(n["weight"], "conv_norm_out.weight"), _f32(n["bias"], "conv_norm_out.bias"))}
+
+
+def _norm_out_backward(ends, saved, da, g, prefix):
+    n = ends["conv_norm_out."]
+    dx, _, g[prefix + "conv_norm_out.weight"], g[prefix + "conv_norm_out.bias"] = groupnorm_silu_backward(saved["x"], saved["stats"], n["weight"], n["bias"], da)
+    return dx
+
+
+def encoder_forward_train(params, x_nchw):
+    """The VAE encoder (conv_in, the down blocks, the mid block, conv_norm_out + SiLU, conv_out) on caller-owned fp32 parameters under diffusers' names
+    (`encoder.*`, synth.encoder_manifest), keeping what the backward needs.  x fp32 NCHW [B, 3, H, W].  -> (moments fp32 NCHW [B, 2L, h, w], saved)"""
+    x = _nchw3(x_nchw, "x")
+    ctx = context(x.device)
+    ctx.call("vt_op_backward_operands_check")
+    ends, blks, mid = _split_model(params, "encoder.", "down_blocks")
+    saved = {"x": x}
+    h = conv_thin_forward(x, ends["conv_in."]["weight"], ends["conv_in."]["bias"])[0]
+    for i, q in enumerate(blks):
+        h, saved[f"down_blocks.{i}."] = down_block_forward_train(q, h)
+    h, saved["mid_block."] = mid_block_forward_train(mid, h)
+    saved["conv_norm_out."] = _norm_out_forward(ctx, ends, h)
+    y = _conv(ctx, saved["conv_norm_out."]["a16"], _f32(ends["conv_out."]["weight"], "conv_out.weight"), _f32(ends["conv_out."]["bias"], "conv_out.bias"))
+    return y.permute(0, 3, 1, 2).contiguous(), saved
+
+
+def encoder_backward(params, saved, d_moments, *, splits=0, boundaries=None):
+    """d_moments fp32 NCHW, the gradient of encoder_forward_train's moments.  -> grads: fp32, keyed and ordered like params.  boundaries (optional dict)
+    receives the gradient (fp32 NHWC) of every stage's input: "conv_norm_out", "mid_block", "down_blocks.<i>" (tools/vae_backward_boundaries.py)."""
+    at = boundaries if boundaries is not None else {}
+    d = _f32(d_moments, "d_moments")
+    context(d.device).call("vt_op_backward_operands_check")
+    ends, blks, mid = _split_model(params, "encoder.", "down_blocks")
+    g = {}
+    dy = d.permute(0, 2, 3, 1).contiguous()
+    dy, g["encoder.conv_out.weight"], g["encoder.conv_out.bias"] = latent_conv_out_backward(dy, saved["conv_norm_out."]["a16"], ends["conv_out."]["weight"], splits=splits)
+    at["conv_norm_out"] = dy = _norm_out_backward(ends, saved["conv_norm_out."], dy, g, "encoder.")
+    dy, gp = mid_block_backward(mid, saved["mid_block."], dy, splits=splits)
+    at["mid_block"] = dy
+    g.update({"encoder.mid_block." + k: v for k, v in gp.items()})
+    dy16 = None
+    for i in reversed(range(len(blks))):
+        if i == 0:          # conv_in's weight gradient takes the bf16 copy norm1's pass writes: no cast pass at full resolution
+            dy, gp, dy16 = down_block_backward(blks[i], saved[f"down_blocks.{i}."], dy, splits=splits, want_dx16=True)
+        else:
+            dy, gp = down_block_backward(blks[i], saved[f"down_blocks.{i}."], dy, splits=splits)
+        g.update({f"encoder.down_blocks.{i}." + k: v for k, v in gp.items()})
+        at[f"down_blocks.{i}"] = dy
+    g["encoder.conv_in.weight"], g["encoder.conv_in.bias"] = conv_in_backward(dy, saved["x"], splits=splits, dy16=dy16)
+    return {k: g[k] for k in params}
+
+
+def decoder_forward_train(params, z_nchw):
+    """The VAE's image decoder (conv_in, the mid block, the up blocks, conv_norm_out + SiLU, conv_out) on caller-owned fp32 parameters under diffusers'
+    names (`decoder.*`, synth.image_decoder_manifest).  z fp32 NCHW [B, L, h, w], L <= 64.  -> (image fp32 NCHW [B, 3, H, W], saved).  conv_in runs on
+    the latents staged as bf16 NHWC, zero-padded to 64 channels (the inference decoder pads to 32: the same sums); conv_out on vt_op_conv2d with its 3
+    couts zero-padded to 32, as the inference decoder's."""
+    z = _f32(z_nchw, "z")
+    ctx = context(z.device)
+    ctx.call("vt_op_backward_operands_check")
+    ends, blks, mid = _split_model(params, "decoder.", "up_blocks")
+    w_in, w_out = _f32(ends["conv_in."]["weight"], "conv_in.weight"), _f32(ends["conv_out."]["weight"], "conv_out.weight")
+    L, nout = w_in.shape[1], w_out.shape[0]
+    if z.dim() != 4 or z.shape[1] != L or L > WGRAD_C or nout != 3:
+        raise ValueError(f"z must be NCHW with conv_in's {L} <= {WGRAD_C} channels, and conv_out must have 3 output channels")
+    z16 = _pad_channels(z.permute(0, 2, 3, 1).to(torch.bfloat16), WGRAD_C).contiguous()
+    saved = {"z16": z16}
+    h = _conv(ctx, z16, torch.nn.functional.pad(w_in, (0, 0, 0, 0, 0, WGRAD_C - L)), _f32(ends["conv_in."]["bias"], "conv_in.bias"))
+    h, saved["mid_block."] = mid_block_forward_train(mid, h)
+    for i, q in enumerate(blks):
+        h, saved[f"up_blocks.{i}."] = up_block_forward_train(q, h)
+    saved["conv_norm_out."] = _norm_out_forward(ctx, ends, h)
+    y = _conv(ctx, saved["conv_norm_out."]["a16"], torch.nn.functional.pad(w_out, (0, 0, 0, 0, 0, 0, 0, 32 - nout)),
+              torch.nn.functional.pad(_f32(ends["conv_out."]["bias"], "conv_out.bias"), (0, 32 - nout)))
+    return y[..., :nout].permute(0, 3, 1, 2).contiguous(), saved
+
+
+def decoder_backward(params, saved, d_image, *, splits=0, boundaries=None):
+    """d_image fp32 NCHW [B, 3, H, W], the gradient of decoder_forward_train's image.  -> (dz fp32 NCHW [B, L, h, w], grads keyed and ordered like params).
+    boundaries (optional dict) receives the gradient (fp32 NHWC) of every stage's input: "conv_norm_out", "up_blocks.<i>", "mid_block"."""
+    at = boundaries if boundaries is not None else {}
+    d = _nchw3(d_image, "d_image")
+    context(d.device).call("vt_op_backward_operands_check")
+    ends, blks, mid = _split_model(params, "decoder.", "up_blocks")
+    g = {}
+    dy, g["decoder.conv_out.weight"], g["decoder.conv_out.bias"] = conv_out_backward(d, saved["conv_norm_out."]["a16"], ends["conv_out."]["weight"], splits=splits)
+    at["conv_norm_out"] = dy = _norm_out_backward(ends, saved["conv_norm_out."], dy, g, "decoder.")
+    for i in reversed(range(len(blks))):
+        dy, gp = up_block_backward(blks[i], saved[f"up_blocks.{i}."], dy, splits=splits)
+        at[f"up_blocks.{i}"] = dy
+        g.update({f"decoder.up_blocks.{i}." + k: v for k, v in gp.items()})
+    dy, gp = mid_block_backward(mid, saved["mid_block."], dy, splits=splits)
+    at["mid_block"] = dy
+    g.update({"decoder.mid_block." + k: v for k, v in gp.items()})
+    dz, g["decoder.conv_in.weight"], g["decoder.conv_in.bias"] = latent_conv_in_backward(dy, saved["z16"], ends["conv_in."]["weight"], splits=splits)
+    return dz.permute(0, 3, 1, 2).contiguous(), {k: g[k] for k in params}
+
+
+# ---- what a batch keeps between forward and backward: pure-Python formulas, exactly the bytes of the `saved` structures ---------------------------------
+
+def attention_vt_pitch(S):
+    """vt_op_attention_vt_pitch in Python: S rounded up to 8, moved off the pitches that are multiples of 2 KB"""
+    ld = (S + 7) // 8 * 8
+    return ld + 2048 + 64 if (ld * 2) % 2048 == 0 else ld
+
+
+def _resnet_saved_bytes(P, B, ci, co):
+    return P * (ci * 4 + co * 4 + ci * 2 + co * 2) + 2 * B * GROUPS * 2 * 4 + (P * ci * 2 if ci != co else 0)
+
+
+def _mid_saved_bytes(B, S, C):
+    P = B * S
+    attn = P * C * (4 + 2 + 4 + 2 + 4) + B * C * attention_vt_pitch(S) * 2 + P * 4 + 4 * P * 4 + B * GROUPS * 2 * 4     # x, h16, qk16, o16, o; vT16; shift; sums; stats
+    return 2 * _resnet_saved_bytes(P, B, C, C) + attn
+
+
+def _structure_of(params_or_config, prefix):
+    if "block_out" in params_or_config or "layers_per_block" in params_or_config:
+        from . import synth
+        params_or_config = (synth.encoder_manifest if prefix == "encoder." else synth.image_decoder_manifest)(**params_or_config)
+    return model_structure(params_or_config, prefix)
+
+
+def _blocks_saved_bytes(st, B, h, w, up):
+    n = 0
+    for blk in st["blocks"]:
+        for ci, co in blk["resnets"]:
+            n += _resnet_saved_bytes(B * h * w, B, ci, co)
+        if blk["resample"]:
+            n += B * h * w * blk["resnets"][-1][1] * 2                    # the resampling layer's bf16 operand
+            h, w = (2 * h, 2 * w) if up else (h // 2, w // 2)
+    return n, h, w
+
+
+def encoder_saved_bytes(params_or_config, B, H, W):
+    """Bytes encoder_forward_train's `saved` holds for a [B, 3, H, W] batch (the image included).  params_or_config: the parameters (tensors or
+    shapes under `encoder.*`) or the keywords of synth.encoder_manifest."""
+    st = _structure_of(params_or_config, "encoder.")
+    n, h, w = _blocks_saved_bytes(st, B, H, W, False)
+    C = st["mid"]
+    return B * 3 * H * W * 4 + n + _mid_saved_bytes(B, h * w, C) + B * h * w * C * (4 + 2) + B * GROUPS * 2 * 4
+
+
+def decoder_saved_bytes(params_or_config, B, h, w):
+    """Bytes decoder_forward_train's `saved` holds for [B, L, h, w] latents.  params_or_config as in encoder_saved_bytes (`decoder.*`,
+    synth.image_decoder_manifest)."""
+    st = _structure_of(params_or_config, "decoder.")
+    C = st["mid"]
+    n = B * h * w * WGRAD_C * 2 + _mid_saved_bytes(B, h * w, C)
+    m, H, W = _blocks_saved_bytes(st, B, h, w, True)
+    return n + m + B * H * W * st["blocks"][-1]["resnets"][-1][1] * (4 + 2) + B * GROUPS * 2 * 4
