@@ -601,7 +601,7 @@ int vt_decode_image(vt_context* ctx, const float* z_nchw, int B, int h, int w, i
  * alone (partials per 4096 elements, added in index order by a second launch): bit-identical from run to run.
  *
  * vt_posterior_sample: moments fp32 NCHW [B][2C][hw] (mean | logvar, vt_encode mode 0); logvar is clamped to [-30, 20].
- *   z_out (fp32 [B][C][hw], may be NULL) = mean + std eps with std = fp32(exp(0.5 logvar)) and one fp32 multiply and one fp32 add;
+ *   z_out (fp32 [B][C][hw], may be NULL) = mean + std eps with std = fp32(exp(0.5 logvar)), as ONE fused fp32 multiply-add fma(std, eps, mean): a single rounding;
  *   kl_out (fp64 [B], may be NULL) = 0.5 sum(mean^2 + var - 1 - logvar).  eps is a counter-based standard normal keyed on
  *   (seed, draw) and (first_image + b, element index within the image): two 64-bit words of vt_head_mix64, u1 = ((x1 >> 11) + 1) 2^-53
  *   in (0, 1], u2 = (x2 >> 11) 2^-53, eps = fp32(sqrt(-2 ln u1) cos(2 pi u2)) evaluated in fp64.  An image's noise depends on its
@@ -637,6 +637,40 @@ int vt_vae_loss_update(vt_context* ctx, void* state, size_t state_bytes, const v
                        const void* labels_a, const void* labels_p, int labels_dtype /* VT_F32 | VT_U8 */, int N, int B, int C, int hw,
                        long long first_image, double* rows_out /* [B][VT_VAE_LOSS_ROW] or NULL */, void* stream);
 int vt_vae_loss_read(vt_context* ctx, const void* state, size_t state_bytes, void* out, size_t out_bytes, void* stream);
+
+/* ---- gradient of the VAE's training loss <- one step of train_vae.py:131-179:
+ *   total = w_rec mse_loss(recon, target) + w_kl log(1 + kl_mean / 10000) + w_tri ImprovedTripletLoss(z_a, z_p, z_n, labels_a, labels_p)
+ * with kl_mean the batch mean of (kl_a + kl_p + kl_n) / 3 and the triplet term the batch mean of the weighted hinge, cosine or euclidean
+ * (`similarity`).  --use_simplified_vae_loss is w_kl = 0.  The contrastive term has no gradient here: a call without a negative stream is
+ * refused.  Self-contained: it reads and writes no vt_vae_loss_* state block, recomputes the per-image sums with the forward's own device
+ * functions, and regenerates every eps from the counter (seed, draw, first_image + b, element): anchor / positive / negative give
+ * `moments` (fp32 NCHW [B][2C][hw]) and `draw`, and `z` must be NULL.  Same discipline as the forward: sizes checked on the host before
+ * anything is launched (VT_ERR_WORKSPACE for a small workspace, VT_ERR_INVALID for a null / misaligned pointer, an out-of-range shape, a
+ * missing negative, a non-finite weight or margin; nothing is written), one stream, no host synchronisation, no atomics, fp64 arithmetic
+ * from the fp32 inputs with one rounding at the store, bit-identical from run to run.
+ *   dz_dec (fp32 [B][C][hw] or NULL): the gradient of the latent the image was decoded from, sampled from the ANCHOR's moments with draw
+ *     `dz_draw`; it is added to the anchor's d mean and, under that draw's eps, to its d logvar.
+ *   recon, target fp32 [B][3][H][W], both or neither (then the reconstruction term is 0); labels as vt_vae_loss_update takes them.
+ * Outputs, each may be NULL:
+ *   d_recon fp32 [B][3][H][W] = w_rec 2 (recon - target) / (B 3HW);
+ *   d_moments_a / _p / _n fp32 [B][2C][hw]: d mean = g + c_kl mean, d logvar = in_clamp (0.5 sum_draws g std eps + c_kl 0.5 (var - 1)) with
+ *     g the element's d total / d z (the triplet term; for the anchor's decode draw, dz_dec), c_kl = w_kl / (3 B 10000 (1 + kl_mean / 10000)),
+ *     std = fp32(exp(0.5 logvar)) as the forward rounds it, var = exp(0.5 logvar)^2 in fp64, and in_clamp = 1 for -30 <= logvar <= 20
+ *     (inclusive, as torch.clamp's backward), else 0.  The hinge has derivative 0 at 0;
+ *   rows_out fp64 [B][VT_VAE_LOSS_ROW]: vt_vae_loss_update's columns with margin_triplet = margin, the same bits; the contrastive
+ *     columns 12 and 13 are 0;
+ *   loss_out fp64 [4]: reconstruction, kl (log1p of the batch's kl_mean / 10000), triplet (of `similarity`) and total, each batch sum
+ *     taken one image after the other.
+ * workspace: 256-B aligned, vt_vae_loss_backward_workspace_bytes(B, C, hw, H, W) bytes (0: shape out of range; H = W = 0: no image). */
+#define VT_VAE_COSINE 0
+#define VT_VAE_EUCLIDEAN 1
+size_t vt_vae_loss_backward_workspace_bytes(int B, int C, int hw, int H, int W);
+int vt_vae_loss_backward(vt_context* ctx, const vt_vae_loss_input* anchor, const vt_vae_loss_input* positive, const vt_vae_loss_input* negative,
+                         const float* dz_dec /* or NULL */, int dz_draw, const float* recon, const float* target, int H, int W,
+                         const void* labels_a, const void* labels_p, int labels_dtype /* VT_F32 | VT_U8 */, int N, int B, int C, int hw,
+                         unsigned long long seed, long long first_image, double w_rec, double w_kl, double w_tri, double margin,
+                         int similarity /* VT_VAE_COSINE | VT_VAE_EUCLIDEAN */, float* d_recon, float* d_moments_a, float* d_moments_p,
+                         float* d_moments_n, double* rows_out, double* loss_out /* [4] */, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- single operators (parity tests drive each kernel through the same ABI) ------------------
  * NHWC bf16 activations, weights in the reference's own layouts (fp32 host order is converted by

@@ -6,9 +6,12 @@
 (b) conv_out's data gradient (vt_op_conv_thin_forward, transpose_rotate) beside torch.nn.grad.conv2d_input on bf16 tensors.
 (c) encoder_backward and decoder_backward of the FLUX configuration on synth weights at the given image sides, beside torch autograd's backward of the
     same model under bf16 autocast; torch.cuda.max_memory_allocated of a forward + backward beside encoder_saved_bytes / decoder_saved_bytes.
+(d) --joined: vae_loss_and_grads (one step of train_vae: three encodes, the anchor's decode, the loss, all 244 gradients) at
+    batch 1, beside the reference-shaped torch step -- three encodes, sample, one decode, the loss, backward() -- under bf16 autocast, with the peak
+    allocated memory of both and vae_train_saved_bytes.  With --joined only (d) runs.
 Everything is warmed first and timed in interleaved rounds; the figures are medians over the rounds.
 
-Usage: python tools/bench_vae_backward.py [--rounds 5] [--iters 3] [--side 1024] [--model-sides 512,1024] [--skip-torch] [--skip-models] [--out FILE]
+Usage: python tools/bench_vae_backward.py [--rounds 5] [--iters 3] [--side 1024] [--model-sides 512,1024] [--skip-torch] [--skip-models] [--joined] [--out FILE]
 Prints text lines and, last, one JSON line (also written to --out)."""
 import argparse
 import json
@@ -208,6 +211,50 @@ def bench_model(kind, side, rounds, iters, with_torch):
     return rec
 
 
+def t_step(q, a, pos, neg, weights, margin=1.0):
+    """the reference's training step in torch: encode three times, sample, decode the anchor's latent, CombinedLoss without labels"""
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        moments = [t_encoder(q, x).float() for x in (a, pos, neg)]
+    mean, lv = zip(*((m[:, :16], torch.clamp(m[:, 16:], -30.0, 20.0)) for m in moments))
+    z = [mu + torch.exp(0.5 * l) * torch.randn_like(mu) for mu, l in zip(mean, lv)]
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        recon = t_decoder(q, mean[0] + torch.exp(0.5 * lv[0]) * torch.randn_like(mean[0])).float()
+    kl = [0.5 * torch.sum(mu * mu + torch.exp(l) - 1.0 - l, dim=(1, 2, 3)) for mu, l in zip(mean, lv)]
+    za, zp, zn = (F.normalize(t.flatten(1), p=2, dim=1) for t in z)
+    trip = F.relu((1 - (za * zp).sum(1)) - (1 - (za * zn).sum(1)) + margin).mean()
+    return (weights["reconstruction"] * F.mse_loss(recon, a) + weights["kl"] * torch.log(1 + ((kl[0] + kl[1] + kl[2]) / 3).mean() / 10000)
+            + weights["triplet"] * trip)
+
+
+def bench_joined(side, rounds, iters, with_torch):
+    p = {k: v.to(DEV) for k, v in synth.synth_state_dict({**synth.encoder_manifest(), **synth.image_decoder_manifest()}, seed=5).items()}
+    a, pos, neg = (synth.synth_images(1, side, side, seed=s).to(DEV) for s in (6, 7, 8))
+    weights = {"reconstruction": 0.01, "kl": 1e-2, "triplet": 1.0}
+    ours = lambda: vb.vae_loss_and_grads(p, a, pos, neg, weights=weights)  # noqa: E731
+    rec = {"side": side, "saved_bytes": int(vb.vae_train_saved_bytes(p, 1, side, side)), "peak_allocated": int(peak_of(ours))}
+    calls = {"vae_loss_and_grads": ours}
+    print(f"joined step @ {side}^2: saved {rec['saved_bytes'] / 2 ** 20:.0f} MiB, peak {rec['peak_allocated'] / 2 ** 20:.0f} MiB; torch's step next", flush=True)
+    if with_torch:
+        try:
+            q = {k: v.clone().requires_grad_(True) for k, v in p.items()}
+            leaves = list(q.values())
+            t_call = lambda: torch.autograd.grad(t_step(q, a, pos, neg, weights), leaves)  # noqa: E731
+            rec["torch_peak_allocated"] = int(peak_of(t_call))
+            print(f"joined step @ {side}^2: torch's first step done, peak {rec['torch_peak_allocated'] / 2 ** 20:.0f} MiB; timing next", flush=True)
+            calls["torch_step_bf16_autocast"] = t_call
+        except Exception as e:  # noqa: BLE001
+            calls.pop("torch_step_bf16_autocast", None)
+            rec["note"] = f"torch step not measured: {type(e).__name__}: {e}"
+    ms = interleaved(calls, rounds, iters)
+    rec["ms"] = {k: round(v, 3) for k, v in ms.items()}
+    if "torch_step_bf16_autocast" in ms:
+        rec["step_over_torch"] = round(ms["vae_loss_and_grads"] / ms["torch_step_bf16_autocast"], 3)
+    print(f"joined step @ {side}^2: " + "  ".join(f"{k} {v:.2f} ms" for k, v in ms.items()) + f"  saved {rec['saved_bytes'] / 2 ** 20:.0f} MiB, peak "
+          f"{rec['peak_allocated'] / 2 ** 20:.0f} MiB" + (f", torch peak {rec['torch_peak_allocated'] / 2 ** 20:.0f} MiB" if "torch_peak_allocated" in rec else ""),
+          flush=True)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -216,10 +263,23 @@ def main():
     ap.add_argument("--model-sides", default="512,1024")
     ap.add_argument("--skip-torch", action="store_true")
     ap.add_argument("--skip-models", action="store_true")
+    ap.add_argument("--joined", action="store_true", help="only the joined train step, (d)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_vae_backward needs a HIP device")
+    if a.joined:
+        res = {"tool": "bench_vae_backward --joined", "batch": 1, "rounds": a.rounds, "iters": a.iters, "device": torch.cuda.get_device_name(0), "joined": []}
+        for side in [int(s) for s in a.model_sides.split(",") if s]:
+            res["joined"].append(bench_joined(side, a.rounds, a.iters, not a.skip_torch))
+            torch.cuda.empty_cache()
+        line = json.dumps(res)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     res = {"tool": "bench_vae_backward", "batch": 1, "rounds": a.rounds, "iters": a.iters, "device": torch.cuda.get_device_name(0),
            "thin": bench_thin(a.side, a.rounds, a.iters, not a.skip_torch), "models": []}
     torch.cuda.empty_cache()

@@ -2,12 +2,14 @@
 
     python tools/bench_vae_loss.py                  # vt_posterior_sample, vt_vae_loss_update in flight and given z
     python tools/bench_vae_loss.py --cli --n 32     # evaluate_vae's images/s against three encodes + one decode on resident batches
+    python tools/bench_vae_loss.py --backward       # vt_vae_loss_backward: the image pass, the latent pass and the whole call
 
 Each call is event-timed next to (a) the torch-eager sequence the reference's classes would run on the same device tensors (randn + the
 element-wise chain of sample(), kl(), F.mse_loss, F.normalize / pairwise_distance and the hinge) and (b) a torch device-to-device copy of
 the bytes the call reads (the copy also writes them: 2 x the traffic), interleaved --reps times in one process; one JSON line per
 measurement with the median and the best milliseconds.  --cli writes --n generated PNGs, runs the CLI's pass in this process and then the
-bare encode / decode loop on batches that stay in HBM."""
+bare encode / decode loop on batches that stay in HBM.  --backward times the loss's gradient beside (a) a torch copy that moves the bytes the
+call reads PLUS writes (a copy of half of them: it reads and writes each) and (b) torch eager autograd of the same loss on fp32 tensors."""
 import argparse
 import json
 import os
@@ -107,6 +109,56 @@ def bench_kernels(args):
         print(json.dumps(out), flush=True)
 
 
+def bench_backward(args):
+    from vae_tagger_amd.vae_losses import backward_workspace_bytes, loss_backward_device
+    B, C, h, res = args.batch, 16, args.res // 8, args.res
+    g = torch.Generator().manual_seed(0)
+    moments = [torch.randn(B, 2 * C, h, h, generator=g).cuda() for _ in range(3)]
+    recon, target = (torch.rand(B, 3, res, res, generator=g).cuda() * 2 - 1 for _ in range(2))
+    dz = (torch.randn(B, C, h, h, generator=g) * 1e-3).cuda()
+    la, lp = ((torch.rand(B, args.tags, generator=g) < 0.02).float().cuda() for _ in range(2))
+    ctx = _lib.Context(0)
+    d_recon, d_moments = torch.empty_like(recon), torch.empty(3 * B, 2 * C, h, h, device="cuda")
+    dm = [d_moments[i * B:(i + 1) * B] for i in range(3)]
+    loss_out = torch.empty(4, dtype=torch.float64, device="cuda")
+    ws = torch.empty(backward_workspace_bytes(B, C, h * h, res, res) + 256, dtype=torch.uint8, device="cuda")
+    weights = {"reconstruction": 0.01, "kl": 1e-2, "triplet": 1.0}
+    ins = [(m, k + 1) for k, m in enumerate(moments)]
+    common = dict(weights=weights, workspace=ws, context=ctx)
+    nbytes = lambda ts: sum(t.numel() * t.element_size() for t in ts)
+    image_bytes = nbytes([recon, target, d_recon])                      # read recon, target; write d_recon
+    latent_bytes = nbytes(moments + [dz, d_moments])                    # read the moments and dz_dec once; write the three d_moments
+    copies = {k: (torch.empty(n // 2, dtype=torch.uint8, device="cuda"), torch.empty(n // 2, dtype=torch.uint8, device="cuda"))
+              for k, n in (("image", image_bytes), ("latent", latent_bytes), ("both", image_bytes + latent_bytes))}
+    q = [m.clone().requires_grad_(True) for m in moments]
+    qr = recon.clone().requires_grad_(True)
+
+    def eager():
+        mse, kl, trip = eager_loss(q, qr, target, la, lp)
+        total = weights["reconstruction"] * mse + weights["kl"] * kl + weights["triplet"] * trip
+        return torch.autograd.grad(total, q + [qr])
+    groups = {
+        "backward_image_pass": ({"device": lambda: loss_backward_device(*ins, recon=recon, target=target, d_recon=d_recon, **common),
+                                 "copy_of_bytes_read_and_written": lambda: copies["image"][1].copy_(copies["image"][0])}, image_bytes),
+        "backward_latent_pass": ({"device": lambda: loss_backward_device(*ins, dz_dec=dz, labels_a=la, labels_p=lp, d_moments=dm, loss_out=loss_out, **common),
+                                  "copy_of_bytes_read_and_written": lambda: copies["latent"][1].copy_(copies["latent"][0])}, latent_bytes),
+        "backward_whole_call": ({"device": lambda: loss_backward_device(*ins, dz_dec=dz, recon=recon, target=target, labels_a=la, labels_p=lp,
+                                                                        d_recon=d_recon, d_moments=dm, loss_out=loss_out, **common),
+                                 "copy_of_bytes_read_and_written": lambda: copies["both"][1].copy_(copies["both"][0]), "eager_autograd_fp32": eager},
+                                image_bytes + latent_bytes),
+    }
+    for name, (fns, n) in groups.items():
+        r = timed(fns, args.reps)
+        out = {"measurement": name, "batch": B, "res": res, "mb_read_and_written": round(n / 1e6, 1), "reps": args.reps}
+        for k, (med, best) in r.items():
+            out[k + "_ms_median"], out[k + "_ms_best"] = round(med, 4), round(best, 4)
+        out["device_gb_per_s"] = round(n / 1e9 / (r["device"][0] / 1e3), 1)
+        out["device_over_copy"] = round(r["device"][0] / r["copy_of_bytes_read_and_written"][0], 2)
+        if "eager_autograd_fp32" in r:
+            out["device_over_eager"] = round(r["device"][0] / r["eager_autograd_fp32"][0], 3)
+        print(json.dumps(out), flush=True)
+
+
 def bench_cli(args):
     from PIL import Image
     from vae_tagger_amd import evaluate_vae
@@ -172,8 +224,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--cli", action="store_true")
     ap.add_argument("--n", type=int, default=32)
+    ap.add_argument("--backward", action="store_true")
     args = ap.parse_args()
-    (bench_cli if args.cli else bench_kernels)(args)
+    (bench_cli if args.cli else bench_backward if args.backward else bench_kernels)(args)
 
 
 if __name__ == "__main__":

@@ -44,6 +44,7 @@ class VAELossInput(_c.Structure):
 
 
 VAE_LOSS_ROW, VAE_LOSS_HEAD_BYTES = 19, 512              # VT_VAE_LOSS_ROW, VT_VAE_LOSS_HEAD_BYTES
+VAE_COSINE, VAE_EUCLIDEAN = 0, 1                         # VT_VAE_COSINE, VT_VAE_EUCLIDEAN
 
 
 # name -> (restype, argtypes); every symbol include/vae_tagger_hip.h declares
@@ -151,6 +152,10 @@ PROTOTYPES = {
     "vt_vae_loss_update": (_i, [_vp, _vp, _sz, _c.POINTER(VAELossInput), _c.POINTER(VAELossInput), _c.POINTER(VAELossInput), _vp, _vp, _i, _i,
                                 _vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _vp]),
     "vt_vae_loss_read": (_i, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    "vt_vae_loss_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "vt_vae_loss_backward": (_i, [_vp, _c.POINTER(VAELossInput), _c.POINTER(VAELossInput), _c.POINTER(VAELossInput), _vp, _i, _vp, _vp, _i, _i,
+                                  _vp, _vp, _i, _i, _i, _i, _i, _c.c_ulonglong, _ll, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _i,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vt_encoder_flops":(_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),

@@ -15,134 +15,13 @@ using namespace vt;
 
 namespace {
 
-constexpr int VL_T = 256;                   // threads of a partial's workgroup
-constexpr int VL_STEP = 4 * VL_T;           // elements one sweep of the workgroup covers
-constexpr int VL_SWEEPS = VT_VAE_CHUNK / VL_STEP;
 constexpr int VL_KL_T = 1024;               // vt_posterior_sample's kl_out: one workgroup per image
-
-struct VaeStream { const float* moments; const float* z; int draw; int present; };
-struct VaeLatentArg { VaeStream s[3]; };
-
-__device__ __forceinline__ bool vl_bad(float x) { return !(fabsf(x) <= 3.0e38f); }
-
-// the element's standard normal: Box-Muller in fp64 on two words of the image key, rounded to fp32 once
-__device__ __forceinline__ float vae_eps(uint64_t image_key, uint64_t e) {
-#pragma clang fp contract(off)
-    const uint64_t x1 = vt_head_mix64(image_key ^ (2 * e)), x2 = vt_head_mix64(image_key ^ (2 * e + 1));
-    const double u1 = (double)((x1 >> 11) + 1) * 0x1p-53, u2 = (double)(x2 >> 11) * 0x1p-53;
-    return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
-}
-
-// z = mean + fp32(exp(0.5 logvar)) eps in explicit fp32 steps, and the element's KL term mean^2 + var - 1 - logvar (var = std^2, fp64).
-// A NaN logvar stays NaN through the clamp, as torch.clamp keeps it.
-__device__ __forceinline__ float vae_z(float mean, float logvar, float eps, double& kl_term) {
-#pragma clang fp contract(off)
-    const float lc = logvar < -30.0f ? -30.0f : (logvar > 20.0f ? 20.0f : logvar);
-    const double sd = exp(0.5 * (double)lc);
-    kl_term = (double)mean * (double)mean + sd * sd - 1.0 - (double)lc;
-    return __fadd_rn(mean, __fmul_rn((float)sd, eps));
-}
-
-// four consecutive floats from e0 (a multiple of 4): one 16-byte load, or guarded scalar loads with the same element-to-thread mapping
-template <bool VEC>
-__device__ __forceinline__ void vl_load4(const float* __restrict__ p, long long e0, long long n, float out[4]) {
-    if (VEC) {
-        const float4 v = *(const float4*)(p + e0);
-        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) out[k] = e0 + k < n ? p[e0 + k] : 0.0f;
-    }
-}
-
-// the workgroup's NV running sums -> partial[0 .. NV-1] and the non-finite count -> partial[NV] (as uint64): wave tree, then waves in order
-template <int NV>
-__device__ __forceinline__ void vl_block_fold(double (&acc)[NV], unsigned bad, double* __restrict__ partial) {
-#pragma clang fp contract(off)
-    __shared__ double s_red[VL_T / 64][NV];
-    __shared__ unsigned s_bad[VL_T / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-        for (int d = 32; d > 0; d >>= 1) acc[i] += __shfl_down(acc[i], d);
-    for (int d = 32; d > 0; d >>= 1) bad += __shfl_down(bad, d);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) s_red[wave][i] = acc[i];
-        s_bad[wave] = bad;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        double v = s_red[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < VL_T / 64; ++w) v += s_red[w][threadIdx.x];
-        partial[threadIdx.x] = v;
-    } else if (threadIdx.x == NV) {
-        unsigned long long b = 0;
-#pragma unroll
-        for (int w = 0; w < VL_T / 64; ++w) b += s_bad[w];
-        ((unsigned long long*)partial)[NV] = b;
-    }
-}
 
 // grid (chunks of D, B).  partial: aa pp nn ap an dap dan kl_a kl_p kl_n | non-finite
 template <bool VEC>
 __global__ __launch_bounds__(VL_T) void vae_latent_kernel(VaeLatentArg a, const double* __restrict__ params, long long D, long long first_image,
                                                           long long chunks, double* __restrict__ partials) {
-#pragma clang fp contract(off)
-    const long long b = blockIdx.y, chunk = blockIdx.x;
-    const unsigned long long seed = ((const unsigned long long*)params)[3];
-    uint64_t key[3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) key[s] = vt_vae_image_key(vt_vae_stream_key(seed, (uint64_t)(int64_t)a.s[s].draw), (uint64_t)(first_image + b));
-    const bool has_n = a.s[2].present != 0;
-    double acc[10];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) acc[i] = 0.0;
-    unsigned bad = 0;
-    for (int j = 0; j < VL_SWEEPS; ++j) {
-        const long long e0 = chunk * VT_VAE_CHUNK + (long long)j * VL_STEP + 4 * (long long)threadIdx.x;
-        if (e0 >= D) break;
-        float z[3][4];
-        double kt[3][4];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { z[s][k] = 0.0f; kt[s][k] = 0.0; }
-            if (!a.s[s].present) continue;
-            float mean[4], lv[4];
-            if (a.s[s].moments) {
-                const float* m = a.s[s].moments + 2 * b * D;
-                vl_load4<VEC>(m, e0, D, mean);
-                vl_load4<VEC>(m + D, e0, D, lv);
-            }
-            if (a.s[s].z) vl_load4<VEC>(a.s[s].z + b * D, e0, D, z[s]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (e0 + k >= D) continue;
-                if (a.s[s].moments) {
-                    const float eps = a.s[s].z ? 0.0f : vae_eps(key[s], (uint64_t)(e0 + k));
-                    const float zs = vae_z(mean[k], lv[k], eps, kt[s][k]);
-                    if (!a.s[s].z) z[s][k] = zs;
-                    bad += (vl_bad(mean[k]) ? 1u : 0u) + (vl_bad(lv[k]) ? 1u : 0u);
-                }
-                bad += vl_bad(z[s][k]) ? 1u : 0u;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (e0 + k >= D) continue;
-            const double va = (double)z[0][k], vp = (double)z[1][k], vn = (double)z[2][k];
-            const double dp = va - vp + 1e-6;
-            acc[0] += va * va; acc[1] += vp * vp; acc[3] += va * vp; acc[5] += dp * dp;
-            if (has_n) {
-                const double dn = va - vn + 1e-6;
-                acc[2] += vn * vn; acc[4] += va * vn; acc[6] += dn * dn;
-            }
-            acc[7] += kt[0][k]; acc[8] += kt[1][k]; acc[9] += kt[2][k];
-        }
-    }
-    vl_block_fold<10>(acc, bad, partials + VT_VAE_LAT_PART * (b * chunks + chunk));
+    vl_latent_partials<VEC>(a, ((const unsigned long long*)params)[3], D, first_image, chunks, partials);
 }
 
 // grid (chunks of E, B).  partial: sum (recon - target)^2 | non-finite
@@ -170,24 +49,6 @@ __global__ __launch_bounds__(VL_T) void vae_image_kernel(const float* __restrict
     vl_block_fold<1>(acc, bad, partials + VT_VAE_IMG_PART * (b * chunks + chunk));
 }
 
-__device__ __forceinline__ double vl_label(const float* p, long long i) { return (double)p[i]; }
-__device__ __forceinline__ double vl_label(const unsigned char* p, long long i) { return p[i] ? 1.0 : 0.0; }
-// F.relu / torch.clamp(min=0): a NaN stays a NaN
-__device__ __forceinline__ double vl_relu(double x) { return x <= 0.0 ? 0.0 : x; }
-__device__ __forceinline__ double vl_wave_sum(double v) {
-#pragma clang fp contract(off)
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;
-}
-__device__ __forceinline__ double vl_contrastive(double dist, double sim, double thr, double margin) {
-#pragma clang fp contract(off)
-    const double similar = sim > thr ? 1.0 : 0.0;
-    const double gap = vl_relu(margin - dist);
-    return (similar * (dist * dist) + (1.0 - similar) * (gap * gap)) * (sim > thr ? sim : 1.0 - sim);
-}
-
-struct VaeRowArg { int has_kl[3]; int has_n, has_recon, has_labels; };
-
 // grid B, one wave: an image's partials in index order and its labels -> the image's row
 template <typename L>
 __global__ __launch_bounds__(64) void vae_row_kernel(VaeRowArg f, const double* __restrict__ params, const double* __restrict__ lat, long long lat_chunks,
@@ -195,57 +56,12 @@ __global__ __launch_bounds__(64) void vae_row_kernel(VaeRowArg f, const double* 
                                                      const L* __restrict__ labels_p, int N, double* __restrict__ rows, double* __restrict__ rows_out,
                                                      unsigned long long* __restrict__ bad_out) {
 #pragma clang fp contract(off)
-    const int l = threadIdx.x;
     const long long b = blockIdx.x;
-    double v[10];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) v[i] = 0.0;
-    unsigned long long bad = 0;
-    for (long long i = l; i < lat_chunks; i += 64) {
-        const double* p = lat + VT_VAE_LAT_PART * (b * lat_chunks + i);
-#pragma unroll
-        for (int k = 0; k < 10; ++k) v[k] += p[k];
-        bad += ((const unsigned long long*)p)[10];
-    }
-    double se = 0.0;
-    if (f.has_recon)
-        for (long long i = l; i < img_chunks; i += 64) {
-            const double* p = img + VT_VAE_IMG_PART * (b * img_chunks + i);
-            se += p[0];
-            bad += ((const unsigned long long*)p)[1];
-        }
-    double sa = 0.0, ov = 0.0, un = 0.0;
-    if (f.has_labels)
-        for (int j = l; j < N; j += 64) {
-            const double ya = vl_label(labels_a, b * N + j), yp = vl_label(labels_p, b * N + j);
-            sa += ya; ov += ya * yp; un += ya + yp - ya * yp;
-        }
-#pragma unroll
-    for (int k = 0; k < 10; ++k) v[k] = vl_wave_sum(v[k]);
-    se = vl_wave_sum(se); sa = vl_wave_sum(sa); ov = vl_wave_sum(ov); un = vl_wave_sum(un);
-    for (int d = 32; d > 0; d >>= 1) bad += __shfl_down(bad, d);
-    if (l != 0) return;
-    const double mt = params[0], mc = params[1], thr = params[2];
-    double r[VT_VAE_LOSS_ROW];
-    r[0] = f.has_recon ? se / (double)E : 0.0;
-    r[1] = f.has_kl[0] ? 0.5 * v[7] : 0.0;
-    r[2] = f.has_kl[1] ? 0.5 * v[8] : 0.0;
-    r[3] = f.has_kl[2] ? 0.5 * v[9] : 0.0;
-    const int nk = f.has_kl[0] + f.has_kl[1] + f.has_kl[2];
-    r[4] = nk ? (r[1] + r[2] + r[3]) / (double)nk : 0.0;
-    r[5] = log1p(r[4] / 10000.0);
-    const double na = fmax(sqrt(v[0]), 1e-12), np = fmax(sqrt(v[1]), 1e-12), nn = fmax(sqrt(v[2]), 1e-12);
-    r[6] = 1.0 - v[3] / (na * np);
-    r[7] = f.has_n ? 1.0 - v[4] / (na * nn) : 0.0;
-    r[8] = sqrt(v[5]);
-    r[9] = f.has_n ? sqrt(v[6]) : 0.0;
-    const double w = f.has_labels ? 1.0 + 0.5 * (ov / (sa + 1e-8)) : 1.0;
-    const double sim = ov / (un + 1e-8);
-    r[10] = f.has_n ? vl_relu(r[6] - r[7] + mt) * w : 0.0;
-    r[11] = f.has_n ? vl_relu(r[8] - r[9] + mt) * w : 0.0;
-    r[12] = vl_contrastive(r[6], sim, thr, mc);
-    r[13] = vl_contrastive(r[8], sim, thr, mc);
-    r[14] = sa; r[15] = ov; r[16] = un; r[17] = w; r[18] = sim;
+    double v[10], w[4], r[VT_VAE_LOSS_ROW];
+    unsigned long long bad;
+    vl_row_sums(f, (int)threadIdx.x, b, lat, lat_chunks, img, img_chunks, labels_a, labels_p, N, v, w, bad);
+    if (threadIdx.x != 0) return;
+    vl_row_values(f, params[0], params[1], params[2], E, v, w, r);
 #pragma unroll
     for (int k = 0; k < VT_VAE_LOSS_ROW; ++k) {
         rows[VT_VAE_LOSS_ROW * b + k] = r[k];
@@ -336,11 +152,6 @@ __global__ __launch_bounds__(VL_KL_T) void vae_kl_kernel(const float* __restrict
     }
 }
 
-bool vl_misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-bool vl_shape_ok(int B, int C, int hw) {
-    return B >= 1 && B <= VT_EVAL_MAX_B && C >= 1 && hw >= 1 && (long long)C * hw <= VT_VAE_MAX_D;
-}
-bool vl_image_ok(int H, int W) { return H >= 1 && W >= 1 && 3ll * H * W <= VT_VAE_MAX_D; }
 int vl_check_state(vt_context* c, const char* who, const void* state, size_t state_bytes, size_t need) {
     if (!state || vl_misaligned(state, ALIGN)) return c->fail(VT_ERR_INVALID, "%s: state is null or not 256-B aligned", who);
     if (state_bytes < need) return c->fail(VT_ERR_WORKSPACE, "%s: state holds %zu bytes, %zu needed", who, state_bytes, need);

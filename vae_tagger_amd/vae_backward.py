@@ -10,8 +10,11 @@ an operator refuses raises VTError.
 The whole-model functions work in NCHW at their ends (the image, the moments, the latents) and in NHWC inside; encoder_saved_bytes / decoder_saved_bytes
 say what a batch keeps between forward and backward before anything is allocated.
 
-This is NOT train_vae: there is no optimiser, no loss gradient (MSE / KL / triplet), no backward of posterior.sample, no joining of encoder and decoder
-and no CLI here; the image's own gradient is not computed.
+vae_loss_and_grads joins them into one step of train_vae.py: the three encodes, the anchor's decode, the loss (vt_vae_loss_backward: MSE, KL, triplet
+and the backward of posterior.sample) and the gradients of all encoder and decoder tensors.
+
+This is NOT train_vae: there is no optimiser, no gradient clipping, no checkpoint and no CLI here; the contrastive term and AdaptiveLossWeights have no
+gradient; the image's own gradient is not computed.
 """
 import ctypes
 
@@ -864,3 +867,77 @@ def decoder_saved_bytes(params_or_config, B, h, w):
     n = B * h * w * WGRAD_C * 2 + _mid_saved_bytes(B, h * w, C)
     m, H, W = _blocks_saved_bytes(st, B, h, w, True)
     return n + m + B * H * W * st["blocks"][-1]["resnets"][-1][1] * (4 + 2) + B * GROUPS * 2 * 4
+
+
+# ---- one step of train_vae: the three encodes, the anchor's decode, the loss and all 244 gradients --------------------------------------
+
+DECODE_DRAW, TRIPLET_DRAWS = 0, (1, 2, 3)       # evaluate_vae's convention: the decoded latent is draw 0, the triplet's latents draws 1, 2, 3
+
+
+def vae_loss_and_grads(params, anchor, positive, negative, labels_a=None, labels_p=None, *, weights, margin=1.0, similarity_type="cosine", seed=0,
+                       first_image=0, splits=0, saved=None, boundaries=None):
+    """The training loss of train_vae.py (lines 131-179 of the reference; vae_losses.loss_backward_device) on one batch and its gradient in every
+    parameter.  params: all `encoder.*` and `decoder.*` tensors (fp32, diffusers' names); anchor / positive / negative fp32 NCHW [B, 3, H, W]; labels
+    [B, N] fp32 or uint8 / bool, or None; weights: {"reconstruction", "kl", "triplet"} (the simplified loss is kl = 0).
+    -> (losses, grads): losses {"reconstruction", "kl", "triplet", "total"}, 0-d float64 device tensors (no synchronisation); grads fp32, keyed and
+    ordered like params.  One encoder pass on the 3B images [a; p; n] (GroupNorm is per image: the reference's three calls), the anchor's latent
+    (draw 0) decoded, nothing decoded from the positive or the negative, no scaling or shift factor -- as the reference's VAE wrapper.
+    saved (optional dict) receives what the step keeps between its forward and its backward: "encoder", "decoder", "moments", "z", "recon"
+    (vae_train_saved_bytes); boundaries (optional dict) the two models' own, under "decoder" and "encoder", and "dz" (fp32 NCHW)."""
+    from . import vae_losses
+    a = _nchw3(anchor, "anchor")
+    ctx = context(a.device)
+    ctx.call("vt_op_backward_operands_check")
+    if negative is None:
+        raise ValueError("a negative stream is required: the contrastive term has no gradient here")
+    if positive.shape != a.shape or negative.shape != a.shape:
+        raise ValueError("anchor, positive and negative are [B, 3, H, W] tensors of one shape")
+    enc = {k: v for k, v in params.items() if k.startswith("encoder.")}
+    dec = {k: v for k, v in params.items() if k.startswith("decoder.")}
+    if len(enc) + len(dec) != len(params) or not enc or not dec:
+        raise ValueError("params holds the encoder.* and the decoder.* tensors and nothing else")
+    B = a.shape[0]
+    moments, saved_e = encoder_forward_train(enc, torch.cat([a, _nchw3(positive, "positive"), _nchw3(negative, "negative")]))
+    L, h, w = moments.shape[1] // 2, moments.shape[2], moments.shape[3]
+    z = torch.empty(B, L, h, w, dtype=torch.float32, device=a.device)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctx.call("vt_posterior_sample", _vp(moments), B, L, h * w, seed, DECODE_DRAW, int(first_image), _vp(z), None, _stream(z))
+    recon, saved_d = decoder_forward_train(dec, z)
+    if recon.shape != a.shape:
+        raise ValueError(f"the decoder gives {tuple(recon.shape)} images for {tuple(a.shape)} inputs: the two models' resampling levels differ")
+    if saved is not None:
+        saved.update({"encoder": saved_e, "decoder": saved_d, "moments": moments, "z": z, "recon": recon})
+    streams = [(moments[i * B:(i + 1) * B], d) for i, d in enumerate(TRIPLET_DRAWS)]
+    common = dict(weights=weights, margin=margin, similarity_type=similarity_type, seed=seed, first_image=first_image, recon=recon, target=a, context=ctx)
+    d_recon = torch.empty_like(recon)
+    vae_losses.loss_backward_device(*streams, d_recon=d_recon, **common)
+    at = boundaries if boundaries is not None else {}
+    at["decoder"], at["encoder"] = {}, {}
+    at["dz"], g = decoder_backward(dec, saved_d, d_recon, splits=splits, boundaries=at["decoder"])
+    dz = at["dz"]
+    d_moments = torch.empty_like(moments)
+    loss_out = torch.empty(4, dtype=torch.float64, device=a.device)
+    vae_losses.loss_backward_device(*streams, dz_dec=dz, dz_draw=DECODE_DRAW, labels_a=labels_a, labels_p=labels_p,
+                                    d_moments=[d_moments[i * B:(i + 1) * B] for i in range(3)], loss_out=loss_out, **common)
+    g.update(encoder_backward(enc, saved_e, d_moments, splits=splits, boundaries=at["encoder"]))
+    return dict(zip(vae_losses.LOSS_NAMES, loss_out.unbind())), {k: g[k] for k in params}
+
+
+def vae_train_saved_bytes(params_or_config, B, H, W):
+    """Bytes vae_loss_and_grads keeps between its forward and its backward for a [B, 3, H, W] batch: the encoder's `saved` at 3B images, the decoder's at
+    B latents, and its own moments (3B), decoded latent and reconstruction.  params_or_config: the parameters (tensors or shapes) or the keywords
+    synth.encoder_manifest and synth.image_decoder_manifest share; an empty dict is those manifests' defaults, the FLUX configuration."""
+    if not params_or_config:
+        from . import synth
+        params_or_config = {**synth.encoder_manifest(), **synth.image_decoder_manifest()}
+    st = _structure_of(_only(params_or_config, "encoder."), "encoder.")
+    levels = sum(1 for blk in st["blocks"] if blk["resample"])
+    h, w, L = H >> levels, W >> levels, st["conv_out"][0] // 2
+    own = (3 * B * 2 * L * h * w + B * L * h * w + B * 3 * H * W) * 4
+    return encoder_saved_bytes(_only(params_or_config, "encoder."), 3 * B, H, W) + decoder_saved_bytes(_only(params_or_config, "decoder."), B, h, w) + own
+
+
+def _only(params_or_config, prefix):
+    if "block_out" in params_or_config or "layers_per_block" in params_or_config:
+        return params_or_config
+    return {k: v for k, v in params_or_config.items() if k.startswith(prefix)}

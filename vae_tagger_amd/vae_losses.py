@@ -1,6 +1,6 @@
 """Validation loss of the VAE: the number train_vae.py keeps `best_vae` by (train_vae.py:216-268; train_full.py:290-338) --
 reconstruction MSE, KL of the three posteriors, the triplet loss on sampled latents (and the contrastive term) -- accumulated batch by
-batch.  Forward only.
+batch -- and the gradient of the training loss, the same formulas differentiated (loss_backward_host / loss_backward_device).
 
 Host side: HostVAELossState, a numpy fp64 model of the device block fed the same way (from improved_losses' mirrors), the block's
 layout, and finish_state, the report.  Device side: DeviceVAELossAccumulator over vt_vae_loss_* of the C ABI; nothing is read back per
@@ -308,3 +308,202 @@ class DeviceVAELossAccumulator:
 
     def read(self, weights, similarity_type="cosine", simplified=False):
         return finish_state(self.read_state(), weights, similarity_type, simplified)
+
+
+# ---- the gradient of the training loss (vt_vae_loss_backward) --------------------------------------------------------------
+LOSS_NAMES = ("reconstruction", "kl", "triplet", "total")      # loss_out
+
+
+def _stream(item):
+    """(moments, draw) or update()'s (moments, None, draw) -> (moments, draw): the gradient samples in flight and takes no stored z"""
+    if len(item) == 3:
+        if item[1] is not None:
+            raise ValueError("the loss's gradient regenerates z from the counter and takes no stored z")
+        item = (item[0], item[2])
+    if item[0] is None:
+        raise ValueError("a stream needs its moments")
+    return item[0], int(item[1])
+
+
+def _weights(weights):
+    w = tuple(float(weights.get(k, 0.0)) for k in ("reconstruction", "kl", "triplet"))
+    if not all(np.isfinite(w)):
+        raise ValueError("the weights must be finite")
+    return w
+
+
+def backward_workspace_bytes(B, C, hw, H=0, W=0):
+    """vt_vae_loss_backward_workspace_bytes in host arithmetic: the forward's scratch, a coefficient record per image, one for the batch."""
+    return state_bytes(B, C, hw, H, W) - HEAD_BYTES + _align(8 * 8 * B) + _align(8 * 8)
+
+
+def forward_z(mean, std32, eps):
+    """z = fma(std, eps, mean) of fp32 values rounded once to fp32, as the device forms it (csrc/vt_vae_loss.h vae_z_of), exactly: the product of
+    two fp32 values is exact in fp64; the fp64 sum s and its rounding error (TwoSum) give the exact value, and the error decides the one case in
+    which rounding s again would go wrong -- s exactly half way between two fp32 values."""
+    a = np.asarray(mean, dtype=np.float32).astype(np.float64)
+    p = np.asarray(std32, dtype=np.float32).astype(np.float64) * np.asarray(eps, dtype=np.float32).astype(np.float64)
+    s = a + p
+    t = s - a
+    err = (a - (s - t)) + (p - t)
+    with np.errstate(over="ignore", invalid="ignore"):
+        r = s.astype(np.float32)
+        down, up = np.nextafter(r, np.float32(-np.inf)), np.nextafter(r, np.float32(np.inf))
+        r64 = r.astype(np.float64)
+        tie_down, tie_up = s == 0.5 * (r64 + down.astype(np.float64)), s == 0.5 * (r64 + up.astype(np.float64))
+        # at a tie astype took the even neighbour; the exact value lies on err's side of s
+        r = np.where(tie_down & (err > 0), r, np.where(tie_down & (err < 0), down, r))
+        r = np.where(tie_up & (err < 0), r, np.where(tie_up & (err > 0), up, r))
+    return r.astype(np.float32)
+
+
+def loss_backward_host(anchor, positive, negative, *, weights, margin=1.0, similarity_type="cosine", seed=0, first_image=0, dz_dec=None,
+                       dz_draw=0, recon=None, target=None, labels_a=None, labels_p=None, eps=None, z_forward=None):
+    """The fp64 numpy mirror of vt_vae_loss_backward.  anchor / positive / negative: (moments [B, 2C, h, w], draw).  weights: a dict with
+    "reconstruction", "kl", "triplet".  eps (optional): (eps_a, eps_p, eps_n, eps_dec) fp32 arrays to use instead of the host model of the
+    counter-based normal (improved_losses.normal_draw); z_forward (optional): the three streams' fp32 z as the device's forward formed them
+    (vt_posterior_sample), instead of forward_z.  -> {"d_recon", "d_moments": [a, p, n], "rows" [B, ROW], "losses" [4]}; z is the
+    forward's fp32 z and std its fp32 std, as on the device."""
+    if negative is None:
+        raise ValueError("a negative stream is required: the contrastive term has no gradient here")
+    w_rec, w_kl, w_tri = _weights(weights)
+    if not np.isfinite(margin):
+        raise ValueError("the margin must be finite")
+    streams = [_stream(s) for s in (anchor, positive, negative)]
+    shape = np.asarray(streams[0][0]).shape
+    B, C = shape[0], shape[1] // 2
+    D = int(np.prod(shape[1:])) // 2
+    draws = [d for _, d in streams] + [int(dz_draw)]
+    if eps is None:
+        eps = [np.stack([il.normal_draw(seed, d, first_image + i, D) for i in range(B)]) for d in draws]
+    eps = [np.asarray(e, dtype=np.float32).reshape(B, D) for e in eps]
+    mean, lv, sd, std32, z = [], [], [], [], []
+    for (m, _), e in zip(streams, eps):
+        m = np.asarray(m, dtype=np.float32).reshape(B, 2, D)
+        mean.append(m[:, 0]), lv.append(m[:, 1])
+        sd.append(np.exp(0.5 * np.clip(lv[-1].astype(np.float64), -30.0, 20.0)))
+        std32.append(sd[-1].astype(np.float32))
+        z.append(forward_z(mean[-1], std32[-1], e).astype(np.float64) if z_forward is None else
+                 np.asarray(z_forward[len(z)], dtype=np.float32).reshape(B, D).astype(np.float64))
+    rows = rows_from_mirrors(z[0], z[1], z[2], tuple(il.kl_elements(np.asarray(m).reshape(B, 2 * C, -1)) for m, _ in streams), recon, target,
+                             labels_a, labels_p, margin_triplet=margin)
+    rows[:, 12:14] = 0.0
+    euclid = similarity_type != "cosine"
+    col = 11 if euclid else 10
+    sums = np.zeros(3)
+    for r in rows:                                                            # (one image after the other, as the device adds them)
+        sums += (r[0], r[4], r[col])
+    losses = np.array([sums[0] / B, float(il.kl_log(sums[1] / B)), sums[2] / B, 0.0])
+    losses[3] = w_rec * losses[0] + w_kl * losses[1] + w_tri * losses[2]
+    c_kl = w_kl / (3.0 * B * 10000.0 * (1.0 + sums[1] / B / 10000.0))
+    x = rows[:, 8 if euclid else 6] - rows[:, 9 if euclid else 7] + float(margin)
+    t = (w_tri * rows[:, 17] / B * np.where(x <= 0.0, 0.0, 1.0))[:, None]
+    a, p, n = z
+    if euclid:
+        dp, dn = a - p + 1e-6, a - n + 1e-6
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tp = np.where(rows[:, 8:9] > 0.0, t / rows[:, 8:9], 0.0)
+            tn = np.where(rows[:, 9:10] > 0.0, t / rows[:, 9:10], 0.0)
+        g = [dp * tp - dn * tn, -(dp * tp), dn * tn]
+    else:
+        r_ = [np.sqrt((v * v).sum(1, keepdims=True)) for v in z]
+        N_ = [np.maximum(v, 1e-12) for v in r_]
+        ap, an = (a * p).sum(1, keepdims=True), (a * n).sum(1, keepdims=True)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ka = np.where(r_[0] >= 1e-12, t * (ap / N_[1] - an / N_[2]) / (N_[0] * N_[0] * r_[0]), 0.0)
+            kp = np.where(r_[1] >= 1e-12, t * ap / (N_[0] * N_[1] * N_[1] * r_[1]), 0.0)
+            kn = np.where(r_[2] >= 1e-12, t * an / (N_[0] * N_[2] * N_[2] * r_[2]), 0.0)
+        ipn, inn = t / (N_[0] * N_[1]), t / (N_[0] * N_[2])
+        g = [a * ka - p * ipn + n * inn, p * kp - a * ipn, a * inn - n * kn]
+    d_moments = []
+    for s in range(3):
+        d_mean, sampled = g[s], g[s] * std32[s] * eps[s].astype(np.float64)
+        if s == 0 and dz_dec is not None:
+            dz = np.asarray(dz_dec, dtype=np.float64).reshape(B, D)
+            d_mean, sampled = d_mean + dz, sampled + dz * std32[0] * eps[3].astype(np.float64)
+        inside = (lv[s] >= -30.0) & (lv[s] <= 20.0)
+        d_lv = np.where(inside, 0.5 * sampled + c_kl * (0.5 * (sd[s] * sd[s] - 1.0)), 0.0)
+        d_moments.append(np.stack([d_mean + c_kl * mean[s], d_lv], 1).reshape(shape))
+    d_recon = None
+    if recon is not None:
+        r64, t64 = np.asarray(recon, dtype=np.float64), np.asarray(target, dtype=np.float64)
+        d_recon = w_rec * 2.0 / (float(B) * float(r64[0].size)) * (r64 - t64)
+    return {"d_recon": d_recon, "d_moments": d_moments, "rows": rows, "losses": losses}
+
+
+def loss_backward_device(anchor, positive, negative, *, weights, margin=1.0, similarity_type="cosine", seed=0, first_image=0, dz_dec=None,
+                         dz_draw=0, recon=None, target=None, labels_a=None, labels_p=None, d_recon=None, d_moments=None, rows_out=None,
+                         loss_out=None, workspace=None, context=None):
+    """One vt_vae_loss_backward on torch's current stream; no host synchronisation.  anchor / positive / negative: (moments, draw) (or
+    update()'s (moments, None, draw)) with moments contiguous fp32 device tensors [B, 2C, h, w].  Outputs are written only where given:
+    d_recon fp32 like recon; d_moments a sequence of three fp32 tensors like the moments, each or all None (they may be the three slices
+    of one [3B, 2C, h, w] tensor); rows_out float64 [B, ROW]; loss_out float64 [4] (LOSS_NAMES).  workspace: a uint8 device tensor of
+    at least backward_workspace_bytes + 256 bytes, or None to allocate one."""
+    import torch
+    from . import _lib
+    if negative is None:
+        raise ValueError("a negative stream is required: the contrastive term has no gradient here")
+    w = _weights(weights)
+    if not np.isfinite(margin):
+        raise ValueError("the margin must be finite")
+    streams = [_stream(s) for s in (anchor, positive, negative)]
+    m0 = streams[0][0]
+    dev = m0.device
+
+    def f32(t, shape, what):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or (
+                shape is not None and tuple(t.shape) != tuple(shape)):
+            raise ValueError(f"{what}: expected a contiguous fp32 tensor{'' if shape is None else ' ' + str(tuple(shape))} on {dev}")
+        return t
+
+    if not isinstance(m0, torch.Tensor) or m0.dim() < 3 or m0.shape[1] % 2 or not m0.is_cuda:
+        raise ValueError("moments are [B, 2C, h, w] tensors on a HIP device")
+    for m, _ in streams:
+        f32(m, m0.shape, "moments")
+    B, C, hw = m0.shape[0], m0.shape[1] // 2, int(np.prod(m0.shape[2:]))
+    f32(dz_dec, (B, C) + tuple(m0.shape[2:]), "dz_dec")
+    H = W = 0
+    if recon is not None or target is not None or d_recon is not None:
+        if recon is None or target is None or recon.dim() != 4 or recon.shape[1] != 3 or recon.shape[0] != B:
+            raise ValueError("recon and target are [B, 3, H, W] tensors of one shape")
+        f32(recon, None, "recon"), f32(target, recon.shape, "target"), f32(d_recon, recon.shape, "d_recon")
+        H, W = recon.shape[2], recon.shape[3]
+    dm = list(d_moments) if d_moments is not None else [None] * 3
+    if len(dm) != 3:
+        raise ValueError("d_moments holds three tensors (or None): anchor, positive, negative")
+    for t in dm:
+        f32(t, m0.shape, "d_moments")
+    N, dt = 0, _lib.VT_F32
+    if labels_a is not None and labels_p is not None:
+        if labels_a.dtype == torch.bool:
+            labels_a, labels_p = labels_a.view(torch.uint8), labels_p.view(torch.uint8)
+        if labels_a.dtype != labels_p.dtype or labels_a.dtype not in (torch.float32, torch.uint8) or labels_a.dim() != 2 or (
+                labels_a.shape != labels_p.shape or labels_a.shape[0] != B or labels_a.device != dev or labels_p.device != dev
+                or not labels_a.is_contiguous() or not labels_p.is_contiguous()):
+            raise ValueError("labels are contiguous [B, N] tensors of one shape, fp32 or uint8 / bool, on the moments' device")
+        N, dt = labels_a.shape[1], (_lib.VT_U8 if labels_a.dtype == torch.uint8 else _lib.VT_F32)
+    else:
+        labels_a = labels_p = None
+    for t, n, what in ((rows_out, B * ROW, "rows_out"), (loss_out, 4, "loss_out")):
+        if t is not None and (t.dtype != torch.float64 or t.device != dev or not t.is_contiguous() or t.numel() != n):
+            raise ValueError(f"{what} is a contiguous float64 tensor of {n} elements on {dev}")
+    if context is None:
+        from .vae_backward import context as backward_context          # the package's one cache of per-device contexts for the backward entry points
+        context = backward_context(dev)
+    ctx = context
+    need = ctx.lib.vt_vae_loss_backward_workspace_bytes(B, C, hw, H, W)
+    if need == 0:
+        raise ValueError(f"{B} images of {C} x {hw} latents and {H} x {W} pixels are not supported")
+    if workspace is None:
+        workspace = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+    off = -workspace.data_ptr() % 256
+    ins = [_lib.VAELossInput(m.data_ptr(), None, d) for m, d in streams]
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    ctx.call("vt_vae_loss_backward", ctypes.byref(ins[0]), ctypes.byref(ins[1]), ctypes.byref(ins[2]), ptr(dz_dec), int(dz_draw), ptr(recon), ptr(target),
+             H, W, ptr(labels_a), ptr(labels_p), dt, N, B, C, hw, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image), w[0], w[1], w[2], float(margin),
+             _lib.VAE_COSINE if similarity_type == "cosine" else _lib.VAE_EUCLIDEAN, ptr(d_recon), ptr(dm[0]), ptr(dm[1]), ptr(dm[2]), ptr(rows_out),
+             ptr(loss_out), ctypes.c_void_p(workspace.data_ptr() + off), max(workspace.numel() - off, 0),
+             ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+
