@@ -672,6 +672,37 @@ int vt_vae_loss_backward(vt_context* ctx, const vt_vae_loss_input* anchor, const
                          int similarity /* VT_VAE_COSINE | VT_VAE_EUCLIDEAN */, float* d_recon, float* d_moments_a, float* d_moments_p,
                          float* d_moments_n, double* rows_out, double* loss_out /* [4] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the optimiser of the VAE train step (csrc/vae_optim.hip): clip_grad_norm_ and AdamW over n gradient tensors where they lie ----
+ * The parameters live in one fp32 arena, the Adam moments m and v in two more of the same layout: tensor i owns a slot of
+ * ceil(numel[i] / VT_VAE_OPTIM_TILE) tiles of VT_VAE_OPTIM_TILE floats, slots follow each other in the order given, so a tile never
+ * straddles two tensors and every slot is 16-B aligned; the padding is zero and stays zero (it is never read from a gradient and
+ * never stored).  vt_vae_optim_layout is that rule as a pure host function: offsets_out[i] (floats; may be NULL) and *total_out (may
+ * be NULL); VT_ERR_INVALID for n < 1, a null numel or a numel <= 0.
+ * `grads` is a HOST array of n device pointers (fp32, contiguous, 4-B aligned; a 16-B aligned one takes the float4 path), `numel` a HOST
+ * array; both are read during the call only.  They travel in kernel arguments, `chunk` tensors per launch (0: VT_VAE_OPTIM_CHUNK, else 1
+ * .. VT_VAE_OPTIM_CHUNK): no host-to-device copy, no staging, no allocation, no host synchronisation; the results do not depend on `chunk`.
+ * Everything is checked on the host before anything is launched: null / misaligned pointer, n < 1, numel <= 0, max_norm <= 0, an arena
+ * smaller than the layout's total or an out-of-range optimiser argument is VT_ERR_INVALID, a small workspace VT_ERR_WORKSPACE, and a
+ * refused call writes nothing.
+ *   vt_vae_optim_norm   one workgroup per tile squares in fp64 and writes one fp64 partial at the tile's global index (workspace: 256-B
+ *                       aligned, vt_vae_optim_workspace_bytes(numel, n) bytes, 0 for arguments the call would refuse); a last
+ *                       single-workgroup launch adds the partials in an order fixed by their count and writes scalars_out (device, 16-B aligned) =
+ *                       { fp64 norm^2, fp32 norm = (float)sqrt(norm^2), fp32 coef = min(1, max_norm / (norm + 1e-6f)) }, vt_head_clip's
+ *                       formula.  No atomics; bit-identical from run to run; the gradients are not written.
+ *   vt_vae_optim_step   AdamW's update number t (1-based) as vt_head_step, per element the same source; with `scalars` (device, what
+ *                       vt_vae_optim_norm wrote; may be NULL) and coef < 1 the gradient is first multiplied by coef, one fp32 multiply
+ *                       with one rounding.  Reads g, p, m, v and writes p, m, v: the gradients are neither zeroed nor written.
+ *                       arena_floats: the floats each of params / m / v (256-B aligned) holds. */
+#define VT_VAE_OPTIM_TILE 4096
+#define VT_VAE_OPTIM_CHUNK 64
+int vt_vae_optim_layout(const long long* numel /* host [n] */, int n, long long* offsets_out /* host [n] or NULL */, long long* total_out);
+size_t vt_vae_optim_workspace_bytes(const long long* numel /* host [n] */, int n);
+int vt_vae_optim_norm(vt_context* ctx, const float* const* grads /* host [n] */, const long long* numel /* host [n] */, int n, float max_norm,
+                      void* scalars_out, void* workspace, size_t workspace_bytes, int chunk, void* stream);
+int vt_vae_optim_step(vt_context* ctx, float* params, float* m, float* v, size_t arena_floats, const float* const* grads /* host [n] */,
+                      const long long* numel /* host [n] */, int n, const void* scalars /* or NULL */, double lr, double beta1, double beta2,
+                      double eps, double weight_decay, long long t, int chunk, void* stream);
+
 /* ---- single operators (parity tests drive each kernel through the same ABI) ------------------
  * NHWC bf16 activations, weights in the reference's own layouts (fp32 host order is converted by
  * the caller to bf16 [Cout][kh][kw][Cin]); fp32 accumulate.

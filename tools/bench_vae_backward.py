@@ -8,7 +8,8 @@
     same model under bf16 autocast; torch.cuda.max_memory_allocated of a forward + backward beside encoder_saved_bytes / decoder_saved_bytes.
 (d) --joined: vae_loss_and_grads (one step of train_vae: three encodes, the anchor's decode, the loss, all 244 gradients) at
     batch 1, beside the reference-shaped torch step -- three encodes, sample, one decode, the loss, backward() -- under bf16 autocast, with the peak
-    allocated memory of both and vae_train_saved_bytes.  With --joined only (d) runs.
+    allocated memory of both and vae_train_saved_bytes; then the whole train step (VAETrainer.train_step: the same backward, clip_grad_norm_ and AdamW over the
+    244 gradients where they lie) and the optimiser's share of it.  With --joined only (d) runs.
 Everything is warmed first and timed in interleaved rounds; the figures are medians over the rounds.
 
 Usage: python tools/bench_vae_backward.py [--rounds 5] [--iters 3] [--side 1024] [--model-sides 512,1024] [--skip-torch] [--skip-models] [--joined] [--out FILE]
@@ -233,6 +234,16 @@ def bench_joined(side, rounds, iters, with_torch):
     ours = lambda: vb.vae_loss_and_grads(p, a, pos, neg, weights=weights)  # noqa: E731
     rec = {"side": side, "saved_bytes": int(vb.vae_train_saved_bytes(p, 1, side, side)), "peak_allocated": int(peak_of(ours))}
     calls = {"vae_loss_and_grads": ours}
+    # the whole train step: the same backward on the trainer's parameter views, then clip and AdamW where the gradients lie
+    from vae_tagger_amd.train_vae import VAETrainer
+    trainer = VAETrainer(p, weights=weights, device=DEV)
+    calls["train_step"] = lambda: trainer.train_step(a, pos, neg, lr=1e-6, weight_decay=1e-6, max_grad_norm=1.0)  # noqa: E731
+    held = vb.vae_loss_and_grads(trainer.params, a, pos, neg, weights=weights)[1]
+
+    def optimiser_only():
+        trainer.clip(held, 1.0)
+        trainer.step(held, 1e-6, 1e-6)
+    calls["clip_and_adamw"] = optimiser_only
     print(f"joined step @ {side}^2: saved {rec['saved_bytes'] / 2 ** 20:.0f} MiB, peak {rec['peak_allocated'] / 2 ** 20:.0f} MiB; torch's step next", flush=True)
     if with_torch:
         try:
@@ -247,6 +258,8 @@ def bench_joined(side, rounds, iters, with_torch):
             rec["note"] = f"torch step not measured: {type(e).__name__}: {e}"
     ms = interleaved(calls, rounds, iters)
     rec["ms"] = {k: round(v, 3) for k, v in ms.items()}
+    rec["optimiser_share_of_train_step"] = round(ms["clip_and_adamw"] / ms["train_step"], 4)
+    print(f"train step @ {side}^2: {ms['train_step']:.2f} ms, of which clip + AdamW {ms['clip_and_adamw']:.3f} ms ({100 * rec['optimiser_share_of_train_step']:.2f} %)", flush=True)
     if "torch_step_bf16_autocast" in ms:
         rec["step_over_torch"] = round(ms["vae_loss_and_grads"] / ms["torch_step_bf16_autocast"], 3)
     print(f"joined step @ {side}^2: " + "  ".join(f"{k} {v:.2f} ms" for k, v in ms.items()) + f"  saved {rec['saved_bytes'] / 2 ** 20:.0f} MiB, peak "

@@ -45,6 +45,7 @@ class VAELossInput(_c.Structure):
 
 VAE_LOSS_ROW, VAE_LOSS_HEAD_BYTES = 19, 512              # VT_VAE_LOSS_ROW, VT_VAE_LOSS_HEAD_BYTES
 VAE_COSINE, VAE_EUCLIDEAN = 0, 1                         # VT_VAE_COSINE, VT_VAE_EUCLIDEAN
+VAE_OPTIM_TILE, VAE_OPTIM_CHUNK = 4096, 64               # VT_VAE_OPTIM_TILE, VT_VAE_OPTIM_CHUNK
 
 
 # name -> (restype, argtypes); every symbol include/vae_tagger_hip.h declares
@@ -156,6 +157,11 @@ PROTOTYPES = {
     "vt_vae_loss_backward": (_i, [_vp, _c.POINTER(VAELossInput), _c.POINTER(VAELossInput), _c.POINTER(VAELossInput), _vp, _i, _vp, _vp, _i, _i,
                                   _vp, _vp, _i, _i, _i, _i, _i, _c.c_ulonglong, _ll, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _i,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vt_vae_optim_layout": (_i, [_c.POINTER(_ll), _i, _c.POINTER(_ll), _c.POINTER(_ll)]),
+    "vt_vae_optim_workspace_bytes": (_sz, [_c.POINTER(_ll), _i]),
+    "vt_vae_optim_norm": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_ll), _i, _f, _vp, _vp, _sz, _i, _vp]),
+    "vt_vae_optim_step": (_i, [_vp, _vp, _vp, _vp, _sz, _c.POINTER(_vp), _c.POINTER(_ll), _i, _vp, _c.c_double, _c.c_double, _c.c_double,
+                               _c.c_double, _c.c_double, _ll, _i, _vp]),
     "vt_encoder_flops":(_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),
     "vt_debug_trace": (_i, [_vp, _i, _c.POINTER(_c.c_ulonglong), _i, _c.POINTER(_i)]),

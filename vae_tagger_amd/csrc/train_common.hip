@@ -51,18 +51,7 @@ __global__ __launch_bounds__(256) VT_NO_PACKED_F32 void train_scale_kernel(float
 }
 
 // (VT_NO_PACKED_F32: the compiler would pair these float4 lanes into packed fp32 ops with a source op_sel -- vt_common.h)
-// torch.optim.AdamW (single-tensor path): p *= 1 - lr wd; m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g g;
-// p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps); g = 0
-__device__ __forceinline__ void adamw_one(float& p, float& g, float& m, float& v, float decay, float w1, float beta2, float w2, float step_size,
-                                          float rbc2, float eps) {
-#pragma clang fp contract(off)
-    p = p * decay;
-    m = m + w1 * (g - m);
-    v = v * beta2 + w2 * (g * g);
-    const float denom = sqrtf(v) / rbc2 + eps;
-    p = p - step_size * (m / denom);
-    g = 0.f;
-}
+// the per-element arithmetic is adamw_one of vt_train.h (shared with vae_optim.hip)
 __global__ __launch_bounds__(256) VT_NO_PACKED_F32 void train_adamw_kernel(float4* __restrict__ P, float4* __restrict__ G, float4* __restrict__ M, float4* __restrict__ V,
                                                           long long n4, float decay, float w1, float beta2, float w2, float step_size, float rbc2,
                                                           float eps) {

@@ -1,0 +1,262 @@
+// The optimiser of the VAE train step: clip_grad_norm_ and AdamW over n freshly allocated fp32 gradient tensors, read where they lie.
+// The block trainers (train_common.hip) own one state block whose kernels write the gradients into it; here the backward hands over 244
+// tensors that change address every step, so their pointers travel in kernel arguments: a by-value table of { gradient, slot offset,
+// numel } for up to VT_VAE_OPTIM_CHUNK tensors per launch (24 B each, 1.5 KB a table), a handful of launches per pass, no copy, no staging.
+// Parameters, m and v live in three arenas of one layout (vt_vae_optim_layout): tensor i owns ceil(numel / VT_VAE_OPTIM_TILE) tiles, so a
+// workgroup's tile lies inside one tensor and its global index -- which is where its squared-norm partial goes -- is fixed by the shapes.
+// The trainers' conventions hold: fp32 storage, fp64 reductions in an order fixed by the shapes, no atomics, nothing synchronises the host.
+#include <math.h>
+
+#include "vt_common.h"
+#include "vt_context.h"
+#include "vt_train.h"
+
+using namespace vt;
+
+namespace {
+
+constexpr long long TILE = VT_VAE_OPTIM_TILE;
+constexpr int QUADS = VT_VAE_OPTIM_TILE / 4 / 256;          // float4s of a tile per thread
+static_assert(VT_VAE_OPTIM_TILE % 1024 == 0, "a tile is a whole number of float4s per thread of a 256-thread workgroup");
+
+struct OptimEntry { const float* g; long long off; long long numel; };     // off: the slot's first float in the arenas, a multiple of TILE
+struct OptimTable { OptimEntry e[VT_VAE_OPTIM_CHUNK]; int count; };
+static_assert(sizeof(OptimTable) <= 2048, "the table and the scalars beside it stay well under the 4 KB of kernel arguments");
+
+// workgroup b of a launch -> its tensor (the last entry whose first tile is <= b; the entries' tiles follow each other) and the tile
+// inside it.  b is uniform, so these are scalar loads from the argument block.
+__device__ __forceinline__ int optim_find(const OptimTable& t, long long b, long long* tile) {
+    const long long base = t.e[0].off / TILE;
+    int lo = 0, hi = t.count - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (t.e[mid].off / TILE - base <= b) lo = mid; else hi = mid - 1;
+    }
+    *tile = b - (t.e[lo].off / TILE - base);
+    return lo;
+}
+
+// One workgroup per tile.  Thread j owns the float4s j, j + 256, ... of the tile and adds their squares x, y, z, w in that order, in
+// fp64; a gradient that is not 16-B aligned, and the float4 that the tensor's end cuts, are loaded one float at a time into the same
+// places, so the partial has the same bits either way.  Elements past numel are never loaded.
+__global__ __launch_bounds__(256) void vae_optim_sq_kernel(OptimTable t, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    long long tile;
+    const OptimEntry e = t.e[optim_find(t, blockIdx.x, &tile)];
+    const float* __restrict__ g = e.g;
+    const bool vec = ((uintptr_t)g & 15) == 0;
+    double sq = 0.0;
+    float4 x[QUADS];
+    if (vec && (tile + 1) * TILE <= e.numel) {                  // a whole tile of an aligned tensor: every load is issued before the first add
+#pragma unroll
+        for (int r = 0; r < QUADS; ++r) x[r] = *(const float4*)(g + tile * TILE + 4 * ((long long)threadIdx.x + 256 * r));
+    } else {
+#pragma unroll
+        for (int r = 0; r < QUADS; ++r) {
+            const long long i = tile * TILE + 4 * ((long long)threadIdx.x + 256 * r);
+            x[r] = float4{0.f, 0.f, 0.f, 0.f};
+            if (i + 4 <= e.numel) {
+                if (vec) x[r] = *(const float4*)(g + i);
+                else { x[r].x = g[i]; x[r].y = g[i + 1]; x[r].z = g[i + 2]; x[r].w = g[i + 3]; }
+            } else if (i < e.numel) {
+                x[r].x = g[i];
+                if (i + 1 < e.numel) x[r].y = g[i + 1];
+                if (i + 2 < e.numel) x[r].z = g[i + 2];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < QUADS; ++r) {
+        sq = sq + (double)x[r].x * (double)x[r].x;
+        sq = sq + (double)x[r].y * (double)x[r].y;
+        sq = sq + (double)x[r].z * (double)x[r].z;
+        sq = sq + (double)x[r].w * (double)x[r].w;
+    }
+    const double total = block_sum_256d(sq, red);
+    if (threadIdx.x == 0) part[e.off / TILE + tile] = total;
+}
+
+// one workgroup: the partials in an order fixed by their count -> { norm^2, norm, coef }, train_clip_kernel's formula
+__global__ __launch_bounds__(256) void vae_optim_clip_kernel(const double* __restrict__ part, long long n, float max_norm, TrainScalars* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    // thread j adds partials j, j + 256, ... in that order, as four chains (index / 256 mod 4) whose loads do not wait for each other
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 1024) {
+        a0 += part[i];
+        if (i + 256 < n) a1 += part[i + 256];
+        if (i + 512 < n) a2 += part[i + 512];
+        if (i + 768 < n) a3 += part[i + 768];
+    }
+    const double total = block_sum_256d(((a0 + a1) + a2) + a3, red);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(total);
+        const float coef = max_norm / (norm + 1e-6f);
+        TrainScalars v;
+        v.sq = total; v.norm = norm; v.coef = coef < 1.0f ? coef : 1.0f;
+        *out = v;
+    }
+}
+
+// the clip's scale folded in: g * coef as one fp32 multiply.  The product is pinned in a register: with -ffp-contract=fast on the
+// command line the backend would fuse it into adamw_one's g - m whatever the pragma says, and the fused difference has other bits.
+__device__ __forceinline__ float optim_scaled(float g, float coef, bool scale) {
+#pragma clang fp contract(off)
+    if (scale) {
+        g = g * coef;
+        asm volatile("" : "+v"(g));
+    }
+    return g;
+}
+
+struct AdamArgs { float decay, w1, beta2, w2, step_size, rbc2, eps; };
+
+// One workgroup per tile, thread j on the float4s j, j + 256, ...  A float4 that lies inside the tensor: p, m, v are loaded and stored as
+// float4 (the slot is 16-B aligned), g as a float4 when its pointer is 16-B aligned, else as four floats.  The float4 that the tensor's
+// end cuts: one guarded float at a time, so a padding lane is never loaded from the gradient and never stored.  The gradient is only read.
+// (VT_NO_PACKED_F32: the compiler would pair these float4 lanes into packed fp32 ops with a source op_sel -- vt_common.h)
+__global__ __launch_bounds__(256) VT_NO_PACKED_F32 void vae_optim_adamw_kernel(OptimTable t, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V,
+                                                                              const TrainScalars* __restrict__ sc, AdamArgs a) {
+    long long tile;
+    const OptimEntry e = t.e[optim_find(t, blockIdx.x, &tile)];
+    const float* __restrict__ g = e.g;
+    const bool vec = ((uintptr_t)g & 15) == 0;
+    const float coef = sc ? sc->coef : 1.0f;
+    const bool scale = coef < 1.0f;
+#pragma unroll
+    for (int r = 0; r < QUADS; ++r) {
+        const long long i = tile * TILE + 4 * ((long long)threadIdx.x + 256 * r);
+        const long long o = e.off + i;
+        if (i + 4 <= e.numel) {
+            float4 x;
+            if (vec) x = *(const float4*)(g + i);
+            else { x.x = g[i]; x.y = g[i + 1]; x.z = g[i + 2]; x.w = g[i + 3]; }
+            float4 p = *(float4*)(P + o), m = *(float4*)(M + o), v = *(float4*)(V + o);
+            x.x = optim_scaled(x.x, coef, scale); x.y = optim_scaled(x.y, coef, scale);
+            x.z = optim_scaled(x.z, coef, scale); x.w = optim_scaled(x.w, coef, scale);
+            adamw_one(p.x, x.x, m.x, v.x, a.decay, a.w1, a.beta2, a.w2, a.step_size, a.rbc2, a.eps);
+            adamw_one(p.y, x.y, m.y, v.y, a.decay, a.w1, a.beta2, a.w2, a.step_size, a.rbc2, a.eps);
+            adamw_one(p.z, x.z, m.z, v.z, a.decay, a.w1, a.beta2, a.w2, a.step_size, a.rbc2, a.eps);
+            adamw_one(p.w, x.w, m.w, v.w, a.decay, a.w1, a.beta2, a.w2, a.step_size, a.rbc2, a.eps);
+            *(float4*)(P + o) = p; *(float4*)(M + o) = m; *(float4*)(V + o) = v;
+        } else {
+            for (int k = 0; k < 3; ++k) {
+                if (i + k >= e.numel) break;
+                float x = optim_scaled(g[i + k], coef, scale);
+                float p = P[o + k], m = M[o + k], v = V[o + k];
+                adamw_one(p, x, m, v, a.decay, a.w1, a.beta2, a.w2, a.step_size, a.rbc2, a.eps);
+                P[o + k] = p; M[o + k] = m; V[o + k] = v;
+            }
+        }
+    }
+}
+
+// the arguments both entry points share: n, the tensors, the chunk; `total` = floats of an arena, `tiles` = total / TILE
+int optim_check(vt_context* c, const char* who, const float* const* grads, const long long* numel, int n, int chunk, long long* total) {
+    if (n < 1 || !grads || !numel) return c->fail(VT_ERR_INVALID, "%s: n = %d tensors (>= 1) with host arrays of gradients and numels expected", who, n);
+    if (chunk < 0 || chunk > VT_VAE_OPTIM_CHUNK) return c->fail(VT_ERR_INVALID, "%s: chunk = %d, 0 or 1 to %d expected", who, chunk, VT_VAE_OPTIM_CHUNK);
+    long long off = 0;
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] <= 0 || numel[i] > (1ll << 40)) return c->fail(VT_ERR_INVALID, "%s: tensor %d has numel = %lld, 1 to 2^40 expected", who, i, numel[i]);
+        if (!grads[i] || ((uintptr_t)grads[i] & 3)) return c->fail(VT_ERR_INVALID, "%s: gradient %d is null or not 4-B aligned", who, i);
+        off += (numel[i] + TILE - 1) / TILE * TILE;
+    }
+    *total = off;
+    return VT_OK;
+}
+
+// the tensors `chunk` at a time: launch(table, tiles of the table)
+template <class Launch>
+int optim_chunks(vt_context* c, const char* who, const float* const* grads, const long long* numel, int n, int chunk, Launch&& launch) {
+    if (chunk == 0) chunk = VT_VAE_OPTIM_CHUNK;
+    long long off = 0;
+    for (int first = 0; first < n; first += chunk) {
+        OptimTable t;
+        t.count = n - first < chunk ? n - first : chunk;
+        long long tiles = 0;
+        for (int k = 0; k < VT_VAE_OPTIM_CHUNK; ++k) {
+            if (k < t.count) {
+                const long long nt = (numel[first + k] + TILE - 1) / TILE;
+                t.e[k].g = grads[first + k]; t.e[k].off = off; t.e[k].numel = numel[first + k];
+                off += nt * TILE; tiles += nt;
+            } else {
+                t.e[k].g = nullptr; t.e[k].off = 0; t.e[k].numel = 0;
+            }
+        }
+        if (tiles > 0x7fffffffll) return c->fail(VT_ERR_INVALID, "%s: %lld tiles in one launch", who, tiles);
+        launch(t, (unsigned)tiles);
+        HIPCK(c, hipGetLastError(), who);
+    }
+    return VT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vt_vae_optim_layout(const long long* numel, int n, long long* offsets_out, long long* total_out) {
+    if (n < 1 || !numel) return VT_ERR_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (numel[i] <= 0 || numel[i] > (1ll << 40)) return VT_ERR_INVALID;
+    long long off = 0;
+    for (int i = 0; i < n; ++i) {
+        if (offsets_out) offsets_out[i] = off;
+        off += (numel[i] + TILE - 1) / TILE * TILE;
+    }
+    if (total_out) *total_out = off;
+    return VT_OK;
+}
+
+size_t vt_vae_optim_workspace_bytes(const long long* numel, int n) {
+    long long total = 0;
+    if (vt_vae_optim_layout(numel, n, nullptr, &total) != VT_OK) return 0;
+    return align_up(sizeof(double) * (size_t)(total / TILE));
+}
+
+int vt_vae_optim_norm(vt_context* c, const float* const* grads, const long long* numel, int n, float max_norm, void* scalars_out, void* workspace,
+                      size_t workspace_bytes, int chunk, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    const char* who = "vt_vae_optim_norm";
+    long long total = 0;
+    VTCK(optim_check(c, who, grads, numel, n, chunk, &total));
+    if (!(max_norm > 0.f)) return c->fail(VT_ERR_INVALID, "%s: max_norm = %g must be positive", who, max_norm);
+    if (!scalars_out || ((uintptr_t)scalars_out & 15)) return c->fail(VT_ERR_INVALID, "%s: scalars_out is null or not 16-B aligned", who);
+    if (!workspace || ((uintptr_t)workspace & (ALIGN - 1))) return c->fail(VT_ERR_INVALID, "%s: workspace is null or not 256-B aligned", who);
+    const size_t need = align_up(sizeof(double) * (size_t)(total / TILE));
+    if (workspace_bytes < need) return c->fail(VT_ERR_WORKSPACE, "%s: workspace holds %zu bytes, %zu needed", who, workspace_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    double* part = (double*)workspace;
+    VTCK(optim_chunks(c, who, grads, numel, n, chunk, [&](const OptimTable& t, unsigned tiles) {
+        hipLaunchKernelGGL(vae_optim_sq_kernel, dim3(tiles), dim3(256), 0, s, t, part);
+    }));
+    hipLaunchKernelGGL(vae_optim_clip_kernel, dim3(1), dim3(256), 0, s, (const double*)part, total / TILE, max_norm, (TrainScalars*)scalars_out);
+    HIPCK(c, hipGetLastError(), who);
+    return VT_OK;
+}
+
+int vt_vae_optim_step(vt_context* c, float* params, float* m, float* v, size_t arena_floats, const float* const* grads, const long long* numel, int n,
+                      const void* scalars, double lr, double beta1, double beta2, double eps, double weight_decay, long long t, int chunk,
+                      void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    const char* who = "vt_vae_optim_step";
+    long long total = 0;
+    VTCK(optim_check(c, who, grads, numel, n, chunk, &total));
+    if (!params || !m || !v || (((uintptr_t)params | (uintptr_t)m | (uintptr_t)v) & (ALIGN - 1)))
+        return c->fail(VT_ERR_INVALID, "%s: params, m or v is null or not 256-B aligned", who);
+    if (arena_floats < (size_t)total) return c->fail(VT_ERR_INVALID, "%s: the arenas hold %zu floats, %lld needed", who, arena_floats, total);
+    if ((uintptr_t)scalars & 15) return c->fail(VT_ERR_INVALID, "%s: scalars is not 16-B aligned", who);
+    if (t < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !isfinite(lr) || !isfinite(weight_decay))
+        return c->fail(VT_ERR_INVALID, "%s: t >= 1, betas in [0, 1), eps >= 0 and finite lr / weight_decay expected", who);
+    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
+    const AdamArgs a = {(float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2),
+                        (float)eps};
+    hipStream_t s = (hipStream_t)stream;
+    return optim_chunks(c, who, grads, numel, n, chunk, [&](const OptimTable& tb, unsigned tiles) {
+        hipLaunchKernelGGL(vae_optim_adamw_kernel, dim3(tiles), dim3(256), 0, s, tb, params, m, v, (const TrainScalars*)scalars, a);
+    });
+}
+
+}  // extern "C"

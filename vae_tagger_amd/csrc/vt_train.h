@@ -43,6 +43,21 @@ inline long long vt_train_merge_chunk4(size_t P, int norm_parts) { return (long 
 int vt_train_grads_export(vt_context* c, const char* who, const TrainBlock& b, const void* state, void* dst, size_t dst_bytes, hipStream_t s);
 int vt_train_grads_merge(vt_context* c, const char* who, const TrainBlock& b, void* state, const void* src, size_t stride_floats, int K,
                          const double* weights, hipStream_t s);
+// The per-element AdamW of train_common.hip's block step and of vae_optim.hip's multi-tensor step: one source, so both units compile the
+// same arithmetic.  torch.optim.AdamW (single-tensor path): p *= 1 - lr wd; m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g g;
+// p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps); g = 0
+#if defined(__HIPCC__)
+__device__ __forceinline__ void adamw_one(float& p, float& g, float& m, float& v, float decay, float w1, float beta2, float w2, float step_size,
+                                          float rbc2, float eps) {
+#pragma clang fp contract(off)
+    p = p * decay;
+    m = m + w1 * (g - m);
+    v = v * beta2 + w2 * (g * g);
+    const float denom = sqrtf(v) / rbc2 + eps;
+    p = p - step_size * (m / denom);
+    g = 0.f;
+}
+#endif
 // VT_HEAD_PARAM .. VT_HEAD_ADAM_V of the tensor at float offset `toff` with `numel` floats, or VT_HEAD_NORM -> byte range of the block
 int vt_train_section(vt_context* c, const char* who, const TrainBlock& b, int kind, size_t toff, size_t numel, size_t* off, size_t* bytes);
 int vt_train_read(vt_context* c, const char* who, const void* state, size_t off, size_t bytes, void* out, size_t out_bytes, hipStream_t s);

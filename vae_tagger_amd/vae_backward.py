@@ -13,8 +13,8 @@ say what a batch keeps between forward and backward before anything is allocated
 vae_loss_and_grads joins them into one step of train_vae.py: the three encodes, the anchor's decode, the loss (vt_vae_loss_backward: MSE, KL, triplet
 and the backward of posterior.sample) and the gradients of all encoder and decoder tensors.
 
-This is NOT train_vae: there is no optimiser, no gradient clipping, no checkpoint and no CLI here; the contrastive term and AdaptiveLossWeights have no
-gradient; the image's own gradient is not computed.
+The optimiser, gradient clipping, checkpoints and the CLI are vae_tagger_amd/train_vae.py (VAETrainer reads these gradients where they lie; DESIGN.md
+section 4.25), not here; the contrastive term and AdaptiveLossWeights have no gradient; the image's own gradient is not computed.
 """
 import ctypes
 
