@@ -454,3 +454,30 @@ def test_c_abi_error_paths_return_codes_and_messages(ops):
     assert L.vt_status(ctx.handle, 1, None, None) == 1 and L.vt_status(ctx.handle, 1, ctypes.byref(st), None) == 0 and st.value == 0
     assert L.vt_create(10 ** 6, ctypes.byref(ctypes.c_void_p())) == 2                                        # no such device
     ctx.close()
+
+
+def test_conv2d_gn_refuses_a_null_bias_before_it_launches(ops):
+    """vt_op_conv2d_gn on a halo-eligible shape (1 x 8 x 8, 32 -> 128: the weights are repacked into the operator scratch first) with a null bias:
+    refused, and the same valid call gives the same bytes after the refused one as before it."""
+    from vae_tagger_amd._lib import VTError
+    from _util import vp
+    B, H, W, Cin, Cout = 1, 8, 8, 32, 128
+    x = _rand((B, H, W, Cin), 1).to("cuda", torch.bfloat16)
+    w = _rand((Cout, 3, 3, Cin), 2, 0.1).to("cuda", torch.bfloat16)
+    b, gamma, beta = (_rand((Cout,), s).cuda() for s in (3, 4, 5))
+    ws = torch.empty(ops.ctx.lib.vt_op_conv2d_gn_workspace_bytes(B, H, W, Cout) + 256, device="cuda", dtype=torch.uint8)
+
+    def call(bias):
+        o32 = torch.full((B, H, W, Cout), float("nan"), device="cuda")
+        ss = torch.full((B, Cout, 2), float("nan"), device="cuda")
+        ops.ctx.call("vt_op_conv2d_gn", vp(x), vp(w), vp(bias), None, vp(o32), None, B, H, W, Cin, Cout, 3, 1, 1, 1, 32, 1e-6, vp(gamma), vp(beta), vp(ss),
+                     vp(ws), ops.stream)
+        torch.cuda.synchronize()
+        return o32.cpu(), ss.cpu()
+
+    o_before, ss_before = call(b)
+    assert torch.isfinite(o_before).all() and torch.isfinite(ss_before).all()
+    with pytest.raises(VTError, match="bias required"):
+        call(None)
+    o_after, ss_after = call(b)
+    assert torch.equal(o_before.view(torch.int32), o_after.view(torch.int32)) and torch.equal(ss_before.view(torch.int32), ss_after.view(torch.int32))

@@ -2,7 +2,7 @@
 // DESIGN.md section 4.20.
 #include <math.h>
 
-#include "vt_context.h"
+#include "vt_ops.h"
 
 namespace vt {
 namespace {
@@ -73,9 +73,7 @@ int vt_op_attention_forward_train(vt_context* c, const float* x, const float* gn
         return c->fail(VT_ERR_INVALID, "vt_op_attention_forward_train: null buffer");
     if (c->f16_ops || c->fp8 || c->attn_mode != 0 || !c->attn_qk_kernel || !c->attn_pv_kernel || !c->attn_proj_kernel)
         return c->fail(VT_ERR_INVALID, "vt_op_attention_forward_train: runs the default bf16 launches only (flags 7, 9, 11, 12, 17 and 18 at their defaults)");
-    const size_t need = vt_op_attention_forward_train_workspace_bytes(B, S, C);
-    if (!ws || ((uintptr_t)ws % ALIGN) || ws_bytes < need)
-        return c->fail(VT_ERR_INVALID, "vt_op_attention_forward_train: workspace must be 256-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
+    VTCK(check_workspace(c, "vt_op_attention_forward_train", ws, ws_bytes, vt_op_attention_forward_train_workspace_bytes(B, S, C), ALIGN));
     hipStream_t s = (hipStream_t)stream;
     const FwdWs w = carve_fwd((char*)ws, B, S, C);
     // weights -> the bf16 operands of the encoder's packing ([Wq; Wk], Wv, Wo row-major; bq | bk), on the stream
@@ -127,10 +125,7 @@ int vt_op_attention_core_backward_stages(vt_context* c, const void* qk16, const 
     if (B <= 0 || S <= 0) return c->fail(VT_ERR_INVALID, "vt_op_attention_core_backward: B and S must be >= 1");
     if (!qk16 || !vT16 || !o || !dout || !shift || !sums || !dq || !dk || !dv) return c->fail(VT_ERR_INVALID, "vt_op_attention_core_backward: null buffer");
     if (group < 0 || nsplit < 0) return c->fail(VT_ERR_INVALID, "vt_op_attention_core_backward: group and nsplit must be >= 0 (0 = chosen from the shape)");
-    const size_t need = vt_op_attention_core_backward_workspace_bytes(B, S, C);
-    if (!ws || ((uintptr_t)ws % ALIGN) || ws_bytes < need)
-        return c->fail(VT_ERR_INVALID, "vt_op_attention_core_backward: workspace must be 256-byte aligned and hold vt_op_attention_core_backward_workspace_bytes = %zu "
-                       "bytes (got %zu)", need, ws_bytes);
+    VTCK(check_workspace(c, "vt_op_attention_core_backward", ws, ws_bytes, vt_op_attention_core_backward_workspace_bytes(B, S, C), ALIGN));
     hipStream_t s = (hipStream_t)stream;
     const BwdWs w = carve_bwd((char*)ws, B, S, C);
     const int lp = (int)attn_pitch_of(S), ld8 = (S + 7) / 8 * 8, Sp = (int)round64(S);

@@ -1,6 +1,6 @@
 // C ABI (include/vae_tagger_hip.h): context life cycle, weight upload, flags, status word, the decoder / evaluator / preprocess /
 // resize entry points, diagnostics and the profiler read-out.  The encoder lives in weights.hip (packing), encoder.hip and
-// attention.hip (launch schedule); the single-layer entry points in ops.hip.
+// attention.hip (launch schedule); the single-layer entry points in ops.hip and ops_backward.hip.
 // No torch types, no host synchronisation inside hot-path calls, caller-owned buffers.
 #include <math.h>
 #include <string.h>

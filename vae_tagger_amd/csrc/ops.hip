@@ -1,21 +1,10 @@
-// The vt_op_* single-layer entry points: one kernel (or one conv of the encoder's schedule) on caller-owned buffers.
-#include <algorithm>
-
-#include "vt_context.h"
+// The vt_op_* forward single-layer entry points: one kernel (or one conv of the encoder's schedule) on caller-owned buffers, and the synchronising
+// test entries (vt_op_conv3x3_block, vt_op_conv3x3_fp8, vt_op_conv_in).  The backward operators are ops_backward.hip.
+#include "vt_ops.h"
 
 using namespace vt;
 
 namespace {
-
-// the halo-type kernels read repacked weights: the context keeps one scratch buffer for them, grown on demand
-int ensure_op_scratch(vt_context* c, size_t bytes) {
-    if (c->op_scratch_bytes >= bytes) return VT_OK;
-    if (c->op_scratch) (void)hipFree(c->op_scratch);
-    c->op_scratch = nullptr; c->op_scratch_bytes = 0;
-    HIPCK(c, hipMalloc(&c->op_scratch, bytes), "hipMalloc(op scratch)");
-    c->op_scratch_bytes = bytes;
-    return VT_OK;
-}
 
 template <class V>
 hipError_t to_device(void* dst, const std::vector<V>& v) { return hipMemcpy(dst, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice); }
@@ -34,15 +23,14 @@ int vt_op_conv2d(vt_context* c, const void* x, const void* w, const float* bias,
     if (Hout < 1 || Wout < 1) return c->fail(VT_ERR_INVALID, "vt_op_conv2d: empty output");
     hipStream_t s = (hipStream_t)stream;
     if (c->use_halo_conv && ksize == 3 && stride == 1 && pad_lo == 1 && pad_hi == 1 && vt_conv3x3_halo_supported(Cin, Cout)) {
-        VTCK(ensure_op_scratch(c, (size_t)Cout * 9 * Cin * 2));
-        HIPCK(c, vt_launch_repack_ohwi_to_halo((const bf16_t*)w, (bf16_t*)c->op_scratch, Cin, Cout, s), "repack");
         Conv3x3Args h{};
-        h.X = (const bf16_t*)x; h.Wp = (const bf16_t*)c->op_scratch; h.bias = bias; h.res = res; h.out_f32 = o32;
+        VTCK(repack_halo(c, w, Cin, Cout, s, &h.Wp));
+        h.X = (const bf16_t*)x; h.bias = bias; h.res = res; h.out_f32 = o32;
         h.out_bf16 = (bf16_t*)o16; h.zeros = c->zeros; h.batch = B; h.H = Hin; h.W = Win; h.Cin = Cin; h.Cout = Cout;
         return launch_halo(c, h, s, "vt_op_conv2d(halo)");
     }
     if (c->s2_halo && ksize == 3 && stride == 2 && pad_lo == 0 && pad_hi == 1 && Hin >= 2 && Win >= 2 && vt_conv3x3_s2_supported(Cin, Cout)) {
-        VTCK(ensure_op_scratch(c, (size_t)Cout * 9 * Cin * 2));
+        VTCK(c->ensure_op_scratch((size_t)Cout * 9 * Cin * 2));
         HIPCK(c, vt_launch_repack_ohwi_to_s2((const bf16_t*)w, (bf16_t*)c->op_scratch, Cin, Cout, s), "repack");
         ConvW cw; cw.cin = Cin; cw.cout = Cout; cw.k = 3; cw.wp2 = (const bf16_t*)c->op_scratch; cw.b = bias;
         return run_conv(c, cw, (const bf16_t*)x, B, Hin, Win, 2, 0, Hout, Wout, res, o32, (bf16_t*)o16, s);
@@ -66,11 +54,10 @@ int vt_op_norm_silu_conv3x3(vt_context* c, const void* x, int x_dtype, const flo
     if (x_dtype != VT_F32 && x_dtype != VT_BF16) return c->fail(VT_ERR_INVALID, "vt_op_norm_silu_conv3x3: x must be f32 or bf16");
     if (!vt_conv3x3_halo_supported(Cin, Cout) || Cin * 8 > 8192) return c->fail(VT_ERR_INVALID, "vt_op_norm_silu_conv3x3: unsupported channel counts %d -> %d", Cin, Cout);
     hipStream_t s = (hipStream_t)stream;
-    VTCK(ensure_op_scratch(c, (size_t)Cout * 9 * Cin * 2));
-    HIPCK(c, vt_launch_repack_ohwi_to_halo((const bf16_t*)w, (bf16_t*)c->op_scratch, Cin, Cout, s), "repack");
     Conv3x3Args h{};
+    VTCK(repack_halo(c, w, Cin, Cout, s, &h.Wp));
     h.X = x_dtype == VT_BF16 ? (const bf16_t*)x : nullptr; h.Xf32 = x_dtype == VT_F32 ? (const float*)x : nullptr;
-    h.scale_shift = scale_shift; h.Wp = (const bf16_t*)c->op_scratch; h.bias = bias; h.res = res; h.out_f32 = o32;
+    h.scale_shift = scale_shift; h.bias = bias; h.res = res; h.out_f32 = o32;
     h.out_bf16 = (bf16_t*)o16; h.zeros = c->zeros; h.batch = B; h.H = H; h.W = W; h.Cin = Cin; h.Cout = Cout;
     return launch_halo(c, h, s, "vt_op_norm_silu_conv3x3");
 }
@@ -89,27 +76,20 @@ int vt_op_conv2d_gn(vt_context* c, const void* x, const void* w, const float* bi
                     float eps, const float* gamma, const float* beta, float* scale_shift, void* ws, void* stream) {
     if (!c) return VT_ERR_INVALID;
     DeviceGuard guard(c);
-    if (!gamma || !beta || !scale_shift || !ws || groups < 1 || groups > 64 || Cout % groups) return c->fail(VT_ERR_INVALID, "vt_op_conv2d_gn: bad argument");
-    const int cpg = Cout / groups;
-    if (cpg != 4 && cpg != 8 && cpg != 16) return c->fail(VT_ERR_INVALID, "vt_op_conv2d_gn: channels per group must be 4, 8 or 16");
+    // ---- every refusal of this function comes before its first launch (run_conv makes its own before it launches)
+    if (!ws) return c->fail(VT_ERR_INVALID, "vt_op_conv2d_gn: bad argument");
+    VTCK(check_gn_epilogue(c, "vt_op_conv2d_gn", gamma, beta, scale_shift, Cout, groups));
+    if (!bias) return c->fail(VT_ERR_INVALID, "vt_op_conv2d_gn: bias required");
     const int Hout = (Hin + pad_lo + pad_hi - ksize) / stride + 1, Wout = (Win + pad_lo + pad_hi - ksize) / stride + 1;
     ConvW cw; cw.cin = Cin; cw.cout = Cout; cw.k = ksize; cw.w = (const bf16_t*)w; cw.b = bias;
     hipStream_t s = (hipStream_t)stream;
-    if (c->use_halo_conv && ksize == 3 && stride == 1 && pad_lo == 1 && pad_hi == 1 && vt_conv3x3_halo_supported(Cin, Cout)) {
-        VTCK(ensure_op_scratch(c, (size_t)Cout * 9 * Cin * 2));
-        HIPCK(c, vt_launch_repack_ohwi_to_halo(cw.w, (bf16_t*)c->op_scratch, Cin, Cout, s), "repack");
-        cw.wp = (const bf16_t*)c->op_scratch;
-    }
-    if (!bias) return c->fail(VT_ERR_INVALID, "vt_op_conv2d_gn: bias required");
+    if (c->use_halo_conv && ksize == 3 && stride == 1 && pad_lo == 1 && pad_hi == 1 && vt_conv3x3_halo_supported(Cin, Cout))
+        VTCK(repack_halo(c, w, Cin, Cout, s, &cw.wp));
     GnState gn; gn.partial = (float*)ws;
     ConvOpts o; o.gn = &gn; o.groups = groups;
-    const int saved = c->fuse_gn_stats; c->fuse_gn_stats = 1;
-    int r = run_conv(c, cw, (const bf16_t*)x, B, Hin, Win, stride, pad_lo, Hout, Wout, res, o32, (bf16_t*)o16, s, o);
-    c->fuse_gn_stats = saved;
-    if (r) return r;
-    if (gn.parts == 0) return c->fail(VT_ERR_INVALID, "vt_op_conv2d_gn: this shape has no stats epilogue");
-    HIPCK(c, vt_launch_gn_finalize(gn.partial, gn.parts, B, Cout, groups, eps, gamma, beta, scale_shift, s), "gn_finalize");
-    return VT_OK;
+    FuseGnStats stats_on(c);
+    VTCK(run_conv(c, cw, (const bf16_t*)x, B, Hin, Win, stride, pad_lo, Hout, Wout, res, o32, (bf16_t*)o16, s, o));
+    return finish_gn_stats(c, "vt_op_conv2d_gn", gn, B, Cout, groups, eps, gamma, beta, scale_shift, s);
 }
 
 // Upsample2D (nearest 2x + conv3x3) of the low-resolution x: the folded kernel, or with vt_set_flag(ctx, 22, 1) / a shape it refuses the
@@ -126,7 +106,7 @@ static int op_upsample2x_conv3x3(vt_context* c, const void* x, const float* w, c
     const int parts_max = std::max({vt_conv3x3_up2_tiles(h, wd), vt_conv3x3_halo_tiles_max(2 * h, 2 * wd), vt_conv_gemm_ptiles(4 * h * wd, C)});
     const size_t gn_bytes = want_gn ? align_up((size_t)B * parts_max * groups * 3 * 4) : 0;
     const size_t w_bytes = align_up((size_t)C * C * 16 * 2), up_bytes = align_up((size_t)B * 4 * h * wd * C * 2);
-    VTCK(ensure_op_scratch(c, gn_bytes + w_bytes + (folded ? 0 : up_bytes)));
+    VTCK(c->ensure_op_scratch(gn_bytes + w_bytes + (folded ? 0 : up_bytes)));
     char* p = (char*)c->op_scratch;
     GnState gn; gn.partial = (float*)p; p += gn_bytes;
     bf16_t* wp = (bf16_t*)p; p += w_bytes;
@@ -146,16 +126,10 @@ static int op_upsample2x_conv3x3(vt_context* c, const void* x, const float* w, c
         ConvW cw; cw.cin = C; cw.cout = C; cw.k = 3; cw.b = bias;
         if (halo) { cw.wp = wp; cw.wp16 = wp; } else cw.w = wp;
         ConvOpts o; o.x_f16 = f16; o.groups = want_gn ? groups : 32; o.gn = want_gn ? &gn : nullptr;
-        const int saved = c->fuse_gn_stats; c->fuse_gn_stats = 1;
-        const int r = run_conv(c, cw, up, B, 2 * h, 2 * wd, 1, 1, 2 * h, 2 * wd, nullptr, o32, nullptr, s, o);
-        c->fuse_gn_stats = saved;
-        if (r) return r;
+        FuseGnStats stats_on(c);
+        VTCK(run_conv(c, cw, up, B, 2 * h, 2 * wd, 1, 1, 2 * h, 2 * wd, nullptr, o32, nullptr, s, o));
     }
-    if (want_gn) {
-        if (gn.parts == 0) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_gn: this shape has no stats epilogue");
-        HIPCK(c, vt_launch_gn_finalize(gn.partial, gn.parts, B, C, groups, eps, gamma, beta, scale_shift, s), "gn_finalize");
-    }
-    return VT_OK;
+    return want_gn ? finish_gn_stats(c, "vt_op_upsample2x_conv3x3_gn", gn, B, C, groups, eps, gamma, beta, scale_shift, s) : VT_OK;
 }
 
 int vt_op_upsample2x_conv3x3(vt_context* c, const void* x, const float* w_oihw, const float* bias, float* o32, int B, int h, int w, int C,
@@ -169,9 +143,8 @@ int vt_op_upsample2x_conv3x3_gn(vt_context* c, const void* x, const float* w_oih
                                 int groups, float eps, const float* gamma, const float* beta, float* scale_shift, void* stream) {
     if (!c) return VT_ERR_INVALID;
     DeviceGuard guard(c);
-    if (!gamma || !beta || !scale_shift || !bias || groups < 1 || groups > 64 || C % groups) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_gn: bad argument");
-    const int cpg = C / groups;
-    if (cpg != 4 && cpg != 8 && cpg != 16) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_gn: channels per group must be 4, 8 or 16");
+    if (!bias) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_gn: bad argument");
+    VTCK(check_gn_epilogue(c, "vt_op_upsample2x_conv3x3_gn", gamma, beta, scale_shift, C, groups));
     return op_upsample2x_conv3x3(c, x, w_oihw, bias, o32, B, h, w, C, groups, eps, gamma, beta, scale_shift, (hipStream_t)stream);
 }
 
@@ -261,12 +234,8 @@ int vt_op_conv3x3_block(vt_context* c, const void* x, int x_planar, const float*
     const bool want_gn = scale_shift != nullptr;
     const int Ho = stride == 2 ? H / 2 : H, Wo = stride == 2 ? W / 2 : W;
     if (want_gn) {
-        if (!gamma || !beta || groups < 1 || groups > 64 || Cout % groups) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: bad GroupNorm argument");
-        const int cpg = Cout / groups;
-        if (cpg != 4 && cpg != 8 && cpg != 16) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: channels per group must be 4, 8 or 16");
-        const size_t need = vt_op_conv3x3_block_workspace_bytes(B, H, W, Cout, stride);
-        if (!ws || ((uintptr_t)ws % ALIGN) || ws_bytes < need)
-            return c->fail(VT_ERR_WORKSPACE, "vt_op_conv3x3_block: workspace must be 256-B aligned and hold vt_op_conv3x3_block_workspace_bytes = %zu bytes (got %zu)", need, ws_bytes);
+        VTCK(check_gn_epilogue(c, "vt_op_conv3x3_block", gamma, beta, scale_shift, Cout, groups));
+        VTCK(check_workspace(c, "vt_op_conv3x3_block", ws, ws_bytes, vt_op_conv3x3_block_workspace_bytes(B, H, W, Cout, stride), ALIGN, VT_ERR_WORKSPACE));
         // the generic GEMM (flag 0 / 13 off, or a stride-2 conv with an fp16 residual) has a stats epilogue on whole 128- / 256-cout tiles only
         const bool gemm = stride == 1 ? !c->use_halo_conv : !(c->s2_halo && !(res && rdt == 2));
         if (gemm && Cout > 128 && (Cout % 256)) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: the generic GEMM has no stats epilogue for %d couts", Cout);
@@ -300,14 +269,9 @@ int vt_op_conv3x3_block(vt_context* c, const void* x, int x_planar, const float*
     ConvOpts o;
     o.x_f16 = f16; o.o16_f16 = out16_f16 != 0; o.planar = stride == 1 ? out16_planar != 0 : x_planar != 0; o.rdt = rdt;
     o.sc = has_sc ? &scf : nullptr; o.gn = want_gn ? &gn : nullptr; o.groups = want_gn ? groups : 32;
-    const int saved = c->fuse_gn_stats; c->fuse_gn_stats = 1;
-    const int r = run_conv(c, cw, (const bf16_t*)x, B, H, W, stride, stride == 1 ? 1 : 0, Ho, Wo, res, out, (bf16_t*)o16, s, o);
-    c->fuse_gn_stats = saved;
-    if (r) return r;
-    if (want_gn) {
-        if (gn.parts == 0) return c->fail(VT_ERR_INVALID, "vt_op_conv3x3_block: this shape has no stats epilogue");
-        HIPCK(c, vt_launch_gn_finalize(gn.partial, gn.parts, B, Cout, groups, eps, gamma, beta, scale_shift, s), "gn_finalize");
-    }
+    FuseGnStats stats_on(c);
+    VTCK(run_conv(c, cw, (const bf16_t*)x, B, H, W, stride, stride == 1 ? 1 : 0, Ho, Wo, res, out, (bf16_t*)o16, s, o));
+    if (want_gn) VTCK(finish_gn_stats(c, "vt_op_conv3x3_block", gn, B, Cout, groups, eps, gamma, beta, scale_shift, s));
     HIPCK(c, hipStreamSynchronize(s), "vt_op_conv3x3_block sync");
     return VT_OK;
 }
@@ -367,331 +331,6 @@ int vt_op_groupnorm(vt_context* c, const void* x, int x_dtype, int B, int HW, in
     HIPCK(c, vt_launch_gn_stats(x, f, B, HW, C, groups, partial, &nchunks, s), "gn_stats");
     HIPCK(c, vt_launch_gn_finalize(partial, nchunks, B, C, groups, eps, gamma, beta, ss, s), "gn_finalize");
     HIPCK(c, vt_launch_gn_apply(x, f, ss, (bf16_t*)y, B, HW, C, silu, s), "gn_apply");
-    return VT_OK;
-}
-
-// ---- backward of the resnet block's layers: bf16 operands whatever flag 18 says, fp32 results, no atomics ----
-
-size_t vt_op_cast_bias_grad_workspace_bytes(long long rows, int C) {
-    const int chunks = vt_cast_bias_chunks(rows, C);
-    return chunks > 0 ? align_up((size_t)chunks * C * sizeof(double)) : 0;
-}
-
-int vt_op_cast_bias_grad(vt_context* c, const float* dy, void* dy16, float* dbias, long long rows, int C, void* ws, size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    if (!dy || (!dy16 && !dbias)) return c->fail(VT_ERR_INVALID, "vt_op_cast_bias_grad: null buffer");
-    if (rows <= 0 || !vt_cast_bias_supported(C) || vt_cast_bias_chunks(rows, C) <= 0)
-        return c->fail(VT_ERR_INVALID, "vt_op_cast_bias_grad: needs rows > 0 and C a multiple of 4, at most 1024 (got rows %lld, C %d)", rows, C);
-    if (dbias && (!ws || ((uintptr_t)ws % 16) || ws_bytes < vt_op_cast_bias_grad_workspace_bytes(rows, C)))
-        return c->fail(VT_ERR_INVALID, "vt_op_cast_bias_grad: workspace must be 16-byte aligned and hold vt_op_cast_bias_grad_workspace_bytes = %zu bytes (got %zu)",
-                       vt_op_cast_bias_grad_workspace_bytes(rows, C), ws_bytes);
-    HIPCK(c, vt_launch_cast_bias_grad(dy, (bf16_t*)dy16, dbias, rows, C, (double*)ws, (hipStream_t)stream), "vt_op_cast_bias_grad");
-    return VT_OK;
-}
-
-// dx = conv(dy16, W'), W'[ci][ky'][kx'][co] = bf16(W[co][ci][2 - ky'][2 - kx']): the forward conv with Cout input and Cin output channels.  The packed
-// weights go to the operator scratch behind `keep` bytes the caller has its own use for (the literal routes of the resampling layers).
-static int conv_dgrad_launch(vt_context* c, const void* dy16, const float* w_oihw, const float* dx_add, float* dx, int B, int H, int W, int Cin, int Cout,
-                             int ksize, size_t keep, hipStream_t s, const char* what) {
-    const int taps = ksize * ksize;
-    const size_t w_bytes = align_up((size_t)Cin * taps * Cout * 2);
-    const bool halo = c->use_halo_conv && ksize == 3 && vt_conv3x3_halo_supported(Cout, Cin);
-    VTCK(ensure_op_scratch(c, keep + w_bytes * (halo ? 2 : 1)));
-    bf16_t* wt = (bf16_t*)((char*)c->op_scratch + keep);
-    HIPCK(c, vt_launch_pack_dgrad_weights(w_oihw, wt, Cin, Cout, ksize, s), "pack_dgrad_weights");
-    if (halo) {
-        bf16_t* wp = (bf16_t*)((char*)wt + w_bytes);
-        HIPCK(c, vt_launch_repack_ohwi_to_halo(wt, wp, Cout, Cin, s), "repack");
-        Conv3x3Args h{};
-        h.X = (const bf16_t*)dy16; h.Wp = wp; h.res = dx_add; h.out_f32 = dx; h.zeros = c->zeros; h.batch = B; h.H = H; h.W = W; h.Cin = Cout; h.Cout = Cin;
-        return launch_halo(c, h, s, what);
-    }
-    ConvGemmArgs a{};
-    a.X = (const bf16_t*)dy16; a.W = wt; a.res = dx_add; a.out_f32 = dx; a.zeros = c->zeros;
-    a.Hin = H; a.Win = W; a.Hout = H; a.Wout = W; a.Cin = Cout; a.Cout = Cin; a.Wrows = Cin; a.ksize = ksize; a.stride = 1; a.pad = ksize / 2;
-    a.ldx = Cout; a.ldw = taps * Cout; a.ldo = Cin; a.ldr = Cin;
-    a.x_bs = (long long)H * W * Cout; a.o_bs = (long long)H * W * Cin; a.r_bs = a.o_bs; a.batch = B; a.alpha = 1.f; a.bias_mode = 0;
-    return launch_gemm(c, a, s, what);
-}
-
-int vt_op_conv_backward_data(vt_context* c, const void* dy16, const float* w_oihw, const float* dx_add, float* dx, int B, int H, int W, int Cin, int Cout,
-                             int ksize, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    if (!dy16 || !w_oihw || !dx) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_data: null buffer");
-    if (ksize != 1 && ksize != 3) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_data: ksize must be 1 or 3 (stride 1, pad ksize / 2), got %d", ksize);
-    if (B <= 0 || H <= 0 || W <= 0 || Cin < 8 || (Cin % 8) || Cout < 8 || (Cout % 8))
-        return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_data: Cin and Cout must be multiples of 8 and B, H, W >= 1 (got %d -> %d, %d x %d x %d)", Cin, Cout, B, H, W);
-    return conv_dgrad_launch(c, dy16, w_oihw, dx_add, dx, B, H, W, Cin, Cout, ksize, 0, (hipStream_t)stream, "vt_op_conv_backward_data");
-}
-
-static int wgrad_splits(int B, int H, int W, int Cin, int Cout, int splits) {
-    const int steps = vt_conv_wgrad_steps(B, H, W);
-    if (splits <= 0) return vt_conv_wgrad_auto_splits(B, H, W, Cin, Cout);
-    return splits > steps ? steps : splits;             // more slices than pixel steps: clamped, every slice holds at least one step
-}
-
-size_t vt_op_conv_backward_weight_workspace_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int splits) {
-    if (!vt_conv_wgrad_supported(Cin, Cout, ksize) || vt_conv_wgrad_steps(B, H, W) <= 0) return 0;
-    return align_up((size_t)wgrad_splits(B, H, W, Cin, Cout, splits) * Cout * Cin * ksize * ksize * sizeof(float));
-}
-
-int vt_op_conv_backward_weight(vt_context* c, const void* dy16, const void* a16, float* dw, int B, int H, int W, int Cin, int Cout, int ksize, int splits,
-                               void* ws, size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    if (!dy16 || !a16 || !dw) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: null buffer");
-    if (!vt_conv_wgrad_supported(Cin, Cout, ksize))
-        return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: Cin and Cout must be multiples of 64 and ksize 1 or 3 (got %d -> %d, ksize %d)", Cin, Cout, ksize);
-    if (B <= 0 || H <= 0 || W <= 0 || vt_conv_wgrad_steps(B, H, W) <= 0) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: B, H, W must be >= 1");
-    if (splits < 0) return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: splits must be >= 0 (0 = chosen from the shape)");
-    const size_t need = vt_op_conv_backward_weight_workspace_bytes(B, H, W, Cin, Cout, ksize, splits);
-    if (!ws || ((uintptr_t)ws % 16) || ((uintptr_t)dw % 16) || ws_bytes < need)
-        return c->fail(VT_ERR_INVALID, "vt_op_conv_backward_weight: workspace must be 16-byte aligned and hold vt_op_conv_backward_weight_workspace_bytes = %zu "
-                       "bytes (got %zu)", need, ws_bytes);
-    ConvWgradArgs a{};
-    a.dy = (const bf16_t*)dy16; a.a = (const bf16_t*)a16; a.dw = dw; a.ws = (float*)ws; a.batch = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksize = ksize;
-    a.splits = wgrad_splits(B, H, W, Cin, Cout, splits);
-    HIPCK(c, vt_launch_conv_wgrad(a, (hipStream_t)stream), "vt_op_conv_backward_weight");
-    return VT_OK;
-}
-
-// ---- backward of the two resampling layers: Downsample2D's stride-2 conv and Upsample2D ----
-
-// Downsample2D: y = conv3x3(pad(x, (0,1,0,1)), W), stride 2.  dy16 [B][H/2][W/2][Cout] -> dx [B][H][W][Cin].  The scatter kernel, or with
-// vt_set_flag(ctx, 23, 1) / channel counts it refuses the literal route: dy16 scattered to the odd positions of a zeroed H x W tensor, then
-// vt_op_conv_backward_data's launch.
-int vt_op_conv_s2_backward_data(vt_context* c, const void* dy16, const float* w_oihw, const float* dx_add, float* dx, int B, int H, int W, int Cin, int Cout,
-                                void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    if (!dy16 || !w_oihw || !dx) return c->fail(VT_ERR_INVALID, "vt_op_conv_s2_backward_data: null buffer");
-    if (B <= 0 || H < 2 || W < 2 || Cin < 8 || (Cin % 8) || Cout < 8 || (Cout % 8))
-        return c->fail(VT_ERR_INVALID, "vt_op_conv_s2_backward_data: Cin and Cout must be multiples of 8, B >= 1 and H, W >= 2 (got %d -> %d, %d x %d x %d)", Cin, Cout,
-                       B, H, W);
-    if ((long long)H * W * std::max(Cin, Cout) >= (1LL << 31)) return c->fail(VT_ERR_INVALID, "vt_op_conv_s2_backward_data: image too large (32-bit per-image offsets)");
-    hipStream_t s = (hipStream_t)stream;
-    if (!c->s2_dgrad_literal && vt_conv3x3_s2_dgrad_supported(Cin, Cout) && (Cout % 64) == 0) {
-        VTCK(ensure_op_scratch(c, align_up((size_t)Cout * 9 * Cin * 2)));
-        HIPCK(c, vt_launch_pack_s2_dgrad(w_oihw, (bf16_t*)c->op_scratch, Cin, Cout, s), "pack_s2_dgrad");
-        ConvS2DgradArgs a{};
-        a.dy = (const bf16_t*)dy16; a.Wp = (const bf16_t*)c->op_scratch; a.dx_add = dx_add; a.dx = dx; a.zeros = c->zeros;
-        a.batch = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-        HIPCK(c, vt_launch_conv3x3_s2_dgrad(a, s), "conv3x3_s2_dgrad");
-        return VT_OK;
-    }
-    const size_t keep = align_up((size_t)B * H * W * Cout * 2);
-    VTCK(ensure_op_scratch(c, keep + 2 * align_up((size_t)Cin * 9 * Cout * 2)));      // (sized once: the launch below must not move the buffer)
-    HIPCK(c, vt_launch_scatter_odd_nhwc16(dy16, c->op_scratch, B, H, W, Cout, s), "scatter_odd");
-    return conv_dgrad_launch(c, c->op_scratch, w_oihw, dx_add, dx, B, H, W, Cin, Cout, 3, keep, s, "vt_op_conv_s2_backward_data(literal)");
-}
-
-static int rs_wgrad_splits(int mode, int B, int Hdy, int Wdy, int Cin, int Cout, int splits) {
-    const int steps = vt_conv_wgrad_rs_steps(mode, B, Hdy, Wdy);
-    if (splits <= 0) return vt_conv_wgrad_rs_auto_splits(mode, B, Hdy, Wdy, Cin, Cout);
-    return splits > steps ? steps : splits;
-}
-
-static size_t rs_wgrad_ws_bytes(int mode, int B, int Hdy, int Wdy, int Cin, int Cout, int splits) {
-    if (splits < 0 || !vt_conv_wgrad_supported(Cin, Cout, 3) || vt_conv_wgrad_rs_steps(mode, B, Hdy, Wdy) <= 0) return 0;
-    return align_up((size_t)rs_wgrad_splits(mode, B, Hdy, Wdy, Cin, Cout, splits) * Cout * Cin * 9 * sizeof(float));
-}
-
-static int rs_wgrad(vt_context* c, const char* name, int mode, const void* dy16, const void* a16, float* dw, int B, int Hdy, int Wdy, int aH, int aW, int Cin, int Cout,
-                    int splits, void* ws, size_t ws_bytes, void* stream) {
-    if (!dy16 || !a16 || !dw) return c->fail(VT_ERR_INVALID, "%s: null buffer", name);
-    if (!vt_conv_wgrad_supported(Cin, Cout, 3)) return c->fail(VT_ERR_INVALID, "%s: channel counts must be multiples of 64 (got %d -> %d)", name, Cin, Cout);
-    if (B <= 0 || aH < (mode == 1 ? 2 : 1) || aW < (mode == 1 ? 2 : 1) || vt_conv_wgrad_rs_steps(mode, B, Hdy, Wdy) <= 0)
-        return c->fail(VT_ERR_INVALID, "%s: B must be >= 1 and the layer's input at least %s (got %d x %d x %d)", name, mode == 1 ? "2 x 2" : "1 x 1", B, aH, aW);
-    if (splits < 0) return c->fail(VT_ERR_INVALID, "%s: splits must be >= 0 (0 = chosen from the shape)", name);
-    const size_t need = rs_wgrad_ws_bytes(mode, B, Hdy, Wdy, Cin, Cout, splits);
-    if (!ws || ((uintptr_t)ws % 16) || ((uintptr_t)dw % 16) || ws_bytes < need)
-        return c->fail(VT_ERR_INVALID, "%s: workspace must be 16-byte aligned and hold %s_workspace_bytes = %zu bytes (got %zu)", name, name, need, ws_bytes);
-    ConvWgradArgs a{};
-    a.dy = (const bf16_t*)dy16; a.a = (const bf16_t*)a16; a.dw = dw; a.ws = (float*)ws; a.batch = B; a.H = Hdy; a.W = Wdy; a.aH = aH; a.aW = aW; a.Cin = Cin; a.Cout = Cout;
-    a.ksize = 3; a.splits = rs_wgrad_splits(mode, B, Hdy, Wdy, Cin, Cout, splits);
-    HIPCK(c, vt_launch_conv_wgrad_rs(a, mode, (hipStream_t)stream), name);
-    return VT_OK;
-}
-
-size_t vt_op_conv_s2_backward_weight_workspace_bytes(int B, int H, int W, int Cin, int Cout, int splits) {
-    if (H < 2 || W < 2) return 0;
-    return rs_wgrad_ws_bytes(1, B, H / 2, W / 2, Cin, Cout, splits);
-}
-
-int vt_op_conv_s2_backward_weight(vt_context* c, const void* dy16, const void* a16, float* dw, int B, int H, int W, int Cin, int Cout, int splits, void* ws,
-                                  size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    return rs_wgrad(c, "vt_op_conv_s2_backward_weight", 1, dy16, a16, dw, B, H / 2, W / 2, H, W, Cin, Cout, splits, ws, ws_bytes, stream);
-}
-
-// Upsample2D: y = conv3x3(nearest2x(x), W).  dy16 [B][2h][2w][C] -> dx [B][h][w][C].  The route follows the forward's: the gather kernel on the
-// transposed folded matrices, or with vt_set_flag(ctx, 22, 1) / a C it refuses the literal one on bf16(W): vt_op_conv_backward_data's launch at
-// 2h x 2w into scratch, then the 2x2 sum.
-int vt_op_upsample2x_conv3x3_backward_data(vt_context* c, const void* dy16, const float* w_oihw, const float* dx_add, float* dx, int B, int h, int wd, int C,
-                                           void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    if (!dy16 || !w_oihw || !dx) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_backward_data: null buffer");
-    if (B <= 0 || h <= 0 || wd <= 0 || C < 8 || (C % 8))
-        return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_backward_data: C must be a multiple of 8 and B, h, w >= 1 (got %d, %d x %d x %d)", C, B, h, wd);
-    if ((long long)B * h * wd * C >= (1LL << 29)) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_backward_data: tensor too large for the operator entry");
-    hipStream_t s = (hipStream_t)stream;
-    if (!c->up2_literal && vt_conv3x3_up2_dgrad_supported(C)) {
-        VTCK(ensure_op_scratch(c, align_up((size_t)C * 16 * C * 2)));
-        HIPCK(c, vt_launch_pack_up2_dgrad(w_oihw, (bf16_t*)c->op_scratch, C, s), "pack_up2_dgrad");
-        ConvUp2DgradArgs a{};
-        a.dy = (const bf16_t*)dy16; a.Wp = (const bf16_t*)c->op_scratch; a.dx_add = dx_add; a.dx = dx; a.zeros = c->zeros; a.batch = B; a.H = h; a.W = wd; a.C = C;
-        HIPCK(c, vt_launch_conv3x3_up2_dgrad(a, s), "conv3x3_up2_dgrad");
-        return VT_OK;
-    }
-    const size_t keep = align_up((size_t)B * 4 * h * wd * C * sizeof(float));
-    VTCK(ensure_op_scratch(c, keep + 2 * align_up((size_t)C * 9 * C * 2)));
-    float* t = (float*)c->op_scratch;
-    VTCK(conv_dgrad_launch(c, dy16, w_oihw, nullptr, t, B, 2 * h, 2 * wd, C, C, 3, keep, s, "vt_op_upsample2x_conv3x3_backward_data(literal)"));
-    HIPCK(c, vt_launch_sum2x2_f32(t, dx_add, dx, B, h, wd, C, s), "sum2x2");
-    return VT_OK;
-}
-
-size_t vt_op_upsample2x_conv3x3_backward_weight_workspace_bytes(int B, int h, int w, int C, int splits) {
-    if (h < 1 || w < 1 || h >= (1 << 29) || w >= (1 << 29)) return 0;
-    return rs_wgrad_ws_bytes(2, B, 2 * h, 2 * w, C, C, splits);
-}
-
-int vt_op_upsample2x_conv3x3_backward_weight(vt_context* c, const void* dy16, const void* x16, float* dw, int B, int h, int w, int C, int splits, void* ws,
-                                             size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    if (h >= (1 << 29) || w >= (1 << 29)) return c->fail(VT_ERR_INVALID, "vt_op_upsample2x_conv3x3_backward_weight: shape too large");
-    return rs_wgrad(c, "vt_op_upsample2x_conv3x3_backward_weight", 2, dy16, x16, dw, B, 2 * h, 2 * w, h, w, C, C, splits, ws, ws_bytes, stream);
-}
-
-// ---- the full-resolution end convs, 3 channels on one side ----
-
-static int thin_wgrad_splits(int B, int H, int W, int Cw, int splits) {
-    const int steps = vt_conv_thin_wgrad_steps(B, H, W);
-    if (splits <= 0) return vt_conv_thin_wgrad_auto_splits(B, H, W, Cw);
-    return splits > steps ? steps : splits;
-}
-
-size_t vt_op_conv_thin_backward_weight_workspace_bytes(int B, int H, int W, int Cw, int splits) {
-    if (splits < 0 || !vt_conv_thin_wgrad_supported(Cw) || vt_conv_thin_wgrad_steps(B, H, W) <= 0) return 0;
-    return align_up(vt_conv_thin_wgrad_ws_bytes(Cw, thin_wgrad_splits(B, H, W, Cw, splits)));
-}
-
-int vt_op_conv_thin_backward_weight(vt_context* c, const float* thin, const void* wide16, int thin_is_input, float* dw, float* thin_sums, int B, int H, int W,
-                                    int Cw, int splits, void* ws, size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    VTCK(vt_op_backward_operands_check(c));
-    if (!thin || !wide16 || !dw) return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: null buffer");
-    if (!vt_conv_thin_wgrad_supported(Cw))
-        return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: Cw must be a multiple of 64, at most 512 (got %d)", Cw);
-    if (B <= 0 || H <= 0 || W <= 0 || vt_conv_thin_wgrad_steps(B, H, W) <= 0) return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: B, H, W must be >= 1");
-    if (splits < 0) return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: splits must be >= 0 (0 = chosen from the shape)");
-    const size_t need = vt_op_conv_thin_backward_weight_workspace_bytes(B, H, W, Cw, splits);
-    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
-        return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_backward_weight: workspace must be 16-byte aligned and hold "
-                       "vt_op_conv_thin_backward_weight_workspace_bytes = %zu bytes (got %zu)", need, ws_bytes);
-    ConvThinWgradArgs a{};
-    a.thin = thin; a.wide = (const bf16_t*)wide16; a.dw = dw; a.thin_sums = thin_sums; a.ws = ws; a.batch = B; a.H = H; a.W = W; a.Cw = Cw;
-    a.thin_is_input = thin_is_input; a.splits = thin_wgrad_splits(B, H, W, Cw, splits);
-    HIPCK(c, vt_launch_conv_thin_wgrad(a, (hipStream_t)stream), "vt_op_conv_thin_backward_weight");
-    return VT_OK;
-}
-
-// packed weights (the larger of the two layouts), then C zeros for the bias
-static size_t thin_forward_pack_bytes(int C) { return align_up(std::max((size_t)27 * C * sizeof(float), (size_t)2 * 128 * 32 * 2)); }
-
-size_t vt_op_conv_thin_forward_workspace_bytes(int C) {
-    if (C < 8 || (C % 8)) return 0;
-    return thin_forward_pack_bytes(C) + align_up((size_t)C * sizeof(float));
-}
-
-int vt_op_conv_thin_forward(vt_context* c, const float* x, const float* w, const float* bias, int transpose_rotate, float* o32, void* o16, int B, int H, int W,
-                            int C, void* ws, size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    VTCK(vt_op_backward_operands_check(c));
-    if (!x || !w || (!o32 && !o16)) return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_forward: null buffer");
-    if (B <= 0 || H <= 0 || W <= 0 || C < 8 || (C % 8) || C > 256)
-        return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_forward: C must be a multiple of 8, at most 256, and B, H, W >= 1 (got %d, %d x %d x %d)", C, B, H, W);
-    const size_t need = vt_op_conv_thin_forward_workspace_bytes(C);
-    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
-        return c->fail(VT_ERR_INVALID, "vt_op_conv_thin_forward: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    const bool mfma = C == 128 && c->conv_in_mfma;
-    float* zero_bias = (float*)((char*)ws + thin_forward_pack_bytes(C));
-    if (transpose_rotate) bias = nullptr;
-    HIPCK(c, vt_launch_pack_conv_thin(w, bias, transpose_rotate != 0, mfma, ws, zero_bias, C, s), "pack_conv_thin");
-    const float* b = bias ? bias : zero_bias;
-    if (mfma) HIPCK(c, vt_launch_conv_in_mfma(x, (const bf16_t*)ws, b, o32, (bf16_t*)o16, nullptr, nullptr, nullptr, B, H, W, s), "vt_op_conv_thin_forward");
-    else HIPCK(c, vt_launch_conv_in(x, (const float*)ws, b, o32, (bf16_t*)o16, nullptr, nullptr, 0, nullptr, B, H, W, C, s), "vt_op_conv_thin_forward");
-    return VT_OK;
-}
-
-// The block functions (vae_backward.py) mix these operators with the forward ones, which follow flag 18: they ask here first.
-int vt_op_backward_operands_check(vt_context* c) {
-    if (!c) return VT_ERR_INVALID;
-    if (c->f16_ops) return c->fail(VT_ERR_INVALID, "the resnet block's backward runs on bf16 operands: fp16-operand mode (vt_set_flag 18) must be off");
-    return VT_OK;
-}
-
-size_t vt_op_groupnorm_stats_workspace_bytes(int B, int HW, int C) {
-    const size_t n = vt_gn_stats64_ws_bytes(B, HW, C);
-    return n ? align_up(n) : 0;
-}
-
-int vt_op_groupnorm_stats(vt_context* c, const float* x, int B, int HW, int C, int groups, float eps, float* stats, void* ws, size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    if (!x || !stats) return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: null buffer");
-    if (B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups))
-        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: channels per group must be 2, 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
-    const size_t need = vt_op_groupnorm_stats_workspace_bytes(B, HW, C);
-    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
-        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_stats: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
-    HIPCK(c, vt_launch_gn_stats64(x, B, HW, C, groups, eps, stats, ws, (hipStream_t)stream), "vt_op_groupnorm_stats");
-    return VT_OK;
-}
-
-size_t vt_op_groupnorm_silu_backward_workspace_bytes(int B, int HW, int C) {
-    const size_t n = vt_gn_silu_bwd_ws_bytes(B, HW, C);
-    return n ? align_up(n) : 0;
-}
-
-int vt_op_groupnorm_silu_backward(vt_context* c, const float* x, const float* stats, const float* gamma, const float* beta, const float* da,
-                                  const float* dx_add, float* dx, void* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws,
-                                  size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    if (!x || !stats || !gamma || !beta || !da || !dx) return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: null buffer");
-    if (B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups))
-        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: channels per group must be 2, 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
-    const size_t need = vt_op_groupnorm_silu_backward_workspace_bytes(B, HW, C);
-    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
-        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_silu_backward: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
-    HIPCK(c, vt_launch_gn_silu_backward(x, stats, gamma, beta, da, dx_add, dx, (bf16_t*)dx16, dgamma, dbeta, B, HW, C, groups, ws, (hipStream_t)stream),
-          "vt_op_groupnorm_silu_backward");
-    return VT_OK;
-}
-
-size_t vt_op_groupnorm_backward_workspace_bytes(int B, int HW, int C) { return vt_op_groupnorm_silu_backward_workspace_bytes(B, HW, C); }
-
-int vt_op_groupnorm_backward(vt_context* c, const float* x, const float* stats, const float* gamma, const float* beta, const float* dh, const float* dx_add,
-                             float* dx, void* dx16, float* dgamma, float* dbeta, int B, int HW, int C, int groups, void* ws, size_t ws_bytes, void* stream) {
-    if (!c) return VT_ERR_INVALID;
-    DeviceGuard guard(c);
-    if (!x || !stats || !gamma || !beta || !dh || !dx) return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: null buffer");
-    if (B <= 0 || HW <= 0 || groups > 64 || !vt_gn_silu_bwd_supported(C, groups))
-        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: channels per group must be 2, 4, 8 or 16 and C a power of two from 16 to 1024 (got C %d, %d groups)", C, groups);
-    const size_t need = vt_op_groupnorm_backward_workspace_bytes(B, HW, C);
-    if (!ws || ((uintptr_t)ws % 16) || ws_bytes < need)
-        return c->fail(VT_ERR_INVALID, "vt_op_groupnorm_backward: workspace must be 16-byte aligned and hold %zu bytes (got %zu)", need, ws_bytes);
-    HIPCK(c, vt_launch_gn_backward(x, stats, gamma, beta, dh, dx_add, dx, (bf16_t*)dx16, dgamma, dbeta, B, HW, C, groups, ws, (hipStream_t)stream),
-          "vt_op_groupnorm_backward");
     return VT_OK;
 }
 

@@ -1,6 +1,7 @@
 // Internal to the host side of the library: the context behind the C ABI, the packed-weight tables, and the few functions that
-// cross the host units (weights.hip, encoder.hip, vae_run.hip, image_decoder.hip, attention.hip, ops.hip, capi.hip): the conv / GroupNorm
-// launch helpers of encoder.hip and attention.hip's entry.  The run layer both VAE schedules are built on (VaeRun: workspace plan and
+// cross the host units (weights.hip, encoder.hip, vae_run.hip, image_decoder.hip, attention.hip, attention_backward.hip, ops.hip,
+// ops_backward.hip, capi.hip): the conv / GroupNorm launch helpers of encoder.hip and attention.hip's entry.  What the operator entries share
+// on top of it (their argument checks) is vt_ops.h.  The run layer both VAE schedules are built on (VaeRun: workspace plan and
 // carve, resnet / mid-attention / conv_out steps) has a header of its own, vt_vae_run.h.  Nothing here is part of the public header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -177,6 +178,16 @@ struct vt_context {
     void free_allocs(std::vector<void*>& v) {
         for (void* p : v) (void)hipFree(p);
         v.clear();
+    }
+    // the operators' halo-type kernels read repacked weights: op_scratch, one buffer for them, grown on demand (its contents are not kept)
+    int ensure_op_scratch(size_t bytes) {
+        if (op_scratch_bytes >= bytes) return VT_OK;
+        if (op_scratch) (void)hipFree(op_scratch);
+        op_scratch = nullptr; op_scratch_bytes = 0;
+        const hipError_t e = hipMalloc(&op_scratch, bytes);
+        if (e != hipSuccess) return hipfail(e, "hipMalloc(op scratch)");
+        op_scratch_bytes = bytes;
+        return VT_OK;
     }
     const vt::HostTensor* find(const std::string& k) const {
         auto it = weights.find(k);

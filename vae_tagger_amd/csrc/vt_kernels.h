@@ -1,4 +1,4 @@
-// Internal launcher interface between the kernel translation units and the host units behind the C ABI (weights.hip, encoder.hip, attention.hip, ops.hip, capi.hip).
+// Internal launcher interface between the kernel translation units and the host units behind the C ABI (weights.hip, encoder.hip, attention.hip, ops.hip, ops_backward.hip, capi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vt_common.h"

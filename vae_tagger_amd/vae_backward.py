@@ -61,18 +61,41 @@ def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)      # (torch's allocations are 512-byte aligned)
 
 
+def _call_ws(ctx, op, size_args, t, *args):
+    """ctx.call(op, *args, ws, ws_bytes, stream): the workspace is what `<op>_workspace_bytes(*size_args)` asks for (none with size_args None), on
+    t's device, the stream torch's current one there."""
+    n = getattr(ctx.lib, op + "_workspace_bytes")(*size_args) if size_args is not None else 0
+    ws = _workspace(n, t.device)
+    ctx.call(op, *args, _vp(ws), ws.numel(), _stream(t))
+
+
+def _grads_like(params, *parts):
+    """the gradients of parts ((prefix, grads keyed without it), ...) under their full names, keyed and ordered like params"""
+    g = {p + k: v for p, gp in parts for k, v in gp.items()}
+    return {k: g[k] for k in params}
+
+
 def cast_bias_grad(dy, *, want_dy16=True, want_bias=True):
     """dy fp32 [..., C] -> (bf16 copy or None, column sums over all leading dimensions or None), one pass."""
     dy = _f32(dy, "dy")
-    ctx = context(dy.device)
     C = dy.shape[-1]
     rows = dy.numel() // C
     dy16 = torch.empty(dy.shape, dtype=torch.bfloat16, device=dy.device) if want_dy16 else None
     db = torch.empty(C, dtype=torch.float32, device=dy.device) if want_bias else None
-    n = ctx.lib.vt_op_cast_bias_grad_workspace_bytes(rows, C) if want_bias else 0
-    ws = _workspace(n, dy.device)
-    ctx.call("vt_op_cast_bias_grad", _vp(dy), _vp(dy16), _vp(db), rows, C, _vp(ws), ws.numel(), _stream(dy))
+    _call_ws(context(dy.device), "vt_op_cast_bias_grad", (rows, C) if want_bias else None, dy, _vp(dy), _vp(dy16), _vp(db), rows, C)
     return dy16, db
+
+
+def _dy16_and_bias(dy, need_bias, need_dy16=True):
+    """dy: the fp32 gradient, or its bf16 copy when no bias gradient is asked for (a producer that already wrote the copy saves the cast pass).
+    -> (dy16, dbias or None); no pass at all where neither is needed."""
+    if dy.dtype == torch.bfloat16:
+        if need_bias:
+            raise ValueError("the bias gradient needs the fp32 dy")
+        return dy, None
+    if not (need_dy16 or need_bias):
+        return None, None
+    return cast_bias_grad(dy, want_dy16=need_dy16, want_bias=need_bias)
 
 
 def conv_backward_data(dy16, weight, *, dx_add=None):
@@ -97,22 +120,16 @@ def conv_backward_weight(dy16, a16, ksize, *, splits=0):
     Cin = a16.shape[-1]
     if tuple(a16.shape[:3]) != (B, H, W):
         raise ValueError("a16 does not match dy16")
-    ctx = context(dy16.device)
     dw = torch.empty(Cout, Cin, ksize, ksize, dtype=torch.float32, device=dy16.device)
-    ws = _workspace(ctx.lib.vt_op_conv_backward_weight_workspace_bytes(B, H, W, Cin, Cout, ksize, int(splits)), dy16.device)
-    ctx.call("vt_op_conv_backward_weight", _vp(dy16), _vp(a16), _vp(dw), B, H, W, Cin, Cout, ksize, int(splits), _vp(ws), ws.numel(), _stream(dy16))
+    shape = (B, H, W, Cin, Cout, ksize, int(splits))
+    _call_ws(context(dy16.device), "vt_op_conv_backward_weight", shape, dy16, _vp(dy16), _vp(a16), _vp(dw), *shape)
     return dw
 
 
 def conv_backward(dy, a16, weight, *, need_input=True, need_weight=True, need_bias=True, dx_add=None, splits=0):
     """Backward of y = conv(a16, bf16(weight)) + bias, stride 1, 3x3 pad 1 or 1x1.  dy: the fp32 gradient [B, H, W, Cout], or its bf16 copy when
     no bias gradient is asked for (a producer that already wrote the copy saves the cast pass).  -> (dx or None, dW or None, dbias or None)."""
-    if dy.dtype == torch.bfloat16:
-        if need_bias:
-            raise ValueError("the bias gradient needs the fp32 dy")
-        dy16, db = dy, None
-    else:
-        dy16, db = cast_bias_grad(dy, want_bias=need_bias)
+    dy16, db = _dy16_and_bias(dy, need_bias)
     dw = conv_backward_weight(dy16, a16, weight.shape[2], splits=splits) if need_weight else None
     dx = conv_backward_data(dy16, weight, dx_add=dx_add) if need_input else None
     return dx, dw, db
@@ -121,21 +138,17 @@ def conv_backward(dy, a16, weight, *, need_input=True, need_weight=True, need_bi
 def groupnorm_stats(x, groups=GROUPS, eps=EPS):
     """x fp32 [B, ..., C] -> (mean, rstd) fp32 [B, groups, 2]"""
     x = _f32(x, "x")
-    ctx = context(x.device)
     B, C = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * C)
     stats = torch.empty(B, groups, 2, dtype=torch.float32, device=x.device)
-    ws = _workspace(ctx.lib.vt_op_groupnorm_stats_workspace_bytes(B, HW, C), x.device)
-    ctx.call("vt_op_groupnorm_stats", _vp(x), B, HW, C, groups, float(eps), _vp(stats), _vp(ws), ws.numel(), _stream(x))
+    _call_ws(context(x.device), "vt_op_groupnorm_stats", (B, HW, C), x, _vp(x), B, HW, C, groups, float(eps), _vp(stats))
     return stats
 
 
-def groupnorm_silu_backward(x, stats, gamma, beta, da, *, dx_add=None, want_dx16=False):
-    """Backward of a = silu(GroupNorm(x)).  -> (dx fp32, dx16 bf16 or None, dgamma, dbeta); dx_add (fp32, x's shape) is added into dx."""
-    x, da = _f32(x, "x"), _f32(da, "da")
-    if da.shape != x.shape or (dx_add is not None and _f32(dx_add, "dx_add").shape != x.shape):
-        raise ValueError("da and dx_add must have x's shape")
-    ctx = context(x.device)
+def _groupnorm_backward(op, x, stats, gamma, beta, d, d_name, dx_add, want_dx16):
+    x, d = _f32(x, "x"), _f32(d, d_name)
+    if d.shape != x.shape or (dx_add is not None and _f32(dx_add, "dx_add").shape != x.shape):
+        raise ValueError(f"{d_name} and dx_add must have x's shape")
     B, C = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * C)
     groups = stats.shape[1]
@@ -143,10 +156,19 @@ def groupnorm_silu_backward(x, stats, gamma, beta, da, *, dx_add=None, want_dx16
     dx16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_dx16 else None
     dg = torch.empty(C, dtype=torch.float32, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device)
-    ws = _workspace(ctx.lib.vt_op_groupnorm_silu_backward_workspace_bytes(B, HW, C), x.device)
-    ctx.call("vt_op_groupnorm_silu_backward", _vp(x), _vp(_f32(stats, "stats")), _vp(_f32(gamma, "gamma")), _vp(_f32(beta, "beta")), _vp(da), _vp(dx_add),
-             _vp(dx), _vp(dx16), _vp(dg), _vp(db), B, HW, C, groups, _vp(ws), ws.numel(), _stream(x))
+    _call_ws(context(x.device), op, (B, HW, C), x, _vp(x), _vp(_f32(stats, "stats")), _vp(_f32(gamma, "gamma")), _vp(_f32(beta, "beta")), _vp(d), _vp(dx_add),
+             _vp(dx), _vp(dx16), _vp(dg), _vp(db), B, HW, C, groups)
     return dx, dx16, dg, db
+
+
+def groupnorm_silu_backward(x, stats, gamma, beta, da, *, dx_add=None, want_dx16=False):
+    """Backward of a = silu(GroupNorm(x)).  -> (dx fp32, dx16 bf16 or None, dgamma, dbeta); dx_add (fp32, x's shape) is added into dx."""
+    return _groupnorm_backward("vt_op_groupnorm_silu_backward", x, stats, gamma, beta, da, "da", dx_add, want_dx16)
+
+
+def groupnorm_backward(x, stats, gamma, beta, dh, *, dx_add=None, want_dx16=False):
+    """Backward of h = GroupNorm(x) (no activation).  -> (dx fp32, dx16 bf16 or None, dgamma, dbeta); dx_add (fp32, x's shape) is added into dx."""
+    return _groupnorm_backward("vt_op_groupnorm_backward", x, stats, gamma, beta, dh, "dh", dx_add, want_dx16)
 
 
 # ---- the block ------------------------------------------------------------------------------------------------------------------------------------
@@ -236,7 +258,7 @@ def resnet_block_backward(params, saved, dy, *, splits=0, want_dx16=False):
     # 6. norm1 + SiLU, the shortcut's gradient added in the same pass
     dx, dx16, g["norm1.weight"], g["norm1.bias"] = groupnorm_silu_backward(saved["x"], saved["stats1"], params["norm1.weight"], params["norm1.bias"], da1, dx_add=dxs,
                                                                               want_dx16=want_dx16)
-    g = {k: g[k] for k in params}
+    g = _grads_like(params, ("", g))
     return (dx, g, dx16) if want_dx16 else (dx, g)
 
 
@@ -263,10 +285,9 @@ def downsample_backward_weight(dy16, a16, *, splits=0):
     Cout = dy16.shape[-1]
     if tuple(dy16.shape[:3]) != (B, H // 2, W // 2):
         raise ValueError("a16 does not match dy16")
-    ctx = context(dy16.device)
     dw = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=dy16.device)
-    ws = _workspace(ctx.lib.vt_op_conv_s2_backward_weight_workspace_bytes(B, H, W, Cin, Cout, int(splits)), dy16.device)
-    ctx.call("vt_op_conv_s2_backward_weight", _vp(dy16), _vp(a16), _vp(dw), B, H, W, Cin, Cout, int(splits), _vp(ws), ws.numel(), _stream(dy16))
+    shape = (B, H, W, Cin, Cout, int(splits))
+    _call_ws(context(dy16.device), "vt_op_conv_s2_backward_weight", shape, dy16, _vp(dy16), _vp(a16), _vp(dw), *shape)
     return dw
 
 
@@ -291,20 +312,14 @@ def upsample_backward_weight(dy16, x16, *, splits=0):
     B, h, w, C = x16.shape
     if tuple(dy16.shape) != (B, 2 * h, 2 * w, C):
         raise ValueError("x16 does not match dy16")
-    ctx = context(dy16.device)
     dw = torch.empty(C, C, 3, 3, dtype=torch.float32, device=dy16.device)
-    ws = _workspace(ctx.lib.vt_op_upsample2x_conv3x3_backward_weight_workspace_bytes(B, h, w, C, int(splits)), dy16.device)
-    ctx.call("vt_op_upsample2x_conv3x3_backward_weight", _vp(dy16), _vp(x16), _vp(dw), B, h, w, C, int(splits), _vp(ws), ws.numel(), _stream(dy16))
+    shape = (B, h, w, C, int(splits))
+    _call_ws(context(dy16.device), "vt_op_upsample2x_conv3x3_backward_weight", shape, dy16, _vp(dy16), _vp(x16), _vp(dw), *shape)
     return dw
 
 
 def _resample_backward(data_fn, weight_fn, dy, need_input, need_weight, need_bias, splits):
-    if dy.dtype == torch.bfloat16:
-        if need_bias:
-            raise ValueError("the bias gradient needs the fp32 dy")
-        dy16, db = dy, None
-    else:
-        dy16, db = cast_bias_grad(dy, want_bias=need_bias)
+    dy16, db = _dy16_and_bias(dy, need_bias)
     dw = weight_fn(dy16, splits) if need_weight else None
     dx = data_fn(dy16) if need_input else None
     return dx, dw, db
@@ -390,17 +405,18 @@ def _block_forward_train(params, x, resample, forward):
 def _block_backward(params, saved, dy, resample, backward, splits, want_dx16=False):
     context(dy.device).call("vt_op_backward_operands_check")
     parts, rs = _split_block(params, resample)
-    g = {}
+    g = []
     if rs is not None:
-        dy, g[resample + "weight"], g[resample + "bias"] = backward(_f32(dy, "dy"), saved[resample]["x16"], rs["weight"], splits=splits)
+        dy, dw, db = backward(_f32(dy, "dy"), saved[resample]["x16"], rs["weight"], splits=splits)
+        g.append((resample, {"weight": dw, "bias": db}))
     dx16 = None
     for p in reversed(list(parts)):
         if want_dx16 and p == "resnets.0.":
             dy, gp, dx16 = resnet_block_backward(parts[p], saved[p], dy, splits=splits, want_dx16=True)
         else:
             dy, gp = resnet_block_backward(parts[p], saved[p], dy, splits=splits)
-        g.update({p + k: v for k, v in gp.items()})
-    g = {k: g[k] for k in params}
+        g.append((p, gp))
+    g = _grads_like(params, *g)
     return (dy, g, dx16) if want_dx16 else (dy, g)
 
 
@@ -433,25 +449,6 @@ ATTN_PARAMS = ["group_norm.weight", "group_norm.bias", "to_q.weight", "to_q.bias
 ATTN_SAVED = ["x", "h16", "qk16", "vT16", "o16", "o", "shift", "sums", "stats"]
 
 
-def groupnorm_backward(x, stats, gamma, beta, dh, *, dx_add=None, want_dx16=False):
-    """Backward of h = GroupNorm(x) (no activation).  -> (dx fp32, dx16 bf16 or None, dgamma, dbeta); dx_add (fp32, x's shape) is added into dx."""
-    x, dh = _f32(x, "x"), _f32(dh, "dh")
-    if dh.shape != x.shape or (dx_add is not None and _f32(dx_add, "dx_add").shape != x.shape):
-        raise ValueError("dh and dx_add must have x's shape")
-    ctx = context(x.device)
-    B, C = x.shape[0], x.shape[-1]
-    HW = x.numel() // (B * C)
-    groups = stats.shape[1]
-    dx = torch.empty_like(x)
-    dx16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_dx16 else None
-    dg = torch.empty(C, dtype=torch.float32, device=x.device)
-    db = torch.empty(C, dtype=torch.float32, device=x.device)
-    ws = _workspace(ctx.lib.vt_op_groupnorm_backward_workspace_bytes(B, HW, C), x.device)
-    ctx.call("vt_op_groupnorm_backward", _vp(x), _vp(_f32(stats, "stats")), _vp(_f32(gamma, "gamma")), _vp(_f32(beta, "beta")), _vp(dh), _vp(dx_add),
-             _vp(dx), _vp(dx16), _vp(dg), _vp(db), B, HW, C, groups, _vp(ws), ws.numel(), _stream(x))
-    return dx, dx16, dg, db
-
-
 def attention_core_backward(qk16, vT16, o, do, shift, sums, *, want_bf16=True, group=0, nsplit=0):
     """dq, dk, dv of o = softmax(q k^T / sqrt(C)) v from what attention_block_forward_train saved.  qk16 bf16 [B, S, 2C], vT16 bf16 [B, C, pitch],
     o and do fp32 [B, S, C], shift fp32 [B, S], sums fp32 [4, B, S].  -> (dq, dk, dv fp32 [B, S, C], (dq16, dk16, dv16) or None).  `group` (images per
@@ -466,9 +463,8 @@ def attention_core_backward(qk16, vT16, o, do, shift, sums, *, want_bf16=True, g
             raise ValueError("shift must be [B, S] and sums [4, B, S]")
     outs = [torch.empty(B, S, C, dtype=torch.float32, device=o.device) for _ in range(3)]
     outs16 = [torch.empty(B, S, C, dtype=torch.bfloat16, device=o.device) for _ in range(3)] if want_bf16 else [None] * 3
-    ws = _workspace(ctx.lib.vt_op_attention_core_backward_workspace_bytes(B, S, C), o.device)
-    ctx.call("vt_op_attention_core_backward", _vp(qk16), _vp(vT16), _vp(o), _vp(do), _vp(shift), _vp(sums), *[_vp(t) for t in outs], *[_vp(t) for t in outs16],
-             B, S, C, int(group), int(nsplit), _vp(ws), ws.numel(), _stream(o))
+    _call_ws(ctx, "vt_op_attention_core_backward", (B, S, C), o, _vp(qk16), _vp(vT16), _vp(o), _vp(do), _vp(shift), _vp(sums), *[_vp(t) for t in outs],
+             *[_vp(t) for t in outs16], B, S, C, int(group), int(nsplit))
     return outs[0], outs[1], outs[2], (tuple(outs16) if want_bf16 else None)
 
 
@@ -500,9 +496,8 @@ def attention_block_forward_train(params, x):
              "vT16": torch.empty(B, C, pitch, dtype=bf, device=dev), "o16": torch.empty(B, H, W, C, dtype=bf, device=dev),
              "o": torch.empty(B, S, C, dtype=f32, device=dev), "shift": torch.empty(B, S, dtype=f32, device=dev),
              "sums": torch.empty(4, B, S, dtype=f32, device=dev), "stats": torch.empty(B, GROUPS, 2, dtype=f32, device=dev)}
-    ws = _workspace(ctx.lib.vt_op_attention_forward_train_workspace_bytes(B, S, C), dev)
-    ctx.call("vt_op_attention_forward_train", _vp(x), *[_vp(params[n]) for n in ATTN_PARAMS], _vp(y), *[_vp(saved[n]) for n in ATTN_SAVED[1:]], B, S, C,
-             _vp(ws), ws.numel(), _stream(x))
+    _call_ws(ctx, "vt_op_attention_forward_train", (B, S, C), x, _vp(x), *[_vp(params[n]) for n in ATTN_PARAMS], _vp(y), *[_vp(saved[n]) for n in ATTN_SAVED[1:]],
+             B, S, C)
     return y, saved
 
 
@@ -532,7 +527,7 @@ def attention_block_backward(params, saved, dy, *, splits=0, group=0, nsplit=0):
     # 4. the norm, the residual's dy added in the same pass
     dx, _, g["group_norm.weight"], g["group_norm.bias"] = groupnorm_backward(saved["x"], saved["stats"], params["group_norm.weight"], params["group_norm.bias"], dh,
                                                                               dx_add=dy)
-    return dx, {k: g[k] for k in params}
+    return dx, _grads_like(params, ("", g))
 
 
 # ---- the mid block: resnets.0, attentions.0, resnets.1 ---------------------------------------------------------------------------------------------
@@ -565,12 +560,12 @@ def mid_block_forward_train(params, x):
 def mid_block_backward(params, saved, dy, *, splits=0):
     """dy fp32 NHWC, the gradient of mid_block_forward_train's y.  -> (dx fp32 NHWC, grads keyed like params)"""
     parts = _split_mid(params)
-    g = {}
+    g = []
     for p, kind in reversed(MID_PARTS):
         bwd = resnet_block_backward if kind == "resnet" else attention_block_backward
         dy, gp = bwd(parts[p], saved[p], dy, splits=splits)
-        g.update({p + k: v for k, v in gp.items()})
-    return dy, {k: g[k] for k in params}
+        g.append((p, gp))
+    return dy, _grads_like(params, *g)
 
 
 # ---- the end convs (DESIGN.md section 4.23) ---------------------------------------------------------------------------------------------------------
@@ -594,12 +589,10 @@ def conv_thin_backward_weight(thin_nchw, wide16, thin_is_input, *, want_sums=Fal
     Cw = wide16.shape[-1]
     if tuple(wide16.shape[:3]) != (B, H, W):
         raise ValueError("wide16 does not match thin")
-    ctx = context(thin.device)
     dw = torch.empty((Cw, 3, 3, 3) if thin_is_input else (3, Cw, 3, 3), dtype=torch.float32, device=thin.device)
     sums = torch.empty(3, dtype=torch.float32, device=thin.device) if want_sums else None
-    ws = _workspace(ctx.lib.vt_op_conv_thin_backward_weight_workspace_bytes(B, H, W, Cw, int(splits)), thin.device)
-    ctx.call("vt_op_conv_thin_backward_weight", _vp(thin), _vp(wide16), int(bool(thin_is_input)), _vp(dw), _vp(sums), B, H, W, Cw, int(splits), _vp(ws), ws.numel(),
-             _stream(thin))
+    shape = (B, H, W, Cw, int(splits))
+    _call_ws(context(thin.device), "vt_op_conv_thin_backward_weight", shape, thin, _vp(thin), _vp(wide16), int(bool(thin_is_input)), _vp(dw), _vp(sums), *shape)
     return dw, sums
 
 
@@ -613,11 +606,9 @@ def conv_thin_forward(x_nchw, weight, bias=None, *, transpose_rotate=False, want
         raise ValueError("weight must be [C, 3, 3, 3], or [3, C, 3, 3] with transpose_rotate")
     if bias is not None and tuple(_f32(bias, "bias").shape) != (C,):
         raise ValueError("bias must be [C]")
-    ctx = context(x.device)
     o32 = torch.empty(B, H, W, C, dtype=torch.float32, device=x.device) if want_f32 else None
     o16 = torch.empty(B, H, W, C, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
-    ws = _workspace(ctx.lib.vt_op_conv_thin_forward_workspace_bytes(C), x.device)
-    ctx.call("vt_op_conv_thin_forward", _vp(x), _vp(weight), _vp(bias), int(bool(transpose_rotate)), _vp(o32), _vp(o16), B, H, W, C, _vp(ws), ws.numel(), _stream(x))
+    _call_ws(context(x.device), "vt_op_conv_thin_forward", (C,), x, _vp(x), _vp(weight), _vp(bias), int(bool(transpose_rotate)), _vp(o32), _vp(o16), B, H, W, C)
     return o32, o16
 
 
@@ -625,14 +616,9 @@ def conv_in_backward(dy, x_nchw, *, need_weight=True, need_bias=True, splits=0, 
     """Backward of encoder.conv_in, y = conv(x, W) + b with x the fp32 NCHW image.  dy: the fp32 gradient NHWC [B, H, W, C], or its bf16 copy when no bias
     gradient is asked for; dy16 (optional): the bf16 copy a producer already wrote beside the fp32 dy.  -> (dW [C, 3, 3, 3], db); the image's own gradient
     is not offered."""
-    if dy.dtype == torch.bfloat16:
-        if need_bias:
-            raise ValueError("the bias gradient needs the fp32 dy")
-        dy16, db = dy, None
-    else:
-        want16 = need_weight and dy16 is None
-        c16, db = cast_bias_grad(dy, want_dy16=want16, want_bias=need_bias) if (want16 or need_bias) else (None, None)
-        dy16 = c16 if dy16 is None else dy16
+    c16, db = _dy16_and_bias(dy, need_bias, need_dy16=need_weight and dy16 is None)
+    if dy16 is None or dy.dtype == torch.bfloat16:
+        dy16 = c16
     dw = conv_thin_backward_weight(x_nchw, dy16, True, splits=splits)[0] if need_weight else None
     return dw, db
 
@@ -755,17 +741,17 @@ def encoder_backward(params, saved, d_moments, *, splits=0, boundaries=None):
     at["conv_norm_out"] = dy = _norm_out_backward(ends, saved["conv_norm_out."], dy, g, "encoder.")
     dy, gp = mid_block_backward(mid, saved["mid_block."], dy, splits=splits)
     at["mid_block"] = dy
-    g.update({"encoder.mid_block." + k: v for k, v in gp.items()})
+    parts = [("encoder.mid_block.", gp)]
     dy16 = None
     for i in reversed(range(len(blks))):
         if i == 0:          # conv_in's weight gradient takes the bf16 copy norm1's pass writes: no cast pass at full resolution
             dy, gp, dy16 = down_block_backward(blks[i], saved[f"down_blocks.{i}."], dy, splits=splits, want_dx16=True)
         else:
             dy, gp = down_block_backward(blks[i], saved[f"down_blocks.{i}."], dy, splits=splits)
-        g.update({f"encoder.down_blocks.{i}." + k: v for k, v in gp.items()})
+        parts.append((f"encoder.down_blocks.{i}.", gp))
         at[f"down_blocks.{i}"] = dy
     g["encoder.conv_in.weight"], g["encoder.conv_in.bias"] = conv_in_backward(dy, saved["x"], splits=splits, dy16=dy16)
-    return {k: g[k] for k in params}
+    return _grads_like(params, ("", g), *parts)
 
 
 def decoder_forward_train(params, z_nchw):
@@ -803,15 +789,16 @@ def decoder_backward(params, saved, d_image, *, splits=0, boundaries=None):
     g = {}
     dy, g["decoder.conv_out.weight"], g["decoder.conv_out.bias"] = conv_out_backward(d, saved["conv_norm_out."]["a16"], ends["conv_out."]["weight"], splits=splits)
     at["conv_norm_out"] = dy = _norm_out_backward(ends, saved["conv_norm_out."], dy, g, "decoder.")
+    parts = []
     for i in reversed(range(len(blks))):
         dy, gp = up_block_backward(blks[i], saved[f"up_blocks.{i}."], dy, splits=splits)
         at[f"up_blocks.{i}"] = dy
-        g.update({f"decoder.up_blocks.{i}." + k: v for k, v in gp.items()})
+        parts.append((f"decoder.up_blocks.{i}.", gp))
     dy, gp = mid_block_backward(mid, saved["mid_block."], dy, splits=splits)
     at["mid_block"] = dy
-    g.update({"decoder.mid_block." + k: v for k, v in gp.items()})
+    parts.append(("decoder.mid_block.", gp))
     dz, g["decoder.conv_in.weight"], g["decoder.conv_in.bias"] = latent_conv_in_backward(dy, saved["z16"], ends["conv_in."]["weight"], splits=splits)
-    return dz.permute(0, 3, 1, 2).contiguous(), {k: g[k] for k in params}
+    return dz.permute(0, 3, 1, 2).contiguous(), _grads_like(params, ("", g), *parts)
 
 
 # ---- what a batch keeps between forward and backward: pure-Python formulas, exactly the bytes of the `saved` structures ---------------------------------
@@ -919,8 +906,8 @@ def vae_loss_and_grads(params, anchor, positive, negative, labels_a=None, labels
     loss_out = torch.empty(4, dtype=torch.float64, device=a.device)
     vae_losses.loss_backward_device(*streams, dz_dec=dz, dz_draw=DECODE_DRAW, labels_a=labels_a, labels_p=labels_p,
                                     d_moments=[d_moments[i * B:(i + 1) * B] for i in range(3)], loss_out=loss_out, **common)
-    g.update(encoder_backward(enc, saved_e, d_moments, splits=splits, boundaries=at["encoder"]))
-    return dict(zip(vae_losses.LOSS_NAMES, loss_out.unbind())), {k: g[k] for k in params}
+    ge = encoder_backward(enc, saved_e, d_moments, splits=splits, boundaries=at["encoder"])
+    return dict(zip(vae_losses.LOSS_NAMES, loss_out.unbind())), _grads_like(params, ("", g), ("", ge))
 
 
 def vae_train_saved_bytes(params_or_config, B, H, W):
