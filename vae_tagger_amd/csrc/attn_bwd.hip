@@ -369,12 +369,7 @@ hipError_t vt_launch_attn_bwd_qk(const AttnBwdQkArgs& a, hipStream_t s) {
     const long long nblk = (long long)((a.S + QB - 1) / QB) * a.batch * nsp;
     if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_qk_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_qk_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_qk_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF);
-        return e;
-    });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, 2 * KBUF, attn_bwd_qk_kernel<0>, attn_bwd_qk_kernel<1>, attn_bwd_qk_kernel<2>);
     if (ea != hipSuccess) return ea;
     if (a.mode == 0) hipLaunchKernelGGL(attn_bwd_qk_kernel<0>, dim3((unsigned)nblk), dim3(512), 2 * KBUF, s, a);
     else if (a.mode == 1) hipLaunchKernelGGL(attn_bwd_qk_kernel<1>, dim3((unsigned)nblk), dim3(512), 2 * KBUF, s, a);
@@ -390,12 +385,9 @@ hipError_t vt_launch_attn_bwd_pv(const AttnBwdPvArgs& a, hipStream_t s) {
     const bool narrow = qblk * 2 < 192;
     const long long nblk = qblk * (narrow ? 4 : 2);
     if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-    static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_pv_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * ROWB);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_pv_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * ROWB);
-        return e;
-    });
+    static std::atomic<unsigned long long> attr_256{0}, attr_128{0};
+    hipError_t ea = vt_dynamic_smem_once(attr_256, 2 * 256 * ROWB, attn_bwd_pv_kernel<256>);
+    if (ea == hipSuccess) ea = vt_dynamic_smem_once(attr_128, 2 * 128 * ROWB, attn_bwd_pv_kernel<128>);
     if (ea != hipSuccess) return ea;
     if (narrow) hipLaunchKernelGGL(attn_bwd_pv_kernel<128>, dim3((unsigned)nblk), dim3(512), 2 * 128 * ROWB, s, a);
     else hipLaunchKernelGGL(attn_bwd_pv_kernel<256>, dim3((unsigned)nblk), dim3(512), 2 * 256 * ROWB, s, a);

@@ -23,13 +23,10 @@
 
 #include <type_traits>
 
-#include "vt_common.h"
+#include "vt_halo.h"
 #include "vt_kernels.h"
 
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int QB = 256;        // query rows per workgroup (8 waves x 32)
 constexpr int KT = 128;        // keys per LDS tile = one k-step of P.V
@@ -37,11 +34,6 @@ constexpr int D = 512;         // head dim
 constexpr int KROWB = D;       // bytes per key row in LDS (e4m3)
 constexpr int KBUF = KT * KROWB;    // 64 KB
 
-__device__ __forceinline__ int opaque8(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-__device__ __forceinline__ i32x8 cat8(i32x4 lo, i32x4 hi) { return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Q.K^T: P8 fragments + segment sums
@@ -73,7 +65,7 @@ __global__ __launch_bounds__(512, 2) void attn_qk_fp8_kernel(const AttnQk8Args a
         const unsigned char* src = row < a.S ? qb + (long long)row * a.ldq + fq * 32 : (const unsigned char*)a.zeros;
         const int step = row < a.S ? 128 : 0;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[j][ks] = cat8(*(const i32x4*)(src + ks * step), *(const i32x4*)(src + ks * step + (row < a.S ? 16 : 0)));
+        for (int ks = 0; ks < 4; ++ks) qf[j][ks] = vt_cat8(*(const i32x4*)(src + ks * step), *(const i32x4*)(src + ks * step + (row < a.S ? 16 : 0)));
     }
     float rv[2], sh2[2];
 #pragma unroll
@@ -93,7 +85,7 @@ __global__ __launch_bounds__(512, 2) void attn_qk_fp8_kernel(const AttnQk8Args a
     const int skey = 32 * (sr_ >> 2) + (sr_ & 3);                         // ... their key inside the block, before the row tile's 16 (m >> 2) + 4 (m & 3)
     const int schunk = ((lane & 31) ^ sr_) << 4;
     auto stage = [&](int kt, int buf) __attribute__((always_inline)) {
-        const int key_l = kt * KT + opaque8(skey);
+        const int key_l = kt * KT + vt_opaque(skey);
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
             const int key = key_l + 16 * (jj >> 2) + 4 * (jj & 3);
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(512, 2) void attn_qk_fp8_kernel(const AttnQk8Args a
             auto frag = [&](int idx) __attribute__((always_inline)) -> i32x8 {
                 const int ks = idx >> 2, m = 4 * h + (idx & 3);
                 const char* p = ks_base + (ks >> 1) * 256 + m * 16 * KROWB;
-                return cat8(*(const i32x4*)(p + kbase[ks & 1][0]), *(const i32x4*)(p + kbase[ks & 1][1]));
+                return vt_cat8(*(const i32x4*)(p + kbase[ks & 1][0]), *(const i32x4*)(p + kbase[ks & 1][1]));
             };
 #pragma unroll
             for (int p = 0; p < AHEAD; ++p) kf[p] = frag(p);
@@ -272,7 +264,7 @@ __global__ __launch_bounds__(512, 2) void proj_fp8_kernel(const ProjFp8Args a) {
         const unsigned char* src = row < a.nq ? qb + (long long)row * a.ldq + fq * 32 : (const unsigned char*)a.zeros;
         const int step = row < a.nq ? 128 : 0;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[j][ks] = cat8(*(const i32x4*)(src + ks * step), *(const i32x4*)(src + ks * step + (row < a.nq ? 16 : 0)));
+        for (int ks = 0; ks < 4; ++ks) qf[j][ks] = vt_cat8(*(const i32x4*)(src + ks * step), *(const i32x4*)(src + ks * step + (row < a.nq ? 16 : 0)));
         qbias[j] = (a.qbias && row < a.nq) ? a.qbias[row] * a.oscale : 0.f;
     }
     const float alpha = a.alpha * a.oscale;
@@ -281,7 +273,7 @@ __global__ __launch_bounds__(512, 2) void proj_fp8_kernel(const ProjFp8Args a) {
     const int skey = 32 * (sr_ >> 2) + (sr_ & 3);
     const int schunk = ((lane & 31) ^ sr_) << 4;
     auto stage = [&](int kt, int buf) __attribute__((always_inline)) {
-        const int key_l = kt * KT + opaque8(skey);
+        const int key_l = kt * KT + vt_opaque(skey);
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
             const int key = key_l + 16 * (jj >> 2) + 4 * (jj & 3);
@@ -346,7 +338,7 @@ __global__ __launch_bounds__(512, 2) void proj_fp8_kernel(const ProjFp8Args a) {
             auto frag = [&](int idx) __attribute__((always_inline)) -> i32x8 {
                 const int ks = idx >> 2, m = 4 * h + (idx & 3);
                 const char* p = ks_base + (ks >> 1) * 256 + m * 16 * KROWB;
-                return cat8(*(const i32x4*)(p + kbase[ks & 1][0]), *(const i32x4*)(p + kbase[ks & 1][1]));
+                return vt_cat8(*(const i32x4*)(p + kbase[ks & 1][0]), *(const i32x4*)(p + kbase[ks & 1][1]));
             };
 #pragma unroll
             for (int p = 0; p < AHEAD; ++p) kf[p] = frag(p);
@@ -429,7 +421,7 @@ __global__ __launch_bounds__(512, 2) void attn_pv_fp8_kernel(const AttnPv8Args a
         const unsigned char* s = pt + (long long)kt * 4096;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-            d[j] = cat8(__builtin_nontemporal_load((const i32x4*)(s + (j * 2) * 1024)), __builtin_nontemporal_load((const i32x4*)(s + (j * 2 + 1) * 1024)));
+            d[j] = vt_cat8(__builtin_nontemporal_load((const i32x4*)(s + (j * 2) * 1024)), __builtin_nontemporal_load((const i32x4*)(s + (j * 2 + 1) * 1024)));
     };
     stage(0, 0);
     load_p(0, pf);
@@ -443,7 +435,7 @@ __global__ __launch_bounds__(512, 2) void attn_pv_fp8_kernel(const AttnPv8Args a
         constexpr int AHEAD = 3, RING = 4;
         i32x8 af[RING];
         auto frag = [&](int ct) __attribute__((always_inline)) -> i32x8 {
-            return cat8(*(const i32x4*)(vs + ct * 16 * ROWB + foff0), *(const i32x4*)(vs + ct * 16 * ROWB + foff1));
+            return vt_cat8(*(const i32x4*)(vs + ct * 16 * ROWB + foff0), *(const i32x4*)(vs + ct * 16 * ROWB + foff1));
         };
 #pragma unroll
         for (int p = 0; p < AHEAD; ++p) af[p] = frag(p);
@@ -524,10 +516,7 @@ hipError_t vt_launch_attn_qk_fp8(const AttnQk8Args& a, hipStream_t s) {
     const long long nblk = (long long)((a.S + QB - 1) / QB) * a.batch * (a.nsplit > 1 ? a.nsplit : 1);
     if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_qk_fp8_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF);
-        return e != hipSuccess ? e : hipFuncSetAttribute((const void*)attn_qk_fp8_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF);
-    });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, 2 * KBUF, attn_qk_fp8_kernel<1>, attn_qk_fp8_kernel<3>);
     if (ea != hipSuccess) return ea;
     if (a.mode == 1) hipLaunchKernelGGL(attn_qk_fp8_kernel<1>, dim3((unsigned)nblk), dim3(512), 2 * KBUF, s, a);
     else hipLaunchKernelGGL(attn_qk_fp8_kernel<3>, dim3((unsigned)nblk), dim3(512), 2 * KBUF, s, a);
@@ -545,9 +534,7 @@ hipError_t vt_launch_proj_fp8(const ProjFp8Args& a, hipStream_t s) {
     const long long nblk = (long long)((a.nq + QB - 1) / QB) * a.batch * (a.nsplit > 1 ? a.nsplit : 1);
     if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        return hipFuncSetAttribute((const void*)proj_fp8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF);
-    });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, 2 * KBUF, proj_fp8_kernel);
     if (ea != hipSuccess) return ea;
     hipLaunchKernelGGL(proj_fp8_kernel, dim3((unsigned)nblk), dim3(512), 2 * KBUF, s, a);
     return hipGetLastError();
@@ -561,12 +548,9 @@ hipError_t vt_launch_attn_pv_fp8(const AttnPv8Args& a, hipStream_t s) {
     const bool narrow = qblk * 2 < 192;
     const long long nblk = qblk * (narrow ? 4 : 2);
     if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-    static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_pv_fp8_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * ROWB);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_pv_fp8_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * ROWB);
-        return e;
-    });
+    static std::atomic<unsigned long long> attr_256{0}, attr_128{0};
+    hipError_t ea = vt_dynamic_smem_once(attr_256, 2 * 256 * ROWB, attn_pv_fp8_kernel<256>);
+    if (ea == hipSuccess) ea = vt_dynamic_smem_once(attr_128, 2 * 128 * ROWB, attn_pv_fp8_kernel<128>);
     if (ea != hipSuccess) return ea;
     if (narrow) hipLaunchKernelGGL(attn_pv_fp8_kernel<128>, dim3((unsigned)nblk), dim3(512), 2 * 128 * ROWB, s, a);
     else hipLaunchKernelGGL(attn_pv_fp8_kernel<256>, dim3((unsigned)nblk), dim3(512), 2 * 256 * ROWB, s, a);

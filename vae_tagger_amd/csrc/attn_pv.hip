@@ -154,12 +154,9 @@ hipError_t vt_launch_attn_pv(const AttnPvArgs& a, hipStream_t s) {
     const bool narrow = qblk * 2 < 192;                 // the 256-channel form would leave a quarter or more of the CUs without a workgroup
     const long long nblk = qblk * (narrow ? 4 : 2);
     if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-    static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_pv_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * ROWB);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_pv_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * ROWB);
-        return e;
-    });
+    static std::atomic<unsigned long long> attr_256{0}, attr_128{0};
+    hipError_t ea = vt_dynamic_smem_once(attr_256, 2 * 256 * ROWB, attn_pv_kernel<256>);
+    if (ea == hipSuccess) ea = vt_dynamic_smem_once(attr_128, 2 * 128 * ROWB, attn_pv_kernel<128>);
     if (ea != hipSuccess) return ea;
     if (narrow) hipLaunchKernelGGL(attn_pv_kernel<128>, dim3((unsigned)nblk), dim3(512), 2 * 128 * ROWB, s, a);
     else hipLaunchKernelGGL(attn_pv_kernel<256>, dim3((unsigned)nblk), dim3(512), 2 * 256 * ROWB, s, a);

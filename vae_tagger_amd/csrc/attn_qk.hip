@@ -372,7 +372,7 @@ hipError_t vt_launch_attn_qk(const AttnQkArgs& a, hipStream_t s) {
         const long long nblk5 = (long long)((a.S + QB - 1) / QB) * a.batch * nsp;
         if (nblk5 > 0x7fffffffLL) return hipErrorInvalidValue;
         static std::atomic<unsigned long long> attr5{0};
-        hipError_t e5 = vt_once_per_device(attr5, [&] { return hipFuncSetAttribute((const void*)attn_qk_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF); });
+        hipError_t e5 = vt_dynamic_smem_once(attr5, 2 * KBUF, attn_qk_kernel<5>);
         if (e5 != hipSuccess) return e5;
         hipLaunchKernelGGL(attn_qk_kernel<5>, dim3((unsigned)nblk5), dim3(512), 2 * KBUF, s, a);
         return hipGetLastError();
@@ -386,7 +386,7 @@ hipError_t vt_launch_attn_qk(const AttnQkArgs& a, hipStream_t s) {
         const long long nblk4 = (long long)((a.S + QB - 1) / QB) * a.batch * nsp;
         if (nblk4 > 0x7fffffffLL) return hipErrorInvalidValue;
         static std::atomic<unsigned long long> attr4{0};
-        hipError_t e4 = vt_once_per_device(attr4, [&] { return hipFuncSetAttribute((const void*)attn_qk_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF); });
+        hipError_t e4 = vt_dynamic_smem_once(attr4, 2 * KBUF, attn_qk_kernel<4>);
         if (e4 != hipSuccess) return e4;
         hipLaunchKernelGGL(attn_qk_kernel<4>, dim3((unsigned)nblk4), dim3(512), 2 * KBUF, s, a);
         return hipGetLastError();
@@ -403,12 +403,7 @@ hipError_t vt_launch_attn_qk(const AttnQkArgs& a, hipStream_t s) {
     const long long nblk = (long long)((a.S + QB - 1) / QB) * a.batch * (a.nsplit > 1 ? a.nsplit : 1);
     if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_qk_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_qk_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_qk_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KBUF);
-        return e;
-    });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, 2 * KBUF, attn_qk_kernel<1>, attn_qk_kernel<2>, attn_qk_kernel<3>);
     if (ea != hipSuccess) return ea;
     if (a.mode == 1) hipLaunchKernelGGL(attn_qk_kernel<1>, dim3((unsigned)nblk), dim3(512), 2 * KBUF, s, a);
     else if (a.p_frag) hipLaunchKernelGGL(attn_qk_kernel<3>, dim3((unsigned)nblk), dim3(512), 2 * KBUF, s, a);

@@ -18,7 +18,7 @@
 // cout), pixels = B operand; the packed cout rows are interleaved so that a lane holds 16 consecutive couts of one pixel.
 #include <type_traits>
 
-#include "vt_common.h"
+#include "vt_halo.h"
 #include "vt_kernels.h"
 
 #ifdef GNIL_DUMP        // diagnostics build only (tests/diagnostics/halo_partials_lane_dump.py)
@@ -90,46 +90,6 @@ constexpr int TW = 16;        // tile width in pixels (one MFMA column block)
 constexpr int HWID = TW + 2;  // halo width
 constexpr int NW_DEFAULT = 6;  // weight ring depth of the 1-workgroup-per-CU variants
 
-__device__ __forceinline__ void wait_vmcnt(int n) {
-    switch (n) {
-#define C(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        C(0) C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16)
-        C(17) C(18) C(19) C(20) C(21) C(22) C(23) C(24)
-#undef C
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
-// s_waitcnt vmcnt(n) that also names the registers an inline-asm load wrote: nothing that consumes them
-// can be scheduled above the wait (hipcc neither counts asm loads nor knows when their data lands).
-template <typename V>
-__device__ __forceinline__ void wait_vmcnt_tied(int n, V& r0, V& r1) {
-    switch (n) {
-#define C(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" : "+v"(r0), "+v"(r1)::"memory"); break;
-        C(0) C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16)
-#undef C
-        default: asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0), "+v"(r1)::"memory"); break;
-    }
-}
-
-
-// Identity the optimiser cannot see through: stops loop-invariant address arithmetic built on `v` from being
-// hoisted into (and spilled from) long-lived registers -- it is recomputed where it is used instead.
-__device__ __forceinline__ int opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-template <typename V>
-__device__ __forceinline__ void wait_vmcnt_tied1(int n, V& r0) {
-    switch (n) {
-#define C(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" : "+v"(r0)::"memory"); break;
-        C(0) C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16)
-#undef C
-        default: asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0)::"memory"); break;
-    }
-}
-
 // XT selects how the X halo reaches LDS:
 //   0  bf16 activations, copied as they are by LDS-DMA;
 //   1  fp32 tensor (the residual stream), 2  bf16 tensor (a conv1 output): loaded to registers by
@@ -180,20 +140,11 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
     const int wpw = (WPCS % NLD == 0) ? WPW : (wave < WPCS % NLD ? WPW : WPW - 1);
 
     STAMP(0);
-    // ---- tile coordinates.  The divisors are launch constants: the host passes 2^40 / d + 1 multipliers (exact for
-    // n * d < 2^40), so the five runtime integer divisions (~50 instructions each) in front of the first DMA become multiplies.
-    const int tiles_x = a.tiles_x, ctiles = a.ctiles, per_img = a.per_img;
-    auto fdiv = [](int n, unsigned long long m, int d) -> int {
-        return m ? (int)(((unsigned long long)(unsigned)n * m) >> 40) : n / d;
-    };
-    int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int b = fdiv(logical, a.m_per_img, per_img);
-    logical -= b * per_img;
-    const int tile = fdiv(logical, a.m_ctiles, ctiles);
-    const int ct = logical - tile * ctiles;
-    const int tyi = fdiv(tile, a.m_tiles_x, tiles_x);
-    const int ty0 = tyi * ROWS, tx0 = (tile - tyi * tiles_x) * TW;
-    const int c0 = ct * BC;
+    // ---- tile coordinates
+    const VtHaloTile tl = vt_halo_tile_of(a);
+    const int b = tl.b, tile = tl.tile;
+    const int ty0 = tl.tyi * ROWS, tx0 = tl.txi() * TW;
+    const int c0 = tl.ct * BC;
 
     const long long img = (long long)b * a.H * a.W * a.Cin;
     const bf16_t* Xb = a.X ? a.X + img : nullptr;
@@ -232,7 +183,7 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
         if (chunk >= 2) return;
 #endif
         char* dst = xbase + (chunk & 1) * XBUF;
-        int hy = opaque(hy0), hx = hx0, hr = hr0;
+        int hy = vt_opaque(hy0), hx = hx0, hr = hr0;
 #pragma nounroll
         for (int j = 0; j < NXW; ++j) {                              // rolled: few live temporaries beside the accumulators
             const int iy = ty0 - 1 + hy, ix = tx0 - 1 + hx;
@@ -258,9 +209,9 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
         char* dst = wbase + (t % NW) * WBUF;
         const int src_t = KYMAJOR ? t - tap_of_t + vt_halo_step_of_tap(tap_of_t) : t;
 #ifdef W_WINDOW_EXPERIMENT       // timing experiment only (wrong results): every K-step's weights from a window of W_WINDOW_EXPERIMENT tiles
-        const bf16_t* wt = a.Wp + (long long)(src_t % W_WINDOW_EXPERIMENT) * wstep + opaque(wsrc0);
+        const bf16_t* wt = a.Wp + (long long)(src_t % W_WINDOW_EXPERIMENT) * wstep + vt_opaque(wsrc0);
 #else
-        const bf16_t* wt = a.Wp + (long long)src_t * wstep + opaque(wsrc0);
+        const bf16_t* wt = a.Wp + (long long)src_t * wstep + vt_opaque(wsrc0);
 #endif
 #pragma unroll
         for (int j = 0; j < WPW; ++j)
@@ -273,7 +224,7 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
     };
     // register-staged row: 8 channels of one halo pixel (XT 1: 2 x 16 B of fp32, XT 2: 16 B of bf16)
     auto load_row = [&](int j, int chunk, f32x4& r0, f32x4& r1) {
-        const int xs_j = opaque(xsrc[j]);
+        const int xs_j = vt_opaque(xsrc[j]);
         const int off = xs_j >= 0 ? xs_j + chunk * 32 : 0;
         if constexpr (XT == 1) {
             const float* src = xs_j >= 0 ? Xf + off : (const float*)a.zeros;
@@ -286,8 +237,8 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
     };
     // y = silu(x * scale + shift) -> bf16, written where the DMA would have put the raw row
     auto write_row = [&](int j, int chunk, const f32x4& r0, const f32x4& r1) {
-        const float* sp = ssl + (chunk * 32 + opaque(dchunk) * 8) * 2;
-        char* dst = xbase + (chunk & 1) * XBUF + (j * NLD + wave) * 1024 + opaque(lane) * 16;
+        const float* sp = ssl + (chunk * 32 + vt_opaque(dchunk) * 8) * 2;
+        char* dst = xbase + (chunk & 1) * XBUF + (j * NLD + wave) * 1024 + vt_opaque(lane) * 16;
         const bool pad = xsrc[j] < 0;                              // conv zero padding applies AFTER norm + SiLU
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
@@ -365,11 +316,10 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < NXW; ++j) {
-            f32x4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = {0.f, 0.f, 0.f, 0.f};
-            load_row(j, 0, r0, r1);
-            if constexpr (XT == 1) wait_vmcnt_tied(0, r0, r1);
-            else wait_vmcnt_tied1(0, r0);
-            write_row(j, 0, r0, r1);
+            f32x4 r[LX] = {};
+            load_row(j, 0, r[0], r[LX - 1]);
+            vt_wait_vmcnt_tied<16>(0, r);
+            write_row(j, 0, r[0], r[LX - 1]);
         }
 #pragma unroll
         for (int t = 0; t < LEAD; ++t)
@@ -389,11 +339,11 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
     if constexpr (SPF) {
         int ahead0 = nk - 1;
         if (ahead0 > LEAD - 1) ahead0 = LEAD - 1;
-        wait_vmcnt(ahead0 * wpw);                // W(0) and X(0) landed (this wave's pieces) ...
+        vt_wait_vmcnt<24>(ahead0 * wpw);         // W(0) and X(0) landed (this wave's pieces) ...
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();            // ... and everybody else's
         asm volatile("" ::: "memory");
-        const char* ws0 = wbase + opaque(wfoff);
+        const char* ws0 = wbase + vt_opaque(wfoff);
 #pragma unroll
         for (int i = 0; i < TC; ++i) wfc[i] = *(const bf16x8*)(ws0 + i * 16 * HB);
 #pragma unroll
@@ -424,12 +374,12 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
                 int n = WOUT * wpw;
                 if (XT == 0) { if (tap >= 1 && tap <= LEAD - 1) n += NXW; }               // next halo, DMA'd at tap 0
                 else { for (int r = tap - (NW - 1); r <= tap - 1; ++r) if (r >= 0 && r < NXW) n += LX; }
-                wait_vmcnt(n);
+                vt_wait_vmcnt<24>(n);
             } else {
                 int ahead = 8 - tap - (SPF ? 1 : 0);       // nk - 1 - t (- 1): the last chunk ends the K-steps (nk = 9 * nchunk)
                 if (ahead > WOUT) ahead = WOUT;
                 if (ahead < 0) ahead = 0;
-                wait_vmcnt(ahead * wpw);
+                vt_wait_vmcnt<24>(ahead * wpw);
             }
             if (XT != 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's staged rows are written
             asm volatile("" ::: "memory");
@@ -445,7 +395,7 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
                 const int tap_n = (tap + 1) % 9;
                 const int dy_n = tap_n / 3, dx_n = tap_n % 3;            // ky-major walk (KYMAJOR)
                 const char* xs_n = (tap == 8) ? xbase + ((chunk + 1) & 1) * XBUF : xs;
-                const char* ws_n = wbase + ((t + 1) % NW) * WBUF + opaque(wfoff);
+                const char* ws_n = wbase + ((t + 1) % NW) * WBUF + vt_opaque(wfoff);
                 __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int j = 0; j < TP; ++j) {
@@ -475,7 +425,7 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
                 const bool next_group = !LAST || dx < 2;                   // a next dx group exists (X fragments)
                 const int dx_n = (dx + 1) % 3;
                 const char* xs_n = (dx == 2) ? xbase + ((chunk + 1) & 1) * XBUF : xs;
-                const char* ws_n = wbase + ((t + 1) % NW) * WBUF + opaque(wfoff);
+                const char* ws_n = wbase + ((t + 1) % NW) * WBUF + vt_opaque(wfoff);
                 auto refill = [&](int r) {                                 // DYR: halo row r of the next dx group
 #ifndef EXP_NO_FRAG_READS        // timing experiment only (wrong results): the step-0 fragments serve every K-step
                     const int rel = r * HWID + dx_n;
@@ -513,7 +463,7 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
 #endif
                 continue;
             }
-            const char* ws = wbase + (t % NW) * WBUF + opaque(wfoff);     // stage bases beyond 64 KB cannot be ds_read immediates
+            const char* ws = wbase + (t % NW) * WBUF + vt_opaque(wfoff);     // stage bases beyond 64 KB cannot be ds_read immediates
             const int dx = tap / 3, dy = tap % 3;          // dx-major K-step order (see the weight packers)
             bf16x8 wf[TC];
 #pragma unroll
@@ -528,8 +478,7 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
             auto stage_row = [&]() {
                 int n = DLY * wpw;                // W issued in steps r+1 .. tap (this step's W is already out)
                 for (int q = r + 1; q < tap; ++q) if (q < NXW) n += LX;          // rows r+1 .. tap-1
-                if constexpr (XT == 1) wait_vmcnt_tied(n, rq[r % DLY][0], rq[r % DLY][1]);
-                else wait_vmcnt_tied1(n, rq[r % DLY][0]);
+                vt_wait_vmcnt_tied<16>(n, rq[r % DLY]);
                 write_row(r, chunk + 1, rq[r % DLY][0], rq[r % DLY][XT == 1 ? 1 : 0]);
             };
             if constexpr (STAGE) {
@@ -580,7 +529,7 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
                 __builtin_amdgcn_s_barrier();                        // ... and everybody else's: the buffers are free
                 asm volatile("" ::: "memory");
                 {
-                    int hy = opaque(hy0), hx = hx0, hr = hr0;
+                    int hy = vt_opaque(hy0), hx = hx0, hr = hr0;
 #pragma nounroll
                     for (int j = 0; j < NXW; ++j) {
                         const int iy = ty0 - 1 + hy, ix = tx0 - 1 + hx;
@@ -591,17 +540,17 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
                         hx += (NLD * 16) % HWID; hy += (NLD * 16) / HWID;
                         if (hx >= HWID) { hx -= HWID; ++hy; }
                     }
-                    const bf16_t* wt = a.scW + (long long)c * wstep + opaque(wsrc0);
+                    const bf16_t* wt = a.scW + (long long)c * wstep + vt_opaque(wsrc0);
 #pragma unroll
                     for (int j = 0; j < WPW; ++j)
                         if (WPCS % NLD == 0 || j * NLD + wave < WPCS)
                             __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(wt + j * NLD * 16 * 32), VT_LDS_PTR(wbase + (j * NLD + wave) * 1024), 16, 0, 0);
                 }
-                wait_vmcnt(0);
+                vt_wait_vmcnt<24>(0);
                 asm volatile("" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                const char* ws = wbase + opaque(wfoff);
+                const char* ws = wbase + vt_opaque(wfoff);
                 bf16x8 wf[TC];
 #pragma unroll
                 for (int i = 0; i < TC; ++i) wf[i] = *(const bf16x8*)(ws + i * 16 * HB);
@@ -676,7 +625,6 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
             const int pp = j * 16 + fr;
 #pragma unroll
             for (int i = 0; i < TC; i += 2) {
-                typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
                 const f16x8 rh = RES_DMA ? *(const f16x8*)(rbuf + pp * 128 + (((2 * fq + (i >> 1)) ^ (pp & 7)) << 4))
                                          : *(const f16x8*)(a.res_f16 + o + 4 * i);
 #pragma unroll
@@ -685,35 +633,21 @@ void conv3x3_halo_kernel(const Conv3x3Args a) {
         }
         if (a.out_f16) {
 #pragma unroll
-            for (int i = 0; i < TC; i += 2) {
-                typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-                f16x8 h;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { h[r] = (f16_t)acc[i][j][r]; h[4 + r] = (f16_t)acc[i + 1][j][r]; }
-                *(f16x8*)(a.out_f16 + o + 4 * i) = h;
-            }
+            for (int i = 0; i < TC; i += 2) vt_halo_store16(a.out_f16 + o + 4 * i, acc[i][j], acc[i + 1][j]);
         }
         if (a.out_bf16) {
             // a.out16_planar: the 16-bit copy is laid out [Cout/32][H][W][32] (chunk-planar) for the stride-2 phase-plane kernel that reads it
             const long long o16 = a.out16_planar ? (((long long)(b * (a.Cout >> 5) + (cw >> 5)) * a.H + y) * a.W + x) * 32 + (cw & 31) : o;
+#ifdef EPI_NOSTORE
+            constexpr bool STORE = false;
+#else
+            constexpr bool STORE = true;
+#endif
 #pragma unroll
             for (int i = 0; i < TC; i += 2) {
-                if (a.out16_f16) {                             // the operand copy carries fp16 bits when its consumer runs on fp16 operands
-                    typedef _Float16 f16x8o __attribute__((ext_vector_type(8)));
-                    f16x8o h;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { h[r] = (f16_t)acc[i][j][r]; h[4 + r] = (f16_t)acc[i + 1][j][r]; }
-                    *(f16x8o*)((f16_t*)a.out_bf16 + o16 + 4 * i) = h;
-                } else {
-                bf16x8 h;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { h[r] = (bf16_t)acc[i][j][r]; h[4 + r] = (bf16_t)acc[i + 1][j][r]; }
-#ifdef EPI_NOSTORE
-                asm volatile("" :: "v"(h));
-#else
-                *(bf16x8*)(a.out_bf16 + o16 + 4 * i) = h;
-#endif
-                }
+                // the operand copy carries fp16 bits when its consumer runs on fp16 operands
+                if (a.out16_f16) vt_halo_store16((f16_t*)a.out_bf16 + o16 + 4 * i, acc[i][j], acc[i + 1][j]);
+                else vt_halo_store16<STORE>(a.out_bf16 + o16 + 4 * i, acc[i][j], acc[i + 1][j]);
             }
         }
     }
@@ -748,17 +682,11 @@ hipError_t launch(const Conv3x3Args& a, hipStream_t s) {
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = conv3x3_halo_kernel<WP, WC, XT, TPW, NW, F16>;
-    hipError_t ea = vt_once_per_device(attr_done, [&] { return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, 160 * 1024, kern);
     if (ea != hipSuccess) return ea;
-    const long long tiles = (long long)((a.W + TW - 1) / TW) * ((a.H + ROWS - 1) / ROWS);
-    const long long nblk = tiles * (a.Cout / BC) * a.batch;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     Conv3x3Args k = a;
-    k.tiles_x = (a.W + TW - 1) / TW; k.ctiles = a.Cout / BC; k.per_img = (int)(tiles * k.ctiles); k.ptiles = (int)tiles;
-    auto magic = [&](long long d) -> unsigned long long {           // n / d = (n * m) >> 40 for every n < nblk, when n * d < 2^40
-        return (nblk * d < (1LL << 40) && nblk < (1LL << 23)) ? ((1ULL << 40) / (unsigned long long)d + 1ULL) : 0ULL;
-    };
-    k.m_per_img = magic(k.per_img); k.m_ctiles = magic(k.ctiles); k.m_tiles_x = magic(k.tiles_x);
+    const long long nblk = vt_halo_tile_grid(k, (a.W + TW - 1) / TW, (a.H + ROWS - 1) / ROWS, a.Cout / BC, a.batch);
+    if (!nblk) return hipErrorInvalidValue;
 #ifdef HALO_STAMP
     if (s_stamp_nth >= 0) {
         const bool on = a.H == s_stamp_H && a.Cin == s_stamp_Cin && s_stamp_seen++ == s_stamp_nth;
@@ -849,11 +777,10 @@ hipError_t vt_launch_conv3x3_halo(const Conv3x3Args& a, hipStream_t s) {
     if (!a.Wp || !a.zeros || (!a.out_f32 && !a.out_bf16 && !a.out_f16)) return hipErrorInvalidValue;
     if ((a.res && a.res_f16) || (a.res_f16 && a.out_f32)) return hipErrorInvalidValue;
     if (!vt_conv3x3_halo_supported(a.Cin, a.Cout) || a.batch <= 0 || a.H <= 0 || a.W <= 0) return hipErrorInvalidValue;
-    if (a.gn_partial && a.gn_cpg != 4 && a.gn_cpg != 8 && a.gn_cpg != 16) return hipErrorInvalidValue;
-    if ((long long)a.H * a.W * a.Cin >= (1LL << 31)) return hipErrorInvalidValue;        // 32-bit per-image offsets
+    if (!vt_gn_cpg_ok(a.gn_partial, a.gn_cpg) || !vt_fits_i32((long long)a.H * a.W * a.Cin)) return hipErrorInvalidValue;
     if ((a.scX != nullptr) != (a.scW != nullptr)) return hipErrorInvalidValue;
-    if (a.scX && (a.scCin <= 0 || (a.scCin % 32) || a.scale_shift || (long long)a.H * a.W * a.scCin >= (1LL << 31))) return hipErrorInvalidValue;
-    if ((long long)(a.Cin / 32) * 9 * a.Cout * 32 >= (1LL << 31)) return hipErrorInvalidValue;
+    if (a.scX && (a.scCin <= 0 || (a.scCin % 32) || a.scale_shift || !vt_fits_i32((long long)a.H * a.W * a.scCin))) return hipErrorInvalidValue;
+    if (!vt_fits_i32((long long)(a.Cin / 32) * 9 * a.Cout * 32)) return hipErrorInvalidValue;
     if (a.occ2 < 0 || a.occ2 > 4) return hipErrorInvalidValue;
     // input mode: raw bf16 (X), or GroupNorm+SiLU fused into the staging of an fp32 (Xf32) / bf16 (X) tensor
     const int xt = halo_xt(a);

@@ -17,7 +17,7 @@
 // W = e4m3(w / wscale[cout]) packed by the host; the epilogue computes acc * (wscale[cout] / act_scale) + bias.
 #include <type_traits>
 
-#include "vt_common.h"
+#include "vt_halo.h"
 #include "vt_kernels.h"
 
 #ifdef HALO_STAMP
@@ -88,30 +88,6 @@ struct Shape {
     static_assert(WPCS % NWV == 0 && SMEM <= 160 * 1024, "tile shape");
 };
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void wait_vmcnt(int n) {
-    switch (n) {
-#define C(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        C(0) C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16)
-#undef C
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-__device__ __forceinline__ int opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-__device__ __forceinline__ int swz(int row) { return (row ^ (row >> 2)) & 3; }
-
-// 32-byte fragment of LDS row `row`: logical chunks 2 g, 2 g + 1
-__device__ __forceinline__ i32x8 read_frag(const char* base, int row, int g) {
-    const int a = row * HB + (((2 * g) ^ swz(row)) << 4);
-    const i32x4 lo = *(const i32x4*)(base + a), hi = *(const i32x4*)(base + (a ^ 16));
-    return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
 template <int WP, int WX>
 __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(const Conv3x3Fp8Args a) {
     typedef Shape<WP, WX> SH;
@@ -126,26 +102,19 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
     const int g = lane >> 5, li = lane & 31;
     STAMP(0);
 
-    // ---- tile coordinates (launch-constant divisors arrive as 2^40 / d + 1 multipliers)
-    auto fdiv = [](int n, unsigned long long m, int d) -> int {
-        return m ? (int)(((unsigned long long)(unsigned)n * m) >> 40) : n / d;
-    };
-    int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int b = fdiv(logical, a.m_per_img, a.per_img);
-    logical -= b * a.per_img;
-    const int tile = fdiv(logical, a.m_ctiles, a.ctiles);
-    const int ct = logical - tile * a.ctiles;
-    const int tyi = fdiv(tile, a.m_tiles_x, a.tiles_x);
-    const int ty0 = tyi * ROWS, tx0 = (tile - tyi * a.tiles_x) * TWX;
-    const int c0 = ct * BC;
+    // ---- tile coordinates
+    const VtHaloTile tl = vt_halo_tile_of(a);
+    const int b = tl.b, tile = tl.tile;
+    const int ty0 = tl.tyi * ROWS, tx0 = tl.txi() * TWX;
+    const int c0 = tl.ct * BC;
     const unsigned char* Xb = a.X + (long long)b * a.H * a.W * a.Cin;
     const int nchunk = a.Cin >> 6;
     const int nk = nchunk * 9;
 
     // ---- DMA bookkeeping: one wave-instruction = 16 LDS rows x 64 B; lane l -> row (l >> 2), physical chunk (l & 3),
-    // logical chunk = physical ^ swz(row) (swz of a piece's row depends on the row inside the piece only: pieces start at multiples of 16)
+    // logical chunk = physical ^ vt_swz8(row) (swz of a piece's row depends on the row inside the piece only: pieces start at multiples of 16)
     const int drow = lane >> 2;
-    const int dchunk = (lane & 3) ^ swz(drow);
+    const int dchunk = (lane & 3) ^ vt_swz8(drow);
     const int hr0 = wave * 16 + drow;
     const int hy0 = hr0 / HWID, hx0 = hr0 - (hr0 / HWID) * HWID;
     const int wsrc0 = (c0 + wave * 16 + drow) * HB + dchunk * 16;       // byte offset inside a K-step's [Cout][64] tile
@@ -156,7 +125,7 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
         if (chunk >= 2) return;
 #endif
         char* dst = xbase + (chunk & 1) * XBUF;
-        int hy = opaque(hy0), hx = hx0, hr = hr0;
+        int hy = vt_opaque(hy0), hx = hx0, hr = hr0;
 #pragma nounroll
         for (int j = 0; j < NXW; ++j) {
             const int iy = ty0 - 1 + hy, ix = tx0 - 1 + hx;
@@ -174,9 +143,9 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
 #endif
         char* dst = wbase + (t % NW) * WBUF;
 #ifdef W_WINDOW_EXPERIMENT       // timing experiment only (wrong results): every K-step's weights from a window of W_WINDOW_EXPERIMENT tiles
-        const unsigned char* wt = a.Wp + (long long)(t % W_WINDOW_EXPERIMENT) * wstep + opaque(wsrc0);
+        const unsigned char* wt = a.Wp + (long long)(t % W_WINDOW_EXPERIMENT) * wstep + vt_opaque(wsrc0);
 #else
-        const unsigned char* wt = a.Wp + (long long)t * wstep + opaque(wsrc0);
+        const unsigned char* wt = a.Wp + (long long)t * wstep + vt_opaque(wsrc0);
 #endif
 #pragma unroll
         for (int j = 0; j < WPW; ++j)
@@ -206,14 +175,14 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
     {
         int ahead0 = nk - 1;
         if (ahead0 > LEAD - 1) ahead0 = LEAD - 1;
-        wait_vmcnt(ahead0 * WPW);                // W(0) and X(0) landed (this wave's pieces) ...
+        vt_wait_vmcnt<16>(ahead0 * WPW);         // W(0) and X(0) landed (this wave's pieces) ...
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();            // ... and everybody else's
         asm volatile("" ::: "memory");
 #pragma unroll
-        for (int h = 0; h < 2; ++h) wfc[h] = read_frag(wbase, opaque(wrow0) + 32 * h, g);
+        for (int h = 0; h < 2; ++h) wfc[h] = vt_read_frag8(wbase, vt_opaque(wrow0) + 32 * h, g);
 #pragma unroll
-        for (int r = 0; r < TP + 2; ++r) xr[r] = read_frag(xbase, opaque(xrow0) + r * HWID, g);
+        for (int r = 0; r < TP + 2; ++r) xr[r] = vt_read_frag8(xbase, vt_opaque(xrow0) + r * HWID, g);
     }
     STAMP(2);
     STAMP_CLK(11);
@@ -230,13 +199,13 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
             if constexpr (!LAST) {
                 int n = WOUT * WPW;
                 if (tap >= 1 && tap <= LEAD - 1) n += NXW;               // the next halo, DMA'd at tap 0
-                wait_vmcnt(n);
+                vt_wait_vmcnt<16>(n);
             } else {
                 // the last chunk ends the kernel's K-steps (nk = 9 * nchunk): t + 1 = nk - (8 - tap), all compile-time
                 int ahead = 7 - tap;
                 if (ahead > WOUT) ahead = WOUT;
                 if (ahead < 0) ahead = 0;
-                wait_vmcnt(ahead * WPW);
+                vt_wait_vmcnt<16>(ahead * WPW);
             }
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -248,7 +217,7 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
             const char* xs_n = (dx == 2) ? xbase + ((chunk + 1) & 1) * XBUF : xs;
             const char* ws_n = wbase + ((t + 1) % NW) * WBUF;
 #ifndef EXP_NO_FRAG_READS            // timing experiment only (wrong results): the step-0 fragments serve every K-step
-            auto refill = [&](int r) { xr[r] = read_frag(xs_n, opaque(xrow0) + r * HWID + dx_n, g); };
+            auto refill = [&](int r) { xr[r] = vt_read_frag8(xs_n, vt_opaque(xrow0) + r * HWID + dx_n, g); };
 #else
             auto refill = [&](int) {};
 #endif
@@ -272,7 +241,7 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
 #ifndef EXP_NO_FRAG_READS
             if (has_next) {
 #pragma unroll
-                for (int h = 0; h < 2; ++h) wfc[h] = read_frag(ws_n, opaque(wrow0) + 32 * h, g);
+                for (int h = 0; h < 2; ++h) wfc[h] = vt_read_frag8(ws_n, vt_opaque(wrow0) + 32 * h, g);
             }
 #endif
             __builtin_amdgcn_sched_barrier(0);           // a K-step's MFMAs stay inside it (sunk past later barriers they cost spills)
@@ -305,7 +274,7 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
 #pragma unroll
             for (int j = 0; j < WPW; ++j)
                 __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(wt + j * NWV * 16 * 32), VT_LDS_PTR(wbase + (j * NWV + wave) * 1024), 16, 0, 0);
-            wait_vmcnt(0);
+            vt_wait_vmcnt<16>(0);
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -315,12 +284,12 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int row = wrow0 + 32 * h;
-                    wf[h] = *(const bf16x8*)(wbase + row * HB + (((2 * ks + g) ^ swz(row)) << 4));
+                    wf[h] = *(const bf16x8*)(wbase + row * HB + (((2 * ks + g) ^ vt_swz8(row)) << 4));
                 }
 #pragma unroll
                 for (int j = 0; j < TP; ++j) {
                     const int row = (wp * TP + j) * TWX + wx * 32 + li;
-                    const bf16x8 xf = *(const bf16x8*)(xbase + row * HB + (((2 * ks + g) ^ swz(row)) << 4));
+                    const bf16x8 xf = *(const bf16x8*)(xbase + row * HB + (((2 * ks + g) ^ vt_swz8(row)) << 4));
 #pragma unroll
                     for (int h = 0; h < 2; ++h)
                         acc[h][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[h], xf, acc[h][j], 0, 0, 0);
@@ -380,7 +349,6 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
             if (y >= a.H || x >= a.W) continue;
             valid |= 1u << j;
             const long long o = ob + ((long long)y * a.W + x) * a.Cout + cw;
-            typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
             if (a.res) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -403,17 +371,8 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
                 for (int i = 0; i < 4; ++i)
                     *(f32x4*)(a.out_f32 + o + 4 * i) = f32x4{acc[h][j][4 * i], acc[h][j][4 * i + 1], acc[h][j][4 * i + 2], acc[h][j][4 * i + 3]};
             }
-            if (a.out_f16) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    f16x8 hh;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) hh[q] = (f16_t)acc[h][j][8 * i + q];
-                    *(f16x8*)(a.out_f16 + o + 8 * i) = hh;
-                }
-            }
+            if (a.out_f16) vt_halo_store16_f8(a.out_f16 + o, acc[h][j]);
             if (a.out_e4m3) {
-                typedef int i32x4 __attribute__((ext_vector_type(4)));
                 i32x4 o8 = {0, 0, 0, 0};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -430,114 +389,20 @@ __global__ __launch_bounds__(64 * WP * WX * WC, 2) void conv3x3_halo_fp8_kernel(
                 const long long o8a = a.out8_planar ? (((long long)(b * (a.Cout >> 6) + (cw >> 6)) * a.H + y) * a.W + x) * 64 + (cw & 63) : o;
                 *(i32x4*)(a.out_e4m3 + o8a) = o8;
             }
-            if (a.out_bf16) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    bf16x8 hh;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) hh[q] = (bf16_t)acc[h][j][8 * i + q];
-                    *(bf16x8*)(a.out_bf16 + o + 8 * i) = hh;
-                }
-            }
+            if (a.out_bf16) vt_halo_store16_f8(a.out_bf16 + o, acc[h][j]);
         }
     }
     if (a.out_e4m3 && a.status && amax8 > 448.f) atomicOr(a.status, 2);      // e4m3 saturates silently: sticky bit 1 of vt_status
     STAMP(4);
     if (a.gn_partial) {
-        // GroupNorm (n, mean, M2) of this tile's outputs for the next norm.  A group (cpg = 4, 8 or 16 consecutive couts) lives in
-        // one lane; sums are taken relative to a per-(wave half, group) pivot, reduced over the wave's 32 pixel columns, then the
-        // two pixel-row waves are merged with Chan's formula in a fixed order (deterministic).
-        // This phase is latency, not work (its VALU issue is hidden behind the other resident workgroup's MFMAs, but a 128-channel
-        // layer's main loop is shorter than its epilogue): every group's pivot, sums and lane reductions are independent chains
-        // issued together, cross-lane steps are DPP / readlane (no LDS round trips), one branch writes all partials.
+        // GroupNorm (n, mean, M2) of this tile's outputs for the next norm
         float* lds = (float*)(smem + SMEM - WBUF);         // the last weight stage: clear of the residual staging (waves x 16 KB from 0)
         if (!a.res_f16 && !a.scX) {                        // those paths have passed a barrier since the last K-step's fragment reads
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
-        const int cpg = a.gn_cpg;
-        const int gpb = BC / cpg;
-        float npix = 0.f;
-#pragma unroll
-        for (int j = 0; j < TP; ++j) npix += (float)__popcll(__ballot((valid >> j) & 1u) & 0xffffffffull);   // lanes 0..31 = the 32 columns
-        const float n = npix * (float)cpg;
-        const bool full = __ballot(valid != (1u << TP) - 1u) == 0ull;      // the whole wave tile is inside the image
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        auto stats = [&](auto cpg_tag, auto full_tag) {
-            constexpr int CPG = decltype(cpg_tag)::value;
-            constexpr bool FULL = decltype(full_tag)::value;
-            constexpr int NQ = 16 / CPG;
-            float piv[2][NQ], s[2][NQ], ss[2][NQ];
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {             // pivot = the group's first value at the half-wave's first pixel (finite even outside the image)
-                    const int v = __builtin_bit_cast(int, acc[h][0][q * CPG]);
-                    const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(v, 0));
-                    const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(v, 32));
-                    piv[h][q] = g ? p1 : p0;
-                }
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const f32x2 p2 = {piv[h][q], piv[h][q]};
-                    f32x2 s2 = {0.f, 0.f}, q2 = {0.f, 0.f};
-#pragma unroll
-                    for (int j = 0; j < TP; ++j) {
-                        if (FULL || ((valid >> j) & 1u)) {
-#pragma unroll
-                            for (int r = q * CPG; r < (q + 1) * CPG; r += 2) {
-                                const f32x2 d = f32x2{acc[h][j][r], acc[h][j][r + 1]} - p2;
-                                s2 += d; q2 += d * d;
-                            }
-                        }
-                    }
-                    s[h][q] = s2[0] + s2[1]; ss[h][q] = q2[0] + q2[1];
-                }
-            // 32-column sums: inside each 16-lane row, then row 0 -> row 1 and row 2 -> row 3 (row_bcast15): lanes 16..31 / 48..63 hold them
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const float a0 = vt_row16_sum(s[h][q]), b0 = vt_row16_sum(ss[h][q]);
-                    s[h][q] = a0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a0), 0x142, 0xA, 0xF, false));
-                    ss[h][q] = b0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b0), 0x142, 0xA, 0xF, false));
-                }
-            if (li == 16) {
-                const float rn = n > 0.f ? 1.0f / n : 0.f;
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q) {
-                        const float ms = s[h][q] * rn;
-                        const int lg = (wc * 64 + 32 * h + 16 * g + q * CPG) / CPG;
-                        float* d = lds + ((wp * WX + wx) * gpb + lg) * 3;
-                        d[0] = n; d[1] = n > 0.f ? piv[h][q] + ms : 0.f; d[2] = n > 0.f ? fmaxf(ss[h][q] - s[h][q] * ms, 0.f) : 0.f;
-                    }
-            }
-        };
-        auto stats_c = [&](auto cpg_tag) {
-            if (full) stats(cpg_tag, std::true_type{}); else stats(cpg_tag, std::false_type{});
-        };
-        if (cpg == 4) stats_c(std::integral_constant<int, 4>{});
-        else if (cpg == 8) stats_c(std::integral_constant<int, 8>{});
-        else stats_c(std::integral_constant<int, 16>{});
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if ((int)threadIdx.x < gpb) {
-            float nn = 0.f, mean = 0.f, m2 = 0.f;
-#pragma unroll
-            for (int pw = 0; pw < WP * WX; ++pw) {               // the pixel-wave groups, in a fixed order
-                const float* d = lds + (pw * gpb + threadIdx.x) * 3;
-                vt_chan_merge(nn, mean, m2, d[0], d[1], d[2]);
-            }
-            const int G = a.Cout / cpg;
-            float* o = a.gn_partial + (((long long)b * a.ptiles + tile) * G + c0 / cpg + threadIdx.x) * 3;
-            o[0] = nn; o[1] = mean; o[2] = m2;
-        }
+        vt_gn_epilogue_partials_f8<TP, WP, WX>(acc, valid, a, b, tile, c0, wp, wx, wc, lane, lds);
     }
 #ifdef HALO_STAMP
     STAMP(5);
@@ -572,17 +437,11 @@ template <int WP, int WX>
 hipError_t launch_shape(const Conv3x3Fp8Args& a, hipStream_t s) {
     typedef Shape<WP, WX> SH;
     static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] { return hipFuncSetAttribute((const void*)conv3x3_halo_fp8_kernel<WP, WX>, hipFuncAttributeMaxDynamicSharedMemorySize, SH::SMEM); });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, SH::SMEM, conv3x3_halo_fp8_kernel<WP, WX>);
     if (ea != hipSuccess) return ea;
-    const long long tiles = (long long)((a.W + SH::TWX - 1) / SH::TWX) * ((a.H + SH::ROWS - 1) / SH::ROWS);
-    const long long nblk = tiles * (a.Cout / BC) * a.batch;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     Conv3x3Fp8Args k = a;
-    k.tiles_x = (a.W + SH::TWX - 1) / SH::TWX; k.ctiles = a.Cout / BC; k.per_img = (int)(tiles * k.ctiles); k.ptiles = (int)tiles;
-    auto magic = [&](long long d) -> unsigned long long {
-        return (nblk * d < (1LL << 40) && nblk < (1LL << 23)) ? ((1ULL << 40) / (unsigned long long)d + 1ULL) : 0ULL;
-    };
-    k.m_per_img = magic(k.per_img); k.m_ctiles = magic(k.ctiles); k.m_tiles_x = magic(k.tiles_x);
+    const long long nblk = vt_halo_tile_grid(k, (a.W + SH::TWX - 1) / SH::TWX, (a.H + SH::ROWS - 1) / SH::ROWS, a.Cout / BC, a.batch);
+    if (!nblk) return hipErrorInvalidValue;
     hipLaunchKernelGGL((conv3x3_halo_fp8_kernel<WP, WX>), dim3((unsigned)nblk), dim3(SH::NT), SH::SMEM, s, k);
     return hipGetLastError();
 }
@@ -592,11 +451,10 @@ hipError_t vt_launch_conv3x3_halo_fp8(const Conv3x3Fp8Args& a, hipStream_t s) {
     if (!a.X || !a.Wp || !a.mult || !a.zeros || (!a.out_f32 && !a.out_bf16 && !a.out_f16 && !a.out_e4m3)) return hipErrorInvalidValue;
     if ((a.res && a.res_f16) || (a.res_f16 && a.out_f32)) return hipErrorInvalidValue;
     if (!vt_conv3x3_halo_fp8_supported(a.Cin, a.Cout) || a.batch <= 0 || a.H <= 0 || a.W <= 0) return hipErrorInvalidValue;
-    if (a.gn_partial && a.gn_cpg != 4 && a.gn_cpg != 8 && a.gn_cpg != 16) return hipErrorInvalidValue;
-    if ((long long)a.H * a.W * a.Cin >= (1LL << 31)) return hipErrorInvalidValue;        // 32-bit per-image offsets
-    if ((long long)(a.Cin / 64) * 9 * a.Cout * 64 >= (1LL << 31)) return hipErrorInvalidValue;
+    if (!vt_gn_cpg_ok(a.gn_partial, a.gn_cpg)) return hipErrorInvalidValue;
+    if (!vt_fits_i32((long long)a.H * a.W * a.Cin) || !vt_fits_i32((long long)(a.Cin / 64) * 9 * a.Cout * 64)) return hipErrorInvalidValue;
     if ((a.scX != nullptr) != (a.scW != nullptr)) return hipErrorInvalidValue;
-    if (a.scX && (a.scCin <= 0 || (a.scCin % 32) || a.res || a.res_f16 || (long long)a.H * a.W * a.scCin >= (1LL << 31))) return hipErrorInvalidValue;
+    if (a.scX && (a.scCin <= 0 || (a.scCin % 32) || a.res || a.res_f16 || !vt_fits_i32((long long)a.H * a.W * a.scCin))) return hipErrorInvalidValue;
     if (a.shape == 1) return launch_shape<4, 1>(a, s);
     if (a.shape == 2) return launch_shape<2, 2>(a, s);
     if (a.shape != 0) return hipErrorInvalidValue;

@@ -23,7 +23,7 @@
 // its first use.  Weights: ring of three stages, W(t + 2) issued during step t.
 #include <type_traits>
 
-#include "vt_common.h"
+#include "vt_halo.h"
 #include "vt_kernels.h"
 
 namespace {
@@ -61,25 +61,6 @@ __host__ __device__ constexpr int ng_plane(int p) { return p < 2 ? 0 : p < 4 ? 1
 __host__ __device__ constexpr int ng_dx(int p) { return (p < 2 || p == 6) ? 1 : 0; }
 __host__ __device__ constexpr int ng_rows(int p) { return (p < 4 || p == 8) ? 9 : 8; }
 
-__device__ __forceinline__ void wait_vmcnt(int n) {
-    switch (n) {
-#define C(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        C(0) C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12)
-#undef C
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-__device__ __forceinline__ int opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-// the same for a wave-uniform value: the plane-buffer bases must not be combined with the per-lane fragment offsets into
-// loop-invariant address tables (3 slots x 8 bases x 2 pitches live across the whole K loop spill)
-__device__ __forceinline__ int opaque_s(int v) {
-    asm volatile("" : "+s"(v));
-    return v;
-}
-
 // F16: X and Wp hold fp16 bits (v_mfma_f32_16x16x32_f16) -- the fp16-operand mode of the convs (vt_set_flag 18)
 template <bool F16>
 __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_kernel(const Conv3x3S2Args a) {
@@ -91,18 +72,11 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_kernel(const Conv3x3S2A
     const int wp = wave / WC, wc = wave % WC;
     const int fr = lane & 15, fq = lane >> 4;
 
-    // ---- tile coordinates (launch-constant divisors arrive as 2^40 / d + 1 multipliers)
-    auto fdiv = [](int n, unsigned long long m, int d) -> int {
-        return m ? (int)(((unsigned long long)(unsigned)n * m) >> 40) : n / d;
-    };
-    int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int b = fdiv(logical, a.m_per_img, a.per_img);
-    logical -= b * a.per_img;
-    const int tile = fdiv(logical, a.m_ctiles, a.ctiles);
-    const int ct = logical - tile * a.ctiles;
-    const int tyi = fdiv(tile, a.m_tiles_x, a.tiles_x);
-    const int ty0 = tyi * ROWS, tx0 = (tile - tyi * a.tiles_x) * TW;       // output coordinates
-    const int c0 = ct * BC;
+    // ---- tile coordinates
+    const VtHaloTile tl = vt_halo_tile_of(a);
+    const int b = tl.b, tile = tl.tile;
+    const int ty0 = tl.tyi * ROWS, tx0 = tl.txi() * TW;       // output coordinates
+    const int c0 = tl.ct * BC;
     const bf16_t* Xb = a.X + (long long)b * a.H * a.W * a.Cin;
     const int xpix = a.x_planar ? 32 : a.Cin, xchunk = a.x_planar ? a.H * a.W * 32 : 32;      // element strides of a pixel / a 32-channel chunk (wave-uniform)
     const int nchunk = a.Cin >> 5;
@@ -131,7 +105,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_kernel(const Conv3x3S2A
             int piece = j * NWV + wave;
             if (piece >= NPT) piece = NPT - 1;
             const int row0 = (PL == 0 && piece == NP) ? pl_rows(0) - 16 : piece * 16;
-            const int hr = row0 + opaque(drow);
+            const int hr = row0 + vt_opaque(drow);
             const int hy = hr / PITCH, hx = hr - hy * PITCH;
             const int iy = 2 * (ty0 + hy) + PY, ix = 2 * (tx0 + hx) + PX;
             const int lch = (lane & 3) ^ (((hr >> 2) & 1) << 1);         // logical chunk this lane's physical slot holds
@@ -144,7 +118,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_kernel(const Conv3x3S2A
     };
     auto issue_w = [&](int t) {
         char* dst = wbase + (t % NW) * WBUF;
-        const bf16_t* wt = a.Wp + (long long)t * wstep + opaque(wsrc0);
+        const bf16_t* wt = a.Wp + (long long)t * wstep + vt_opaque(wsrc0);
 #pragma unroll
         for (int j = 0; j < WPW; ++j)
             __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(wt + j * NWV * 16 * 32), VT_LDS_PTR(dst + (j * NWV + wave) * 1024), 16, 0, 0);
@@ -187,15 +161,15 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_kernel(const Conv3x3S2A
 
     bf16x8 wfc[TC], xr[TP + 1];
     {
-        wait_vmcnt(WPW + nx_pl(1));              // X(plane 0) and W(0) landed (this wave's pieces) ...
+        vt_wait_vmcnt<12>(WPW + nx_pl(1));       // X(plane 0) and W(0) landed (this wave's pieces) ...
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();            // ... and everybody else's
         asm volatile("" ::: "memory");
-        const char* ws0 = wbase + opaque(wfoff);
+        const char* ws0 = wbase + vt_opaque(wfoff);
 #pragma unroll
         for (int i = 0; i < TC; ++i) wfc[i] = *(const bf16x8*)(ws0 + i * 16 * HB);
 #pragma unroll
-        for (int r = 0; r < TP + 1; ++r) xr[r] = xfrag(xbase + opaque_s(wpoff17), 17, r, 0);
+        for (int r = 0; r < TP + 1; ++r) xr[r] = xfrag(xbase + vt_opaque_s(wpoff17), 17, r, 0);
     }
 
     // ring slot of plane pl of chunk c: (4 c + pl) % 3 = (c + pl) % 3
@@ -217,7 +191,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_kernel(const Conv3x3S2A
                 if (p == 4) n = nx_pl(3);
                 if (p == 6 && !LAST) n = nx_pl(0);
                 if (p == 0) n = nx_pl(1);        // previous chunk's step 8 (or the prologue)
-                wait_vmcnt(n);
+                vt_wait_vmcnt<12>(n);
             }
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -229,8 +203,8 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_kernel(const Conv3x3S2A
             const int npl = ng_plane(p), ndx = ng_dx(p), nrows = ng_rows(p);
             const int npitch = pl_pitch(npl);
             const bool next_chunk = p == 8;
-            const char* xs_n = xbase + opaque_s(slot_of(next_chunk ? cmn : cm, npl) * XSTRIDE + (npitch == 17 ? wpoff17 : wpoff16));
-            const char* ws_n = wbase + ((t + 1) % NW) * WBUF + opaque(wfoff);
+            const char* xs_n = xbase + vt_opaque_s(slot_of(next_chunk ? cmn : cm, npl) * XSTRIDE + (npitch == 17 ? wpoff17 : wpoff16));
+            const char* ws_n = wbase + ((t + 1) % NW) * WBUF + vt_opaque(wfoff);
             (void)pl;
             auto refill = [&](int r, const f32x4& after) {
                 if (has_next && r < nrows) xr[r] = xfrag_after(xs_n, npitch, r, ndx, after);
@@ -306,30 +280,16 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_kernel(const Conv3x3S2A
             if (a.out_f32) *(f32x4*)(a.out_f32 + o + 4 * i) = v;
             acc[i][j] = v;
         }
-        typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
         if (a.out_f16) {
 #pragma unroll
-            for (int i = 0; i < TC; i += 2) {
-                f16x8 h;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { h[r] = (f16_t)acc[i][j][r]; h[4 + r] = (f16_t)acc[i + 1][j][r]; }
-                *(f16x8*)(a.out_f16 + o + 4 * i) = h;
-            }
+            for (int i = 0; i < TC; i += 2) vt_halo_store16(a.out_f16 + o + 4 * i, acc[i][j], acc[i + 1][j]);
         }
         if (a.out_bf16) {
 #pragma unroll
             for (int i = 0; i < TC; i += 2) {
-                if (a.out16_f16) {                             // the copy carries fp16 bits when its consumer (a fused shortcut) runs on fp16 operands
-                    f16x8 h;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { h[r] = (f16_t)acc[i][j][r]; h[4 + r] = (f16_t)acc[i + 1][j][r]; }
-                    *(f16x8*)((f16_t*)a.out_bf16 + o + 4 * i) = h;
-                } else {
-                    bf16x8 h;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { h[r] = (bf16_t)acc[i][j][r]; h[4 + r] = (bf16_t)acc[i + 1][j][r]; }
-                    *(bf16x8*)(a.out_bf16 + o + 4 * i) = h;
-                }
+                // the copy carries fp16 bits when its consumer (a fused shortcut) runs on fp16 operands
+                if (a.out16_f16) vt_halo_store16((f16_t*)a.out_bf16 + o + 4 * i, acc[i][j], acc[i + 1][j]);
+                else vt_halo_store16(a.out_bf16 + o + 4 * i, acc[i][j], acc[i + 1][j]);
             }
         }
     }
@@ -368,26 +328,15 @@ hipError_t vt_launch_repack_ohwi_to_s2(const bf16_t* w, bf16_t* wp, int Cin, int
 hipError_t vt_launch_conv3x3_s2(const Conv3x3S2Args& a, hipStream_t s) {
     if (!a.X || !a.Wp || !a.zeros || (!a.out_f32 && !a.out_bf16 && !a.out_f16)) return hipErrorInvalidValue;
     if (!vt_conv3x3_s2_supported(a.Cin, a.Cout) || a.batch <= 0 || a.H < 2 || a.W < 2) return hipErrorInvalidValue;
-    if (a.gn_partial && a.gn_cpg != 4 && a.gn_cpg != 8 && a.gn_cpg != 16) return hipErrorInvalidValue;
-    if ((long long)a.H * a.W * a.Cin >= (1LL << 31)) return hipErrorInvalidValue;        // 32-bit per-image offsets
-    if ((long long)(a.Cin / 32) * 9 * a.Cout * 32 >= (1LL << 31)) return hipErrorInvalidValue;
+    if (!vt_gn_cpg_ok(a.gn_partial, a.gn_cpg)) return hipErrorInvalidValue;
+    if (!vt_fits_i32((long long)a.H * a.W * a.Cin) || !vt_fits_i32((long long)(a.Cin / 32) * 9 * a.Cout * 32)) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_s2_halo_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv3x3_s2_halo_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        return e;
-    });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, SMEM, conv3x3_s2_halo_kernel<false>, conv3x3_s2_halo_kernel<true>);
     if (ea != hipSuccess) return ea;
     Conv3x3S2Args k = a;
     k.Ho = a.H / 2; k.Wo = a.W / 2;                       // pad (0,1,0,1), 3x3, stride 2: floor((H + 1 - 3) / 2) + 1
-    const long long tiles = vt_conv3x3_s2_tiles(k.Ho, k.Wo);
-    const long long nblk = tiles * (a.Cout / BC) * a.batch;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-    k.tiles_x = (k.Wo + TW - 1) / TW; k.ctiles = a.Cout / BC; k.per_img = (int)(tiles * k.ctiles); k.ptiles = (int)tiles;
-    auto magic = [&](long long d) -> unsigned long long {
-        return (nblk * d < (1LL << 40) && nblk < (1LL << 23)) ? ((1ULL << 40) / (unsigned long long)d + 1ULL) : 0ULL;
-    };
-    k.m_per_img = magic(k.per_img); k.m_ctiles = magic(k.ctiles); k.m_tiles_x = magic(k.tiles_x);
+    const long long nblk = vt_halo_tile_grid(k, (k.Wo + TW - 1) / TW, (k.Ho + ROWS - 1) / ROWS, a.Cout / BC, a.batch);
+    if (!nblk) return hipErrorInvalidValue;
     if (a.f16) hipLaunchKernelGGL(conv3x3_s2_halo_kernel<true>, dim3((unsigned)nblk), dim3(NT), SMEM, s, k);
     else hipLaunchKernelGGL(conv3x3_s2_halo_kernel<false>, dim3((unsigned)nblk), dim3(NT), SMEM, s, k);
     return hipGetLastError();

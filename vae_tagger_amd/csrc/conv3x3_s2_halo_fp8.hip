@@ -10,7 +10,7 @@
 // The generic fp8 GEMM ran these three launches in 3.4 ms per step (1.08 PF).
 #include <type_traits>
 
-#include "vt_common.h"
+#include "vt_halo.h"
 #include "vt_kernels.h"
 
 namespace {
@@ -27,9 +27,6 @@ constexpr int XSTRIDE = 297 * HB;            // plane (0,0): 9 x 33 halo rows
 constexpr int SMEM = NXB * XSTRIDE + NW * WBUF;   // 81 600 B
 static_assert(2 * SMEM <= 160 * 1024, "two workgroups per CU");
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 __host__ __device__ constexpr int pl_py(int pl) { return pl >> 1; }
 __host__ __device__ constexpr int pl_px(int pl) { return pl & 1; }
 __host__ __device__ constexpr int pl_pitch(int pl) { return pl_px(pl) ? 32 : 33; }
@@ -43,30 +40,6 @@ __host__ __device__ constexpr int ng_plane(int p) { return p < 2 ? 0 : p < 4 ? 1
 __host__ __device__ constexpr int ng_dx(int p) { return (p < 2 || p == 6) ? 1 : 0; }
 __host__ __device__ constexpr int ng_rows(int p) { return (p < 4 || p == 8) ? TP + 1 : TP; }
 
-__device__ __forceinline__ void wait_vmcnt(int n) {
-    switch (n) {
-#define C(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        C(0) C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12)
-#undef C
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-__device__ __forceinline__ int opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-__device__ __forceinline__ int opaque_s(int v) {
-    asm volatile("" : "+s"(v));
-    return v;
-}
-__device__ __forceinline__ int swz(int row) { return (row ^ (row >> 2)) & 3; }
-// 32-byte fragment of LDS row `row`: logical chunks 2 g, 2 g + 1
-__device__ __forceinline__ i32x8 read_frag(const char* base, int row, int g) {
-    const int a = row * HB + (((2 * g) ^ swz(row)) << 4);
-    const i32x4 lo = *(const i32x4*)(base + a), hi = *(const i32x4*)(base + (a ^ 16));
-    return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
 __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x3S2Fp8Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const xbase = smem;
@@ -76,25 +49,18 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x
     const int wp = wave / WC, wc = wave % WC;
     const int g = lane >> 5, li = lane & 31;
 
-    auto fdiv = [](int n, unsigned long long m, int d) -> int {
-        return m ? (int)(((unsigned long long)(unsigned)n * m) >> 40) : n / d;
-    };
-    int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int b = fdiv(logical, a.m_per_img, a.per_img);
-    logical -= b * a.per_img;
-    const int tile = fdiv(logical, a.m_ctiles, a.ctiles);
-    const int ct = logical - tile * a.ctiles;
-    const int tyi = fdiv(tile, a.m_tiles_x, a.tiles_x);
-    const int ty0 = tyi * ROWS, tx0 = (tile - tyi * a.tiles_x) * TWX;       // output coordinates
-    const int c0 = ct * BC;
+    const VtHaloTile tl = vt_halo_tile_of(a);
+    const int b = tl.b, tile = tl.tile;
+    const int ty0 = tl.tyi * ROWS, tx0 = tl.txi() * TWX;       // output coordinates
+    const int c0 = tl.ct * BC;
     const unsigned char* Xb = a.X + (long long)b * a.H * a.W * a.Cin;
     const int xpix = a.x_planar ? 64 : a.Cin, xchunk = a.x_planar ? a.H * a.W * 64 : 64;      // byte strides of a pixel / a 64-channel chunk (wave-uniform)
     const int nchunk = a.Cin >> 6;
 
     // ---- DMA bookkeeping: one wave-instruction = 16 LDS rows x 64 B; lane l -> row (l >> 2), physical chunk (l & 3),
-    // logical chunk = physical ^ swz(row) with the row's ACTUAL index (the ragged planes' last piece is shifted back to end at the plane's end)
+    // logical chunk = physical ^ vt_swz8(row) with the row's ACTUAL index (the ragged planes' last piece is shifted back to end at the plane's end)
     const int drow = lane >> 2;
-    const int wdchunk = (lane & 3) ^ swz(drow);                            // weight stages: pieces start at multiples of 16 rows
+    const int wdchunk = (lane & 3) ^ vt_swz8(drow);                            // weight stages: pieces start at multiples of 16 rows
     const int wsrc0 = (c0 + wave * 16 + drow) * HB + wdchunk * 16;
     const int wstep = a.Cout * HB;
 
@@ -107,10 +73,10 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x
             int piece = j * NWV + wave;
             if (piece >= NP) piece = NP - 1;
             const int row0 = (piece == NP - 1) ? NR - 16 : piece * 16;        // (NR - 16 = piece * 16 when the plane is a whole number of pieces)
-            const int hr = row0 + opaque(drow);
+            const int hr = row0 + vt_opaque(drow);
             const int hy = hr / PITCH, hx = hr - hy * PITCH;
             const int iy = 2 * (ty0 + hy) + PY, ix = 2 * (tx0 + hx) + PX;
-            const int lch = (lane & 3) ^ swz(hr);
+            const int lch = (lane & 3) ^ vt_swz8(hr);
             // (a.x_planar: chunk-planar [Cin/64][H][W][64] instead of NHWC -- see conv3x3_s2_halo.hip)
             const void* src = (iy < a.H && ix < a.W) ? (const void*)(Xb + ((iy * a.W + ix) * xpix + chunk * xchunk + lch * 16)) : a.zeros;
             __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(src), VT_LDS_PTR(dst + row0 * HB), 16, 0, 0);
@@ -118,7 +84,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x
     };
     auto issue_w = [&](int t) {
         char* dst = wbase + (t % NW) * WBUF;
-        const unsigned char* wt = a.Wp + (long long)t * wstep + opaque(wsrc0);
+        const unsigned char* wt = a.Wp + (long long)t * wstep + vt_opaque(wsrc0);
 #pragma unroll
         for (int j = 0; j < WPW; ++j)
             __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(wt + j * NWV * 16 * HB), VT_LDS_PTR(dst + (j * NWV + wave) * 1024), 16, 0, 0);
@@ -144,14 +110,14 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x
     const int xrow33 = wp * TP * 33 + li, xrow32 = wp * TP * 32 + li;
     i32x8 wfc[2], xr[TP + 1];
     {
-        wait_vmcnt(WPW + nx_pl(1));              // X(plane 0) and W(0) landed (this wave's pieces) ...
+        vt_wait_vmcnt<12>(WPW + nx_pl(1));       // X(plane 0) and W(0) landed (this wave's pieces) ...
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();            // ... and everybody else's
         asm volatile("" ::: "memory");
 #pragma unroll
-        for (int h = 0; h < 2; ++h) wfc[h] = read_frag(wbase, opaque(wrow0) + 32 * h, g);
+        for (int h = 0; h < 2; ++h) wfc[h] = vt_read_frag8(wbase, vt_opaque(wrow0) + 32 * h, g);
 #pragma unroll
-        for (int r = 0; r < TP + 1; ++r) xr[r] = read_frag(xbase, opaque(xrow33) + r * 33, g);
+        for (int r = 0; r < TP + 1; ++r) xr[r] = vt_read_frag8(xbase, vt_opaque(xrow33) + r * 33, g);
     }
 
     int cm = 0;                                  // chunk % 3: ring slot of plane pl of chunk c = (c + pl) % 3
@@ -171,7 +137,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x
                 if (p == 4) n = nx_pl(3);
                 if (p == 6 && !LAST) n = nx_pl(0);
                 if (p == 0) n = nx_pl(1);
-                wait_vmcnt(n);
+                vt_wait_vmcnt<12>(n);
             }
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -181,10 +147,10 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x
             const bool has_next = !LAST || p < 8;
             const int npl = ng_plane(p), ndx = ng_dx(p), nrows = ng_rows(p);
             const int npitch = pl_pitch(npl);
-            const char* xs_n = xbase + opaque_s(slot_of(p == 8 ? cmn : cm, npl) * XSTRIDE);
+            const char* xs_n = xbase + vt_opaque_s(slot_of(p == 8 ? cmn : cm, npl) * XSTRIDE);
             const char* ws_n = wbase + ((t + 1) % NW) * WBUF;
             auto refill = [&](int r) {
-                if (has_next && r < nrows) xr[r] = read_frag(xs_n, opaque(npitch == 33 ? xrow33 : xrow32) + r * npitch + ndx, g);
+                if (has_next && r < nrows) xr[r] = vt_read_frag8(xs_n, vt_opaque(npitch == 33 ? xrow33 : xrow32) + r * npitch + ndx, g);
             };
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -212,7 +178,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x
             __builtin_amdgcn_s_setprio(0);
             if (has_next) {
 #pragma unroll
-                for (int h = 0; h < 2; ++h) wfc[h] = read_frag(ws_n, opaque(wrow0) + 32 * h, g);
+                for (int h = 0; h < 2; ++h) wfc[h] = vt_read_frag8(ws_n, vt_opaque(wrow0) + 32 * h, g);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -247,7 +213,6 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x
             if (y >= a.Ho || x >= a.Wo) continue;
             valid |= 1u << j;
             const long long o = ob + ((long long)y * a.Wo + x) * a.Cout + cw;
-            typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
             if (a.res) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -261,114 +226,17 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_s2_halo_fp8_kernel(const Conv3x
                 for (int i = 0; i < 4; ++i)
                     *(f32x4*)(a.out_f32 + o + 4 * i) = f32x4{acc[h][j][4 * i], acc[h][j][4 * i + 1], acc[h][j][4 * i + 2], acc[h][j][4 * i + 3]};
             }
-            if (a.out_f16) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    f16x8 hh;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) hh[q] = (f16_t)acc[h][j][8 * i + q];
-                    *(f16x8*)(a.out_f16 + o + 8 * i) = hh;
-                }
-            }
-            if (a.out_bf16) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    bf16x8 hh;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) hh[q] = (bf16_t)acc[h][j][8 * i + q];
-                    *(bf16x8*)(a.out_bf16 + o + 8 * i) = hh;
-                }
-            }
+            if (a.out_f16) vt_halo_store16_f8(a.out_f16 + o, acc[h][j]);
+            if (a.out_bf16) vt_halo_store16_f8(a.out_bf16 + o, acc[h][j]);
         }
     }
     if (a.gn_partial) {
-        // GroupNorm (n, mean, M2) of this tile's outputs (conv3x3_halo_fp8.hip's scheme: a group lives in one lane, pivot-shifted sums,
-        // DPP row sums, the two pixel-row waves merged by Chan's formula in a fixed order)
+        // GroupNorm (n, mean, M2) of this tile's outputs for the next norm; the scratch is the last weight stage
         float* lds = (float*)(smem + SMEM - WBUF);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();                      // every wave has read its last fragments
         asm volatile("" ::: "memory");
-        const int cpg = a.gn_cpg;
-        const int gpb = BC / cpg;
-        float npix = 0.f;
-#pragma unroll
-        for (int j = 0; j < TP; ++j) npix += (float)__popcll(__ballot((valid >> j) & 1u) & 0xffffffffull);
-        const float n = npix * (float)cpg;
-        const bool full = __ballot(valid != (1u << TP) - 1u) == 0ull;
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        auto stats = [&](auto cpg_tag, auto full_tag) {
-            constexpr int CPG = decltype(cpg_tag)::value;
-            constexpr bool FULL = decltype(full_tag)::value;
-            constexpr int NQ = 16 / CPG;
-            float piv[2][NQ], s[2][NQ], ss[2][NQ];
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const int v = __builtin_bit_cast(int, acc[h][0][q * CPG]);
-                    const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(v, 0));
-                    const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(v, 32));
-                    piv[h][q] = g ? p1 : p0;
-                }
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const f32x2 p2 = {piv[h][q], piv[h][q]};
-                    f32x2 s2 = {0.f, 0.f}, q2 = {0.f, 0.f};
-#pragma unroll
-                    for (int j = 0; j < TP; ++j) {
-                        if (FULL || ((valid >> j) & 1u)) {
-#pragma unroll
-                            for (int r = q * CPG; r < (q + 1) * CPG; r += 2) {
-                                const f32x2 d = f32x2{acc[h][j][r], acc[h][j][r + 1]} - p2;
-                                s2 += d; q2 += d * d;
-                            }
-                        }
-                    }
-                    s[h][q] = s2[0] + s2[1]; ss[h][q] = q2[0] + q2[1];
-                }
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const float a0 = vt_row16_sum(s[h][q]), b0 = vt_row16_sum(ss[h][q]);
-                    s[h][q] = a0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a0), 0x142, 0xA, 0xF, false));
-                    ss[h][q] = b0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b0), 0x142, 0xA, 0xF, false));
-                }
-            if (li == 16) {
-                const float rn = n > 0.f ? 1.0f / n : 0.f;
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q) {
-                        const float ms = s[h][q] * rn;
-                        const int lg = (wc * 64 + 32 * h + 16 * g + q * CPG) / CPG;
-                        float* d = lds + (wp * gpb + lg) * 3;
-                        d[0] = n; d[1] = n > 0.f ? piv[h][q] + ms : 0.f; d[2] = n > 0.f ? fmaxf(ss[h][q] - s[h][q] * ms, 0.f) : 0.f;
-                    }
-            }
-        };
-        auto stats_c = [&](auto cpg_tag) {
-            if (full) stats(cpg_tag, std::true_type{}); else stats(cpg_tag, std::false_type{});
-        };
-        if (cpg == 4) stats_c(std::integral_constant<int, 4>{});
-        else if (cpg == 8) stats_c(std::integral_constant<int, 8>{});
-        else stats_c(std::integral_constant<int, 16>{});
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if ((int)threadIdx.x < gpb) {
-            static_assert(WP == 2, "two pixel-row waves are merged");
-            const float* d0 = lds + threadIdx.x * 3;
-            const float* d1 = lds + (gpb + threadIdx.x) * 3;
-            float nn = 0.f, mean = 0.f, m2 = 0.f;
-            vt_chan_merge(nn, mean, m2, d0[0], d0[1], d0[2]);
-            vt_chan_merge(nn, mean, m2, d1[0], d1[1], d1[2]);
-            const int G = a.Cout / cpg;
-            float* o = a.gn_partial + (((long long)b * a.ptiles + tile) * G + c0 / cpg + threadIdx.x) * 3;
-            o[0] = nn; o[1] = mean; o[2] = m2;
-        }
+        vt_gn_epilogue_partials_f8<TP, WP, 1>(acc, valid, a, b, tile, c0, wp, 0, wc, lane, lds);
     }
 }
 
@@ -380,22 +248,15 @@ int vt_conv3x3_s2_fp8_tiles(int Ho, int Wo) { return ((Wo + TWX - 1) / TWX) * ((
 hipError_t vt_launch_conv3x3_s2_fp8(const Conv3x3S2Fp8Args& a, hipStream_t s) {
     if (!a.X || !a.Wp || !a.mult || !a.zeros || (!a.out_f32 && !a.out_bf16 && !a.out_f16)) return hipErrorInvalidValue;
     if (!vt_conv3x3_s2_fp8_supported(a.Cin, a.Cout) || a.batch <= 0 || a.H < 2 || a.W < 2) return hipErrorInvalidValue;
-    if (a.gn_partial && a.gn_cpg != 4 && a.gn_cpg != 8 && a.gn_cpg != 16) return hipErrorInvalidValue;
-    if ((long long)a.H * a.W * a.Cin >= (1LL << 31)) return hipErrorInvalidValue;
-    if ((long long)(a.Cin / 64) * 9 * a.Cout * 64 >= (1LL << 31)) return hipErrorInvalidValue;
+    if (!vt_gn_cpg_ok(a.gn_partial, a.gn_cpg)) return hipErrorInvalidValue;
+    if (!vt_fits_i32((long long)a.H * a.W * a.Cin) || !vt_fits_i32((long long)(a.Cin / 64) * 9 * a.Cout * 64)) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] { return hipFuncSetAttribute((const void*)conv3x3_s2_halo_fp8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM); });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, SMEM, conv3x3_s2_halo_fp8_kernel);
     if (ea != hipSuccess) return ea;
     Conv3x3S2Fp8Args k = a;
     k.Ho = a.H / 2; k.Wo = a.W / 2;
-    const long long tiles = vt_conv3x3_s2_fp8_tiles(k.Ho, k.Wo);
-    const long long nblk = tiles * (a.Cout / BC) * a.batch;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-    k.tiles_x = (k.Wo + TWX - 1) / TWX; k.ctiles = a.Cout / BC; k.per_img = (int)(tiles * k.ctiles); k.ptiles = (int)tiles;
-    auto magic = [&](long long d) -> unsigned long long {
-        return (nblk * d < (1LL << 40) && nblk < (1LL << 23)) ? ((1ULL << 40) / (unsigned long long)d + 1ULL) : 0ULL;
-    };
-    k.m_per_img = magic(k.per_img); k.m_ctiles = magic(k.ctiles); k.m_tiles_x = magic(k.tiles_x);
+    const long long nblk = vt_halo_tile_grid(k, (k.Wo + TWX - 1) / TWX, (k.Ho + ROWS - 1) / ROWS, a.Cout / BC, a.batch);
+    if (!nblk) return hipErrorInvalidValue;
     hipLaunchKernelGGL(conv3x3_s2_halo_fp8_kernel, dim3((unsigned)nblk), dim3(NT), SMEM, s, k);
     return hipGetLastError();
 }

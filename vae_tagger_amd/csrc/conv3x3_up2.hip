@@ -18,7 +18,7 @@
 // Tile: 4 waves, 8 x 16 low-resolution pixels (16 x 32 outputs) x 64 couts per workgroup; a wave owns 2 low-resolution rows x 16 px x 64
 // couts x 4 phases = 32 accumulator tiles (128 VGPRs).  Per chunk the workgroup stages the halo (12 KB) and the chunk's 16 weight tiles
 // (64 KB) in one burst, single-buffered: 76 KB, so TWO workgroups share a CU and one runs its MFMAs while the other stages.
-#include "vt_common.h"
+#include "vt_halo.h"
 #include "vt_kernels.h"
 
 namespace {
@@ -164,30 +164,15 @@ void conv3x3_up2_kernel(const ConvUp2Args a) {
 #pragma unroll
                 for (int i = 0; i < TC; ++i) *(f32x4*)(a.out_f32 + o + 4 * i) = acc[i][jj];
             }
-            typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
             if (a.out_f16) {
 #pragma unroll
-                for (int i = 0; i < TC; i += 2) {
-                    f16x8 h;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { h[r] = (f16_t)acc[i][jj][r]; h[4 + r] = (f16_t)acc[i + 1][jj][r]; }
-                    *(f16x8*)(a.out_f16 + o + 4 * i) = h;
-                }
+                for (int i = 0; i < TC; i += 2) vt_halo_store16(a.out_f16 + o + 4 * i, acc[i][jj], acc[i + 1][jj]);
             }
             if (a.out_16) {
 #pragma unroll
                 for (int i = 0; i < TC; i += 2) {
-                    if (a.out16_f16) {
-                        f16x8 h;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) { h[r] = (f16_t)acc[i][jj][r]; h[4 + r] = (f16_t)acc[i + 1][jj][r]; }
-                        *(f16x8*)((f16_t*)a.out_16 + o + 4 * i) = h;
-                    } else {
-                        bf16x8 h;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) { h[r] = (bf16_t)acc[i][jj][r]; h[4 + r] = (bf16_t)acc[i + 1][jj][r]; }
-                        *(bf16x8*)(a.out_16 + o + 4 * i) = h;
-                    }
+                    if (a.out16_f16) vt_halo_store16((f16_t*)a.out_16 + o + 4 * i, acc[i][jj], acc[i + 1][jj]);
+                    else vt_halo_store16(a.out_16 + o + 4 * i, acc[i][jj], acc[i + 1][jj]);
                 }
             }
         }
@@ -205,7 +190,7 @@ template <bool F16>
 hipError_t launch_up2(const ConvUp2Args& a, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = conv3x3_up2_kernel<F16>;
-    hipError_t ea = vt_once_per_device(attr_done, [&] { return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM); });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, SMEM, kern);
     if (ea != hipSuccess) return ea;
     ConvUp2Args k = a;
     k.tiles_x = (a.W + TW - 1) / TW;
@@ -281,8 +266,7 @@ int vt_conv3x3_up2_tiles(int H, int W) { return ((W + TW - 1) / TW) * ((H + ROWS
 hipError_t vt_launch_conv3x3_up2(const ConvUp2Args& a, hipStream_t s) {
     if (!a.X || !a.Wp || !a.zeros || (!a.out_f32 && !a.out_f16 && !a.out_16)) return hipErrorInvalidValue;
     if (!vt_conv3x3_up2_supported(a.Cin, a.Cout) || a.batch <= 0 || a.H <= 0 || a.W <= 0) return hipErrorInvalidValue;
-    if (a.gn_partial && a.gn_cpg != 4 && a.gn_cpg != 8 && a.gn_cpg != 16) return hipErrorInvalidValue;
-    if ((long long)a.H * a.W * a.Cin >= (1LL << 31)) return hipErrorInvalidValue;           // 32-bit per-image input offsets
+    if (!vt_gn_cpg_ok(a.gn_partial, a.gn_cpg) || !vt_fits_i32((long long)a.H * a.W * a.Cin)) return hipErrorInvalidValue;
     if ((long long)a.H * 2 + 1 >= (1LL << 30) || (long long)a.W * 2 + 1 >= (1LL << 30)) return hipErrorInvalidValue;
     return a.f16 ? launch_up2<true>(a, s) : launch_up2<false>(a, s);
 }

@@ -401,7 +401,7 @@ hipError_t launch_cfg_f8(const ConvGemmArgs& a, hipStream_t s) {
     constexpr int smem = 2 * (BP + BC) * ROWB;
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = conv_gemm_kernel<BP, BC, WP, WC, OCC2, !F16, F16>;
-    hipError_t ea = vt_once_per_device(attr_done, [&] { return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, smem, kern);
     if (ea != hipSuccess) return ea;
     const int HWo = a.Hout * a.Wout;
     const long long nblk = (long long)((HWo + BP - 1) / BP) * ((a.Cout + BC - 1) / BC) * a.batch;
@@ -417,11 +417,7 @@ hipError_t launch_cfg(const ConvGemmArgs& a, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};
     auto kern = conv_gemm_kernel<BP, BC, WP, WC, OCC2>;
     auto gated = conv_gemm_gated_kernel<BP, BC, WP, WC, OCC2>;
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gated, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        return e;
-    });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, smem, kern, gated);
     if (ea != hipSuccess) return ea;
     const int HWo = a.Hout * a.Wout;
     const int ptiles = (HWo + BP - 1) / BP, ctiles = (a.Cout + BC - 1) / BC;
@@ -447,7 +443,7 @@ hipError_t vt_launch_conv_gemm(const ConvGemmArgs& a, hipStream_t s) {
     if (a.res && a.res_f16) return hipErrorInvalidValue;
     if (a.Cin % 8) return hipErrorInvalidValue;                           // k tail handled per 8-element chunk
     if (a.gn_partial) {
-        if (a.gn_cpg != 4 && a.gn_cpg != 8 && a.gn_cpg != 16) return hipErrorInvalidValue;
+        if (!vt_gn_cpg_ok(a.gn_partial, a.gn_cpg)) return hipErrorInvalidValue;
         const int bc = a.Cout <= 32 ? 32 : (a.Cout <= 128 ? 128 : 256);
         if (a.out_mode != 0 || (a.Cout % bc) || a.Cout <= 32) return hipErrorInvalidValue;
     }

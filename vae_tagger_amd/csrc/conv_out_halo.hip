@@ -144,13 +144,9 @@ bool vt_conv_out_halo_supported(int Cin, int Cout) { return Cout == CO && Cin >=
 hipError_t vt_launch_conv_out_halo(const ConvOutArgs& a, hipStream_t s) {
     if (!a.X || !a.Wp || !a.out || !a.zeros || a.batch <= 0 || a.H <= 0 || a.W <= 0 || !vt_conv_out_halo_supported(a.Cin, a.Cout)) return hipErrorInvalidValue;
     if (a.keep <= 0 || a.keep > CO) return hipErrorInvalidValue;
-    if ((long long)a.H * a.W * a.Cin >= (1LL << 31)) return hipErrorInvalidValue;          // 32-bit offsets inside an image
+    if (!vt_fits_i32((long long)a.H * a.W * a.Cin)) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_done{0};
-    hipError_t ea = vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_out_halo_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_out_halo_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        return e;
-    });
+    hipError_t ea = vt_dynamic_smem_once(attr_done, SMEM, conv_out_halo_kernel<false>, conv_out_halo_kernel<true>);
     if (ea != hipSuccess) return ea;
     const long long nblk = (long long)((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH) * a.batch;
     if (nblk <= 0 || nblk > 0x7fffffffLL) return hipErrorInvalidValue;

@@ -300,9 +300,7 @@ hipError_t vt_launch_conv_thin_wgrad(const ConvThinWgradArgs& a_in, hipStream_t 
     a.tiles_y = (a.H + TW_TH - 1) / TW_TH;
     a.thin_is_input = a.thin_is_input != 0;
     static std::atomic<unsigned long long> done{0};
-    hipError_t e = vt_once_per_device(done, [] {
-        return hipFuncSetAttribute((const void*)conv_thin_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS);
-    });
+    hipError_t e = vt_dynamic_smem_once(done, TW_LDS, conv_thin_wgrad_kernel);
     if (e != hipSuccess) return e;
     const long long wgs = (long long)a.splits * (a.Cw / TW_BC);
     if (wgs > 0x7fffffffLL) return hipErrorInvalidValue;

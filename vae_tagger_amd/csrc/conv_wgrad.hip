@@ -278,9 +278,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const f32x4* __restri
 template <int KS>
 hipError_t launch_wgrad(const ConvWgradArgs& a, hipStream_t s) {
     static std::atomic<unsigned long long> done{0};
-    hipError_t e = vt_once_per_device(done, [] {
-        return hipFuncSetAttribute((const void*)conv_wgrad_kernel<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, WgGeom<KS>::LDS);
-    });
+    hipError_t e = vt_dynamic_smem_once(done, WgGeom<KS>::LDS, conv_wgrad_kernel<KS>);
     if (e != hipSuccess) return e;
     const long long wgs = (long long)a.splits * (a.Cin / WG_BC) * (a.Cout / WG_BC);
     if (wgs > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -291,9 +289,7 @@ hipError_t launch_wgrad(const ConvWgradArgs& a, hipStream_t s) {
 template <int MODE>
 hipError_t launch_wgrad_rs(const ConvWgradArgs& a, hipStream_t s) {
     static std::atomic<unsigned long long> done{0};
-    hipError_t e = vt_once_per_device(done, [] {
-        return hipFuncSetAttribute((const void*)conv_wgrad_rs_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, RsGeom<MODE>::LDS);
-    });
+    hipError_t e = vt_dynamic_smem_once(done, RsGeom<MODE>::LDS, conv_wgrad_rs_kernel<MODE>);
     if (e != hipSuccess) return e;
     const long long wgs = (long long)a.splits * (a.Cin / WG_BC) * (a.Cout / WG_BC);
     if (wgs > 0x7fffffffLL) return hipErrorInvalidValue;

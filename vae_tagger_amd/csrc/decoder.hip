@@ -607,11 +607,7 @@ size_t vt_decoder_workspace_floats(int B, int C, int H, int Wd) {
 hipError_t vt_decoder_sort(const float* logits, int B, int N, float* conf, long long* idx, hipStream_t s) {
     if (N <= 0 || B <= 0) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_done{0};
-    CK(vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)dec_sort_local_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, SORT_CH * 8);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dec_sort_local_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, SORT_CH * 8);
-        return e;
-    }));
+    CK(vt_dynamic_smem_once(attr_done, SORT_CH * 8, dec_sort_local_kernel<0>, dec_sort_local_kernel<1>));
     const int chunks = (N + SORT_CH - 1) / SORT_CH;
     unsigned long long* keys = (unsigned long long*)idx;      // the int64 index output doubles as the key array
     int np = 2;

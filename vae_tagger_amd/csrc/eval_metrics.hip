@@ -443,11 +443,7 @@ __global__ __launch_bounds__(256) void eval_recount_emit_kernel(const uint32_t* 
 
 hipError_t sort_rows(unsigned long long* keys, long long rows, long long pitch, long long n, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};
-    CK(vt_once_per_device(attr_done, [&] {
-        hipError_t e = hipFuncSetAttribute((const void*)eval_sort_local_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, VT_SORT_CH * 8);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)eval_sort_local_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, VT_SORT_CH * 8);
-        return e;
-    }));
+    CK(vt_dynamic_smem_once(attr_done, VT_SORT_CH * 8, eval_sort_local_kernel<0>, eval_sort_local_kernel<1>));
     const long long chunks = (n + VT_SORT_CH - 1) / VT_SORT_CH;
     long long top = VT_SORT_CH;
     while (top < n) top <<= 1;

@@ -27,6 +27,21 @@ inline hipError_t vt_once_per_device(std::atomic<unsigned long long>& done, F se
     done.fetch_or(bit, std::memory_order_release);
     return hipSuccess;
 }
+// The usual `set`: every one of `kernels` may be launched with `bytes` of dynamic LDS.  `done` is a static of the launcher.
+template <typename... K>
+inline hipError_t vt_dynamic_smem_once(std::atomic<unsigned long long>& done, int bytes, K... kernels) {
+    return vt_once_per_device(done, [&] {
+        hipError_t e = hipSuccess;
+        ((e = e != hipSuccess ? e : hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)), ...);
+        return e;
+    });
+}
+
+// Launcher checks (a launcher answers hipErrorInvalidValue where one fails).
+// GroupNorm partials from a conv epilogue: a group must lie inside the 16 consecutive couts one lane (or one fq column) holds.
+inline bool vt_gn_cpg_ok(const float* gn_partial, int gn_cpg) { return !gn_partial || gn_cpg == 4 || gn_cpg == 8 || gn_cpg == 16; }
+// The kernels index inside one image (or one packed weight tensor) with 32-bit offsets: n = its element count.
+inline bool vt_fits_i32(long long n) { return n < (1LL << 31); }
 
 #define VT_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define VT_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
@@ -305,6 +320,110 @@ __device__ __forceinline__ void vt_gn_epilogue_partials_il(const f32x4 (&v)[TC][
             vt_chan_merge(nn, mean, m2, d[0], d[1], d[2]);
         }
         float* o = out + threadIdx.x * 3;
+        o[0] = nn; o[1] = mean; o[2] = m2;
+    }
+}
+
+// Variant for the fp8 halo kernels (conv3x3_halo_fp8, conv3x3_s2_halo_fp8): register r of lane (g = lane >> 5, li = lane & 31) in
+// acc[h][j] is cout 64 wc + 32 h + 16 g + r of the block's 128 at pixel column li of the wave's row j; `valid` has bit j set where that
+// pixel exists.  A group (cpg = 4, 8 or 16 consecutive couts) lives in one lane; sums are taken relative to a per-(wave half, group)
+// pivot, reduced over the wave's 32 pixel columns, then the WP * WX pixel-wave groups (this wave is number wp * WX + wx) are merged
+// with Chan's formula in a fixed order (deterministic).  `a` is the kernel's argument block (gn_cpg, gn_partial, ptiles, Cout),
+// (b, tile, c0) this workgroup's image, pixel tile and first cout, `lane` the kernel's own threadIdx.x & 63: the triples go to
+// a.gn_partial[((b * ptiles + tile) * (Cout / cpg) + c0 / cpg + k) * 3], k = the group inside the block.
+// How the arguments are passed is measured, not taste (tools/device_isa_report.py): with the output pointer
+// formed by the caller, the lane index taken again in here, or the wave-uniform wp / wx / wc copied by value, the compiler
+// allocates the registers of the whole kernel differently and the stride-1 kernels' main loops change.  As it stands each of the
+// four kernels differs from its own spelled-out epilogue by the operand order of two commutative instructions.
+// This phase is latency, not work (its VALU issue is hidden behind the other resident workgroup's MFMAs, but a 128-channel
+// layer's main loop is shorter than its epilogue): every group's pivot, sums and lane reductions are independent chains
+// issued together, cross-lane steps are DPP / readlane (no LDS round trips), one branch writes all partials.
+// lds: WP * WX * (128 / cpg) * 3 floats, free for reuse: the CALLER passes the barrier that makes it so (which one differs: a kernel
+// whose residual or shortcut path has already passed a barrier since the last fragment reads skips it).
+template <int TP, int WP, int WX, typename Args>
+__device__ __forceinline__ void vt_gn_epilogue_partials_f8(const f32x16 (&acc)[2][TP], unsigned valid, const Args& a, int b, int tile,
+                                                           int c0, const int& wp, const int& wx, const int& wc, int lane, float* lds) {
+    const int g = lane >> 5, li = lane & 31;
+    const int cpg = a.gn_cpg;
+    const int gpb = 128 / cpg;
+    float npix = 0.f;
+#pragma unroll
+    for (int j = 0; j < TP; ++j) npix += (float)__popcll(__ballot((valid >> j) & 1u) & 0xffffffffull);   // lanes 0..31 = the 32 columns
+    const float n = npix * (float)cpg;
+    const bool full = __ballot(valid != (1u << TP) - 1u) == 0ull;      // the whole wave tile is inside the image
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    auto stats = [&](auto cpg_tag, auto full_tag) {
+        constexpr int CPG = decltype(cpg_tag)::value;
+        constexpr bool FULL = decltype(full_tag)::value;
+        constexpr int NQ = 16 / CPG;
+        float piv[2][NQ], s[2][NQ], ss[2][NQ];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {             // pivot = the group's first value at the half-wave's first pixel (finite even outside the image)
+                const int v = __builtin_bit_cast(int, acc[h][0][q * CPG]);
+                const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(v, 0));
+                const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(v, 32));
+                piv[h][q] = g ? p1 : p0;
+            }
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const f32x2 p2 = {piv[h][q], piv[h][q]};
+                f32x2 s2 = {0.f, 0.f}, q2 = {0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < TP; ++j) {
+                    if (FULL || ((valid >> j) & 1u)) {
+#pragma unroll
+                        for (int r = q * CPG; r < (q + 1) * CPG; r += 2) {
+                            const f32x2 d = f32x2{acc[h][j][r], acc[h][j][r + 1]} - p2;
+                            s2 += d; q2 += d * d;
+                        }
+                    }
+                }
+                s[h][q] = s2[0] + s2[1]; ss[h][q] = q2[0] + q2[1];
+            }
+        // 32-column sums: inside each 16-lane row, then row 0 -> row 1 and row 2 -> row 3 (row_bcast15): lanes 16..31 / 48..63 hold them
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const float a0 = vt_row16_sum(s[h][q]), b0 = vt_row16_sum(ss[h][q]);
+                s[h][q] = a0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a0), 0x142, 0xA, 0xF, false));
+                ss[h][q] = b0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b0), 0x142, 0xA, 0xF, false));
+            }
+        if (li == 16) {
+            const float rn = n > 0.f ? 1.0f / n : 0.f;
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const float ms = s[h][q] * rn;
+                    const int lg = (wc * 64 + 32 * h + 16 * g + q * CPG) / CPG;
+                    float* d = lds + ((wp * WX + wx) * gpb + lg) * 3;
+                    d[0] = n; d[1] = n > 0.f ? piv[h][q] + ms : 0.f; d[2] = n > 0.f ? fmaxf(ss[h][q] - s[h][q] * ms, 0.f) : 0.f;
+                }
+        }
+    };
+    auto stats_c = [&](auto cpg_tag) {
+        if (full) stats(cpg_tag, std::true_type{}); else stats(cpg_tag, std::false_type{});
+    };
+    if (cpg == 4) stats_c(std::integral_constant<int, 4>{});
+    else if (cpg == 8) stats_c(std::integral_constant<int, 8>{});
+    else stats_c(std::integral_constant<int, 16>{});
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if ((int)threadIdx.x < gpb) {
+        float nn = 0.f, mean = 0.f, m2 = 0.f;
+#pragma unroll
+        for (int w = 0; w < WP * WX; ++w) {                    // the pixel-wave groups, in a fixed order
+            const float* d = lds + (w * gpb + threadIdx.x) * 3;
+            vt_chan_merge(nn, mean, m2, d[0], d[1], d[2]);
+        }
+        const int G = a.Cout / cpg;
+        float* o = a.gn_partial + (((long long)b * a.ptiles + tile) * G + c0 / cpg + threadIdx.x) * 3;
         o[0] = nn; o[1] = mean; o[2] = m2;
     }
 }
