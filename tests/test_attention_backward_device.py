@@ -15,8 +15,9 @@ DEV = "cuda:0"
 C = 512
 
 # B, H, W: S = 99 (one ragged query block, two key tiles: empty segments), 320 (two query blocks, five key tiles), 561 (ragged in every unit),
-# 2112 (more than eight query blocks)
-SHAPES = {"S99": (2, 9, 11), "S320": (2, 16, 20), "S561": (2, 17, 33), "S2112": (1, 64, 33)}
+# 2112 (more than eight query blocks); S40x96: batch 96 x one query block = 96 blocks, where the gradient P.V takes its 256-channel form (every other
+# shape here runs four 128-channel workgroups per block), on one partial key tile and a slab with 8 real rows in its second row tile
+SHAPES = {"S99": (2, 9, 11), "S320": (2, 16, 20), "S561": (2, 17, 33), "S2112": (1, 64, 33), "S40x96": (96, 5, 8)}
 
 
 @pytest.fixture(scope="module")

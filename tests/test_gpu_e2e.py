@@ -489,7 +489,7 @@ def test_device_preprocess_is_bit_exact_with_totensor_normalize(vae):
     assert torch.equal(got, ref)
 
 
-@pytest.mark.parametrize("gain,S", [(1.0, 200), (6.0, 200), (1.0, 1024), (6.0, 1024), (6.0, 333), (1.0, 64), (6.0, 64), (1.0, 2048), (6.0, 2048)])   # every GEMM tile config, plain and flagged; 1024 / 2048: Q.K^T key sweep split over 2 / 4 workgroups
+@pytest.mark.parametrize("gain,S", [(1.0, 200), (6.0, 200), (1.0, 1024), (6.0, 1024), (6.0, 333), (1.0, 64), (6.0, 64), (1.0, 2048), (6.0, 2048), (1.0, 40)])   # every GEMM tile config, plain and flagged; 1024 / 2048: Q.K^T key sweep split over 2 / 4 workgroups; 40: batch 96
 def test_mid_attention_without_softmax_pass(gain, S):
     """vt_op_attention (E5): the default path has no softmax pass -- Q.K^T emits exp(s - c_i) with c_i from operand norms,
     P.V divides by the row sums.  Every mode stays on the fp32 reference; with to_q / to_k scaled by 6 the norm bound is
@@ -505,7 +505,9 @@ def test_mid_attention_without_softmax_pass(gain, S):
     m = load_diffusers_vae_from_config(get_diffusers_vae_config())
     m.load_state_dict(sd, strict=False)
     ctx = m.to("cuda").eval()._context()
-    B, C = 3, 512
+    # S = 40 runs at batch 96: one query block per image, 96 in all, so P.V takes its 256-channel form (two workgroups per query block; below
+    # 96 blocks it is four 128-channel ones) on one partial key tile and a slab with 8 real rows in its second row tile
+    B, C = (96 if S == 40 else 3), 512
     g = torch.Generator().manual_seed(int(gain) * 1000 + S)
     x = torch.randn(B, S, C, generator=g).bfloat16()
     res = torch.randn(B, S, C, generator=g)
@@ -549,7 +551,7 @@ def test_mid_attention_without_softmax_pass(gain, S):
         ctx.call("vt_set_flag", 17, 1)
 
 
-@pytest.mark.parametrize("gain,S", [(1.0, 200), (6.0, 200), (1.0, 1024), (3.0, 1024), (1.0, 333), (1.0, 64), (1.0, 2048), (3.0, 2500), (1.0, 130)])
+@pytest.mark.parametrize("gain,S", [(1.0, 200), (6.0, 200), (1.0, 1024), (3.0, 1024), (1.0, 333), (1.0, 64), (1.0, 2048), (3.0, 2500), (1.0, 130), (1.0, 300)])
 def test_mid_block_attention_on_fp8_operands(gain, S):
     """fp8 mode (vt_set_flag 11; attn_fp8.hip): q | k, v^T and the softmax numerators as e4m3, both S x S contractions on
     v_mfma_scale_f32_16x16x128_f8f6f4.  Checked against fp32 attention of the SAME e4m3-rounded q, k, v (what the kernels multiply):
@@ -569,7 +571,11 @@ def test_mid_block_attention_on_fp8_operands(gain, S):
     m = load_diffusers_vae_from_config(get_diffusers_vae_config())
     m.load_state_dict(sd, strict=False)
     ctx = m.to("cuda").eval()._context()
-    B, C = 2, 512
+    # S = 300 runs at batch 48: 96 query blocks, so the e4m3 P.V takes its 256-channel form (below 96 blocks: four 128-channel workgroups per
+    # block), with a partial third key tile and 12 real rows in the last slab.  (Batch 96 at S = 40 would reach the same form, but a maximum
+    # over 2 M outputs of rows that average only 40 numerators sits at 7.5 - 7.9e-3 in a CPU restatement of the e4m3 rounding of P, against
+    # FP8_ATTN_TOL = 8e-3; this shape sits at 3.1e-3, where the other gain-1 cases are.)
+    B, C = (48 if S == 300 else 2), 512
     g = torch.Generator().manual_seed(int(gain) * 1000 + S)
     x = torch.randn(B, S, C, generator=g).bfloat16()
     res = torch.randn(B, S, C, generator=g)

@@ -8,21 +8,20 @@
 //           offset per column, loaded per tile);
 //   mode 2  rows = v16, streamed = do16: the epilogue loads p^T and stores ds^T = alpha * p^T * (dp^T - D_col).
 // attn_bwd_pv_kernel is attn_pv.hip's skeleton with a gradient epilogue: fp32 stores (plus an optional bf16 copy), no row normalisation.
-// The existing kernels are not touched: these are separate instantiations in a separate unit.  No atomics; every output element is written by
+// What the two skeletons share with the forward in a form that leaves every kernel's code alone is in vt_attn.h (the tile decodes, the x^T
+// staging, the fragment-order pieces, the grid rule); the resident-slab load, the bf16 tile staging and both MFMA rings are still written
+// out here as in attn_qk.hip / attn_pv.hip, and have to be kept in step by hand (DESIGN.md section 4.28 says which forms were tried).
+// The kernels are separate instantiations in a separate unit.  No atomics; every output element is written by
 // exactly one lane from a fixed-order accumulation, so results are bit-identical from run to run and independent of the batch, of the image
 // group and of how a sweep is split over workgroups (the split only decides which workgroup runs a tile's epilogue).
 #include <hip/hip_runtime.h>
 
-#include "vt_common.h"
-#include "vt_kernels.h"
+#include "vt_attn.h"
+
+using namespace vt_attn;          // QB = 256 resident rows per workgroup, D = 512
+using namespace vt_attn::b16;     // KT = 64 streamed rows per LDS tile, KROWB / KBUF, ROWB, PT_TILE
 
 namespace {
-
-constexpr int QB = 256;        // resident rows per workgroup (8 waves x 32)
-constexpr int KT = 64;         // streamed rows per LDS tile
-constexpr int D = 512;         // head dim
-constexpr int KROWB = D * 2;   // bytes per streamed row in LDS
-constexpr int KBUF = KT * KROWB;
 
 template <int BM>
 __global__ __launch_bounds__(512, 2) void attn_bwd_qk_kernel(const AttnBwdQkArgs a) {
@@ -30,16 +29,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_qk_kernel(const AttnBwdQkArgs
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fr = lane & 15, fq = lane >> 4;
-    const int qtiles = (a.S + QB - 1) / QB;
-    const int nsplit = a.nsplit > 1 ? a.nsplit : 1;
-    const int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int per_img = qtiles * nsplit;
-    const int b = logical / per_img, qs = logical - b * per_img;
-    const int qt = qs / nsplit, ksp = qs - qt * nsplit;
+    const VtAttnQkTile t = vt_attn_qk_tile(a.S, a.nsplit);
+    const int b = t.b, ksp = t.ksp, nsplit = t.nsplit;
     const bf16_t* qb = a.rows + (long long)b * a.r_bs;
     const bf16_t* kb = a.str + (long long)b * a.s_bs;
     const int nkeys = a.S;
-    const int row0 = qt * QB + wave * 32;
+    const int row0 = t.row0(wave);
     const bool slab_on = row0 < a.S;                               // (wave-uniform) this wave's slab holds at least one real row
 
     // ---- this wave's resident slab: B operand of k-step ks for row tile j = rows[row0 + 16 j + fr][32 ks + 8 fq .. +8]
@@ -87,11 +82,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_qk_kernel(const AttnBwdQkArgs
     auto load_pin = [&](int kt) __attribute__((always_inline)) {
         if constexpr (BM == 1) return;
         if (!slab_on) return;
-        const bf16_t* s = a.Pin + pbase + (long long)kt * 2048;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) pin[j][h] = __builtin_nontemporal_load((const bf16x8*)(s + (j * 2 + h) * 512));
+        vt_attn_frag_load(pin, a.Pin + pbase + (long long)kt * PT_TILE);
     };
     auto epilogue = [&](int kt) __attribute__((always_inline)) {
         const int key0 = kt * KT + 8 * fq;
@@ -122,13 +113,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_qk_kernel(const AttnBwdQkArgs
                     pin[j][h][e] = (bf16_t)val;
                 }
         }
-        if (slab_on) {
-            bf16_t* dst = a.Pout + pbase + (long long)kt * 2048;
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) __builtin_nontemporal_store(pin[j][h], (bf16x8*)(dst + (j * 2 + h) * 512));
-        }
+        if (slab_on) vt_attn_frag_store(a.Pout + pbase + (long long)kt * PT_TILE, pin);
     };
 
     // waves w and w + 4 share a SIMD: one half runs its epilogue behind its MFMAs, the other in front of them (attn_qk.hip)
@@ -173,42 +158,24 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_qk_kernel(const AttnBwdQkArgs
 }
 
 // ---- the gradient P.V: out[q][c] = sum_k P[q][k] x^T[c][k], fp32 (+ bf16 copy) ---------------------------------------------------------------
-constexpr int ROWB = KT * 2;   // bytes per LDS row (one channel, 64 keys)
-
 template <int CB>
 __global__ __launch_bounds__(512, 2) void attn_bwd_pv_kernel(const AttnBwdPvArgs a) {
     constexpr int VBUF = CB * ROWB;
     constexpr int NCT = CB / 16;
-    constexpr int NCP = D / CB;
     extern __shared__ __attribute__((aligned(16))) char smem[];     // 2 x^T tiles
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fr = lane & 15, fq = lane >> 4;
-    const int qblocks = (a.S + QB - 1) / QB;
-    const int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int cb = logical % NCP;
-    const int rest = logical / NCP;
-    const int b = rest / qblocks, qb = rest - b * qblocks;
+    const VtAttnPvTile t = vt_attn_pv_tile<CB>(a.S, wave);
+    const int cb = t.cb, b = t.b, slab = t.slab;
     const int nkt = (a.S + KT - 1) / KT;
-    const int nslab = (a.S + 31) / 32;
-    const int slab = qb * 8 + wave;
-    const bool slab_real = slab < nslab;
-    const bf16_t* pt = a.Pt + (long long)b * a.pt_bs + (long long)(slab_real ? slab : 0) * vt_attn_pt_slab_stride(a.S) + lane * 8;
+    const bf16_t* pt = vt_attn_frag_base(a.Pt + (long long)b * a.pt_bs, a.S, t.slab_real ? slab : 0, lane);
     const bf16_t* vb = a.xt + (long long)b * a.xt_bs + (long long)cb * CB * a.ldx;
     const int ld8 = (a.S + 7) / 8 * 8;                 // keys [S, ld8) of x^T are written as zero; beyond: the zero page
 
-    const int lrow = lane >> 3, lchunk = (lane & 7) ^ lrow;
-    auto stage = [&](int kt, int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int jj = 0; jj < CB / 64; ++jj) {
-            const int R = (jj * 8 + wave) * 8 + lrow;
-            const int ch = (R & ~63) + (R & 3) + 4 * ((R >> 4) & 3) + 16 * ((R >> 2) & 3);
-            const int key = kt * KT + lchunk * 8;
-            const void* src = key < ld8 ? (const void*)(vb + (long long)ch * a.ldx + key) : a.zeros;
-            __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(src), VT_LDS_PTR(smem + buf * VBUF + (jj * 8 + wave) * 1024), 16, 0, 0);
-        }
-    };
-    const int foff[2] = {fr * ROWB + (((0 + fq) ^ (fr & 7)) << 4), fr * ROWB + (((4 + fq) ^ (fr & 7)) << 4)};
+    const VtAttnPvStage<CB, bf16_t> stage(vb, a.ldx, ld8, a.zeros, wave, lane);
+    int foff[2];
+    vt_attn_pv_foff(foff, fr, fq);
 
     f32x4 acc[NCT][2];
 #pragma unroll
@@ -217,20 +184,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_pv_kernel(const AttnBwdPvArgs
         for (int j = 0; j < 2; ++j) acc[ct][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     bf16x8 pf[2][2], pn[2][2];
-    auto load_p = [&](int kt, bf16x8 (&d)[2][2]) __attribute__((always_inline)) {
-        const bf16_t* s = pt + (long long)kt * 2048;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) d[j][h] = __builtin_nontemporal_load((const bf16x8*)(s + (j * 2 + h) * 512));
-    };
-    stage(0, 0);
-    load_p(0, pf);
+    stage(smem, 0, 0);
+    vt_attn_frag_load(pf, pt);
     for (int kt = 0; kt < nkt; ++kt) {
         __syncthreads();
         if (kt + 1 < nkt) {
-            stage(kt + 1, (kt + 1) & 1);
-            load_p(kt + 1, pn);
+            stage(smem, kt + 1, (kt + 1) & 1);
+            vt_attn_frag_load(pn, pt + (long long)(kt + 1) * PT_TILE);
         }
         const char* vs = smem + (kt & 1) * VBUF;
         constexpr int AHEAD = 6;
@@ -256,7 +216,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_pv_kernel(const AttnBwdPvArgs
     }
     // ---- epilogue: lane (fq, fr) holds, for row 16 j + fr of its slab and every 64-channel group G, the 16 consecutive channels
     // 64 G + 16 fq + 4 i + r (tile ct = 4 G + i, register r): four 16-B fp32 stores per group, and two 16-B bf16 stores of the copy
-    if (!slab_real) return;
+    if (!t.slab_real) return;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int row = slab * 32 + j * 16 + fr;
@@ -381,16 +341,14 @@ hipError_t vt_launch_attn_bwd_pv(const AttnBwdPvArgs& a, hipStream_t s) {
     if (!a.Pt || !a.xt || !a.out || !a.zeros || a.batch <= 0 || !vt_attn_bwd_supported(a.S, a.C)) return hipErrorInvalidValue;
     if ((a.ldx % 8) || (a.xt_bs % 8) || (a.ldo % 8) || (a.o_bs % 8) || (a.pt_bs % 8) || a.ldo < D) return hipErrorInvalidValue;
     if (a.ldx < (a.S + 7) / 8 * 8 || (long long)a.C * a.ldx >= (1LL << 31) || a.pt_bs < vt_attn_pt_elems(a.S)) return hipErrorInvalidValue;
-    const long long qblk = (long long)((a.S + QB - 1) / QB) * a.batch;
-    const bool narrow = qblk * 2 < 192;
-    const long long nblk = qblk * (narrow ? 4 : 2);
-    if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+    const VtAttnPvGrid g = vt_attn_pv_grid(a.S, a.batch);
+    if (g.nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_256{0}, attr_128{0};
     hipError_t ea = vt_dynamic_smem_once(attr_256, 2 * 256 * ROWB, attn_bwd_pv_kernel<256>);
     if (ea == hipSuccess) ea = vt_dynamic_smem_once(attr_128, 2 * 128 * ROWB, attn_bwd_pv_kernel<128>);
     if (ea != hipSuccess) return ea;
-    if (narrow) hipLaunchKernelGGL(attn_bwd_pv_kernel<128>, dim3((unsigned)nblk), dim3(512), 2 * 128 * ROWB, s, a);
-    else hipLaunchKernelGGL(attn_bwd_pv_kernel<256>, dim3((unsigned)nblk), dim3(512), 2 * 256 * ROWB, s, a);
+    if (g.narrow) hipLaunchKernelGGL(attn_bwd_pv_kernel<128>, dim3((unsigned)g.nblk), dim3(512), 2 * 128 * ROWB, s, a);
+    else hipLaunchKernelGGL(attn_bwd_pv_kernel<256>, dim3((unsigned)g.nblk), dim3(512), 2 * 256 * ROWB, s, a);
     return hipGetLastError();
 }
 

@@ -19,21 +19,19 @@
 //     Q.K^T stores P8's two key halves of a lane in that same order -- the MFMA only needs A and B to agree.
 // Row sums: of the e4m3-ROUNDED numerators, by the matrix pipe: P.V multiplies P8 with one more row of v^T that holds 1.0 everywhere
 // (an A operand of constants, nothing read), so that a row's weights sum to one exactly and the Q.K^T epilogue carries no sum.
+// attn_qk_fp8_kernel and proj_fp8_kernel share the workgroup decode, the key tile staging and the MFMA ring of a tile half through vt_attn.h, and
+// attn_pv_fp8_kernel takes its decode and v^T staging from there (the bf16 P.V kernels' own); the slab load and kbase are written out twice below
+// (with them in helpers proj_fp8_kernel, or both, changed code).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "vt_halo.h"
-#include "vt_kernels.h"
+#include "vt_attn.h"
+
+using namespace vt_attn;          // QB = 256 query rows per workgroup, D = 512
+using namespace vt_attn::e4m3;    // KT = 128 keys per LDS tile, KROWB / KBUF: bytes per key row / tile in LDS, ROWB
 
 namespace {
-
-constexpr int QB = 256;        // query rows per workgroup (8 waves x 32)
-constexpr int KT = 128;        // keys per LDS tile = one k-step of P.V
-constexpr int D = 512;         // head dim
-constexpr int KROWB = D;       // bytes per key row in LDS (e4m3)
-constexpr int KBUF = KT * KROWB;    // 64 KB
-
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Q.K^T: P8 fragments + segment sums
@@ -47,15 +45,11 @@ __global__ __launch_bounds__(512, 2) void attn_qk_fp8_kernel(const AttnQk8Args a
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fr = lane & 15, fq = lane >> 4;
-    const int qtiles = (a.S + QB - 1) / QB;
-    const int nsplit = a.nsplit > 1 ? a.nsplit : 1;
-    const int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int per_img = qtiles * nsplit;
-    const int b = logical / per_img, qs = logical - b * per_img;
-    const int qt = qs / nsplit, ksp = qs - qt * nsplit;
+    const VtAttnQkTile t = vt_attn_qk_tile(a.S, a.nsplit);
+    const int b = t.b, ksp = t.ksp, nsplit = t.nsplit;
     const unsigned char* qb = a.qk8 + (long long)b * a.qk_bs;
     const unsigned char* kb = qb + D;
-    const int row0 = qt * QB + wave * 32;
+    const int row0 = t.row0(wave);
 
     // ---- this wave's Q slab: B operand of k-step ks for query tile j = q8[row0 + 16 j + fr][128 ks + 32 fq .. + 32]
     i32x8 qf[2][4];
@@ -77,22 +71,7 @@ __global__ __launch_bounds__(512, 2) void attn_qk_fp8_kernel(const AttnQk8Args a
     }
     const float alpha2 = a.alpha * 1.44269504f;
 
-    // ---- key tile staging: one wave-instruction = 2 key rows (1 KB); lane l -> row (l >> 5), physical 16-B chunk (l & 31), which holds
-    // logical chunk (l & 31) ^ (R & 15) (R = LDS row): the 16 rows a fragment read touches hit 16 different chunk slots.
-    // With R = 2 (8 jj + wave) + (lane >> 5): row tile m = jj and r = 2 wave + (lane >> 5) for every jj, so a lane's eight source
-    // addresses of a tile differ by wave-uniform offsets only (kept that way on purpose: eight hoisted 64-bit per-lane addresses spill).
-    const int sr_ = 2 * wave + (lane >> 5);                               // r of this lane's rows
-    const int skey = 32 * (sr_ >> 2) + (sr_ & 3);                         // ... their key inside the block, before the row tile's 16 (m >> 2) + 4 (m & 3)
-    const int schunk = ((lane & 31) ^ sr_) << 4;
-    auto stage = [&](int kt, int buf) __attribute__((always_inline)) {
-        const int key_l = kt * KT + vt_opaque(skey);
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-            const int key = key_l + 16 * (jj >> 2) + 4 * (jj & 3);
-            const void* src = key < a.S ? (const void*)(kb + (long long)key * a.ldq + schunk) : a.zeros;
-            __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(src), VT_LDS_PTR(smem + buf * KBUF + (jj * 8 + wave) * 1024), 16, 0, 0);
-        }
-    };
+    const VtAttn8QkStage stage(kb, a.ldq, a.S, a.zeros, wave, lane);
     // fragment of row tile m at k-step ks: LDS row 16 m + fr, logical chunks 8 ks + 2 fq (+ 1) -> physical ^ fr (low four bits)
     int kbase[2][2];                                       // [ks & 1][half]: the XOR touches chunk bits 0..3, ks >> 1 is an immediate
 #pragma unroll
@@ -103,7 +82,6 @@ __global__ __launch_bounds__(512, 2) void attn_qk_fp8_kernel(const AttnQk8Args a
     // A 128-key tile is worked off in two HALVES of four row tiles (64 keys x 32 queries = 32 accumulator registers): with all eight row
     // tiles in flight the kernel sat at 255 VGPRs and any further state -- the overflow watch below -- spilled ~100 of them.
     f32x4 acc[4][2];
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     i32x4 hold[2][2];                                      // P8 pieces of the tile: [query tile][key half]
     unsigned clampw = 0;                                   // MODE 3: bit 7 of a byte set <=> some stored P8 byte is 448 (the shift may be a SAMPLED maximum)
 
@@ -174,43 +152,22 @@ __global__ __launch_bounds__(512, 2) void attn_qk_fp8_kernel(const AttnQk8Args a
     // MODE 1 may sweep every kstep-th key tile only (a sampled maximum: see run_attention); the two LDS buffers alternate per iteration
     const int kstep = (MODE == 1 && a.kstride > 1) ? a.kstride : 1;
     int it = 0;
-    if (kt0 < nkt) stage(kt0, 0);
+    if (kt0 < nkt) stage(smem, kt0, 0);
     for (int kt = kt0; kt < nkt; kt += kstep, ++it) {
         if (counted && it > (late ? 1 : 0)) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (late) {
-            if (kt + kstep < nkt) stage(kt + kstep, (it + 1) & 1);
+            if (kt + kstep < nkt) stage(smem, kt + kstep, (it + 1) & 1);
             if (it > 0) { epilogue(kt - kstep, 1); if (MODE == 3) store_held(kt - kstep); }
         }
         const char* ks_base = smem + (it & 1) * KBUF;
-        // key fragments (32 B per lane = two ds_read_b128) through a ring of register sets, read AHEAD positions before their MFMAs
-        constexpr int AHEAD = 3, RING = 4;
-        auto half = [&](int h /* compile-time */) __attribute__((always_inline)) {
-            i32x8 kf[RING];
-            auto frag = [&](int idx) __attribute__((always_inline)) -> i32x8 {
-                const int ks = idx >> 2, m = 4 * h + (idx & 3);
-                const char* p = ks_base + (ks >> 1) * 256 + m * 16 * KROWB;
-                return vt_cat8(*(const i32x4*)(p + kbase[ks & 1][0]), *(const i32x4*)(p + kbase[ks & 1][1]));
-            };
-#pragma unroll
-            for (int p = 0; p < AHEAD; ++p) kf[p] = frag(p);
-#pragma unroll
-            for (int idx = 0; idx < 16; ++idx) {
-                if (idx + AHEAD < 16) kf[(idx + AHEAD) % RING] = frag(idx + AHEAD);
-                const int ks = idx >> 2, mm = idx & 3;
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[mm][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(kf[idx % RING], qf[j][ks], ks == 0 ? zero4 : acc[mm][j], 0, 0, 0, 127, 0, 127);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        half(0);
+        vt_attn8_qk_mfma_half<0>(acc, qf, ks_base, kbase);
         epilogue(kt, 0);
-        half(1);
+        vt_attn8_qk_mfma_half<1>(acc, qf, ks_base, kbase);
         if (!late) {
-            if (kt + kstep < nkt) stage(kt + kstep, (it + 1) & 1);
+            if (kt + kstep < nkt) stage(smem, kt + kstep, (it + 1) & 1);
             epilogue(kt, 1);
             if (MODE == 3) store_held(kt);
         }
@@ -246,15 +203,11 @@ __global__ __launch_bounds__(512, 2) void proj_fp8_kernel(const ProjFp8Args a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fr = lane & 15, fq = lane >> 4;
-    const int qtiles = (a.nq + QB - 1) / QB;
-    const int nsplit = a.nsplit > 1 ? a.nsplit : 1;
-    const int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int per_img = qtiles * nsplit;
-    const int b = logical / per_img, qs = logical - b * per_img;
-    const int qt = qs / nsplit, ksp = qs - qt * nsplit;
+    const VtAttnQkTile t = vt_attn_qk_tile(a.nq, a.nsplit);
+    const int b = t.b, ksp = t.ksp, nsplit = t.nsplit;
     const unsigned char* qb = a.q8 + (long long)b * a.q_bs;
     const unsigned char* kb = a.k8 + (long long)b * a.k_bs;
-    const int row0 = qt * QB + wave * 32;
+    const int row0 = t.row0(wave);
 
     i32x8 qf[2][4];
     float qbias[2];
@@ -269,18 +222,7 @@ __global__ __launch_bounds__(512, 2) void proj_fp8_kernel(const ProjFp8Args a) {
     }
     const float alpha = a.alpha * a.oscale;
 
-    const int sr_ = 2 * wave + (lane >> 5);
-    const int skey = 32 * (sr_ >> 2) + (sr_ & 3);
-    const int schunk = ((lane & 31) ^ sr_) << 4;
-    auto stage = [&](int kt, int buf) __attribute__((always_inline)) {
-        const int key_l = kt * KT + vt_opaque(skey);
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-            const int key = key_l + 16 * (jj >> 2) + 4 * (jj & 3);
-            const void* src = key < a.nk ? (const void*)(kb + (long long)key * a.ldk + schunk) : a.zeros;
-            __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(src), VT_LDS_PTR(smem + buf * KBUF + (jj * 8 + wave) * 1024), 16, 0, 0);
-        }
-    };
+    const VtAttn8QkStage stage(kb, a.ldk, a.nk, a.zeros, wave, lane);
     int kbase[2][2];
 #pragma unroll
     for (int p = 0; p < 2; ++p)
@@ -325,37 +267,17 @@ __global__ __launch_bounds__(512, 2) void proj_fp8_kernel(const ProjFp8Args a) {
     };
 
     int it = 0;
-    if (kt0 < kt1) stage(kt0, 0);
+    if (kt0 < kt1) stage(smem, kt0, 0);
     for (int kt = kt0; kt < kt1; ++kt, ++it) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (kt + 1 < kt1) stage(kt + 1, (it + 1) & 1);
+        if (kt + 1 < kt1) stage(smem, kt + 1, (it + 1) & 1);
         const char* ks_base = smem + (it & 1) * KBUF;
-        constexpr int AHEAD = 3, RING = 4;
-        auto half = [&](int h /* compile-time */) __attribute__((always_inline)) {
-            i32x8 kf[RING];
-            auto frag = [&](int idx) __attribute__((always_inline)) -> i32x8 {
-                const int ks = idx >> 2, m = 4 * h + (idx & 3);
-                const char* p = ks_base + (ks >> 1) * 256 + m * 16 * KROWB;
-                return vt_cat8(*(const i32x4*)(p + kbase[ks & 1][0]), *(const i32x4*)(p + kbase[ks & 1][1]));
-            };
-#pragma unroll
-            for (int p = 0; p < AHEAD; ++p) kf[p] = frag(p);
-#pragma unroll
-            for (int idx = 0; idx < 16; ++idx) {
-                if (idx + AHEAD < 16) kf[(idx + AHEAD) % RING] = frag(idx + AHEAD);
-                const int ks = idx >> 2, mm = idx & 3;
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[mm][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(kf[idx % RING], qf[j][ks], ks == 0 ? zero4 : acc[mm][j], 0, 0, 0, 127, 0, 127);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        half(0);
+        vt_attn8_qk_mfma_half<0>(acc, qf, ks_base, kbase);
         epilogue_half(kt, 0);
         __builtin_amdgcn_sched_barrier(0);
-        half(1);
+        vt_attn8_qk_mfma_half<1>(acc, qf, ks_base, kbase);
         epilogue_half(kt, 1);
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -364,44 +286,23 @@ __global__ __launch_bounds__(512, 2) void proj_fp8_kernel(const ProjFp8Args a) {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // P.V: o[q][c] = (1 / (8 sum_q)) sum_k P8[q][k] v8^T[c][k]
-constexpr int ROWB = KT;       // bytes per LDS row of the v^T tile (one channel, 128 keys)
-
 template <int CB>
 __global__ __launch_bounds__(512, 2) void attn_pv_fp8_kernel(const AttnPv8Args a) {
     constexpr int VBUF = CB * ROWB;                    // 32 KB (16 KB)
     constexpr int NCT = CB / 16;
-    constexpr int NCP = D / CB;
     extern __shared__ __attribute__((aligned(16))) char smem[];     // 2 v^T tiles
     if (a.gate && *a.gate != a.gate_expect) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fr = lane & 15, fq = lane >> 4;
-    const int qblocks = (a.S + QB - 1) / QB;
-    const int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int cb = logical % NCP;
-    const int rest = logical / NCP;
-    const int b = rest / qblocks, qb = rest - b * qblocks;
+    const VtAttnPvTile t = vt_attn_pv_tile<CB>(a.S, wave);
+    const int cb = t.cb, b = t.b, slab = t.slab;
+    const bool slab_real = t.slab_real;
     const int nkt = (a.S + KT - 1) / KT;
-    const int nslab = (a.S + 31) / 32;
-    const int slab = qb * 8 + wave;
-    const bool slab_real = slab < nslab;
     const unsigned char* pt = a.P8 + (long long)b * a.p_bs + (long long)(slab_real ? slab : 0) * vt_attn_p8_slab_stride(a.S) + lane * 16;
     const unsigned char* vb = a.vt8 + (long long)b * a.vt_bs + (long long)cb * CB * a.ldv;
 
-    // ---- v^T tile staging: one wave-instruction = 8 LDS rows x 128 B; lane l -> row (l >> 3), physical chunk (l & 7),
-    // logical chunk = physical ^ (row & 7); LDS row R holds channel (R & ~63) + (R & 3) + 4 ((R >> 4) & 3) + 16 ((R >> 2) & 3)
-    // (interleaved cout map: a lane ends up with 16 consecutive channels).  Keys >= ldv16 (the written extent) come from the zero page.
-    const int lrow = lane >> 3, lchunk = (lane & 7) ^ lrow;
-    auto stage = [&](int kt, int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int jj = 0; jj < CB / 64; ++jj) {
-            const int R = (jj * 8 + wave) * 8 + lrow;
-            const int ch = (R & ~63) + (R & 3) + 4 * ((R >> 4) & 3) + 16 * ((R >> 2) & 3);
-            const int key = kt * KT + lchunk * 16;
-            const void* src = key < a.kext ? (const void*)(vb + (long long)ch * a.ldv + key) : a.zeros;
-            __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(src), VT_LDS_PTR(smem + buf * VBUF + (jj * 8 + wave) * 1024), 16, 0, 0);
-        }
-    };
+    const VtAttnPvStage<CB, unsigned char> stage(vb, a.ldv, a.kext, a.zeros, wave, lane);      // keys >= kext (the written extent): the zero page
     // A fragment (channel tile ct): LDS row ct*16 + fr, logical chunks 2 fq and 2 fq + 1, read in the order (2 fq + (fq & 1)) first --
     // with both lane quarters of a ds_read_b128 group on "their" first chunk the 16 lanes collide; crossed they do not
     const int c_first = 2 * fq + (fq & 1), c_second = 2 * fq + 1 - (fq & 1);
@@ -423,12 +324,12 @@ __global__ __launch_bounds__(512, 2) void attn_pv_fp8_kernel(const AttnPv8Args a
         for (int j = 0; j < 2; ++j)
             d[j] = vt_cat8(__builtin_nontemporal_load((const i32x4*)(s + (j * 2) * 1024)), __builtin_nontemporal_load((const i32x4*)(s + (j * 2 + 1) * 1024)));
     };
-    stage(0, 0);
+    stage(smem, 0, 0);
     load_p(0, pf);
     for (int kt = 0; kt < nkt; ++kt) {
         __syncthreads();                               // vmcnt(0) + barrier: tile kt (and pf) landed, buffer (kt+1)&1 free
         if (kt + 1 < nkt) {
-            stage(kt + 1, (kt + 1) & 1);
+            stage(smem, kt + 1, (kt + 1) & 1);
             load_p(kt + 1, pn);
         }
         const char* vs = smem + (kt & 1) * VBUF;
@@ -544,16 +445,14 @@ hipError_t vt_launch_attn_pv_fp8(const AttnPv8Args& a, hipStream_t s) {
     if (!a.P8 || !a.vt8 || !a.o || !a.zeros || a.batch <= 0 || !vt_attn_fp8_supported(a.S, a.C)) return hipErrorInvalidValue;
     if ((a.ldv % 16) || (a.vt_bs % 16) || (a.ldo % 8) || (a.o_bs % 8) || (a.p_bs % 16) || (a.kext % 16) || a.kext > a.ldv) return hipErrorInvalidValue;
     if ((long long)a.C * a.ldv >= (1LL << 31)) return hipErrorInvalidValue;
-    const long long qblk = (long long)((a.S + QB - 1) / QB) * a.batch;
-    const bool narrow = qblk * 2 < 192;
-    const long long nblk = qblk * (narrow ? 4 : 2);
-    if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+    const VtAttnPvGrid g = vt_attn_pv_grid(a.S, a.batch);
+    if (g.nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_256{0}, attr_128{0};
     hipError_t ea = vt_dynamic_smem_once(attr_256, 2 * 256 * ROWB, attn_pv_fp8_kernel<256>);
     if (ea == hipSuccess) ea = vt_dynamic_smem_once(attr_128, 2 * 128 * ROWB, attn_pv_fp8_kernel<128>);
     if (ea != hipSuccess) return ea;
-    if (narrow) hipLaunchKernelGGL(attn_pv_fp8_kernel<128>, dim3((unsigned)nblk), dim3(512), 2 * 128 * ROWB, s, a);
-    else hipLaunchKernelGGL(attn_pv_fp8_kernel<256>, dim3((unsigned)nblk), dim3(512), 2 * 256 * ROWB, s, a);
+    if (g.narrow) hipLaunchKernelGGL(attn_pv_fp8_kernel<128>, dim3((unsigned)g.nblk), dim3(512), 2 * 128 * ROWB, s, a);
+    else hipLaunchKernelGGL(attn_pv_fp8_kernel<256>, dim3((unsigned)g.nblk), dim3(512), 2 * 256 * ROWB, s, a);
     return hipGetLastError();
 }
 

@@ -9,17 +9,17 @@
 //   workgroup = 8 waves = 256 query rows x 256 channels (grid: query blocks x 2 channel halves x images; the two halves of a
 //   query block are neighbours in launch order, so the second read of P hits L2); LDS: two v^T tiles (64 KB); one workgroup per CU (196 VGPRs x 8 waves).
 // Rows of the v^T tile are permuted (interleaved cout map of conv_gemm.hip) so that a lane ends up with 16 consecutive channels.
+// The decode, the v^T staging, the fragment offsets, the P piece loads and the grid rule are vt_attn.h's, shared with attn_bwd.hip's gradient P.V
+// (the same sweep with another epilogue) and, staging and decode, with attn_fp8.hip; the sweep itself and its MFMA ring are written out here and
+// there: as one helper, or with the ring as a helper, neither kernel compiled to the code it had.
 #include <hip/hip_runtime.h>
 
-#include "vt_common.h"
-#include "vt_kernels.h"
+#include "vt_attn.h"
+
+using namespace vt_attn;          // QB = 256 query rows per workgroup, D = 512 channels
+using namespace vt_attn::b16;     // KT = 64 keys per tile, ROWB = bytes per LDS row (one channel, 64 keys)
 
 namespace {
-
-constexpr int QB = 256;        // query rows per workgroup (8 waves x 32)
-constexpr int KT = 64;         // keys per tile
-constexpr int DCH = 512;       // channels (head dim)
-constexpr int ROWB = KT * 2;   // bytes per LDS row (one channel, 64 keys)
 
 // CB = channels per workgroup: 256 (two workgroups per query block), or 128 for small grids -- batch 1 at 1024^2 has 64 query
 // blocks, i.e. 128 workgroups of the 256-channel form on 256 CUs; four 128-channel workgroups per block fill the chip
@@ -27,40 +27,20 @@ template <int CB>
 __global__ __launch_bounds__(512, 2) void attn_pv_kernel(const AttnPvArgs a) {
     constexpr int VBUF = CB * ROWB;                    // 32 KB (16 KB)
     constexpr int NCT = CB / 16;                       // 16-channel MFMA tiles per wave
-    constexpr int NCP = DCH / CB;                      // channel parts per query block
     extern __shared__ __attribute__((aligned(16))) char smem[];     // 2 v^T tiles
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fr = lane & 15, fq = lane >> 4;
-    const int qblocks = (a.S + QB - 1) / QB;
-    const int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int cb = logical % NCP;                      // channel part: neighbours share the P stream
-    const int rest = logical / NCP;
-    const int b = rest / qblocks, qb = rest - b * qblocks;
+    const VtAttnPvTile t = vt_attn_pv_tile<CB>(a.S, wave);
+    const int cb = t.cb, b = t.b, slab = t.slab;
     const int nkt = (a.S + KT - 1) / KT;
-    const int nslab = (a.S + 31) / 32;
-    const int slab = qb * 8 + wave;
-    const bool slab_real = slab < nslab;
     // P fragments of (slab, kt): 4 pieces x 64 lanes x 16 B
-    const bf16_t* pt = a.Pt + (long long)b * a.pt_bs + (long long)(slab_real ? slab : 0) * vt_attn_pt_slab_stride(a.S) + lane * 8;
+    const bf16_t* pt = vt_attn_frag_base(a.Pt + (long long)b * a.pt_bs, a.S, t.slab_real ? slab : 0, lane);
     const bf16_t* vb = a.vt + (long long)b * a.vt_bs + (long long)cb * CB * a.ldv;
     const int ld8 = (a.S + 7) / 8 * 8;                 // keys [S, ld8) of v^T are written as zero; beyond: the zero page
-
-    // ---- v^T tile staging: one wave-instruction = 8 LDS rows x 128 B; lane l -> row (l >> 3), physical chunk (l & 7),
-    // logical chunk = physical ^ (row & 7); LDS row R holds channel (R & ~63) + (R & 3) + 4 ((R >> 4) & 3) + 16 ((R >> 2) & 3)
-    const int lrow = lane >> 3, lchunk = (lane & 7) ^ lrow;
-    auto stage = [&](int kt, int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int jj = 0; jj < CB / 64; ++jj) {
-            const int R = (jj * 8 + wave) * 8 + lrow;
-            const int ch = (R & ~63) + (R & 3) + 4 * ((R >> 4) & 3) + 16 * ((R >> 2) & 3);
-            const int key = kt * KT + lchunk * 8;
-            const void* src = key < ld8 ? (const void*)(vb + (long long)ch * a.ldv + key) : a.zeros;
-            __builtin_amdgcn_global_load_lds(VT_GLOBAL_PTR(src), VT_LDS_PTR(smem + buf * VBUF + (jj * 8 + wave) * 1024), 16, 0, 0);
-        }
-    };
-    // A fragment (channel tile ct, key half h): LDS row ct*16 + fr, logical chunk 4 h + fq -> physical ^ (row & 7) = ^ (fr & 7)
-    const int foff[2] = {fr * ROWB + (((0 + fq) ^ (fr & 7)) << 4), fr * ROWB + (((4 + fq) ^ (fr & 7)) << 4)};
+    const VtAttnPvStage<CB, bf16_t> stage(vb, a.ldv, ld8, a.zeros, wave, lane);
+    int foff[2];
+    vt_attn_pv_foff(foff, fr, fq);
 
     f32x4 acc[NCT][2];
 #pragma unroll
@@ -69,19 +49,8 @@ __global__ __launch_bounds__(512, 2) void attn_pv_kernel(const AttnPvArgs a) {
         for (int j = 0; j < 2; ++j) acc[ct][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     bf16x8 pf[2][2], pn[2][2];
-    auto load_p = [&](int kt, bf16x8 (&d)[2][2]) __attribute__((always_inline)) {
-        const bf16_t* s = pt + (long long)kt * 2048;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-#ifdef PFRAG_PLAIN
-            for (int h = 0; h < 2; ++h) d[j][h] = *(const bf16x8*)(s + (j * 2 + h) * 512);
-#else
-            for (int h = 0; h < 2; ++h) d[j][h] = __builtin_nontemporal_load((const bf16x8*)(s + (j * 2 + h) * 512));
-#endif
-    };
-    stage(0, 0);
-    load_p(0, pf);
+    stage(smem, 0, 0);
+    vt_attn_frag_load(pf, pt);
     // (splitting the DMA / P-load issue between the two waves of a SIMD, which gained 13 % in attn_qk.hip, cost 10 % here:
     //  3.76 -> 4.17 ms per step; with two v^T buffers a late-issued tile does not land before the next barrier.  A ring of four
     //  32-key stages with counted vmcnt waits and one raw barrier per stage -- the halo kernel's scheme -- ran 3.80 -> 5.33 ms:
@@ -89,8 +58,8 @@ __global__ __launch_bounds__(512, 2) void attn_pv_kernel(const AttnPvArgs a) {
     for (int kt = 0; kt < nkt; ++kt) {
         __syncthreads();                               // vmcnt(0) + barrier: tile kt (and pf) landed, buffer (kt+1)&1 free
         if (kt + 1 < nkt) {
-            stage(kt + 1, (kt + 1) & 1);
-            load_p(kt + 1, pn);
+            stage(smem, kt + 1, (kt + 1) & 1);
+            vt_attn_frag_load(pn, pt + (long long)(kt + 1) * PT_TILE);
         }
         const char* vs = smem + (kt & 1) * VBUF;
         // v^T fragments through a ring of eight register sets, read AHEAD fragments before the MFMAs that use them: left to the
@@ -119,7 +88,7 @@ __global__ __launch_bounds__(512, 2) void attn_pv_kernel(const AttnPvArgs a) {
     }
     // ---- epilogue: lane (fq, fr) holds, for query row 16 j + fr of its slab and every 64-channel group G, the 16 consecutive
     // channels 64 G + 16 fq + 4 i + r (tile ct = 4 G + i, register r): scale by 1 / row sum, two 16-B bf16 stores per group
-    if (!slab_real) return;
+    if (!t.slab_real) return;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int row = slab * 32 + j * 16 + fr;
@@ -141,7 +110,7 @@ __global__ __launch_bounds__(512, 2) void attn_pv_kernel(const AttnPvArgs a) {
 
 }  // namespace
 
-bool vt_attn_pv_supported(int S, int C) { return C == DCH && S > 0; }
+bool vt_attn_pv_supported(int S, int C) { return C == D && S > 0; }
 // elements of the fragment-ordered P of one image
 long long vt_attn_pt_elems(int S) { return (long long)((S + 31) / 32) * vt_attn_pt_slab_stride(S); }
 
@@ -150,15 +119,13 @@ hipError_t vt_launch_attn_pv(const AttnPvArgs& a, hipStream_t s) {
     if ((a.ldv % 8) || (a.vt_bs % 8) || (a.ldo % 8) || (a.o_bs % 8) || (a.pt_bs % 8) || a.row_bs < a.S) return hipErrorInvalidValue;
     if (a.ldv < (a.S + 7) / 8 * 8 || (long long)a.C * a.ldv >= (1LL << 31)) return hipErrorInvalidValue;
     if (a.split_stride < (long long)a.batch * a.row_bs) return hipErrorInvalidValue;
-    const long long qblk = (long long)((a.S + QB - 1) / QB) * a.batch;
-    const bool narrow = qblk * 2 < 192;                 // the 256-channel form would leave a quarter or more of the CUs without a workgroup
-    const long long nblk = qblk * (narrow ? 4 : 2);
-    if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+    const VtAttnPvGrid g = vt_attn_pv_grid(a.S, a.batch);
+    if (g.nblk > 0x7fffffffLL) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> attr_256{0}, attr_128{0};
     hipError_t ea = vt_dynamic_smem_once(attr_256, 2 * 256 * ROWB, attn_pv_kernel<256>);
     if (ea == hipSuccess) ea = vt_dynamic_smem_once(attr_128, 2 * 128 * ROWB, attn_pv_kernel<128>);
     if (ea != hipSuccess) return ea;
-    if (narrow) hipLaunchKernelGGL(attn_pv_kernel<128>, dim3((unsigned)nblk), dim3(512), 2 * 128 * ROWB, s, a);
-    else hipLaunchKernelGGL(attn_pv_kernel<256>, dim3((unsigned)nblk), dim3(512), 2 * 256 * ROWB, s, a);
+    if (g.narrow) hipLaunchKernelGGL(attn_pv_kernel<128>, dim3((unsigned)g.nblk), dim3(512), 2 * 128 * ROWB, s, a);
+    else hipLaunchKernelGGL(attn_pv_kernel<256>, dim3((unsigned)g.nblk), dim3(512), 2 * 256 * ROWB, s, a);
     return hipGetLastError();
 }

@@ -18,20 +18,20 @@
 // mode 5 (round 4): mode 4 with the attention's to_out epilogue: + residual stream, fp16 / fp32 stores, and GroupNorm (n, mean, M2) partials of the
 //         result per (32-row slab of a wave, group of 16 output channels) for the norm that follows -- the last launch of the default path that
 //         was still on the generic GEMM.
+// attn_bwd.hip (attn_bwd_qk_kernel) repeats this skeleton and attn_fp8.hip has its e4m3 form.  vt_attn.h holds what they share in a form that leaves
+// this kernel's code alone: the constants, the workgroup decode, the fragment-order store and the launcher's checks of modes 4 and 5.  The slab load,
+// the stage lambda, kbase and the fragment ring stay written out here AND in attn_bwd.hip: each of them, moved into a helper of any form tried, changed
+// the code of at least one of the five instantiations, so a fix to one of them still has to be made in both files.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "vt_common.h"
-#include "vt_kernels.h"
+#include "vt_attn.h"
+
+using namespace vt_attn;          // QB = 256 query rows per workgroup, D = 512
+using namespace vt_attn::b16;     // KT = 64 keys per LDS tile, KROWB / KBUF: bytes per key row / tile in LDS
 
 namespace {
-
-constexpr int QB = 256;        // query rows per workgroup (8 waves x 32)
-constexpr int KT = 64;         // keys per LDS tile
-constexpr int D = 512;         // head dim (= channels of the mid block)
-constexpr int KROWB = D * 2;   // bytes per key row in LDS
-constexpr int KBUF = KT * KROWB;
 
 template <int MODE>
 __global__ __launch_bounds__(512, 2) void attn_qk_kernel(const AttnQkArgs a) {
@@ -40,19 +40,14 @@ __global__ __launch_bounds__(512, 2) void attn_qk_kernel(const AttnQkArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fr = lane & 15, fq = lane >> 4;
-    // an XCD gets a contiguous range of workgroups = the query tiles of one image (or a few): its L2 keeps that image's keys
-    const int qtiles = (a.S + QB - 1) / QB;
-    const int nsplit = a.nsplit > 1 ? a.nsplit : 1;
-    const int logical = vt_xcd_remap(blockIdx.x, gridDim.x);
-    const int per_img = qtiles * nsplit;
-    const int b = logical / per_img, qs = logical - b * per_img;
-    const int qt = qs / nsplit, ksp = qs - qt * nsplit;           // the splits of a query block are neighbours: they share its Q rows in L2
+    const VtAttnQkTile t = vt_attn_qk_tile(a.S, a.nsplit);
+    const int b = t.b, ksp = t.ksp, nsplit = t.nsplit;
     const bf16_t* qb = a.q + (long long)b * a.qk_bs;
     constexpr bool LIN = MODE == 4 || MODE == 5;                  // linear-layer forms: separate operands, key tiles split evenly
     const bf16_t* kb = a.k + (long long)b * (LIN ? a.k_bs : a.qk_bs);
     const int nkeys = LIN ? a.nk : a.S;                           // rows of the streamed operand
     const int ldk = LIN ? a.ldk : a.ldq;
-    const int row0 = qt * QB + wave * 32;
+    const int row0 = t.row0(wave);
 
     // ---- this wave's Q slab: B operand of k-step ks for row tile j = q[row0 + 16 j + fr][32 ks + 8 fq .. +8]
     bf16x8 qf[2][16];
@@ -109,18 +104,10 @@ __global__ __launch_bounds__(512, 2) void attn_qk_kernel(const AttnQkArgs a) {
     auto store_held = [&](int kt_prev) __attribute__((always_inline)) {
         if constexpr (MODE == 5) return;                       // (stored by its epilogue, in accumulator layout)
         if constexpr (MODE == 3) {
-            // fragment order (attn_pv.hip): piece (j, h) of this lane as it stands -- 1 KB contiguous per store instruction,
-            // the wave's stream over the key tiles sequential in memory
+            // fragment order (vt_attn.h): piece (j, h) of this lane as it stands
             if (row0 < a.S) {
-                bf16_t* dst = a.P + (long long)b * a.p_bs + (long long)(row0 >> 5) * vt_attn_pt_slab_stride(a.S) + (long long)kt_prev * 2048 + lane * 8;
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-#ifdef PFRAG_PLAIN
-                    for (int h = 0; h < 2; ++h) *(bf16x8*)(dst + (j * 2 + h) * 512) = hold[j][h];
-#else
-                    for (int h = 0; h < 2; ++h) __builtin_nontemporal_store(hold[j][h], (bf16x8*)(dst + (j * 2 + h) * 512));
-#endif
+                bf16_t* dst = a.P + (long long)b * a.p_bs + (long long)(row0 >> 5) * vt_attn_pt_slab_stride(a.S) + (long long)kt_prev * PT_TILE + lane * 8;
+                vt_attn_frag_store(dst, hold);
             }
             return;
         }
@@ -361,34 +348,19 @@ bool vt_attn_qk_supported(int S, int C) { return C == D && S > 0; }
 int vt_attn_linear_parts(int S) { return (S + QB - 1) / QB * 8; }      // 32-row slabs launched per image (mode 5's GroupNorm partials)
 
 hipError_t vt_launch_attn_qk(const AttnQkArgs& a, hipStream_t s) {
-    if (a.mode == 5) {
-        if (!a.q || !a.k || !a.zeros || a.batch <= 0 || !vt_attn_qk_supported(a.S, a.C) || a.nk <= 0 || (a.nk % 16) || a.gate) return hipErrorInvalidValue;
-        if ((a.out_f16 != nullptr) == (a.out_f32 != nullptr) || (a.res_f16 && a.res_f32)) return hipErrorInvalidValue;
-        if ((a.ldq % 8) || (a.ldk % 8) || (a.qk_bs % 8) || (a.k_bs % 8) || (a.ldp % 8) || (a.p_bs % 8) || a.ldp < a.nk) return hipErrorInvalidValue;
-        if ((long long)a.S * a.ldq >= (1LL << 31) || (long long)a.nk * a.ldk >= (1LL << 31)) return hipErrorInvalidValue;
-        if (a.gn_partial && a.gn_parts != vt_attn_linear_parts(a.S)) return hipErrorInvalidValue;
-        const int nsp = a.nsplit > 1 ? a.nsplit : 1;
-        if (nsp > (a.nk + KT - 1) / KT) return hipErrorInvalidValue;
-        const long long nblk5 = (long long)((a.S + QB - 1) / QB) * a.batch * nsp;
-        if (nblk5 > 0x7fffffffLL) return hipErrorInvalidValue;
-        static std::atomic<unsigned long long> attr5{0};
-        hipError_t e5 = vt_dynamic_smem_once(attr5, 2 * KBUF, attn_qk_kernel<5>);
-        if (e5 != hipSuccess) return e5;
-        hipLaunchKernelGGL(attn_qk_kernel<5>, dim3((unsigned)nblk5), dim3(512), 2 * KBUF, s, a);
-        return hipGetLastError();
-    }
-    if (a.mode == 4) {
-        if (!a.q || !a.k || !a.P || !a.zeros || a.batch <= 0 || !vt_attn_qk_supported(a.S, a.C) || a.nk <= 0 || a.gate) return hipErrorInvalidValue;
-        if ((a.ldq % 8) || (a.ldk % 8) || (a.qk_bs % 8) || (a.k_bs % 8) || (a.ldp % 8) || (a.p_bs % 8) || a.ldp < (a.nk + 7) / 8 * 8) return hipErrorInvalidValue;
-        if ((long long)a.S * a.ldq >= (1LL << 31) || (long long)a.nk * a.ldk >= (1LL << 31)) return hipErrorInvalidValue;
-        const int nsp = a.nsplit > 1 ? a.nsplit : 1;
-        if (nsp > (a.nk + KT - 1) / KT) return hipErrorInvalidValue;
-        const long long nblk4 = (long long)((a.S + QB - 1) / QB) * a.batch * nsp;
-        if (nblk4 > 0x7fffffffLL) return hipErrorInvalidValue;
-        static std::atomic<unsigned long long> attr4{0};
-        hipError_t e4 = vt_dynamic_smem_once(attr4, 2 * KBUF, attn_qk_kernel<4>);
-        if (e4 != hipSuccess) return e4;
-        hipLaunchKernelGGL(attn_qk_kernel<4>, dim3((unsigned)nblk4), dim3(512), 2 * KBUF, s, a);
+    if (a.mode == 4 || a.mode == 5) {
+        // mode 5 writes whole groups of 16 output channels (nk a multiple of 16, pitch >= nk), mode 4 whole 16-byte pieces
+        if (!vt_attn_linear_args_ok(a, a.mode == 5 ? a.nk : (a.nk + 7) / 8 * 8)) return hipErrorInvalidValue;
+        if (a.mode == 5) {
+            if ((a.nk % 16) || (a.out_f16 != nullptr) == (a.out_f32 != nullptr) || (a.res_f16 && a.res_f32)) return hipErrorInvalidValue;
+            if (a.gn_partial && a.gn_parts != vt_attn_linear_parts(a.S)) return hipErrorInvalidValue;
+        } else if (!a.P) return hipErrorInvalidValue;
+        const unsigned nblk = (unsigned)((long long)((a.S + QB - 1) / QB) * a.batch * (a.nsplit > 1 ? a.nsplit : 1));     // (fits: checked above)
+        static std::atomic<unsigned long long> attr4{0}, attr5{0};
+        const hipError_t e = a.mode == 5 ? vt_dynamic_smem_once(attr5, 2 * KBUF, attn_qk_kernel<5>) : vt_dynamic_smem_once(attr4, 2 * KBUF, attn_qk_kernel<4>);
+        if (e != hipSuccess) return e;
+        if (a.mode == 5) hipLaunchKernelGGL(attn_qk_kernel<5>, dim3(nblk), dim3(512), 2 * KBUF, s, a);
+        else hipLaunchKernelGGL(attn_qk_kernel<4>, dim3(nblk), dim3(512), 2 * KBUF, s, a);
         return hipGetLastError();
     }
     if (!a.q || !a.k || !a.rowout || !a.zeros || a.batch <= 0 || !vt_attn_qk_supported(a.S, a.C)) return hipErrorInvalidValue;
