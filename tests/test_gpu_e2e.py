@@ -493,7 +493,9 @@ def test_device_preprocess_is_bit_exact_with_totensor_normalize(vae):
 def test_mid_attention_without_softmax_pass(gain, S):
     """vt_op_attention (E5): the default path has no softmax pass -- Q.K^T emits exp(s - c_i) with c_i from operand norms,
     P.V divides by the row sums.  Every mode stays on the fp32 reference; with to_q / to_k scaled by 6 the norm bound is
-    too loose (u - l > 120), the launch group is flagged and c_i is the exact row maximum: bit-identical to mode 1."""
+    too loose (u - l > 120), the launch group is flagged and c_i is the exact row maximum: bit-identical to mode 1.
+    This holds the arithmetic on dense data; which key meets which value (tile edges, the ragged tail mask, segments, images) is held
+    exactly by test_attention_structured_device.py, whose mistakes would fit inside this tolerance."""
     import ctypes
     from vae_tagger_amd.diffusers_vae_loader import get_diffusers_vae_config, load_diffusers_vae_from_config
     from _util import vp
@@ -559,7 +561,8 @@ def test_mid_block_attention_on_fp8_operands(gain, S):
     bf16 output.  Shapes: one / several 128-key tiles, ragged tails, key sweeps split over 2 / 4 workgroups (S = 1024, 2048), and
     gains that make rows peaky.  Mode 0 takes the exponent shift from a first sweep over every 4th / 8th key tile (all of them below
     16 tiles) and redoes a launch group with the exact maximum when a numerator passed e4m3's 448; vt_set_flag(7, 1) always takes the
-    exact maximum.  The flag-14 switch puts the launch back on the bf16 kernels."""
+    exact maximum.  The flag-14 switch puts the launch back on the bf16 kernels.  Key / value indexing of the e4m3 kernels (a wrong, dropped,
+    duplicated or leaked pad key is far inside these tolerances) is held exactly by test_attention_structured_device.py."""
     import ctypes
     from vae_tagger_amd.diffusers_vae_loader import get_diffusers_vae_config, load_diffusers_vae_from_config
     from _util import vp
