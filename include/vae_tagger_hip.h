@@ -629,6 +629,14 @@ int vt_decode_image(vt_context* ctx, const float* z_nchw, int B, int h, int w, i
 typedef struct { const float* moments; const float* z; int draw; } vt_vae_loss_input;
 int vt_posterior_sample(vt_context* ctx, const float* moments, int B, int C, int hw, unsigned long long seed, int draw,
                         long long first_image, float* z_out, double* kl_out, void* stream);
+/* vt_posterior_mode_latent: the tag decoder's input in train_full, DiffusersVAEWrapper.encode's latent from moments that are already there.
+ *   moments fp32 NCHW [B'][2C][hw] with B' >= B (only the first B images are read: the anchors of an [a; p; n] encoder pass);
+ *   latent_out fp32 [B][C][hw] = mean * scaling + shift, the multiply only with has_scaling and the add only with has_shift (the
+ *   configuration's flags), each rounded on its own in fp32 -- the bits of torch's two eager ops.  One pass, float4 loads and stores when
+ *   C * hw % 4 == 0 and both pointers are 16-B aligned, else one guarded float at a time.  A null or misaligned pointer, a shape out of
+ *   range or a non-finite factor whose flag is set is VT_ERR_INVALID, and nothing is written. */
+int vt_posterior_mode_latent(vt_context* ctx, const float* moments, int B, int C, int hw, float scaling, int has_scaling, float shift,
+                             int has_shift, float* latent_out, void* stream);
 size_t vt_vae_loss_state_bytes(int B, int C, int hw, int H, int W);
 int vt_vae_loss_reset(vt_context* ctx, void* state, size_t state_bytes, double margin_triplet, double margin_contrastive,
                       double jaccard_threshold, unsigned long long seed, void* stream);
@@ -702,6 +710,21 @@ int vt_vae_optim_norm(vt_context* ctx, const float* const* grads /* host [n] */,
 int vt_vae_optim_step(vt_context* ctx, float* params, float* m, float* v, size_t arena_floats, const float* const* grads /* host [n] */,
                       const long long* numel /* host [n] */, int n, const void* scalars /* or NULL */, double lr, double beta1, double beta2,
                       double eps, double weight_decay, long long t, int chunk, void* stream);
+/* vt_full_optim_norm: train_full's ONE clip_grad_norm_ over the VAE's gradient tensors and the tag decoder's state blocks together.
+ * The first ten arguments are vt_vae_optim_norm's and mean the same; n may be any prefix of a trainer's tensors (the encoder's come first in
+ * its arenas, so the encoder-only step of the simplified loss is a smaller n on the same arenas).  head_state is the head's block
+ * (vt_head_state_bytes), front_state and cross_state the front's and the cross-attention's, each NULL with size 0 when absent (the plain
+ * decoder has only the head; the cross-attention's comes with the front's); they are checked as vt_head_clip / vt_train_clip /
+ * vt_train_clip3 check them.  The VAE's per-tile partials are written exactly as vt_vae_optim_norm writes them; one single-workgroup
+ * launch then forms S_vae in vt_vae_optim_norm's order, S_blocks in vt_train_clip's (the head's partials in index order, then the
+ * front's, then the cross-attention's), total = S_vae + S_blocks (one fp64 add), norm = (float)sqrt(total), coef = min(1, max_norm /
+ * (norm + 1e-6f)), and writes the same 16 bytes to scalars_out and to every present block's scalars.  The blocks' gradients are then
+ * scaled in place as vt_train_clip scales them; the VAE's gradients are NOT written -- vt_vae_optim_step folds the coefficient in.
+ * No atomics, no host synchronisation; bit-identical from run to run and under any `chunk`; a refused call writes nothing. */
+int vt_full_optim_norm(vt_context* ctx, const float* const* grads /* host [n] */, const long long* numel /* host [n] */, int n, float max_norm,
+                       void* scalars_out, void* workspace, size_t workspace_bytes, int chunk, void* head_state, size_t head_state_bytes,
+                       void* front_state /* or NULL */, size_t front_state_bytes, void* cross_state /* or NULL */, size_t cross_state_bytes,
+                       void* stream);
 
 /* ---- single operators (parity tests drive each kernel through the same ABI) ------------------
  * NHWC bf16 activations, weights in the reference's own layouts (fp32 host order is converted by

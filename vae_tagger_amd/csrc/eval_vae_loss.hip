@@ -152,6 +152,38 @@ __global__ __launch_bounds__(VL_KL_T) void vae_kl_kernel(const float* __restrict
     }
 }
 
+// grid (chunks of D, B): out[b] = mean[b] * scaling + shift, each op only when its flag is set, the multiply and the add rounded separately
+// (torch's two eager ops); the element-to-thread mapping of the sample pass, all loads of a thread issued before its first store
+template <bool VEC>
+__global__ __launch_bounds__(VL_T) void vae_mode_latent_kernel(const float* __restrict__ moments, long long D, float scaling, int has_scaling, float shift,
+                                                               int has_shift, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const long long b = blockIdx.y;
+    const float* m = moments + 2 * b * D;
+    float v[VL_SWEEPS][4];
+#pragma unroll
+    for (int j = 0; j < VL_SWEEPS; ++j) {
+        const long long e0 = (long long)blockIdx.x * VT_VAE_CHUNK + (long long)j * VL_STEP + 4 * (long long)threadIdx.x;
+        if (e0 < D) vl_load4<VEC>(m, e0, D, v[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < VL_SWEEPS; ++j) {
+        const long long e0 = (long long)blockIdx.x * VT_VAE_CHUNK + (long long)j * VL_STEP + 4 * (long long)threadIdx.x;
+        if (e0 >= D) break;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float x = v[j][k];
+            if (has_scaling) {
+                x = x * scaling;
+                asm volatile("" : "+v"(x));         // (-ffp-contract=fast on the command line would fuse the product into the add below)
+            }
+            if (has_shift) x = x + shift;
+            v[j][k] = x;
+        }
+        vl_store4<VEC>(out + b * D, e0, D, v[j]);
+    }
+}
+
 int vl_check_state(vt_context* c, const char* who, const void* state, size_t state_bytes, size_t need) {
     if (!state || vl_misaligned(state, ALIGN)) return c->fail(VT_ERR_INVALID, "%s: state is null or not 256-B aligned", who);
     if (state_bytes < need) return c->fail(VT_ERR_WORKSPACE, "%s: state holds %zu bytes, %zu needed", who, state_bytes, need);
@@ -185,6 +217,27 @@ int vt_posterior_sample(vt_context* c, const float* moments, int B, int C, int h
     if (kl_out) {
         hipLaunchKernelGGL(vae_kl_kernel, dim3((unsigned)B), dim3(VL_KL_T), 0, s, moments, D, kl_out); VLCK(c, "posterior_sample kl");
     }
+    return VT_OK;
+}
+
+int vt_posterior_mode_latent(vt_context* c, const float* moments, int B, int C, int hw, float scaling, int has_scaling, float shift, int has_shift,
+                             float* latent_out, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    const char* who = "vt_posterior_mode_latent";
+    if (!vl_shape_ok(B, C, hw)) return c->fail(VT_ERR_INVALID, "%s: B = %d (1..%d), C = %d or hw = %d out of range", who, B, VT_EVAL_MAX_B, C, hw);
+    if (!moments || !latent_out || vl_misaligned(moments, 4) || vl_misaligned(latent_out, 4))
+        return c->fail(VT_ERR_INVALID, "%s: moments or latent_out is null or misaligned", who);
+    if ((has_scaling && !isfinite(scaling)) || (has_shift && !isfinite(shift)))
+        return c->fail(VT_ERR_INVALID, "%s: scaling = %g and shift = %g must be finite where their flags are set", who, scaling, shift);
+    const long long D = (long long)C * hw;
+    const dim3 grid((unsigned)vt_vae_chunks(D), (unsigned)B);
+    hipStream_t s = (hipStream_t)stream;
+    if (D % 4 == 0 && !vl_misaligned(moments, 16) && !vl_misaligned(latent_out, 16))
+        hipLaunchKernelGGL(vae_mode_latent_kernel<true>, grid, dim3(VL_T), 0, s, moments, D, scaling, has_scaling != 0, shift, has_shift != 0, latent_out);
+    else
+        hipLaunchKernelGGL(vae_mode_latent_kernel<false>, grid, dim3(VL_T), 0, s, moments, D, scaling, has_scaling != 0, shift, has_shift != 0, latent_out);
+    VLCK(c, "posterior_mode_latent");
     return VT_OK;
 }
 

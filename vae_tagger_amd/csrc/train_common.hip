@@ -125,10 +125,15 @@ int vt_train_clip_blocks(vt_context* c, const char* who, const TrainBlockRef* bl
     k.count = n;
     hipLaunchKernelGGL(train_clip_kernel, dim3(1), dim3(256), 0, s, k, max_norm);
     HIPCK(c, hipGetLastError(), who);
+    return vt_train_scale_blocks(c, who, blocks, n, s);
+}
+
+int vt_train_scale_blocks(vt_context* c, const char* who, const TrainBlockRef* blocks, int n, hipStream_t s) {
     for (int i = 0; i < n; ++i) {
         const long long n4 = (long long)(blocks[i].layout->P / 4);
         hipLaunchKernelGGL(train_scale_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
-                           (float4*)((char*)blocks[i].state + blocks[i].layout->grads), n4, k.sc[i]);
+                           (float4*)((char*)blocks[i].state + blocks[i].layout->grads), n4,
+                           (const TrainScalars*)((char*)blocks[i].state + blocks[i].layout->scalars));
         HIPCK(c, hipGetLastError(), who);
     }
     return VT_OK;

@@ -310,6 +310,29 @@ int head_check_batch(vt_context* c, const char* who, const HeadLayout& l, const 
 
 }  // namespace
 
+// vt_train.h: the context's decoder-side blocks in clip order, checked as vt_head_clip / vt_train_clip / vt_train_clip3 check them
+int vt_train_decoder_blocks(vt_context* c, const char* who, void* head_state, size_t head_bytes, void* front_state, size_t front_bytes,
+                            void* cross_state, size_t cross_bytes, DecoderBlocks* out) {
+    VTCK(head_check(c, who, head_state, head_bytes, &out->head));
+    out->ref[0] = {&out->head, head_state};
+    out->n = 1;
+    const bool has_front = front_state || front_bytes, has_cross = cross_state || cross_bytes;
+    if (has_cross && !has_front) return c->fail(VT_ERR_INVALID, "%s: a cross-attention block comes with the front's", who);
+    if (has_front) {
+        if (!vt_front_trainable(c->dec)) return c->fail(VT_ERR_INVALID, "%s: this decoder's front is not trainable", who);
+        out->front = vt_front_layout(c->dec);
+        VTCK(vt_train_check(c, who, out->front, front_state, front_bytes));
+        out->ref[out->n++] = {&out->front, front_state};
+    }
+    if (has_cross) {
+        if (!vt_cross_trainable(c->dec)) return c->fail(VT_ERR_INVALID, "%s: this decoder has no trainable cross-attention", who);
+        out->cross = vt_cross_layout(c->dec);
+        VTCK(vt_train_check(c, who, out->cross, cross_state, cross_bytes));
+        out->ref[out->n++] = {&out->cross, cross_state};
+    }
+    return VT_OK;
+}
+
 extern "C" {
 
 int vt_decoder_feature_dim(const vt_context* c) {

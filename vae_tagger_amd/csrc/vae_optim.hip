@@ -99,6 +99,44 @@ __global__ __launch_bounds__(256) void vae_optim_clip_kernel(const double* __res
     }
 }
 
+// the joint clip of train_full, one workgroup: S_vae over the VAE's tile partials exactly as vae_optim_clip_kernel adds them, then S_blocks
+// over the decoder-side blocks' partials exactly as train_clip_kernel adds them (head, front, cross; an absent block has n = 0), then ONE
+// fp64 add, the VAE first -> { norm^2, norm, coef } by the same formula, the same 16 bytes to the VAE's scalars and to every present block's
+struct JointBlocks { const double* part[VT_CLIP_MAX_BLOCKS]; int n[VT_CLIP_MAX_BLOCKS]; TrainScalars* sc[VT_CLIP_MAX_BLOCKS]; int count; };
+__global__ __launch_bounds__(256) void full_optim_clip_kernel(const double* __restrict__ part, long long n, JointBlocks blocks, float max_norm,
+                                                              TrainScalars* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 1024) {
+        a0 += part[i];
+        if (i + 256 < n) a1 += part[i + 256];
+        if (i + 512 < n) a2 += part[i + 512];
+        if (i + 768 < n) a3 += part[i + 768];
+    }
+    const double s_vae = block_sum_256d(((a0 + a1) + a2) + a3, red);
+    double s_blocks = 0.0;
+#pragma unroll
+    for (int k = 0; k < VT_CLIP_MAX_BLOCKS; ++k) {
+        const double* __restrict__ p = blocks.part[k];
+        double a = 0.0;
+        for (int i = threadIdx.x; i < blocks.n[k]; i += 256) a += p[i];
+        const double t = block_sum_256d(a, red);
+        s_blocks = k ? s_blocks + t : t;
+    }
+    if (threadIdx.x == 0) {
+        const double total = s_vae + s_blocks;
+        const float norm = (float)sqrt(total);
+        const float coef = max_norm / (norm + 1e-6f);
+        TrainScalars v;
+        v.sq = total; v.norm = norm; v.coef = coef < 1.0f ? coef : 1.0f;
+        *out = v;
+#pragma unroll
+        for (int k = 0; k < VT_CLIP_MAX_BLOCKS; ++k)
+            if (k < blocks.count) *blocks.sc[k] = v;
+    }
+}
+
 // the clip's scale folded in: g * coef as one fp32 multiply.  The product is pinned in a register: with -ffp-contract=fast on the
 // command line the backend would fuse it into adamw_one's g - m whatever the pragma says, and the fused difference has other bits.
 __device__ __forceinline__ float optim_scaled(float g, float coef, bool scale) {
@@ -166,6 +204,18 @@ int optim_check(vt_context* c, const char* who, const float* const* grads, const
     return VT_OK;
 }
 
+// what the two norm entries check beyond optim_check: the bound, the scalars and the partials' workspace
+int norm_check(vt_context* c, const char* who, const float* const* grads, const long long* numel, int n, float max_norm, const void* scalars_out,
+               const void* workspace, size_t workspace_bytes, int chunk, long long* total) {
+    VTCK(optim_check(c, who, grads, numel, n, chunk, total));
+    if (!(max_norm > 0.f)) return c->fail(VT_ERR_INVALID, "%s: max_norm = %g must be positive", who, max_norm);
+    if (!scalars_out || ((uintptr_t)scalars_out & 15)) return c->fail(VT_ERR_INVALID, "%s: scalars_out is null or not 16-B aligned", who);
+    if (!workspace || ((uintptr_t)workspace & (ALIGN - 1))) return c->fail(VT_ERR_INVALID, "%s: workspace is null or not 256-B aligned", who);
+    const size_t need = align_up(sizeof(double) * (size_t)(*total / TILE));
+    if (workspace_bytes < need) return c->fail(VT_ERR_WORKSPACE, "%s: workspace holds %zu bytes, %zu needed", who, workspace_bytes, need);
+    return VT_OK;
+}
+
 // the tensors `chunk` at a time: launch(table, tiles of the table)
 template <class Launch>
 int optim_chunks(vt_context* c, const char* who, const float* const* grads, const long long* numel, int n, int chunk, Launch&& launch) {
@@ -220,12 +270,7 @@ int vt_vae_optim_norm(vt_context* c, const float* const* grads, const long long*
     DeviceGuard guard(c);
     const char* who = "vt_vae_optim_norm";
     long long total = 0;
-    VTCK(optim_check(c, who, grads, numel, n, chunk, &total));
-    if (!(max_norm > 0.f)) return c->fail(VT_ERR_INVALID, "%s: max_norm = %g must be positive", who, max_norm);
-    if (!scalars_out || ((uintptr_t)scalars_out & 15)) return c->fail(VT_ERR_INVALID, "%s: scalars_out is null or not 16-B aligned", who);
-    if (!workspace || ((uintptr_t)workspace & (ALIGN - 1))) return c->fail(VT_ERR_INVALID, "%s: workspace is null or not 256-B aligned", who);
-    const size_t need = align_up(sizeof(double) * (size_t)(total / TILE));
-    if (workspace_bytes < need) return c->fail(VT_ERR_WORKSPACE, "%s: workspace holds %zu bytes, %zu needed", who, workspace_bytes, need);
+    VTCK(norm_check(c, who, grads, numel, n, max_norm, scalars_out, workspace, workspace_bytes, chunk, &total));
     hipStream_t s = (hipStream_t)stream;
     double* part = (double*)workspace;
     VTCK(optim_chunks(c, who, grads, numel, n, chunk, [&](const OptimTable& t, unsigned tiles) {
@@ -234,6 +279,34 @@ int vt_vae_optim_norm(vt_context* c, const float* const* grads, const long long*
     hipLaunchKernelGGL(vae_optim_clip_kernel, dim3(1), dim3(256), 0, s, (const double*)part, total / TILE, max_norm, (TrainScalars*)scalars_out);
     HIPCK(c, hipGetLastError(), who);
     return VT_OK;
+}
+
+int vt_full_optim_norm(vt_context* c, const float* const* grads, const long long* numel, int n, float max_norm, void* scalars_out, void* workspace,
+                       size_t workspace_bytes, int chunk, void* head_state, size_t head_state_bytes, void* front_state, size_t front_state_bytes,
+                       void* cross_state, size_t cross_state_bytes, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    const char* who = "vt_full_optim_norm";
+    long long total = 0;
+    VTCK(norm_check(c, who, grads, numel, n, max_norm, scalars_out, workspace, workspace_bytes, chunk, &total));
+    DecoderBlocks d;
+    VTCK(vt_train_decoder_blocks(c, who, head_state, head_state_bytes, front_state, front_state_bytes, cross_state, cross_state_bytes, &d));
+    JointBlocks k;
+    for (int i = 0; i < VT_CLIP_MAX_BLOCKS; ++i) {
+        const TrainBlockRef& b = d.ref[i < d.n ? i : 0];
+        k.part[i] = (const double*)((char*)b.state + b.layout->normpart);
+        k.n[i] = i < d.n ? b.layout->norm_parts : 0;
+        k.sc[i] = (TrainScalars*)((char*)b.state + b.layout->scalars);
+    }
+    k.count = d.n;
+    hipStream_t s = (hipStream_t)stream;
+    double* part = (double*)workspace;
+    VTCK(optim_chunks(c, who, grads, numel, n, chunk, [&](const OptimTable& t, unsigned tiles) {
+        hipLaunchKernelGGL(vae_optim_sq_kernel, dim3(tiles), dim3(256), 0, s, t, part);
+    }));
+    hipLaunchKernelGGL(full_optim_clip_kernel, dim3(1), dim3(256), 0, s, (const double*)part, total / TILE, k, max_norm, (TrainScalars*)scalars_out);
+    HIPCK(c, hipGetLastError(), who);
+    return vt_train_scale_blocks(c, who, d.ref, d.n, s);
 }
 
 int vt_vae_optim_step(vt_context* c, float* params, float* m, float* v, size_t arena_floats, const float* const* grads, const long long* numel, int n,

@@ -29,6 +29,9 @@ int vt_train_check(vt_context* c, const char* who, const TrainBlock& b, const vo
 constexpr int VT_CLIP_MAX_BLOCKS = 3;
 struct TrainBlockRef { const TrainBlock* layout; void* state; };
 int vt_train_clip_blocks(vt_context* c, const char* who, const TrainBlockRef* blocks, int n, float max_norm, hipStream_t s);
+// the second half of vt_train_clip_blocks on its own: every block's gradients *= the coefficient in its scalars when that is < 1
+// (vae_optim.hip's joint clip writes the scalars itself, from the VAE's partials and the blocks')
+int vt_train_scale_blocks(vt_context* c, const char* who, const TrainBlockRef* blocks, int n, hipStream_t s);
 int vt_train_step(vt_context* c, const char* who, const TrainBlock& b, void* state, double lr, double beta1, double beta2, double eps,
                   double weight_decay, long long t, hipStream_t s);
 // The gradient exchange of a sharded run.  export: the block's `grads` section (P floats, padding included) -> dst, device to device.
@@ -357,3 +360,14 @@ inline CrossWorkspace vt_cross_workspace(int B) {
     w.total = off;
     return w;
 }
+
+// ---- the decoder-side blocks of one context, in the order a clip sums them: head, then front, then cross-attention ----------------------
+// (train_head.hip) A null pointer with size 0 means the block is absent: the plain decoder has only the head, and the cross-attention's
+// block comes with the front's.  Every present block is checked as vt_head_clip / vt_train_clip / vt_train_clip3 check theirs.
+struct DecoderBlocks {
+    HeadLayout head; FrontLayout front; CrossLayout cross;
+    TrainBlockRef ref[VT_CLIP_MAX_BLOCKS];
+    int n;
+};
+int vt_train_decoder_blocks(vt_context* c, const char* who, void* head_state, size_t head_bytes, void* front_state, size_t front_bytes,
+                            void* cross_state, size_t cross_bytes, DecoderBlocks* out);

@@ -862,7 +862,7 @@ DECODE_DRAW, TRIPLET_DRAWS = 0, (1, 2, 3)       # evaluate_vae's convention: the
 
 
 def vae_loss_and_grads(params, anchor, positive, negative, labels_a=None, labels_p=None, *, weights, margin=1.0, similarity_type="cosine", seed=0,
-                       first_image=0, splits=0, saved=None, boundaries=None):
+                       first_image=0, splits=0, saved=None, boundaries=None, moments_out=None):
     """The training loss of train_vae.py (lines 131-179 of the reference; vae_losses.loss_backward_device) on one batch and its gradient in every
     parameter.  params: all `encoder.*` and `decoder.*` tensors (fp32, diffusers' names); anchor / positive / negative fp32 NCHW [B, 3, H, W]; labels
     [B, N] fp32 or uint8 / bool, or None; weights: {"reconstruction", "kl", "triplet"} (the simplified loss is kl = 0).
@@ -870,7 +870,8 @@ def vae_loss_and_grads(params, anchor, positive, negative, labels_a=None, labels
     ordered like params.  One encoder pass on the 3B images [a; p; n] (GroupNorm is per image: the reference's three calls), the anchor's latent
     (draw 0) decoded, nothing decoded from the positive or the negative, no scaling or shift factor -- as the reference's VAE wrapper.
     saved (optional dict) receives what the step keeps between its forward and its backward: "encoder", "decoder", "moments", "z", "recon"
-    (vae_train_saved_bytes); boundaries (optional dict) the two models' own, under "decoder" and "encoder", and "dz" (fp32 NCHW)."""
+    (vae_train_saved_bytes); boundaries (optional dict) the two models' own, under "decoder" and "encoder", and "dz" (fp32 NCHW); moments_out
+    (optional list) is appended the encoder pass's moments [3B, 2L, h, w] (train_full's classifier reads the anchors' means from them)."""
     from . import vae_losses
     a = _nchw3(anchor, "anchor")
     ctx = context(a.device)
@@ -885,6 +886,8 @@ def vae_loss_and_grads(params, anchor, positive, negative, labels_a=None, labels
         raise ValueError("params holds the encoder.* and the decoder.* tensors and nothing else")
     B = a.shape[0]
     moments, saved_e = encoder_forward_train(enc, torch.cat([a, _nchw3(positive, "positive"), _nchw3(negative, "negative")]))
+    if moments_out is not None:
+        moments_out.append(moments)
     L, h, w = moments.shape[1] // 2, moments.shape[2], moments.shape[3]
     z = torch.empty(B, L, h, w, dtype=torch.float32, device=a.device)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -908,6 +911,55 @@ def vae_loss_and_grads(params, anchor, positive, negative, labels_a=None, labels
                                     d_moments=[d_moments[i * B:(i + 1) * B] for i in range(3)], loss_out=loss_out, **common)
     ge = encoder_backward(enc, saved_e, d_moments, splits=splits, boundaries=at["encoder"])
     return dict(zip(vae_losses.LOSS_NAMES, loss_out.unbind())), _grads_like(params, ("", g), ("", ge))
+
+
+def vae_triplet_loss_and_grads(params, anchor, positive, negative, labels_a=None, labels_p=None, *, triplet_weight=1.0, margin=1.0,
+                               similarity_type="cosine", seed=0, first_image=0, splits=0, saved=None, moments_out=None):
+    """The VAE side of train_full's simplified loss (the reference's train_full.py:227-234 with SimplifiedCombinedLoss, improved_losses.py:160-193):
+    triplet_weight x the triplet loss on the three sampled latents and nothing else.  The reconstruction never enters that loss, so every `decoder.*`
+    tensor has no gradient there; here nothing is decoded: one encoder pass on [a; p; n], one vt_vae_loss_backward without recon, target, dz_dec or
+    d_recon and with kl = 0, one encoder backward.  params: the `encoder.*` tensors (others are ignored and get no gradient).
+    -> (losses, grads): losses as vae_loss_and_grads' (reconstruction is 0, kl the monitored value, total = triplet_weight x triplet); grads fp32 of
+    the `encoder.*` tensors ONLY, keyed and ordered like them -- bit for bit vae_loss_and_grads' at weights {reconstruction 0, kl 0, triplet
+    triplet_weight} with the same seed and first_image.  saved (optional dict) receives "encoder" and "moments" (vae_triplet_saved_bytes);
+    moments_out (optional list) is appended the moments [3B, 2L, h, w]."""
+    from . import vae_losses
+    a = _nchw3(anchor, "anchor")
+    ctx = context(a.device)
+    ctx.call("vt_op_backward_operands_check")
+    if negative is None:
+        raise ValueError("a negative stream is required: the contrastive term has no gradient here")
+    if positive.shape != a.shape or negative.shape != a.shape:
+        raise ValueError("anchor, positive and negative are [B, 3, H, W] tensors of one shape")
+    enc = {k: v for k, v in params.items() if k.startswith("encoder.")}
+    if not enc:
+        raise ValueError("params holds no encoder.* tensor")
+    B = a.shape[0]
+    moments, saved_e = encoder_forward_train(enc, torch.cat([a, _nchw3(positive, "positive"), _nchw3(negative, "negative")]))
+    if moments_out is not None:
+        moments_out.append(moments)
+    if saved is not None:
+        saved.update({"encoder": saved_e, "moments": moments})
+    streams = [(moments[i * B:(i + 1) * B], d) for i, d in enumerate(TRIPLET_DRAWS)]
+    d_moments = torch.empty_like(moments)
+    loss_out = torch.empty(4, dtype=torch.float64, device=a.device)
+    vae_losses.loss_backward_device(*streams, weights={"reconstruction": 0.0, "kl": 0.0, "triplet": float(triplet_weight)}, margin=margin,
+                                    similarity_type=similarity_type, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, first_image=first_image, labels_a=labels_a,
+                                    labels_p=labels_p, d_moments=[d_moments[i * B:(i + 1) * B] for i in range(3)], loss_out=loss_out, context=ctx)
+    ge = encoder_backward(enc, saved_e, d_moments, splits=splits)
+    return dict(zip(vae_losses.LOSS_NAMES, loss_out.unbind())), ge
+
+
+def vae_triplet_saved_bytes(params_or_config, B, H, W):
+    """Bytes vae_triplet_loss_and_grads keeps between its forward and its backward for a [B, 3, H, W] batch: the encoder's `saved` at 3B images and
+    the moments (3B) -- no decoded latent, no reconstruction, nothing of the image decoder.  params_or_config as in vae_train_saved_bytes."""
+    if not params_or_config:
+        from . import synth
+        params_or_config = synth.encoder_manifest()
+    st = _structure_of(_only(params_or_config, "encoder."), "encoder.")
+    levels = sum(1 for blk in st["blocks"] if blk["resample"])
+    h, w, L = H >> levels, W >> levels, st["conv_out"][0] // 2
+    return encoder_saved_bytes(_only(params_or_config, "encoder."), 3 * B, H, W) + 3 * B * 2 * L * h * w * 4
 
 
 def vae_train_saved_bytes(params_or_config, B, H, W):
