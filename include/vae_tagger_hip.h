@@ -725,6 +725,25 @@ int vt_full_optim_norm(vt_context* ctx, const float* const* grads /* host [n] */
                        void* scalars_out, void* workspace, size_t workspace_bytes, int chunk, void* head_state, size_t head_state_bytes,
                        void* front_state /* or NULL */, size_t front_state_bytes, void* cross_state /* or NULL */, size_t cross_state_bytes,
                        void* stream);
+/* The gradient exchange of a sharded train_vae: the gradient as ONE row of the arenas' layout, so that rank r of K
+ * can own the tiles [r S, (r + 1) S), S = ceil(tiles / K), merge only those and gather the rest.  `grads`, `numel`, n and `chunk` as above.
+ *   vt_vae_grads_export  writes EVERY float of row[0, row_floats) (device, 256-B aligned; row_floats a multiple of VT_VAE_OPTIM_TILE, at
+ *                        least the layout's total): tensor i at its slot offset, zero in the rest of its last tile and from the total on.
+ *                        No memset is needed before it; elements past numel[i] are never loaded; the bits do not depend on `chunk` or on
+ *                        a gradient's alignment.
+ *   vt_vae_grads_merge   for e in [0, floats): out[e] = (float)acc with acc = weights[0] * (double)x_0, then for r = 1 .. K-1 in that order
+ *                        acc = acc + weights[r] * (double)x_r, x_r = rows[r * row_stride_floats + first_float + e]; every product and
+ *                        every sum is rounded to fp64 on its own.  The first product is NOT added to 0.0: K = 1 with weight 1 is the
+ *                        identity, -0.0 included.  `weights`: K HOST doubles, finite and non-negative, read during the call; 1 <= K <= 64;
+ *                        first_float and floats multiples of VT_VAE_OPTIM_TILE, floats > 0, first_float + floats <= row_stride_floats (a
+ *                        multiple of 4); rows and out 16-B aligned device memory that do not overlap.  One workgroup per tile, no atomics:
+ *                        merging a range in one call or in pieces gives the same bytes.
+ * vt_vae_optim_norm and vt_vae_optim_step then run unchanged on pointers INTO the merged row (slot offsets are multiples of the tile).
+ * A refused call (VT_ERR_INVALID) launches nothing; nothing synchronises the host. */
+int vt_vae_grads_export(vt_context* ctx, const float* const* grads /* host [n] */, const long long* numel /* host [n] */, int n, float* row,
+                        size_t row_floats, int chunk, void* stream);
+int vt_vae_grads_merge(vt_context* ctx, const float* rows, size_t row_stride_floats, int K, const double* weights /* host [K] */,
+                       size_t first_float, size_t floats, float* out, void* stream);
 
 /* ---- single operators (parity tests drive each kernel through the same ABI) ------------------
  * NHWC bf16 activations, weights in the reference's own layouts (fp32 host order is converted by

@@ -36,19 +36,12 @@ __device__ __forceinline__ int optim_find(const OptimTable& t, long long b, long
     return lo;
 }
 
-// One workgroup per tile.  Thread j owns the float4s j, j + 256, ... of the tile and adds their squares x, y, z, w in that order, in
-// fp64; a gradient that is not 16-B aligned, and the float4 that the tensor's end cuts, are loaded one float at a time into the same
-// places, so the partial has the same bits either way.  Elements past numel are never loaded.
-__global__ __launch_bounds__(256) void vae_optim_sq_kernel(OptimTable t, double* __restrict__ part) {
-#pragma clang fp contract(off)
-    __shared__ double red[4];
-    long long tile;
-    const OptimEntry e = t.e[optim_find(t, blockIdx.x, &tile)];
+// Thread j's float4s j, j + 256, ... of tile `tile` of a gradient: a gradient that is not 16-B aligned, and the float4 that the tensor's end
+// cuts, are loaded one float at a time into the same places; what lies past numel is 0 and is never loaded.
+__device__ __forceinline__ void optim_load_tile(const OptimEntry& e, long long tile, float4 (&x)[QUADS]) {
     const float* __restrict__ g = e.g;
     const bool vec = ((uintptr_t)g & 15) == 0;
-    double sq = 0.0;
-    float4 x[QUADS];
-    if (vec && (tile + 1) * TILE <= e.numel) {                  // a whole tile of an aligned tensor: every load is issued before the first add
+    if (vec && (tile + 1) * TILE <= e.numel) {                  // a whole tile of an aligned tensor: every load is issued before the first use
 #pragma unroll
         for (int r = 0; r < QUADS; ++r) x[r] = *(const float4*)(g + tile * TILE + 4 * ((long long)threadIdx.x + 256 * r));
     } else {
@@ -66,6 +59,18 @@ __global__ __launch_bounds__(256) void vae_optim_sq_kernel(OptimTable t, double*
             }
         }
     }
+}
+
+// One workgroup per tile.  Thread j owns the float4s j, j + 256, ... of the tile and adds their squares x, y, z, w in that order, in
+// fp64 (optim_load_tile: the partial has the same bits whether the gradient is 16-B aligned or not).
+__global__ __launch_bounds__(256) void vae_optim_sq_kernel(OptimTable t, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    long long tile;
+    const OptimEntry e = t.e[optim_find(t, blockIdx.x, &tile)];
+    double sq = 0.0;
+    float4 x[QUADS];
+    optim_load_tile(e, tile, x);
 #pragma unroll
     for (int r = 0; r < QUADS; ++r) {
         sq = sq + (double)x[r].x * (double)x[r].x;
@@ -187,6 +192,64 @@ __global__ __launch_bounds__(256) VT_NO_PACKED_F32 void vae_optim_adamw_kernel(O
                 P[o + k] = p; M[o + k] = m; V[o + k] = v;
             }
         }
+    }
+}
+
+// The gradient exchange of a sharded train_vae: the n gradient tensors packed into ONE fp32 row of the arenas' layout, so that ranks can
+// exchange and merge ranges of tiles.  One workgroup per tile, the loads of optim_load_tile, four float4 stores per thread: the rest of a
+// tensor's last tile is written as zero, so a row needs no memset.
+__global__ __launch_bounds__(256) void vae_grads_export_kernel(OptimTable t, float* __restrict__ row) {
+    long long tile;
+    const OptimEntry e = t.e[optim_find(t, blockIdx.x, &tile)];
+    float4 x[QUADS];
+    optim_load_tile(e, tile, x);
+    float* __restrict__ dst = row + e.off + tile * TILE;
+#pragma unroll
+    for (int r = 0; r < QUADS; ++r) *(float4*)(dst + 4 * ((long long)threadIdx.x + 256 * r)) = x[r];
+}
+
+// the tiles of a row behind the layout's total (the padding that makes the owners' ranges equal): zero
+__global__ __launch_bounds__(256) void vae_grads_zero_kernel(float* __restrict__ dst) {
+    float* __restrict__ d = dst + (long long)blockIdx.x * TILE;
+#pragma unroll
+    for (int r = 0; r < QUADS; ++r) *(float4*)(d + 4 * ((long long)threadIdx.x + 256 * r)) = float4{0.f, 0.f, 0.f, 0.f};
+}
+
+// out[e] = (float)(w[0] x_0 + w[1] x_1 + ... + w[K-1] x_{K-1}), x_r = rows[r * stride + first + e], in fp64, added in that order, every
+// product and every sum rounded on its own (train_merge_kernel's arithmetic, except that the first product is not added to 0.0: with
+// K = 1 and w = 1 the merge is the identity on every bit pattern of a number, -0.0 included).  One workgroup per tile of the range, thread
+// j on float4s j, j + 256, ...; the ranks are taken MERGE_GROUP at a time and a group's loads of a float4 position are all issued before
+// its first add, so at K = 8 a wave has eight independent loads in flight per position.  A rank whose weight is 0 is still read.
+constexpr int MERGE_GROUP = 8;
+struct MergeWeights { double w[VT_MERGE_MAX_RANKS]; };
+__global__ __launch_bounds__(256) VT_NO_PACKED_F32 void vae_grads_merge_kernel(const float* __restrict__ rows, long long stride, int K, MergeWeights w,
+                                                                               float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const long long base = (long long)blockIdx.x * TILE + 4 * (long long)threadIdx.x;      // (rows already points at first_float)
+#pragma unroll
+    for (int q = 0; q < QUADS; ++q) {
+        const long long i = base + 1024 * q;
+        double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
+        for (int r0 = 0; r0 < K; r0 += MERGE_GROUP) {
+            float4 v[MERGE_GROUP];
+#pragma unroll
+            for (int k = 0; k < MERGE_GROUP; ++k)
+                if (r0 + k < K) v[k] = *(const float4*)(rows + (long long)(r0 + k) * stride + i);
+#pragma unroll
+            for (int k = 0; k < MERGE_GROUP; ++k) {
+                if (r0 + k < K) {
+                    const double wr = w.w[r0 + k];
+                    double px = wr * (double)v[k].x, py = wr * (double)v[k].y, pz = wr * (double)v[k].z, pw = wr * (double)v[k].w;
+                    // (pinned: -ffp-contract=fast on the command line would fuse a product into the add that follows, pragma or not)
+                    asm volatile("" : "+v"(px), "+v"(py), "+v"(pz), "+v"(pw));
+                    if (r0 + k == 0) { ax = px; ay = py; az = pz; aw = pw; }
+                    else { ax = ax + px; ay = ay + py; az = az + pz; aw = aw + pw; }
+                }
+            }
+        }
+        float4 o;
+        o.x = (float)ax; o.y = (float)ay; o.z = (float)az; o.w = (float)aw;
+        *(float4*)(out + i) = o;
     }
 }
 
@@ -330,6 +393,53 @@ int vt_vae_optim_step(vt_context* c, float* params, float* m, float* v, size_t a
     return optim_chunks(c, who, grads, numel, n, chunk, [&](const OptimTable& tb, unsigned tiles) {
         hipLaunchKernelGGL(vae_optim_adamw_kernel, dim3(tiles), dim3(256), 0, s, tb, params, m, v, (const TrainScalars*)scalars, a);
     });
+}
+
+int vt_vae_grads_export(vt_context* c, const float* const* grads, const long long* numel, int n, float* row, size_t row_floats, int chunk,
+                        void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    const char* who = "vt_vae_grads_export";
+    long long total = 0;
+    VTCK(optim_check(c, who, grads, numel, n, chunk, &total));
+    if (!row || ((uintptr_t)row & (ALIGN - 1))) return c->fail(VT_ERR_INVALID, "%s: row is null or not 256-B aligned", who);
+    if (row_floats % TILE || row_floats < (size_t)total)
+        return c->fail(VT_ERR_INVALID, "%s: a row of %zu floats, a multiple of %lld that is at least %lld expected", who, row_floats, TILE, total);
+    const long long pad_tiles = ((long long)row_floats - total) / TILE;
+    if (pad_tiles > 0x7fffffffll) return c->fail(VT_ERR_INVALID, "%s: %lld tiles of padding in one launch", who, pad_tiles);
+    hipStream_t s = (hipStream_t)stream;
+    VTCK(optim_chunks(c, who, grads, numel, n, chunk, [&](const OptimTable& t, unsigned tiles) {
+        hipLaunchKernelGGL(vae_grads_export_kernel, dim3(tiles), dim3(256), 0, s, t, row);
+    }));
+    if (pad_tiles) {
+        hipLaunchKernelGGL(vae_grads_zero_kernel, dim3((unsigned)pad_tiles), dim3(256), 0, s, row + total);
+        HIPCK(c, hipGetLastError(), who);
+    }
+    return VT_OK;
+}
+
+int vt_vae_grads_merge(vt_context* c, const float* rows, size_t row_stride_floats, int K, const double* weights, size_t first_float, size_t floats,
+                       float* out, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    const char* who = "vt_vae_grads_merge";
+    if (K < 1 || K > VT_MERGE_MAX_RANKS) return c->fail(VT_ERR_INVALID, "%s: K = %d ranks, 1 to %d expected", who, K, VT_MERGE_MAX_RANKS);
+    if (!rows || ((uintptr_t)rows & 15) || !out || ((uintptr_t)out & 15)) return c->fail(VT_ERR_INVALID, "%s: rows or out is null or not 16-B aligned", who);
+    if (floats == 0 || floats % TILE || first_float % TILE || floats / TILE > 0x7fffffffull)
+        return c->fail(VT_ERR_INVALID, "%s: first_float = %zu and floats = %zu, multiples of %lld with floats > 0 expected", who, first_float, floats, TILE);
+    if (row_stride_floats % 4 || first_float + floats > row_stride_floats)
+        return c->fail(VT_ERR_INVALID, "%s: a row stride of %zu floats, a multiple of 4 that holds first_float + floats = %zu expected", who,
+                       row_stride_floats, first_float + floats);
+    if (!weights) return c->fail(VT_ERR_INVALID, "%s: weights is null", who);
+    MergeWeights w;
+    for (int r = 0; r < VT_MERGE_MAX_RANKS; ++r) {
+        w.w[r] = r < K ? weights[r] : 0.0;
+        if (!isfinite(w.w[r]) || w.w[r] < 0.0) return c->fail(VT_ERR_INVALID, "%s: weight %d = %g must be finite and non-negative", who, r, w.w[r]);
+    }
+    hipLaunchKernelGGL(vae_grads_merge_kernel, dim3((unsigned)(floats / TILE)), dim3(256), 0, (hipStream_t)stream, rows + first_float,
+                       (long long)row_stride_floats, K, w, out);
+    HIPCK(c, hipGetLastError(), who);
+    return VT_OK;
 }
 
 }  // extern "C"

@@ -3,11 +3,15 @@ triplet loss, clip_grad_norm_, AdamW under a learning-rate schedule, validation 
 
     python -m vae_tagger_amd.train_vae --json_path data.json --tags_csv_path tags.csv [--vae_checkpoint ae.safetensors | --vae_config_path cfg.json]
         [--use_bucketing] [--max_grad_norm 1.0] [--resume_from vae_output/checkpoint-4] ...
+    torchrun --nproc-per-node 8 -m vae_tagger_amd.train_vae ... --train_batch_size 1 --sharded
 
   optim_layout   where every tensor lies in the optimiser's arenas (the mirror of vt_vae_optim_layout)
   VAETrainer     the parameters and the Adam moments in three fp32 arenas, and the step on them: forward_backward
                  (vae_backward.vae_loss_and_grads on views of the parameter arena: no copy), clip (vt_vae_optim_norm: clip_grad_norm_ over the
                  244 gradient tensors where they lie), step (vt_vae_optim_step: AdamW with the clip's scale folded in), commit into a loaded model
+  VAEGradientExchange   --sharded's one cross-rank operation per step: export into a row of the arenas' layout (vt_vae_grads_export), the
+                 ranks' slices cross, every rank merges the tiles it owns in rank order (vt_vae_grads_merge; merge_rows_host is its mirror), the
+                 merged slices are gathered; clip and step then run on views into the merged row
   train / main   the CLI: the reference's flags and defaults; per epoch a validation pass (evaluate_vae.run_checkpoint) and the reference's files
 
 What differs from the reference, on purpose.  The train / validation split and the epoch order come from the seed alone (train.split_indices,
@@ -17,7 +21,21 @@ a run that was resumed, write the same bytes.  With --use_bucketing a batch has 
 ANCHOR's bucket (evaluate_vae's rule).  The positive and the negative are not decoded (the reference decodes them and throws the result away).
 Nothing is read back per step: the running loss sum stays on the device and is read, with the health word, every --logging_steps and at the end
 of an epoch.  fp32 parameters and moments, bf16 MFMA operands: --mixed_precision and the other flags of IGNORED_ARGUMENTS are accepted and ignored.
-Not here: sharded training, gradient accumulation or checkpointing, the contrastive term, AdaptiveLossWeights.
+Not here: gradient accumulation or checkpointing, the contrastive term, AdaptiveLossWeights.
+
+--sharded (under torchrun, one rank per GPU; the reference runs under `accelerate`).  --train_batch_size is per rank.  The epoch is planned as
+without the flag, at the global batch B * world, and rank r takes the contiguous slice [r B, (r + 1) B) of every global batch with
+first_image = images + r B: a run at world K and batch B sees the batches of the one-device run at batch K B -- the same triplets, the same
+noise (keyed on the global image index), steps_per_epoch, learning rates and `images` -- and differs from it in summation order only.  Rank r of K
+owns tiles [r S, (r + 1) S) of the gradient row, S = ceil(T / K): per step it sends and receives 2 (K - 1) / K of the row (a ring all-reduce's
+traffic; a formula -- no multi-GPU scaling figure has been measured).  The weights w_r = n_r / sum n come from the plan, so nothing is read
+back and no count is exchanged; a rank whose slice is empty skips forward and backward and joins at weight 0.  What is optimised is
+sum_r w_r L_r: with kl = 0 (the default simplified loss) the concatenated batch's loss, since MSE and the triplet term are batch means; under
+--full_vae_loss the log(1 + mean KL / 10000) term is taken PER RANK (what DDP computes), which is not the concatenated batch's.  Every rank
+keeps the whole state and applies the same bytes: nothing is broadcast, and the run fails if the ranks' state digests differ.  Rank 0 alone
+prints, validates and writes files (train_report.json gains "sharded"); the others wait at a barrier.  VT_CLI_GLOO=1 (ranks share a GPU; the
+rows go through the CPU) and VT_CLI_ONE_RANK_GROUP=1 (one rank, the exchange forced) are rehearsals, as in train_decoder.  Sharded
+validation and a ZeRO-style sharded optimiser are not here.
 """
 import argparse
 import ctypes
@@ -228,6 +246,24 @@ class VAETrainer:
         self.step(grads, lr, weight_decay, betas, eps)
         return losses
 
+    # -- the gradient exchange of a sharded run (VAEGradientExchange below) ---------------------------------------------------------------
+    def export_gradients(self, grads, row, chunk=0):
+        """The gradients packed into `row` (fp32, 256-B aligned, a multiple of TILE floats that is at least `total`) in the arenas' layout:
+        every float of the row is written (vt_vae_grads_export)."""
+        self.ctx.call("vt_vae_grads_export", self._grad_pointers(grads), self._numel_arr, len(self.numels), ctypes.c_void_p(row.data_ptr()),
+                      row.numel(), int(chunk), self._stream())
+
+    def merge_gradients(self, rows, row_stride, weights, first_float, floats, out):
+        """out[e] = (float)(w[0] x_0 + ... + w[K-1] x_{K-1}) over e in [0, floats), x_r = rows[r * row_stride + first_float + e], in fp64 and in
+        rank order (vt_vae_grads_merge; merge_rows_host states the arithmetic)."""
+        w = [float(x) for x in weights]
+        self.ctx.call("vt_vae_grads_merge", ctypes.c_void_p(rows.data_ptr()), int(row_stride), len(w), (ctypes.c_double * max(1, len(w)))(*w),
+                      int(first_float), int(floats), ctypes.c_void_p(out.data_ptr()), self._stream())
+
+    def gradient_views(self, row):
+        """{key: view of `row` at the tensor's slot}, keyed and ordered like params: what clip and step take after a merge."""
+        return {k: row[o:o + n].view(self.shapes[k]) for k, o, n in zip(self.params, self.offsets, self.numels)}
+
     def grad_norm(self):
         """(total L2 norm, clip coefficient) of the last clip(): the one method of the step that synchronises."""
         raw = self._scalars.cpu().numpy().view(np.uint8)
@@ -275,6 +311,203 @@ class VAETrainer:
         vae.load_decoder_state_dict({k: v for k, v in self.params.items() if k.startswith("decoder.")}, strict=True)
 
 
+# ---- sharded training: the batch's shards, the owners' ranges, the gradient exchange ------------------------------------------------------
+MAX_RANKS = 64                                           # VT_MERGE_MAX_RANKS
+
+
+def shard_of_batch(idx, rank, world, per_rank_batch):
+    """Rank `rank`'s contiguous slice of a global batch of at most world * per_rank_batch positions (empty when the batch ends before it)."""
+    if not 0 <= rank < world or per_rank_batch < 1:
+        raise ValueError("shard_of_batch: 0 <= rank < world and a per-rank batch of at least 1 expected")
+    return idx[rank * per_rank_batch:(rank + 1) * per_rank_batch]
+
+
+def shard_weights(n_global, world, per_rank_batch):
+    """w[r] = n_r / sum n over the ranks' slices of a global batch of n_global images: the merged gradient of per-rank batch-mean gradients is
+    then the concatenated batch's mean gradient.  Known on every rank from the plan alone: no count is exchanged."""
+    counts = [len(shard_of_batch(range(int(n_global)), r, world, per_rank_batch)) for r in range(world)]
+    if n_global < 1 or sum(counts) != n_global:
+        raise ValueError(f"a global batch of {n_global} images does not fit {world} ranks of {per_rank_batch}")
+    return [c / n_global for c in counts]
+
+
+def owner_split(total_floats, world):
+    """(S, row_floats): rank r owns tiles [r S, (r + 1) S) of the gradient row, S = ceil(T / world) for the layout's T = total / TILE tiles, and
+    the row is padded to world * S tiles so that every rank's range has the same size."""
+    if total_floats < TILE or total_floats % TILE or not 1 <= world <= MAX_RANKS:
+        raise ValueError(f"owner_split: a layout total (a multiple of {TILE}) and 1 to {MAX_RANKS} ranks expected")
+    S = (total_floats // TILE + world - 1) // world
+    return S, world * S * TILE
+
+
+def merge_rows_host(rows, weights):
+    """What vt_vae_grads_merge computes, in numpy: K fp32 arrays and K weights -> fp32, out[e] = (float)acc with acc = w[0] * (double)x_0, then
+    acc = acc + w[r] * (double)x_r for r = 1 .. K-1 in that order -- train.merge_gradients_host with the first term taken as w[0] x_0 and not
+    added to 0.0, so K = 1 at weight 1 returns its input bit for bit (-0.0 included)."""
+    rows = [np.asarray(b, dtype=np.float32).reshape(-1) for b in rows]
+    w = [np.float64(x) for x in weights]
+    if len(rows) != len(w) or not rows:
+        raise ValueError("merge_rows_host: one weight per row, at least one row")
+    acc = w[0] * rows[0].astype(np.float64)              # (numpy rounds each ufunc's result: nothing is fused)
+    for r in range(1, len(rows)):
+        acc = acc + w[r] * rows[r].astype(np.float64)
+    return acc.astype(np.float32)
+
+
+class _DeviceTransport:
+    """RCCL: the ranks' slices cross in ONE all_to_all_single with equal splits, the merged slices in ONE all_gather_into_tensor."""
+
+    def __init__(self, ex, group):
+        self.ex, self.group, self.in_place = ex, group, True
+        self._recv = torch.empty(ex.world * ex.slice_floats, dtype=torch.float32, device=ex.device)
+        self.bytes_sent = self.bytes_received = 2 * (ex.world - 1) * 4 * ex.slice_floats
+
+    def scatter(self, mine):
+        """-> (rows, row stride, first float) of the K ranks' copies of this rank's range: rank q's slice r goes to rank r"""
+        import torch.distributed as dist
+        dist.all_to_all_single(self._recv, mine, group=self.group)
+        return self._recv, self.ex.slice_floats, 0
+
+    def gather(self, merged):
+        """every rank's merged range into every rank's merged row; in place when torch takes a slice of the output as the input"""
+        import torch.distributed as dist
+        own = merged[self.ex.first_float:self.ex.first_float + self.ex.slice_floats]
+        if self.in_place:
+            try:
+                dist.all_gather_into_tensor(merged, own, group=self.group)
+                return
+            except (RuntimeError, ValueError):          # (refused at the argument check, before anything is sent)
+                self.in_place = False
+        dist.all_gather_into_tensor(merged, own.clone(), group=self.group)
+
+
+class _HostTransport:
+    """gloo, the rehearsal on shared GPUs only (as train.GradientExchange): whole rows and merged slices through the CPU with all_gather.
+    The kernels and the merged bytes are the device transport's; the traffic is not."""
+
+    def __init__(self, ex, group):
+        self.ex, self.group = ex, group
+        self._all = torch.empty(ex.world * ex.row_floats, dtype=torch.float32, device=ex.device)
+        self.bytes_sent = self.bytes_received = (ex.world - 1) * 4 * (ex.row_floats + ex.slice_floats)
+
+    def scatter(self, mine):
+        import torch.distributed as dist
+        parts = [torch.empty(self.ex.row_floats, dtype=torch.float32) for _ in range(self.ex.world)]
+        dist.all_gather(parts, mine.cpu(), group=self.group)
+        self._all.copy_(torch.cat(parts))
+        return self._all, self.ex.row_floats, self.ex.first_float
+
+    def gather(self, merged):
+        import torch.distributed as dist
+        own = merged[self.ex.first_float:self.ex.first_float + self.ex.slice_floats]
+        parts = [torch.empty(self.ex.slice_floats, dtype=torch.float32) for _ in range(self.ex.world)]
+        dist.all_gather(parts, own.cpu(), group=self.group)
+        merged.copy_(torch.cat(parts))
+
+
+class InProcessRanks:
+    """The transport of K emulated ranks inside ONE process, without a process group (the device tests): the K exchanges are driven in
+    lockstep -- every rank's export(), then every rank's merge(), then every rank's gather() -- and a rank reads the others' rows directly."""
+
+    def __init__(self, world):
+        self.world, self.exchanges = int(world), [None] * int(world)
+
+    def scatter(self, ex, mine):
+        lo, n = ex.first_float, ex.slice_floats
+        return torch.cat([other.row[lo:lo + n] for other in self.exchanges]), n, 0
+
+    def gather(self, ex, merged):
+        n = ex.slice_floats
+        for q, other in enumerate(self.exchanges):
+            if other is not ex:
+                merged[q * n:(q + 1) * n].copy_(other.merged[q * n:(q + 1) * n])
+
+
+class _InProcessEndpoint:
+    def __init__(self, ranks, ex):
+        self.ranks, self.ex = ranks, ex
+        ranks.exchanges[ex.rank] = ex
+        self.bytes_sent = self.bytes_received = 2 * (ex.world - 1) * 4 * ex.slice_floats
+
+    def scatter(self, mine):
+        return self.ranks.scatter(self.ex, mine)
+
+    def gather(self, merged):
+        self.ranks.gather(self.ex, merged)
+
+
+class VAEGradientExchange:
+    """The cross-rank operation of a sharded train_vae step.  The gradient is 244 fresh tensors (84 M floats for FLUX), so no rank gathers
+    every row: each rank exports its gradients into one row of the arenas' layout (padded to K S tiles), the ranks' slices cross so that rank r
+    holds every rank's copy of ITS tiles [r S, (r + 1) S), it merges those K slices in rank order (fp64, weights from the plan), and the merged
+    slices are gathered into every rank's merged row.  Per rank and step 2 (K - 1) / K of the row is sent and as much received -- a ring
+    all-reduce's traffic (a formula: no multi-GPU scaling figure has been measured) -- with the summation order fixed by the rank count,
+    the same bytes on every rank, no atomics, no all-reduce, no parameter broadcast and no host synchronisation.
+
+    exchange(grads, weights) -> {key: view into the merged row}, keyed and ordered like trainer.params: what clip() and step() take.
+    Without a group, or on a one-rank group without force_collective, it returns the gradients it was given and launches nothing.
+    emulated = (InProcessRanks, rank): one of K ranks emulated inside one process (export / merge / gather are then driven in lockstep)."""
+
+    def __init__(self, trainer, group=None, force_collective=False, *, emulated=None):
+        import torch.distributed as dist
+        self.trainer, self.group, self.device = trainer, group, trainer.device
+        grouped = emulated is None and group is not None and dist.is_available() and dist.is_initialized()
+        self.world, self.rank, self.backend = 1, 0, None
+        if grouped:
+            self.world, self.rank, self.backend = dist.get_world_size(group), dist.get_rank(group), dist.get_backend(group)
+        elif emulated is not None:
+            self.world, self.rank, self.backend = emulated[0].world, int(emulated[1]), "in-process"
+        if self.world > MAX_RANKS:
+            raise ValueError(f"{self.world} ranks: the gradient merge takes at most {MAX_RANKS}")
+        self.active = emulated is not None or (grouped and (self.world > 1 or bool(force_collective)))
+        self.calls, self.transport = 0, None
+        if not self.active:
+            return
+        self.slice_tiles, self.row_floats = owner_split(trainer.total, self.world)
+        self.slice_floats = self.slice_tiles * TILE
+        self.first_float = self.rank * self.slice_floats
+        self.row, self.merged = trainer._aligned(self.row_floats), trainer._aligned(self.row_floats)
+        self.views = trainer.gradient_views(self.merged)
+        if emulated is not None:
+            self.transport = _InProcessEndpoint(emulated[0], self)
+        else:
+            self.transport = (_HostTransport if self.backend == "gloo" else _DeviceTransport)(self, group)
+
+    @property
+    def bytes_sent_per_step(self):
+        return self.transport.bytes_sent if self.active else 0
+
+    @property
+    def bytes_received_per_step(self):
+        return self.transport.bytes_received if self.active else 0
+
+    def export(self, grads):
+        """this rank's gradients into its row; None (the rank's slice of the batch is empty: no forward, no backward) is a row of zeros"""
+        if grads is None:
+            self.row.zero_()
+        else:
+            self.trainer.export_gradients(grads, self.row)
+
+    def merge(self, weights):
+        if len(weights) != self.world:
+            raise ValueError(f"{len(weights)} weights for {self.world} ranks")
+        rows, stride, first = self.transport.scatter(self.row)
+        self.trainer.merge_gradients(rows, stride, weights, first, self.slice_floats,
+                                     self.merged[self.first_float:self.first_float + self.slice_floats])
+
+    def gather(self):
+        self.transport.gather(self.merged)
+        self.calls += 1
+        return self.views
+
+    def exchange(self, grads, weights):
+        if not self.active:
+            return grads
+        self.export(grads)
+        self.merge(weights)
+        return self.gather()
+
+
 # ---- the CLI --------------------------------------------------------------------------------------------------------------------------
 def build_parser():
     p = argparse.ArgumentParser(description="VAE 训练 (重建 + KL + 三元组损失), 前向、反向与优化器都在GPU上。")
@@ -315,6 +548,7 @@ def build_parser():
     p.add_argument("--resume_from", type=str, default=None, help="continue from a best_checkpoint/ or checkpoint-{e}/ directory")
     p.add_argument("--stop_after_epochs", type=int, default=0, help="end the run after this many epochs of --num_epochs (0: all); the schedule is --num_epochs'")
     p.add_argument("--workers", type=int, default=0, help="image decode threads (0 = min(16, cores))")
+    p.add_argument("--sharded", action="store_true", help="data-parallel run under torchrun, one rank per GPU: --train_batch_size is per rank")
     return p
 
 
@@ -322,6 +556,20 @@ def ignored_arguments(args):
     """The reference's flags that mean nothing here and were set to something."""
     defaults = build_parser().parse_args(["--json_path", "", "--tags_csv_path", ""])
     return [k for k in IGNORED_ARGUMENTS if getattr(args, k, None) != getattr(defaults, k)]
+
+
+def check_sharded(args, environ=None):
+    """--sharded is refused, by a message that names it, before any device work: without a process group to join (torchrun's WORLD_SIZE > 1, or
+    the one-rank rehearsal VT_CLI_ONE_RANK_GROUP=1) and above the merge's 64 ranks."""
+    if not getattr(args, "sharded", False):
+        return
+    env = os.environ if environ is None else environ
+    world = int(env.get("WORLD_SIZE", "1"))
+    if world > MAX_RANKS:
+        raise SystemExit(f"--sharded: {world} ranks, the gradient merge takes at most {MAX_RANKS}")
+    if world <= 1 and env.get("VT_CLI_ONE_RANK_GROUP") != "1":
+        raise SystemExit("--sharded needs a process group: start the run under torchrun with one rank per GPU "
+                         "(VT_CLI_ONE_RANK_GROUP=1 rehearses the exchange on one rank)")
 
 
 def plan_train_batches(order, batch_size, buckets=None):
@@ -376,6 +624,24 @@ def model_config(vae):
 
 
 def train(args):
+    """The run; with --sharded, this rank's part of it: the process group is joined BEFORE any GPU call of this process, and every rank but
+    rank 0 runs silently (rank 0 alone prints, validates and writes files)."""
+    check_sharded(args)
+    if not getattr(args, "sharded", False):
+        return _train(args, None)
+    import contextlib
+    import torch.distributed as dist
+    from .infer_full import _dist_setup
+    world, rank, dev_index = _dist_setup()
+    torch.cuda.set_device(dev_index)
+    shard = SimpleNamespace(world=world, rank=rank, group=dist.group.WORLD, dist=dist)
+    if rank == 0:
+        return _train(args, shard)
+    with open(os.devnull, "w") as null, contextlib.redirect_stdout(null):
+        return _train(args, shard)
+
+
+def _train(args, shard):
     from concurrent.futures import ThreadPoolExecutor
     from safetensors.torch import load_file
     from . import evaluate_vae
@@ -392,7 +658,11 @@ def train(args):
     ignored = ignored_arguments(args)
     if ignored:
         print("ignored arguments (they mean nothing on this device): " + ", ".join("--" + k for k in ignored))
-    os.makedirs(args.output_dir, exist_ok=True)
+    sharded = shard is not None
+    world, rank = (shard.world, shard.rank) if sharded else (1, 0)
+    chief, B = rank == 0, args.train_batch_size                                # --sharded: B is per rank, a global batch is B * world
+    if chief:
+        os.makedirs(args.output_dir, exist_ok=True)
     device = torch.device("cuda", torch.cuda.current_device())
     simplified = bool(args.use_simplified_vae_loss) and not args.full_vae_loss
     args.use_simplified_vae_loss = simplified                                  # (the validation pass reads it)
@@ -424,7 +694,21 @@ def train(args):
         weights["kl"] = 0.0
     trainer = VAETrainer(model, weights=weights, margin=args.triplet_margin, similarity_type=args.similarity_type, seed=args.seed)
     config = model_config(model.vae)
-    spe = steps_per_epoch(len(train_idx), args.train_batch_size, train_buckets)
+    exchange = VAEGradientExchange(trainer, shard.group, force_collective=True) if sharded else None
+
+    def gather_objects(obj):
+        out = [None] * world
+        shard.dist.all_gather_object(out, obj, group=shard.group)
+        return out
+
+    def agreed_digest(what):
+        """every rank's optimizer_state_sha256, in rank order; the run fails where they differ (nothing is broadcast to repair it)"""
+        digests = gather_objects(trainer.optimizer_state_sha256().hexdigest())
+        if len(set(digests)) != 1:
+            raise RuntimeError(f"--sharded: the ranks' states differ {what}: {digests}")
+        return digests
+
+    spe = steps_per_epoch(len(train_idx), B * world, train_buckets)
     total_steps = args.num_epochs * spe
     run = {"step": 0, "epoch": 0, "images": 0, "best_val_loss": None, "history": {"train_loss": [], "val_loss": [], "learning_rates": []}}
     if args.resume_from:
@@ -440,6 +724,10 @@ def train(args):
     report_path = os.path.join(args.output_dir, "train_report.json")
     report = {"epochs": [], "clip": args.max_grad_norm > 0, "max_grad_norm": args.max_grad_norm, "ignored_arguments": ignored,
               "steps_per_epoch": spe, "total_steps": total_steps, "simplified": simplified, "arena_bytes": trainer.arena_bytes()}
+    if sharded:
+        report["sharded"] = {"world": world, "backend": exchange.backend, "per_rank_batch": B, "bytes_sent_per_step": exchange.bytes_sent_per_step,
+                             "bytes_received_per_step": exchange.bytes_received_per_step, "exchange_calls": 0,
+                             "state_sha256": agreed_digest("before the first step")}
     if args.resume_from and os.path.exists(report_path):
         with open(report_path, "r", encoding="utf-8") as fh:
             report["epochs"] = json.load(fh).get("epochs", [])[:run["epoch"]]
@@ -451,9 +739,20 @@ def train(args):
     step, images = run["step"], run["images"]
 
     def read_back(loss_sum, losses, what):
-        """the one place the host waits for the device inside an epoch: the running sum, the last step's terms, the health word"""
-        values = torch.stack([loss_sum] + [losses[k] for k in ("total", "reconstruction", "kl", "triplet")]).cpu().tolist()
+        """the one place the host waits for the device inside an epoch: the running sum, the last step's terms, the health word.  --sharded: a
+        rank's running sum is of w_r L_r; the K sums are gathered and added in rank order on the host (the terms shown are this rank's own,
+        zeros on a rank that has had no image yet), and every rank raises where any rank's numbers are bad."""
+        terms = [losses[k] for k in ("total", "reconstruction", "kl", "triplet")] if losses is not None else [torch.zeros_like(loss_sum)] * 4
+        values = torch.stack([loss_sum] + terms).cpu().tolist()
         st = trainer.ctx.status()
+        if sharded:
+            every = gather_objects((values[0], st, all(math.isfinite(v) for v in values)))
+            values[0] = every[0][0]
+            for other in every[1:]:
+                values[0] = values[0] + other[0]
+            bad = [(r, e) for r, e in enumerate(every) if e[1] or not e[2]]
+            if bad:
+                raise FloatingPointError(f"{what}: (rank, (running sum, device health word, finite)) {bad}")
         if st or not all(math.isfinite(v) for v in values):
             raise FloatingPointError(f"{what}: loss terms {values[1:]}, running sum {values[0]}, device health word {st}")
         return values
@@ -465,17 +764,31 @@ def train(args):
             triplets = {i: evaluate_vae.sample_triplet(args.seed * TRIPLET_SEED_STRIDE + epoch + 1, i, train_labels) for i in order}
             loss_sum = torch.zeros((), dtype=torch.float64, device=device)
             lrs, saved_bytes, epoch_images, losses = [], 0, 0, None
-            for k, (bucket, idx) in enumerate(plan_train_batches(order, args.train_batch_size, train_buckets)):
-                xa = load(pool, idx, bucket)
-                xp = load(pool, [triplets[i][0] for i in idx], bucket)
-                xn = load(pool, [triplets[i][1] for i in idx], bucket)
-                ia = torch.as_tensor(idx, device=device)
-                ip = torch.as_tensor([triplets[i][0] for i in idx], device=device)
+            for k, (bucket, batch) in enumerate(plan_train_batches(order, B * world, train_buckets)):
+                idx = shard_of_batch(batch, rank, world, B) if sharded else batch      # this rank's contiguous slice of the global batch
+                if idx:
+                    xa = load(pool, idx, bucket)
+                    xp = load(pool, [triplets[i][0] for i in idx], bucket)
+                    xn = load(pool, [triplets[i][1] for i in idx], bucket)
+                    ia = torch.as_tensor(idx, device=device)
+                    ip = torch.as_tensor([triplets[i][0] for i in idx], device=device)
                 lr = args.learning_rate * lr_schedule(args.lr_scheduler_type, step, args.lr_warmup_steps, total_steps)
-                losses = trainer.train_step(xa, xp, xn, label_t[ia], label_t[ip], images, lr=lr, weight_decay=args.weight_decay,
-                                            max_grad_norm=args.max_grad_norm)
-                loss_sum = loss_sum + losses["total"]
-                saved_bytes = max(saved_bytes, trainer.saved_bytes(xa.shape))
+                if not sharded:
+                    losses = trainer.train_step(xa, xp, xn, label_t[ia], label_t[ip], images, lr=lr, weight_decay=args.weight_decay,
+                                                max_grad_norm=args.max_grad_norm)
+                    loss_sum = loss_sum + losses["total"]
+                else:
+                    w, grads = shard_weights(len(batch), world, B), None
+                    if idx:                                                      # an empty slice: no forward, no backward, a zero row at weight 0
+                        losses, grads = trainer.forward_backward(xa, xp, xn, label_t[ia], label_t[ip], images + rank * B)
+                        loss_sum = loss_sum + w[rank] * losses["total"]
+                    merged = exchange.exchange(grads, w)
+                    if args.max_grad_norm > 0:
+                        trainer.clip(merged, args.max_grad_norm)
+                    trainer.step(merged, lr, args.weight_decay)
+                if idx:
+                    saved_bytes = max(saved_bytes, trainer.saved_bytes(xa.shape))
+                idx = batch                                                      # (the counters below are the global batch's)
                 lrs.append(lr)
                 step, images, epoch_images = step + 1, images + len(idx), epoch_images + len(idx)
                 if k % args.logging_steps == 0:
@@ -485,6 +798,11 @@ def train(args):
             v = read_back(loss_sum, losses, f"epoch {epoch}")
             seconds = time.perf_counter() - t0
             train_loss = v[0] / len(lrs)
+            if sharded:
+                report["sharded"].update(state_sha256=agreed_digest(f"after epoch {epoch}"), exchange_calls=exchange.calls)
+                if not chief:                                                    # rank 0 validates and writes; the others meet it at the barrier
+                    shard.dist.barrier(group=shard.group)
+                    continue
             trainer.commit(model)
             state, _, _ = evaluate_vae.run_checkpoint(args, model, val_data, val_labels, val_triplets, val_batches, device=device)
             val_loss = evaluate_vae.build_report(state, args)["val_loss"]
@@ -512,6 +830,10 @@ def train(args):
                                      "grad_norm": None if norm is None else {"norm": norm[0], "coef": norm[1]},
                                      "saved_bytes_per_step": saved_bytes, "optimizer_state_sha256": trainer.optimizer_state_sha256().hexdigest()})
             _write_json(report_path, report)
+            if sharded:
+                shard.dist.barrier(group=shard.group)
+    if not chief:
+        return report
     print("训练完成，保存训练历史...")
     _write_json(os.path.join(args.output_dir, "training_history.json"), history)
     print("VAE训练完成！")
