@@ -744,6 +744,23 @@ int vt_vae_grads_export(vt_context* ctx, const float* const* grads /* host [n] *
                         size_t row_floats, int chunk, void* stream);
 int vt_vae_grads_merge(vt_context* ctx, const float* rows, size_t row_stride_floats, int K, const double* weights /* host [K] */,
                        size_t first_float, size_t floats, float* out, void* stream);
+/* vt_vae_grads_accumulate: gradient accumulation of train_full -- the n fresh gradient tensors of one micro-step
+ * into ONE fp32 row of the arenas' layout that holds the sum across micro-steps.  `grads`, `numel`, n, `chunk`, `row` and `row_floats` as
+ * for vt_vae_grads_export.  Per element g of tensor i, at its slot:
+ *   t = scale * g                one fp32 multiply; scale == 1 leaves the bits, -0.0 included
+ *   first != 0:  row = t         and +0.0 in the rest of the tensor's last tile and from the layout's total to row_floats: every float of
+ *                                the row is written, no memset is needed, and with scale == 1 the row is vt_vae_grads_export's byte for byte
+ *   first == 0:  a = row; if `scalars` (device TrainScalars, 16-B aligned, or NULL) holds a coef (fp32 at byte 12) < 1, a = coef * a, one
+ *                fp32 multiply rounded on its own; row = a + t, one fp32 add.  Two products and one add, three separately rounded
+ *                operations, never a fused multiply-add.  A NaN or >= 1 coef multiplies nothing (vt_vae_optim_step's rule).  Padding is
+ *                neither read nor written.
+ * So the coefficient that the clip of the PREVIOUS micro-step wrote is applied to the accumulated row here, as the row is read anyway, and
+ * not by a pass of its own.  One 256-thread workgroup per tile, no atomics; elements past numel[i] are never loaded; the bits do not depend
+ * on `chunk` or on a gradient's alignment.  VT_ERR_INVALID, with nothing launched: n < 1, a null grads / numel / row, a numel <= 0, a
+ * misaligned or short row, a non-finite scale, misaligned scalars, a chunk outside 0 .. VT_VAE_OPTIM_CHUNK.  No host synchronisation. */
+int vt_vae_grads_accumulate(vt_context* ctx, const float* const* grads /* host [n] */, const long long* numel /* host [n] */, int n,
+                            float* row, size_t row_floats, float scale, const void* scalars /* device TrainScalars, or NULL */, int first,
+                            int chunk, void* stream);
 
 /* ---- single operators (parity tests drive each kernel through the same ABI) ------------------
  * NHWC bf16 activations, weights in the reference's own layouts (fp32 host order is converted by

@@ -5,6 +5,7 @@ VAETrainer.train_step (train_vae) and a DecoderTrainer step (train_decoder --tra
 against a copy of its bytes.  Everything is warmed first and timed by device events in interleaved rounds; the figures are medians over the rounds.
 
 Usage: python tools/bench_train_full.py [--sizes 512 1024] [--tags 10000] [--rounds 5] [--iters 2] [--out FILE]
+       python tools/bench_train_full.py --accumulate A ...      gradient accumulation instead (accumulate_bench)
 Prints text lines and, last, one JSON line (also written to --out)."""
 import argparse
 import json
@@ -54,6 +55,85 @@ def make_decoder(tags, seed):
     return d.to(DEV).eval()
 
 
+def accumulate_bench(a):
+    """--accumulate A: vt_vae_grads_accumulate, starting a sum and adding to one under a pending coefficient, against a torch device copy of the
+    bytes it moves (first: n read + n written; adding: 2 n read + n written) and against the eager sequence it replaces on the same tensors
+    (torch._foreach_mul_ by the coefficient, then torch._foreach_add_(..., alpha=scale)); and FullTrainer.micro_step, not stepping and
+    stepping, against train_step of the same trainer class -- the step a run without accumulation takes."""
+    import struct
+    import numpy as np
+    A = a.accumulate
+    manifest = {**synth.encoder_manifest(), **synth.image_decoder_manifest()}
+    params = synth.synth_state_dict(manifest, seed=0)
+    kw = dict(margin=1.0, similarity_type="cosine", seed=0, scaling_factor=0.3611, shift_factor=0.1159)
+    rec = {"tool": "bench_train_full --accumulate", "device": torch.cuda.get_device_name(0), "tags": a.tags, "accumulation_steps": A,
+           "rounds": a.rounds, "iters": a.iters, "shapes": {}}
+    g = torch.Generator().manual_seed(3)
+    labels = (torch.rand(1, a.tags, generator=g) < 0.01).float().to(DEV)
+    health = 0
+    for loss in ("simplified", "full_loss"):
+        plain = FullTrainer(params, make_decoder(a.tags, 1), weights=WEIGHTS, simplified=loss == "simplified", **kw)
+        accum = FullTrainer(params, make_decoder(a.tags, 1), weights=WEIGHTS, simplified=loss == "simplified", **kw)
+        v = accum.vae
+        n_floats = sum(v.numels[:accum.n])
+        for size in a.sizes:
+            x = [t.to(DEV).contiguous() for t in synth.synth_images(3, size, size, seed=4).split(1)]
+            step = {"n": 0}
+
+            def parent_step():
+                plain.train_step(x[0], x[1], x[2], labels, labels, step["n"], lr=LR, weight_decay=WD, max_grad_norm=MAX_NORM)
+                step["n"] += 1
+
+            def micro(now):
+                accum.micro_step(x[0], x[1], x[2], labels, labels, step["n"], accumulation_steps=A, step_now=now, lr=LR, weight_decay=WD,
+                                 max_grad_norm=MAX_NORM)
+                step["n"] += 1
+            micro(False)                                                         # (so that a stepping micro-step adds to a pending sum, as in a run)
+            ms = interleaved({"train_step": parent_step, "micro_step_not_stepping": lambda: micro(False), "micro_step_stepping": lambda: micro(True)},
+                             a.rounds, a.iters)
+            # the pass alone, on the gradients of one backward
+            _, grads, _ = accum.vae_forward_backward(x[0], x[1], x[2], labels, labels, 0)
+            v._scalars.copy_(torch.from_numpy(np.frombuffer(struct.pack("<dff", 4.0, 2.0, 0.37), dtype=np.float64).copy()).to(DEV))
+            views = list(v.accumulated(accum.n).values())
+            glist = list(grads.values())
+            src = torch.empty(6 * n_floats, dtype=torch.uint8, device=DEV)       # a copy of k bytes moves 2 k
+            dst = torch.empty_like(src)
+
+            def add_pending():
+                v._clipped = True
+                v.accumulate(grads, scale=1.0 / A, first=False, n=accum.n)
+
+            def eager():
+                torch._foreach_mul_(views, 0.37)
+                torch._foreach_add_(views, glist, alpha=1.0 / A)
+            calls = {"accumulate_first": lambda: v.accumulate(grads, scale=1.0 / A, first=True, n=accum.n), "accumulate_add_with_coef": add_pending,
+                     "eager_foreach_mul_add": eager, "copy_of_first_bytes": lambda: dst[:4 * n_floats].copy_(src[:4 * n_floats]),
+                     "copy_of_add_bytes": lambda: dst.copy_(src)}
+            nms = interleaved(calls, a.rounds, max(a.iters, 10))
+            v._clipped, accum.pending = False, 0
+            del grads, glist, src, dst
+            r = {"ms": {k: round(t, 4) for k, t in {**ms, **nms}.items()}, "gradient_floats": n_floats,
+                 "first_over_copy": round(nms["accumulate_first"] / nms["copy_of_first_bytes"], 4),
+                 "add_over_copy": round(nms["accumulate_add_with_coef"] / nms["copy_of_add_bytes"], 4),
+                 "add_over_eager": round(nms["accumulate_add_with_coef"] / nms["eager_foreach_mul_add"], 4),
+                 "stepping_minus_train_step_ms": round(ms["micro_step_stepping"] - ms["train_step"], 4),
+                 "not_stepping_over_train_step": round(ms["micro_step_not_stepping"] / ms["train_step"], 4)}
+            rec["shapes"][f"{loss} 1x{size}x{size}"] = r
+            print(f"{loss} 1 x {size} x {size}: " + "  ".join(f"{k} {t:.3f} ms" for k, t in {**ms, **nms}.items()), flush=True)
+            print(f"  first / copy = {r['first_over_copy']}; add / copy = {r['add_over_copy']}; add / eager = {r['add_over_eager']}; stepping micro-step "
+                  f"- train_step = {r['stepping_minus_train_step_ms']} ms", flush=True)
+        health |= v.ctx.status()
+        del plain, accum, v
+        torch.cuda.empty_cache()
+    rec["health_word"] = health
+    line = json.dumps(rec)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[512, 1024])
@@ -61,9 +141,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--accumulate", type=int, default=0, help="A > 0: time gradient accumulation at A micro-steps instead (accumulate_bench)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_train_full needs a HIP device")
+    if a.accumulate > 0:
+        return accumulate_bench(a)
     manifest = {**synth.encoder_manifest(), **synth.image_decoder_manifest()}
     params = synth.synth_state_dict(manifest, seed=0)
     elements = sum(math.prod(s) for s in manifest.values())

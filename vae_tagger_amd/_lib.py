@@ -165,6 +165,7 @@ PROTOTYPES = {
     "vt_full_optim_norm": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_ll), _i, _f, _vp, _vp, _sz, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "vt_vae_grads_export": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_ll), _i, _vp, _sz, _i, _vp]),
     "vt_vae_grads_merge": (_i, [_vp, _vp, _sz, _i, _c.POINTER(_c.c_double), _sz, _sz, _vp, _vp]),
+    "vt_vae_grads_accumulate": (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_ll), _i, _vp, _sz, _f, _vp, _i, _i, _vp]),
     "vt_posterior_mode_latent": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _f, _i, _vp, _vp]),
     "vt_encoder_flops":(_c.c_double, [_vp, _i, _i]),
     "vt_set_flag": (_i, [_vp, _i, _i]),

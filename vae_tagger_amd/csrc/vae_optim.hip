@@ -215,6 +215,61 @@ __global__ __launch_bounds__(256) void vae_grads_zero_kernel(float* __restrict__
     for (int r = 0; r < QUADS; ++r) *(float4*)(d + 4 * ((long long)threadIdx.x + 256 * r)) = float4{0.f, 0.f, 0.f, 0.f};
 }
 
+// Gradient accumulation of train_full: the n fresh gradient tensors of one micro-step into ONE fp32 row of the arenas' layout that holds the
+// sum across micro-steps.  t = scale * g, one fp32 multiply (skipped at scale == 1: the same bits).  FIRST: row = t over the whole tile,
+// +0.0 past the tensor's end -- the export's stores, so every float of the tensor's tiles is written.  Otherwise a = row, a = coef * a when
+// the scalars hold a coef < 1 (the clip of the micro-step before, applied here and nowhere else), row = a + t: two products and one add,
+// each rounded on its own -- the products are pinned in registers because -ffp-contract=fast would fuse one into the add, pragma or not.
+// The float4 that the tensor's end cuts goes one guarded float at a time: padding is neither read nor written.
+__device__ __forceinline__ float accum_one(float a, float g, float scale, bool scaled, float coef, bool clipped) {
+#pragma clang fp contract(off)
+    if (scaled) g = g * scale;
+    if (clipped) a = a * coef;
+    asm volatile("" : "+v"(g), "+v"(a));
+    return a + g;
+}
+template <bool FIRST>
+__global__ __launch_bounds__(256) VT_NO_PACKED_F32 void vae_grads_accumulate_kernel(OptimTable t, float* __restrict__ row, float scale,
+                                                                                    const TrainScalars* __restrict__ sc) {
+#pragma clang fp contract(off)
+    long long tile;
+    const OptimEntry e = t.e[optim_find(t, blockIdx.x, &tile)];
+    const bool scaled = scale != 1.0f;
+    float4 x[QUADS];
+    optim_load_tile(e, tile, x);
+    float* __restrict__ dst = row + e.off + tile * TILE;
+    if (FIRST) {
+#pragma unroll
+        for (int r = 0; r < QUADS; ++r) {
+            const long long i = tile * TILE + 4 * ((long long)threadIdx.x + 256 * r);
+            if (scaled) {                                       // (a lane past the end stays +0.0 under a negative scale too)
+                if (i < e.numel) x[r].x = x[r].x * scale;
+                if (i + 1 < e.numel) x[r].y = x[r].y * scale;
+                if (i + 2 < e.numel) x[r].z = x[r].z * scale;
+                if (i + 3 < e.numel) x[r].w = x[r].w * scale;
+            }
+            *(float4*)(dst + 4 * ((long long)threadIdx.x + 256 * r)) = x[r];
+        }
+    } else {
+        const float coef = sc ? sc->coef : 1.0f;
+        const bool clipped = coef < 1.0f;                       // a NaN or >= 1 coefficient multiplies nothing (vae_optim_adamw_kernel's rule)
+#pragma unroll
+        for (int r = 0; r < QUADS; ++r) {
+            const long long q = 4 * ((long long)threadIdx.x + 256 * r), i = tile * TILE + q;
+            if (i + 4 <= e.numel) {
+                float4 a = *(float4*)(dst + q);
+                a.x = accum_one(a.x, x[r].x, scale, scaled, coef, clipped); a.y = accum_one(a.y, x[r].y, scale, scaled, coef, clipped);
+                a.z = accum_one(a.z, x[r].z, scale, scaled, coef, clipped); a.w = accum_one(a.w, x[r].w, scale, scaled, coef, clipped);
+                *(float4*)(dst + q) = a;
+            } else if (i < e.numel) {
+                dst[q] = accum_one(dst[q], x[r].x, scale, scaled, coef, clipped);
+                if (i + 1 < e.numel) dst[q + 1] = accum_one(dst[q + 1], x[r].y, scale, scaled, coef, clipped);
+                if (i + 2 < e.numel) dst[q + 2] = accum_one(dst[q + 2], x[r].z, scale, scaled, coef, clipped);
+            }
+        }
+    }
+}
+
 // out[e] = (float)(w[0] x_0 + w[1] x_1 + ... + w[K-1] x_{K-1}), x_r = rows[r * stride + first + e], in fp64, added in that order, every
 // product and every sum rounded on its own (train_merge_kernel's arithmetic, except that the first product is not added to 0.0: with
 // K = 1 and w = 1 the merge is the identity on every bit pattern of a number, -0.0 included).  One workgroup per tile of the range, thread
@@ -412,6 +467,33 @@ int vt_vae_grads_export(vt_context* c, const float* const* grads, const long lon
         hipLaunchKernelGGL(vae_grads_export_kernel, dim3(tiles), dim3(256), 0, s, t, row);
     }));
     if (pad_tiles) {
+        hipLaunchKernelGGL(vae_grads_zero_kernel, dim3((unsigned)pad_tiles), dim3(256), 0, s, row + total);
+        HIPCK(c, hipGetLastError(), who);
+    }
+    return VT_OK;
+}
+
+int vt_vae_grads_accumulate(vt_context* c, const float* const* grads, const long long* numel, int n, float* row, size_t row_floats, float scale,
+                            const void* scalars, int first, int chunk, void* stream) {
+    if (!c) return VT_ERR_INVALID;
+    DeviceGuard guard(c);
+    const char* who = "vt_vae_grads_accumulate";
+    long long total = 0;
+    VTCK(optim_check(c, who, grads, numel, n, chunk, &total));
+    if (!row || ((uintptr_t)row & (ALIGN - 1))) return c->fail(VT_ERR_INVALID, "%s: row is null or not 256-B aligned", who);
+    if (row_floats % TILE || row_floats < (size_t)total)
+        return c->fail(VT_ERR_INVALID, "%s: a row of %zu floats, a multiple of %lld that is at least %lld expected", who, row_floats, TILE, total);
+    if (!isfinite(scale)) return c->fail(VT_ERR_INVALID, "%s: scale = %g must be finite", who, (double)scale);
+    if ((uintptr_t)scalars & 15) return c->fail(VT_ERR_INVALID, "%s: scalars is not 16-B aligned", who);
+    const long long pad_tiles = ((long long)row_floats - total) / TILE;
+    if (pad_tiles > 0x7fffffffll) return c->fail(VT_ERR_INVALID, "%s: %lld tiles of padding in one launch", who, pad_tiles);
+    hipStream_t s = (hipStream_t)stream;
+    const TrainScalars* sc = (const TrainScalars*)scalars;
+    VTCK(optim_chunks(c, who, grads, numel, n, chunk, [&](const OptimTable& t, unsigned tiles) {
+        if (first) hipLaunchKernelGGL(vae_grads_accumulate_kernel<true>, dim3(tiles), dim3(256), 0, s, t, row, scale, sc);
+        else hipLaunchKernelGGL(vae_grads_accumulate_kernel<false>, dim3(tiles), dim3(256), 0, s, t, row, scale, sc);
+    }));
+    if (first && pad_tiles) {                                    // (an accumulating call leaves the zeros the first one wrote)
         hipLaunchKernelGGL(vae_grads_zero_kernel, dim3((unsigned)pad_tiles), dim3(256), 0, s, row + total);
         HIPCK(c, hipGetLastError(), who);
     }

@@ -19,9 +19,14 @@ no gradient flows from the classification loss into the VAE and the two backward
 
 What differs from the reference, on purpose: everything train_vae's docstring lists (the split and the epoch order from the seed alone, triplets per
 epoch and anchor, the counter-based noise, the bucketing rule, nothing read back per step), whose helpers this module imports.  Refused, each with a
-message that names the flag: --gradient_accumulation_steps > 1 (the reference clips every micro-step on the accumulated gradient),
---use_adaptive_weights, --use_quant_conv / --use_post_quant_conv, --sharded, and --triplet_weight <= 0 under the simplified loss (the reference then
-drops the term and the whole VAE has no gradient).
+message that names the flag: --gradient_accumulation_steps > 1 without --accumulate_gradients, --use_adaptive_weights, --use_quant_conv /
+--use_post_quant_conv, --sharded, and --triplet_weight <= 0 under the simplified loss (the reference then drops the term and the whole VAE has no
+gradient).
+
+Gradient accumulation (--accumulate_gradients --gradient_accumulation_steps A; FullTrainer.micro_step, accumulation_plan) is the reference's loop
+(train_full.py:246-255): every micro-step backpropagates loss / A into the accumulated gradient of both models and clips THAT; the optimiser, the
+schedule and the zeroing run when (step + 1) % A == 0 with `step` counted inside the epoch, so an epoch's tail stays pending into the next one.
+A checkpoint taken with micro-steps pending also holds pending_gradients.safetensors, and state.json the three counters.
 """
 import argparse
 import ctypes
@@ -42,7 +47,7 @@ from .train_vae import (MODEL_FILE, OPTIMIZER_FILE, STATE_FILE, TRIPLET_SEED_STR
 
 IGNORED_ARGUMENTS = ("mixed_precision", "cudnn_benchmark", "cudnn_deterministic", "num_workers", "prefetch_factor",
                      "enable_xformers_memory_efficient_attention", "use_safetensors")
-DECODER_FILE, DECODER_OPTIMIZER_FILE = "pytorch_model.bin", "decoder_optimizer.safetensors"
+DECODER_FILE, DECODER_OPTIMIZER_FILE, PENDING_FILE = "pytorch_model.bin", "decoder_optimizer.safetensors", "pending_gradients.safetensors"
 _KINDS = ((_lib.HEAD_PARAM, "param."), (_lib.HEAD_ADAM_M, "exp_avg."), (_lib.HEAD_ADAM_V, "exp_avg_sq."))
 
 
@@ -95,6 +100,7 @@ class FullTrainer:
         self._saved = {}
         self._ws = None
         self.t = 0
+        self.micro = self.pending = 0                                            # micro_step's counters: micro-steps in all, and since the last step
 
     # -- the step ---------------------------------------------------------------------------------------------------------------------------
     def saved_bytes(self, shape):
@@ -138,9 +144,10 @@ class FullTrainer:
                           self.vae._stream())
         return out
 
-    def decoder_forward_backward(self, latent, labels, step):
-        """the decoder side's forward, loss (x the classification weight) and backward; -> the weighted loss, a 0-d float64 device tensor"""
-        scale = self.weights["classification"]
+    def decoder_forward_backward(self, latent, labels, step, loss_scale=None):
+        """the decoder side's forward, loss (x loss_scale; None: the classification weight) and backward, which ADDS to the blocks' gradients;
+        -> the scaled loss, a 0-d float64 device tensor"""
+        scale = self.weights["classification"] if loss_scale is None else float(loss_scale)
         if isinstance(self.dec, DecoderTrainer):
             self.dec.forward_backward(latent, labels, loss_scale=scale, train=True, step=step)
         else:
@@ -203,6 +210,65 @@ class FullTrainer:
         self.step(grads, lr, weight_decay, betas, eps)
         return losses
 
+    def micro_step(self, anchor, positive, negative, labels_a, labels_p=None, first_image=0, *, accumulation_steps, step_now, lr, weight_decay=0.0,
+                   max_grad_norm=1.0, betas=ADAM_BETAS, eps=ADAM_EPS):
+        """One micro-step of train_full under --gradient_accumulation_steps A, the reference's loop (train_full.py:246-255): the loss / A is
+        backpropagated into the accumulated gradient of both models, clip_grad_norm_ runs on that accumulated gradient EVERY micro-step, and
+        the optimiser steps (and zeroes the gradient) only when step_now.  The VAE's sum lives in its trainer's accumulation row
+        (VAETrainer.accumulate at scale 1 / A); the coefficient a clip leaves is applied to the row by the NEXT accumulate, or folded into
+        the step.  The blocks' backward adds into their gradients, the clip scales them in place, their step zeroes them.  `self.micro`
+        counts micro-steps (it keys the decoder side's dropout masks and loss-ring slot; the front's BatchNorm statistics move every
+        micro-step), `self.pending` those since the last optimiser step.  -> losses as train_step's, each x 1 / A (what the reference sums).
+        At A = 1 with step_now this leaves the bytes train_step leaves."""
+        A = int(accumulation_steps)
+        if A < 1:
+            raise ValueError("micro_step: accumulation_steps must be at least 1")
+        row = self.vae.accumulation_row()                                        # (allocated before the memory check of a new batch shape)
+        losses, grads, moments = self.vae_forward_backward(anchor, positive, negative, labels_a, labels_p if labels_p is not None else labels_a, first_image)
+        latent = self.mode_latent(moments, anchor.shape[0])
+        losses = {k: v / A for k, v in losses.items()}
+        losses["classification"] = self.decoder_forward_backward(latent, labels_a, self.micro, self.weights["classification"] / A)
+        losses["total"] = losses["total"] + losses["classification"]
+        self.vae.accumulate(grads, scale=1.0 / A, first=self.pending == 0, n=self.n)
+        del grads, row
+        acc = self.vae.accumulated(self.n)
+        if max_grad_norm > 0:
+            self.clip(acc, max_grad_norm)
+        self.micro += 1
+        if step_now:
+            self.step(acc, lr, weight_decay, betas, eps)
+            self.pending = 0
+        else:
+            self.pending += 1
+        return losses
+
+    def pending_state_dict(self):
+        """What a run interrupted between two optimiser steps carries: the accumulation row with the pending clip coefficient APPLIED (one fp32
+        multiply on the device -- the multiply the next accumulate would have performed first, so a run that loads this with no coefficient
+        pending continues on the same bits) and every block's accumulated gradients.  Host tensors; synchronises."""
+        v = self.vae
+        row = v.accumulation_row()
+        if v._clipped:
+            coef = v.grad_norm()[1]
+            if coef < 1.0:
+                row = row * coef                                                 # (coef is an fp32 value: the scalar multiply is that fp32 multiply)
+        out = {"vae.row": row.detach().cpu().contiguous(), "pending": torch.tensor([self.pending], dtype=torch.int64)}
+        for b in self.blocks:
+            for name, shape in b.shapes.items():
+                out["grad." + name] = b._read(_lib.HEAD_GRAD, name, shape, torch.float32)
+        return out
+
+    def load_pending_state_dict(self, state):
+        want = {"vae.row", "pending"} | {"grad." + name for b in self.blocks for name in b.shapes}
+        if set(state.keys()) != want or state["vae.row"].numel() != self.vae.total:
+            raise ValueError("load_pending_state_dict: vae.row of the arenas' layout, pending and grad.* of this decoder's tensors are expected")
+        self.vae.accumulation_row().copy_(state["vae.row"].to(torch.float32).reshape(-1))
+        self.vae._clipped = False
+        for b in self.blocks:
+            for name in b.shapes:
+                b.write(_lib.HEAD_GRAD, name, state["grad." + name].reshape(b.shapes[name]))
+        self.pending = int(state["pending"][0])
+
     def grad_norm(self):
         """(joint L2 norm, clip coefficient) of the last clip(); synchronises."""
         return self.vae.grad_norm()
@@ -249,6 +315,11 @@ class FullTrainer:
         save_optimizer_state(os.path.join(path, OPTIMIZER_FILE), self.vae.optimizer_state_dict())
         torch.save(self.decoder_state_dict(), os.path.join(path, DECODER_FILE))
         save_file({k: v.contiguous() for k, v in self.decoder_optimizer_state_dict().items()}, os.path.join(path, DECODER_OPTIMIZER_FILE))
+        pending = os.path.join(path, PENDING_FILE)
+        if self.pending > 0:
+            save_file(self.pending_state_dict(), pending)
+        elif os.path.exists(pending):                                            # (a directory written before, at another point of the schedule)
+            os.remove(pending)
 
     def load(self, path):
         from safetensors.torch import load_file
@@ -258,6 +329,9 @@ class FullTrainer:
         self.t = self.vae.t
         if any(b.t != self.t for b in self.blocks):
             raise ValueError(f"{path}: the two optimiser states are at different steps")
+        self.pending = 0
+        if os.path.exists(os.path.join(path, PENDING_FILE)):
+            self.load_pending_state_dict(load_file(os.path.join(path, PENDING_FILE)))
 
     def state_sha256(self):
         """{"vae", "decoder"}: SHA-256 over the parameters and Adam moments of each model"""
@@ -313,7 +387,7 @@ def build_parser():
     p.add_argument("--bucket_step", type=int, default=64, help="分桶的步长")
     p.add_argument("--num_workers", type=int, default=4, help="DataLoader 工作线程数")
     p.add_argument("--prefetch_factor", type=int, default=2, help="DataLoader 预取倍数（每个worker）")
-    p.add_argument("--gradient_accumulation_steps", type=int, default=1, help="梯度累积步数 (refused above 1)")
+    p.add_argument("--gradient_accumulation_steps", type=int, default=1, help="梯度累积步数 (above 1 only with --accumulate_gradients)")
     p.add_argument("--seed", type=int, default=42, help="随机种子")
     p.add_argument("--cudnn_benchmark", action="store_true", help="启用cudnn benchmark以提高卷积性能（输入尺寸固定时建议开启）")
     p.add_argument("--cudnn_deterministic", action="store_true", help="启用确定性cuDNN以提高复现性（可能降低性能）")
@@ -324,6 +398,9 @@ def build_parser():
     p.add_argument("--stop_after_epochs", type=int, default=0, help="end the run after this many epochs of --num_epochs (0: all); the schedule is --num_epochs'")
     p.add_argument("--workers", type=int, default=0, help="image decode threads (0 = min(16, cores))")
     p.add_argument("--sharded", action="store_true", help="refused: the joint step is not sharded")
+    p.add_argument("--accumulate_gradients", action="store_true", help="accept --gradient_accumulation_steps A: the reference's loop, the loss / A "
+                                                                       "into an accumulated gradient that is clipped EVERY micro-step, an optimiser "
+                                                                       "step when (step + 1) %% A == 0 inside an epoch")
     return p
 
 
@@ -337,9 +414,12 @@ def check_args(args):
     """What is refused, before any GPU work; each message names its flag."""
     if args.no_attention:
         args.use_attention = False
-    if args.gradient_accumulation_steps > 1:
-        raise RuntimeError("--gradient_accumulation_steps > 1 is not implemented: the reference clips every micro-step on the accumulated gradient, "
-                           "which nothing here reproduces")
+    accumulate = getattr(args, "accumulate_gradients", False)
+    if args.gradient_accumulation_steps > 1 and not accumulate:
+        raise RuntimeError("--gradient_accumulation_steps > 1 needs --accumulate_gradients: the reference clips every micro-step on the accumulated "
+                           "gradient and steps by the position inside the epoch, which is what that flag runs")
+    if accumulate and args.gradient_accumulation_steps < 1:
+        raise RuntimeError("--accumulate_gradients: --gradient_accumulation_steps must be at least 1")
     if args.use_adaptive_weights:
         from .improved_losses import CombinedLoss
         try:
@@ -361,6 +441,23 @@ def check_args(args):
     if args.train_batch_size < 1 or args.num_epochs < 1 or args.save_steps < 1 or args.logging_steps < 1:
         raise RuntimeError("--train_batch_size, --num_epochs, --save_steps and --logging_steps must be at least 1")
     return args
+
+
+def accumulation_plan(steps_per_epoch, num_epochs, accumulation_steps):
+    """(epoch, step, first, step_now) per micro-step of a run, the reference's rule taken literally (train_full.py:201, 252): `step` counts from 0
+    inside every epoch and the optimiser steps iff (step + 1) % A == 0.  `first`: no micro-gradient is pending, this one starts a new sum.  A tail
+    of an epoch that does not fill a group of A stays pending across the validation pass and into the next epoch, so the next optimiser step
+    carries more than A micro-gradients; what is pending after the last epoch is dropped.  The specification of what train() does with its
+    per-epoch batch index and FullTrainer.pending: the tests hold the run's counters against it."""
+    spe, epochs, A = int(steps_per_epoch), int(num_epochs), int(accumulation_steps)
+    if spe < 1 or epochs < 1 or A < 1:
+        raise ValueError("accumulation_plan: steps_per_epoch, num_epochs and accumulation_steps are at least 1")
+    pending = 0
+    for epoch in range(epochs):
+        for step in range(spe):
+            step_now = (step + 1) % A == 0
+            yield epoch, step, pending == 0, step_now
+            pending = 0 if step_now else pending + 1
 
 
 def _make_decoder(args, n_tags, device):
@@ -447,13 +544,20 @@ def train(args):
     config = model_config(model.vae)
     spe = steps_per_epoch(len(train_idx), args.train_batch_size, train_buckets)
     total_steps = args.num_epochs * spe
-    run = {"step": 0, "epoch": 0, "images": 0, "best_val_loss": None, "history": {"train_loss": [], "val_loss": [], "learning_rates": []}}
+    # `step` counts micro-steps (batches consumed); without accumulation every one of them is an optimiser step
+    A = args.gradient_accumulation_steps if getattr(args, "accumulate_gradients", False) else 1
+    run = {"step": 0, "epoch": 0, "images": 0, "best_val_loss": None, "history": {"train_loss": [], "val_loss": [], "learning_rates": []},
+           "micro_steps": 0, "optimizer_steps": 0, "pending_micro_steps": 0}
     if args.resume_from:
         trainer.load(args.resume_from)
         with open(os.path.join(args.resume_from, STATE_FILE), "r", encoding="utf-8") as fh:
             run = json.load(fh)
-        if run["step"] != trainer.t or run["step"] != run["epoch"] * spe:
+        if run.get("optimizer_steps", run["step"]) != trainer.t or run["step"] != run["epoch"] * spe:
             raise SystemExit(f"{args.resume_from}: step {run['step']} does not match {run['epoch']} epochs of {spe} steps: other data or batch size")
+        if run.get("pending_micro_steps", 0) != trainer.pending or (A == 1 and trainer.pending):
+            raise SystemExit(f"{args.resume_from}: {run.get('pending_micro_steps', 0)} pending micro-steps in {STATE_FILE}, {trainer.pending} in "
+                             f"{PENDING_FILE}, under --gradient_accumulation_steps {A}")
+        trainer.micro = run.get("micro_steps", run["step"])
         print(f"resumed from {args.resume_from}: epoch {run['epoch']}, step {run['step']}, {run['images']} images consumed")
     history = run["history"]
     best = math.inf if run["best_val_loss"] is None else float(run["best_val_loss"])
@@ -496,16 +600,21 @@ def train(args):
             order = epoch_order(len(train_idx), args.seed, epoch)
             triplets = {i: evaluate_vae.sample_triplet(args.seed * TRIPLET_SEED_STRIDE + epoch + 1, i, train_labels) for i in order}
             loss_sum = torch.zeros((), dtype=torch.float64, device=device)
-            lrs, saved_bytes, epoch_images, losses = [], 0, 0, None
+            lrs, saved_bytes, epoch_images, losses, opt_before = [], 0, 0, None, trainer.t
             for k, (bucket, idx) in enumerate(plan_train_batches(order, args.train_batch_size, train_buckets)):
                 xa = load(pool, idx, bucket)
                 xp = load(pool, [triplets[i][0] for i in idx], bucket)
                 xn = load(pool, [triplets[i][1] for i in idx], bucket)
                 ia = torch.as_tensor(idx, device=device)
                 ip = torch.as_tensor([triplets[i][0] for i in idx], device=device)
-                lr = args.learning_rate * lr_schedule(args.lr_scheduler_type, step, args.lr_warmup_steps, total_steps)
-                losses = trainer.train_step(xa, xp, xn, label_t[ia], label_t[ip], images, lr=lr, weight_decay=args.weight_decay,
-                                            max_grad_norm=args.max_grad_norm)
+                # the schedule advances once per optimiser step over total_steps = num_epochs * steps_per_epoch (the reference's num_training_steps)
+                lr = args.learning_rate * lr_schedule(args.lr_scheduler_type, trainer.t, args.lr_warmup_steps, total_steps)
+                if A == 1:
+                    losses = trainer.train_step(xa, xp, xn, label_t[ia], label_t[ip], images, lr=lr, weight_decay=args.weight_decay,
+                                                max_grad_norm=args.max_grad_norm)
+                else:                                                            # accumulation_plan's rule: k restarts every epoch
+                    losses = trainer.micro_step(xa, xp, xn, label_t[ia], label_t[ip], images, accumulation_steps=A, step_now=(k + 1) % A == 0,
+                                                lr=lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
                 loss_sum = loss_sum + losses["total"]
                 saved_bytes = max(saved_bytes, trainer.saved_bytes(xa.shape))
                 lrs.append(lr)
@@ -521,7 +630,7 @@ def train(args):
             state, _, classification = evaluate_vae.run_checkpoint(args, model, val_data, val_labels, val_triplets, val_batches, decoder=decoder,
                                                                    class_weights=class_weights, selected=selected, device=device)
             val_loss = evaluate_vae.build_report(state, args, classification)["val_loss_train_full"]
-            next_lr = args.learning_rate * lr_schedule(args.lr_scheduler_type, step, args.lr_warmup_steps, total_steps)
+            next_lr = args.learning_rate * lr_schedule(args.lr_scheduler_type, trainer.t, args.lr_warmup_steps, total_steps)
             history["train_loss"].append(train_loss)
             history["val_loss"].append(val_loss)
             history["learning_rates"].append(next_lr)                        # (the reference reads the lr after its scheduler's step)
@@ -531,7 +640,8 @@ def train(args):
             if improved:
                 best = val_loss
                 print(f"New best validation loss: {best:.4f}")
-            run = {"step": step, "epoch": epoch + 1, "images": images, "best_val_loss": None if math.isinf(best) else best, "history": history}
+            run = {"step": step, "epoch": epoch + 1, "images": images, "best_val_loss": None if math.isinf(best) else best, "history": history,
+                   "micro_steps": step, "optimizer_steps": trainer.t, "pending_micro_steps": trainer.pending}
             if improved:
                 save_checkpoint("best_checkpoint", run)
                 save_pair("best_vae", "best_decoder")
@@ -545,7 +655,8 @@ def train(args):
             report["epochs"].append({"epoch": epoch, "seconds": seconds, "images_per_second": epoch_images / seconds, "steps": len(lrs),
                                      "images": epoch_images, "learning_rates": lrs, "train_loss": train_loss, "val_loss": val_loss,
                                      "grad_norm": None if norm is None else {"norm": norm[0], "coef": norm[1]},
-                                     "saved_bytes_per_step": saved_bytes, "state_sha256": trainer.state_sha256()})
+                                     "saved_bytes_per_step": saved_bytes, "state_sha256": trainer.state_sha256(), "accumulation_steps": A,
+                                     "optimizer_steps": trainer.t - opt_before})
             _write_json(report_path, report)
     print("训练完成，开始最终评估...")
     _write_json(os.path.join(args.output_dir, "training_history.json"), history)

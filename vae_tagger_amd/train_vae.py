@@ -12,6 +12,8 @@ triplet loss, clip_grad_norm_, AdamW under a learning-rate schedule, validation 
   VAEGradientExchange   --sharded's one cross-rank operation per step: export into a row of the arenas' layout (vt_vae_grads_export), the
                  ranks' slices cross, every rank merges the tiles it owns in rank order (vt_vae_grads_merge; merge_rows_host is its mirror), the
                  merged slices are gathered; clip and step then run on views into the merged row
+  accumulate_rows_host   the numpy mirror of vt_vae_grads_accumulate, the pass behind VAETrainer.accumulate / accumulated: the gradients of
+                 train_full's micro-steps summed in one row of the arenas' layout (train_vae's own CLI has no accumulation: the reference's has none)
   train / main   the CLI: the reference's flags and defaults; per epoch a validation pass (evaluate_vae.run_checkpoint) and the reference's files
 
 What differs from the reference, on purpose.  The train / validation split and the epoch order come from the seed alone (train.split_indices,
@@ -21,7 +23,8 @@ a run that was resumed, write the same bytes.  With --use_bucketing a batch has 
 ANCHOR's bucket (evaluate_vae's rule).  The positive and the negative are not decoded (the reference decodes them and throws the result away).
 Nothing is read back per step: the running loss sum stays on the device and is read, with the health word, every --logging_steps and at the end
 of an epoch.  fp32 parameters and moments, bf16 MFMA operands: --mixed_precision and the other flags of IGNORED_ARGUMENTS are accepted and ignored.
-Not here: gradient accumulation or checkpointing, the contrastive term, AdaptiveLossWeights.
+Not here: gradient accumulation (train_full has it: VAETrainer.accumulate is its VAE side) or checkpointing, the contrastive term,
+AdaptiveLossWeights.
 
 --sharded (under torchrun, one rank per GPU; the reference runs under `accelerate`).  --train_batch_size is per rank.  The epoch is planned as
 without the flag, at the global batch B * world, and rank r takes the contiguous slice [r B, (r + 1) B) of every global batch with
@@ -143,6 +146,7 @@ class VAETrainer:
         self._ws = None
         self._ctx = None
         self._clipped = False
+        self._row = self._row_views = None                                       # the accumulation row (accumulate): absent until a trainer accumulates
         self._saved = {}                                                         # batch shape -> bytes kept between forward and backward
         self.t = 0
 
@@ -179,13 +183,16 @@ class VAETrainer:
         return 3 * 4 * self.total
 
     def check_memory(self, B, H, W):
-        """Refuse a batch shape whose saved activations do not fit beside the arenas, before anything of the step is allocated."""
+        """Refuse a batch shape whose saved activations do not fit beside the arenas, before anything of the step is allocated.  The
+        accumulation row (4 * total bytes) is counted by being there: once allocated it is outside `free`, FullTrainer.micro_step allocates
+        it before a shape's first check, and accumulation_row() makes its own check where a caller allocates it later."""
         from . import vae_backward
         need = vae_backward.vae_train_saved_bytes(self.shapes, B, H, W)
         free = torch.cuda.mem_get_info(self.device)[0] + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         if need > free:
-            raise MemoryError(f"VAETrainer: a [{B}, 3, {H}, {W}] batch keeps {need} bytes between forward and backward beside {self.arena_bytes()} bytes "
-                              f"of parameter and moment arenas; the device has {free} bytes free")
+            raise MemoryError(f"VAETrainer: a [{B}, 3, {H}, {W}] batch keeps {need} bytes between forward and backward beside "
+                              f"{self.arena_bytes() + self.row_bytes()} bytes of parameter and moment arenas"
+                              f"{' and the accumulation row' if self.row_bytes() else ''}; the device has {free} bytes free")
         return need
 
     def saved_bytes(self, shape):
@@ -259,6 +266,47 @@ class VAETrainer:
         w = [float(x) for x in weights]
         self.ctx.call("vt_vae_grads_merge", ctypes.c_void_p(rows.data_ptr()), int(row_stride), len(w), (ctypes.c_double * max(1, len(w)))(*w),
                       int(first_float), int(floats), ctypes.c_void_p(out.data_ptr()), self._stream())
+
+    # -- gradient accumulation (train_full's micro-steps; accumulate_rows_host states the arithmetic) ---------------------------------------
+    def accumulate(self, grads, *, scale, first, n=None, chunk=0):
+        """The gradients of one micro-step, times `scale`, into the trainer's accumulation row (vt_vae_grads_accumulate): first=True starts
+        the sum (every float of the row is written), first=False adds to it -- after the coefficient of a clip() since the last accumulate
+        has been applied to the row, here and nowhere else.  `grads` is keyed and ordered like the first n of params (None: all)."""
+        n = len(self.numels) if n is None else int(n)
+        keys = list(self.params)[:n]
+        if n < 1 or list(grads.keys()) != keys:
+            raise ValueError("the gradients are keyed and ordered like the first n of params")
+        ptrs = (ctypes.c_void_p * n)()
+        for i, (k, g) in enumerate(grads.items()):
+            if g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous() or tuple(g.shape) != self.shapes[k]:
+                raise ValueError(f"{k}: a contiguous fp32 gradient of shape {self.shapes[k]} on {self.device} is expected")
+            ptrs[i] = g.data_ptr()
+        row = self.accumulation_row()
+        scalars = ctypes.c_void_p(self._scalars.data_ptr()) if self._clipped and not first else None
+        self.ctx.call("vt_vae_grads_accumulate", ptrs, _ll_array(self.numels[:n]), n, ctypes.c_void_p(row.data_ptr()), row.numel(), float(scale),
+                      scalars, int(bool(first)), int(chunk), self._stream())
+        self._clipped = False
+
+    def accumulation_row(self):
+        """The fp32 row of the arenas' layout that holds the sum across micro-steps (allocated on first use: 4 * total bytes)."""
+        if self._row is None:
+            if self.device.type == "cuda":
+                free = torch.cuda.mem_get_info(self.device)[0] + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+                if 4 * self.total > free:
+                    raise MemoryError(f"VAETrainer: the accumulation row takes {4 * self.total} bytes beside {self.arena_bytes()} bytes of parameter "
+                                      f"and moment arenas; the device has {free} bytes free")
+            self._row = self._aligned(self.total)
+            self._row_views = self.gradient_views(self._row)
+        return self._row
+
+    def accumulated(self, n=None):
+        """{key: view into the accumulation row} of the first n tensors (None: all): what clip and step take."""
+        self.accumulation_row()
+        views = self._row_views
+        return views if n is None or n == len(views) else {k: views[k] for k in list(views)[:int(n)]}
+
+    def row_bytes(self):
+        return 0 if self._row is None else 4 * self.total
 
     def gradient_views(self, row):
         """{key: view of `row` at the tensor's slot}, keyed and ordered like params: what clip and step take after a merge."""
@@ -352,6 +400,31 @@ def merge_rows_host(rows, weights):
     for r in range(1, len(rows)):
         acc = acc + w[r] * rows[r].astype(np.float64)
     return acc.astype(np.float32)
+
+
+def accumulate_rows_host(row, grads, offsets, numels, scale, coef, first):
+    """What vt_vae_grads_accumulate computes, in numpy fp32 -> the new row (the one given is not changed).  Per element g of tensor i at
+    offsets[i]: t = scale * g; first: row = t, zero everywhere else; otherwise a = row, a = coef * a when coef (None: no scalars) is < 1 -- a NaN
+    or >= 1 coef multiplies nothing -- and row = a + t.  Two products and one add, each rounded to fp32 on its own (numpy rounds each ufunc's
+    result: nothing is fused); what lies outside the tensors' elements keeps its bytes."""
+    row = np.asarray(row, dtype=np.float32).reshape(-1)
+    out = np.zeros_like(row) if first else row.copy()
+    s = np.float32(scale)
+    c = None if coef is None else np.float32(coef)
+    clipped = c is not None and bool(c < np.float32(1.0))
+    for g, o, n in zip(grads, offsets, numels):
+        g = np.asarray(g, dtype=np.float32).reshape(-1)
+        if g.size != n:
+            raise ValueError("accumulate_rows_host: a gradient's size is not its numel")
+        t = g if s == np.float32(1.0) else g * s
+        if first:
+            out[o:o + n] = t
+        else:
+            a = out[o:o + n]
+            if clipped:
+                a = a * c
+            out[o:o + n] = a + t
+    return out
 
 
 class _DeviceTransport:
